@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Headline benchmark: images/s of the `cnn` (WACNN) training step on synthetic 256x256 batches.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
 N > 1: either launched by `python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...` (the
 driver's way: WORLD_SIZE is set) or started plainly, in which case this script starts that launcher itself as a
@@ -9,13 +9,21 @@ child process BEFORE anything touches the GPU and exits with its code.
 
 One step = the reference training iteration (train.py:188-214): forward, R-D loss (lambda=0.0067),
 backward, clip_grad_norm_(1.0), Adam on the 75.2 M parameters, aux loss + Adam on the quantiles; batch 16
-per GPU (BASELINE.json configs[1]; configs[2] = 8 GPUs x 16).  Prints ONE JSON line:
+per GPU (BASELINE.json configs[1]; configs[2] = 8 GPUs x 16).  Prints ONE JSON line.
+
+A plain run sets up, warms up, times the K steps and prints the line:
 
   value / ms_per_step   whole-job images/s over the timed region (barrier + synchronize on both sides, max over ranks)
-  forward / stf         (1 GPU, cnn line only) sub-objects: eval forward of the same model on the same batch, and the stf
-                        model's training step + eval forward, each {value, ms_per_step, roofline_step}
   dist                  backend and world size the collective layer saw (RCCL = "nccl")
   roofline_step         the whole step against the f32-MFMA roofline (206.6 GFLOP / image)
+
+--dump-outputs DIR writes what the last timed step computed as DIR/<name>.npy (float32, see dump_outputs), so that two
+builds can be compared output for output: the inputs depend only on the arguments.
+
+--full adds what takes runs of its own (each can still be switched off with its --no-* option):
+
+  forward / stf         (1 GPU, cnn line only) sub-objects: eval forward of the same model on the same batch, and the stf
+                        model's training step + eval forward, each {value, ms_per_step, roofline_step}
   roofline              the kernel FAMILY (implicit-GEMM conv = forward + input gradients | weight gradients) that is
                         furthest below the roofline among those with >= 15 % of the step's kernel time: algorithmic
                         FLOP of its launches / their HIP-event time, measured live in one extra, serialised step
@@ -39,6 +47,7 @@ STEP_GFLOP_PER_IMG = 206.6      # fwd + dgrad + wgrad
 PEAK_F32_MFMA_TFLOPS = 157.3    # MI355X_MICROARCH.md: v_mfma_f32_32x32x2_f32 dense peak
 BATCH_PER_GPU = 16
 SEED_X, SEED_NOISE = 1234, 4321
+SEED_DUMP, DUMP_PARAM_SAMPLE = 99, 1 << 22     # --dump-outputs: seeded sample of the updated parameters (16 MB)
 
 
 def make_workload(model_name, dev, rank=0, group=None, batch=BATCH_PER_GPU):
@@ -161,6 +170,25 @@ def timed(fn, warmup, steps):
     return (time.perf_counter() - t0) / steps * 1e3
 
 
+def dump_outputs(out_dir, tr, scal, fwd_out):
+    """--dump-outputs: what the caller of the timed path received from its last step, as float32 .npy files (< 20 MB).
+    Eval forward (--fwd-only): x_hat and the y / z likelihoods.  Training step: the returned scalars [bpp, mse, loss,
+    sumlog_y, sumlog_z, grad_sqnorm, aux_loss, 0], the updated quantiles (aux parameters) and a fixed, seeded sample
+    of DUMP_PARAM_SAMPLE elements of the updated main parameters (flat buffer, index drawn with seed SEED_DUMP)."""
+    import numpy as np
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    if fwd_out is not None:
+        arrays = dict(zip(("x_hat", "likelihoods_y", "likelihoods_z"), fwd_out))
+    else:
+        p = tr.flat.p[:tr.flat.n_main]
+        g = torch.Generator().manual_seed(SEED_DUMP)
+        idx = torch.randint(p.numel(), (min(DUMP_PARAM_SAMPLE, p.numel()),), generator=g).sort().values
+        arrays = {"step_scalars": scal, "aux_params": tr.flat.ap, "params_sample": p[idx.to(p.device)]}
+    for name, t in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), t.detach().float().cpu().numpy())
+
+
 def roofline_of(ips, gflop_per_image):
     tf = ips * gflop_per_image / 1e3
     return {"bound": "mfma", "achieved": tf, "peak": PEAK_F32_MFMA_TFLOPS, "unit": "TFLOP/s",
@@ -189,18 +217,23 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-shape-table", action="store_true")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write what the last timed step computed as DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true", help="also measure the per-shape roofline table (one extra, "
+                    "serialised step), the forward / stf sub-objects of the 1-GPU cnn line and the CPU baseline")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-shape-table", action="store_true", help="with --full: skip the per-shape roofline table")
     ap.add_argument("--graph", action="store_true", help="train steps replayed from a captured hipGraph "
                     "(Trainer.step_graphed; single GPU): reported as an extra line")
     ap.add_argument("--fwd-only", action="store_true", help="time eval-mode forward only (reported separately)")
     ap.add_argument("--model", default="cnn", choices=["cnn", "stf", "stf6"], help="cnn = BASELINE.json headline (default); "
                     "stf = configs[3], stf6 = the zigzag variant (SURVEY 8 f3): reported as extra lines")
-    ap.add_argument("--no-extras", action="store_true", help="skip the forward-only and stf sub-objects of the default "
-                    "1-GPU cnn line")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the forward-only and stf sub-objects "
+                    "of the default 1-GPU cnn line")
     args = ap.parse_args()
     if args.gpus < 1:
         sys.exit("--gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        sys.exit("--steps must be >= 1 and --warmup >= 0")
     env_world = os.environ.get("WORLD_SIZE")
     if env_world is None and args.gpus > 1:
         # plain `python bench.py --gpus N`: start one rank per GPU as CHILD processes (nothing here has touched the GPU
@@ -230,12 +263,16 @@ def main():
 
     packed = {}   # eval forward: weights are constant, the MFMA-order copies are packed once (inference serving path)
 
+    fwd_out = [None]   # --fwd-only --dump-outputs: (x_hat, y_likelihoods, z_likelihoods) of the latest call
+
     def one():
         if args.fwd_only:
             from icm_amd import engine as E
             from icm_amd.models import stf6_forward, stf_forward, wacnn_forward
-            {"cnn": wacnn_forward, "stf": stf_forward, "stf6": stf6_forward}[args.model](
+            out = {"cnn": wacnn_forward, "stf": stf_forward, "stf6": stf6_forward}[args.model](
                 E.Tape(need_grad=False, packed_cache=packed), tr.params(), x)
+            if args.dump_outputs:
+                fwd_out[0] = out
             return None
         return tr.step_graphed(x) if args.graph else tr.step(x)
 
@@ -261,11 +298,13 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = t.item()
     last = scal.tolist() if scal is not None else None
+    if args.dump_outputs and rank == 0:   # before anything else runs a step and changes the parameters
+        dump_outputs(args.dump_outputs, tr, scal, fwd_out[0])
 
     # ---- per-shape / per-family roofline: one extra step outside the timed region (every rank runs it: it contains
     # the same collectives), weight gradients serialised on the main stream
     rows = fams = None
-    if not args.no_shape_table:
+    if args.full and not args.no_shape_table:
         side = tr.side
         tr.side = None
         rows, fams, ktot, wall = shape_table(one)
@@ -322,7 +361,7 @@ def main():
             line["profiled_step"] = {"kernel_ms_sum": round(ktot, 3), "wall_ms": round(wall, 3)}
         # ---- sub-objects of the default driver line (1 GPU, cnn train step): the eval forward of the same model on the
         # same batch (the north-star target is stated on the forward) and the stf model's train step + forward
-        if world == 1 and args.model == "cnn" and not args.fwd_only and not args.graph and not args.no_extras:
+        if args.full and world == 1 and args.model == "cnn" and not args.fwd_only and not args.graph and not args.no_extras:
             line["forward"] = forward_bench("cnn", tr.params(), x)
             try:
                 tr2, x2, _ = make_workload("stf", dev, rank)
@@ -334,7 +373,7 @@ def main():
                 del tr2, x2
             except Exception as e:   # the headline line must survive a failure of the extra model
                 line["stf"] = {"error": f"{type(e).__name__}: {e}"}
-        if world == 1 and not args.no_cpu_baseline and args.model == "cnn":
+        if args.full and world == 1 and not args.no_cpu_baseline and args.model == "cnn":
             line["cpu_baseline"] = cpu_baseline(sd_cpu, min(os.cpu_count() or 1, 16), x.cpu())
         print(json.dumps(line, allow_nan=False))
     if world > 1:

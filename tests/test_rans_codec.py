@@ -2,7 +2,8 @@
   (1) oracle/rans_oracle.py -- an exact-integer Python restatement of the stream format (state machine of
       third_party/ryg_rans/rans64.h + CompressAI's published interface conventions), byte for byte;
   (2) oracle/_ref/librans64_ref.so -- a shim compiled from the reference's OWN rans64.h (oracle/build_ref.sh): the
-      escape-free streams of one table must be identical word for word, and the reference decoder must read ours.
+      escape-free streams of one table must be identical word for word, and the reference decoder must read ours
+      (the shim's streams are stored in tests/golden/rans64_ref.npz for machines where it cannot be built).
 The reference holds no golden bitstreams and its coder binaries are never run: the interface layer above the state
 machine is "parity unpinned" (DESIGN.md 2)."""
 import ctypes
@@ -16,6 +17,7 @@ from oracle import rans_oracle as R
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 REF_SO = os.path.join(ROOT, "oracle", "_ref", "librans64_ref.so")
+REF_FIXTURE = os.path.join(ROOT, "tests", "golden", "rans64_ref.npz")
 
 
 def _tables(rng, n=5):
@@ -115,15 +117,8 @@ def test_edge_cases():
         dec.decode_with_indexes(s[:8], [0] * 50, cdfs, sizes, offs)   # truncated stream is detected, not over-read
 
 
-@pytest.mark.skipif(not os.path.exists(REF_SO), reason="oracle/_ref not built (oracle/build_ref.sh needs /root/reference)")
-def test_state_machine_equals_the_reference_header():
-    """escape-free coding with one table: every word equals what Rans64EncPut / Rans64EncFlush of the reference's
-    vendored rans64.h produce, and Rans64DecInit / DecGet / DecAdvance read our stream back"""
-    ref = ctypes.CDLL(REF_SO)
-    u32p, i32p = ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_int32)
-    ref.ref_rans64_encode.restype = ctypes.c_int64
-    ref.ref_rans64_encode.argtypes = [u32p, u32p, ctypes.c_int64, ctypes.c_uint32, u32p, ctypes.c_int64]
-    ref.ref_rans64_decode.argtypes = [u32p, ctypes.c_int64, u32p, ctypes.c_int, ctypes.c_uint32, i32p, ctypes.c_int64]
+def _header_cases():
+    """the escape-free single-table problems of test_state_machine_equals_the_reference_header: (cdf, symbols)"""
     rng = np.random.default_rng(5)
     for trial in range(20):
         m = int(rng.integers(2, 200))
@@ -133,18 +128,52 @@ def test_state_machine_equals_the_reference_header():
         n = int(rng.integers(1, 5000))
         # skewed draws so that renormalisation happens at irregular intervals
         sym = np.minimum((rng.random(n) ** 3 * m).astype(np.int64), m - 1)
+        yield cdf, sym
+
+
+def _ref_header(path=REF_SO):
+    """(encode, decode) over oracle/_ref/librans64_ref.so: Rans64EncPut / EncFlush and DecInit / DecGet / DecAdvance"""
+    ref = ctypes.CDLL(path)
+    u32p, i32p = ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_int32)
+    ref.ref_rans64_encode.restype = ctypes.c_int64
+    ref.ref_rans64_encode.argtypes = [u32p, u32p, ctypes.c_int64, ctypes.c_uint32, u32p, ctypes.c_int64]
+    ref.ref_rans64_decode.argtypes = [u32p, ctypes.c_int64, u32p, ctypes.c_int, ctypes.c_uint32, i32p, ctypes.c_int64]
+
+    def encode(cdf, sym):
+        n = len(sym)
         start = np.ascontiguousarray(cdf[sym]).astype(np.uint32)
         freq = np.ascontiguousarray(cdf[sym + 1] - cdf[sym]).astype(np.uint32)
         out = np.zeros(n + 8, dtype=np.uint32)
         words = ref.ref_rans64_encode(start.ctypes.data_as(u32p), freq.ctypes.data_as(u32p), n, 16,
                                       out.ctypes.data_as(u32p), out.size)
         assert words > 0
-        want = out[:words].tobytes()
-        mine = ans.RansEncoder().encode_with_indexes(sym.tolist(), [0] * n, [cdf.astype(np.int64).tolist()],
-                                                     [len(cdf)], [0])
-        assert mine == want
+        return out[:words].tobytes()
+
+    def decode(stream, cdf, n):
         back = np.zeros(n, dtype=np.int32)
-        sw = np.frombuffer(mine, dtype=np.uint32).copy()
+        sw = np.frombuffer(stream, dtype=np.uint32).copy()
         rc = ref.ref_rans64_decode(sw.ctypes.data_as(u32p), sw.size, cdf.ctypes.data_as(u32p), len(cdf) - 1, 16,
                                    back.ctypes.data_as(i32p), n)
-        assert rc == 0 and back.tolist() == sym.tolist()
+        return rc, back.tolist()
+    return encode, decode
+
+
+def test_state_machine_equals_the_reference_header():
+    """escape-free coding with one table: every word equals what Rans64EncPut / Rans64EncFlush of the reference's
+    vendored rans64.h produce, and Rans64DecInit / DecGet / DecAdvance read our stream back.  The reference's streams
+    are stored in tests/golden/rans64_ref.npz (tests/golden/make_golden_rans.py); where oracle/_ref is built, the
+    header is also run live and must reproduce the stored streams."""
+    fx = np.load(REF_FIXTURE)
+    ref = _ref_header() if os.path.exists(REF_SO) else None
+    for t, (cdf, sym) in enumerate(_header_cases()):
+        n = len(sym)
+        assert np.array_equal(fx[f"cdf_{t}"], cdf) and np.array_equal(fx[f"sym_{t}"], sym), "fixture out of date"
+        want = fx[f"words_{t}"].tobytes()
+        tables = ([cdf.astype(np.int64).tolist()], [len(cdf)], [0])
+        mine = ans.RansEncoder().encode_with_indexes(sym.tolist(), [0] * n, *tables)
+        assert mine == want
+        assert ans.RansDecoder().decode_with_indexes(want, [0] * n, *tables) == sym.tolist()
+        if ref is not None:
+            encode, decode = ref
+            assert encode(cdf, sym) == want
+            assert decode(mine, cdf, n) == (0, sym.tolist())

@@ -5,9 +5,9 @@ set -o pipefail
 R=$GRAFT_REPO_ROOT
 O=$R/gpurun_out/final3; rm -rf $O; mkdir -p $O
 run() { timeout -k 10 "$@"; rc=$?; if [ $rc -ge 124 ]; then echo "KILLED rc=$rc: $*"; exit $rc; fi; return $rc; }
-ICM_SHAPE_TABLE=$O/shapes_train.jsonl run 500 python bench.py > $O/bench.json 2> $O/bench.err || true; tail -1 $O/bench.json | cut -c1-200
-ICM_SHAPE_TABLE=$O/shapes_fwd.jsonl run 300 python bench.py --fwd-only --no-cpu-baseline > $O/bench_fwd.json 2>/dev/null || true; tail -1 $O/bench_fwd.json | cut -c1-160
-ICM_SHAPE_TABLE=$O/shapes_stf.jsonl run 300 python bench.py --model stf --no-cpu-baseline > $O/bench_stf.json 2>/dev/null || true; tail -1 $O/bench_stf.json | cut -c1-160
+ICM_SHAPE_TABLE=$O/shapes_train.jsonl run 500 python bench.py --full > $O/bench.json 2> $O/bench.err || true; tail -1 $O/bench.json | cut -c1-200
+ICM_SHAPE_TABLE=$O/shapes_fwd.jsonl run 300 python bench.py --full --fwd-only --no-cpu-baseline > $O/bench_fwd.json 2>/dev/null || true; tail -1 $O/bench_fwd.json | cut -c1-160
+ICM_SHAPE_TABLE=$O/shapes_stf.jsonl run 300 python bench.py --full --model stf --no-cpu-baseline > $O/bench_stf.json 2>/dev/null || true; tail -1 $O/bench_stf.json | cut -c1-160
 cd /tmp && export TMPDIR=/tmp
 run 400 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof -- python3 $R/bench.py --no-cpu-baseline --no-shape-table --no-extras > $O/prof.log 2>&1 || true
 tail -1 $O/prof.log | cut -c1-160

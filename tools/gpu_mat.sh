@@ -8,5 +8,5 @@ for cfg in "ICM_MATERIALIZE=0" "ICM_MATERIALIZE=1" "ICM_MATERIALIZE=0" "ICM_MATE
   f=$(env $cfg timeout -k 10 200 python bench.py --fwd-only --no-cpu-baseline --no-shape-table 2>/dev/null | tail -1 | python -c "import sys,json; print(round(json.loads(sys.stdin.read())['value'],1))")
   echo "$cfg -> train $v  stf $w  fwd $f"
 done
-ICM_SHAPE_TABLE=$O/shapes_mat.jsonl timeout -k 10 300 python bench.py --no-cpu-baseline > $O/bench_mat.json 2>$O/bench_mat.err
+ICM_SHAPE_TABLE=$O/shapes_mat.jsonl timeout -k 10 300 python bench.py --full --no-cpu-baseline > $O/bench_mat.json 2>$O/bench_mat.err
 python -c "import json; r=json.loads(open('$O/bench_mat.json').read().strip().splitlines()[-1]); print('train', r['value'], {k:(v['ms'],v['tflops']) for k,v in r['roofline_families'].items()})"
