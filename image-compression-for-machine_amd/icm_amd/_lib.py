@@ -80,6 +80,7 @@ SYMBOLS = [
     "icm_rans_decoder_create", "icm_rans_decoder_decode", "icm_rans_decoder_destroy",
     "icm_eb_table_bounds", "icm_eb_pmf_table", "icm_gc_table_centers", "icm_gc_pmf_table", "icm_gc_build_indexes",
     "icm_quantize", "icm_dequantize", "icm_clamp", "icm_pad2d",
+    "icm_msssim_workspace_floats", "icm_msssim_fwd", "icm_msssim_bwd",
 ]
 REDUCE_WS_FLOATS = 8192   # ICM_REDUCE_WS_FLOATS
 
@@ -158,6 +159,10 @@ def lib():
         L.icm_adam_step.argtypes = [vp, vp, vp, vp, i64, C.c_double, C.c_double, C.c_double, C.c_double, i32, vp, f32, f32, vp]
         L.icm_adam_step_hyper.argtypes = [vp, vp, vp, vp, i64, C.c_double, C.c_double, C.c_double, vp, vp, f32, f32, vp]
         L.icm_fill.argtypes = [vp, i64, f32, vp]
+        L.icm_msssim_workspace_floats.argtypes = [i32, i32, i32, i32]
+        L.icm_msssim_workspace_floats.restype = i64
+        L.icm_msssim_fwd.argtypes = [vp, vp, i32, i32, i32, i32, f32, vp, vp, f32, vp, vp, i64, vp]
+        L.icm_msssim_bwd.argtypes = [vp, vp, i32, i32, i32, i32, vp, f32, vp, vp, i64, vp]
         # entropy coding (host) + its device-side table / symbol kernels
         i32p, u8p = C.POINTER(C.c_int32), C.POINTER(C.c_uint8)
         L.icm_pmf_to_quantized_cdf.argtypes = [C.POINTER(C.c_float), i32, i32, i32p]

@@ -2,7 +2,8 @@
 (compressai/utils/eval_model/__main__.py:627-671: collect images, load a checkpoint, ``update(force=True)``, run every
 image through ``inference`` (real rANS bit-streams) or ``inference_entropy_estimation`` (forward pass), average the
 metrics and print the JSON report) on the HIP path.  Same flags (-d/-r/-a/-c/-p/--entropy-estimation/--half/-v), same
-report layout; the task-model branches of the reference (detectron2 / segmentation, :553-625) are out of scope.
+report layout (``--metric psnr,ms-ssim`` adds the "ms-ssim" entry the reference has commented out, :135); the task-model
+branches of the reference (detectron2 / segmentation, :553-625) are out of scope.
 
 Differences kept deliberate: ``--entropy-estimation`` and ``--cuda`` are real booleans (the reference declares them
 without ``type``/``action``, so any string is truthy); ``--half`` is refused (the HIP path is f32 end to end, like the
@@ -54,17 +55,33 @@ def load_checkpoint(arch: str, checkpoint_path: str) -> torch.nn.Module:
 
 
 @torch.no_grad()
-def eval_model(model, filepaths: List[str], entropy_estimation: bool = False, recon_path: str = "") -> Dict[str, float]:
+def eval_model(model, filepaths: List[str], entropy_estimation: bool = False, recon_path: str = "",
+               metric_names=None) -> Dict[str, float]:
     """eval_model/__main__.py:472-487 (per-image metrics averaged over the folder)"""
     device = next(model.parameters()).device
     metrics: Dict[str, float] = defaultdict(float)
     for f in filepaths:
         x = read_image(f).to(device)
         fn = U.inference_entropy_estimation if entropy_estimation else U.inference
-        rv = fn(model, x, recon=(lambda xh, name=os.path.basename(f): reconstruct(xh, name, recon_path)) if recon_path else None)
+        if metric_names is not None and "ms-ssim" in metric_names and min(x.shape[-2:]) <= 160:
+            raise ValueError(f"{f}: {x.shape[-1]}x{x.shape[-2]} is too small for MS-SSIM (both sides must exceed 160 "
+                             "pixels: five levels of an 11-tap window)")
+        rv = fn(model, x, recon=(lambda xh, name=os.path.basename(f): reconstruct(xh, name, recon_path)) if recon_path else None,
+                **({} if metric_names is None else {"metrics": metric_names}))
         for k, v in rv.items():
             metrics[k] += v
     return {k: v / len(filepaths) for k, v in metrics.items()}
+
+
+def parse_metrics(values) -> List[str]:
+    """--metric may be repeated and / or comma-separated; no flag = ["psnr"]"""
+    if not values:
+        return ["psnr"]
+    names = [m.strip() for v in values for m in v.split(",") if m.strip()]
+    unknown = [m for m in names if m not in U.EVAL_METRICS]
+    if unknown or not names:
+        raise ValueError(f"--metric: unknown metric(s) {unknown}; choose from {list(U.EVAL_METRICS)}")
+    return [m for m in U.EVAL_METRICS if m in names]
 
 
 def setup_args() -> argparse.ArgumentParser:
@@ -80,12 +97,19 @@ def setup_args() -> argparse.ArgumentParser:
     p.add_argument("-v", "--verbose", action="store_true", help="verbose mode")
     p.add_argument("-p", "--path", dest="paths", type=str, default=None,
                    help="checkpoint path (default: the architecture's initial weights)")
+    p.add_argument("--metric", dest="metric", action="append", default=None, metavar="{psnr,ms-ssim}",
+                   help="quality metric(s) of the report; repeat the flag or separate by commas (default: psnr)")
     p.add_argument("--limit", type=int, default=0, help="evaluate only the first N images (0 = all)")
     return p
 
 
 def main(argv) -> int:
     args = setup_args().parse_args(argv)
+    try:
+        metric_names = parse_metrics(args.metric)
+    except ValueError as e:
+        print(f"Error: {e}", file=sys.stderr)
+        return 2
     if args.half:
         print("Error: --half is not supported (f32 path).", file=sys.stderr)
         return 2
@@ -103,7 +127,12 @@ def main(argv) -> int:
     model.update(force=True)
     if args.verbose:
         sys.stderr.write(f"Evaluating {args.paths or '<initial weights>'} on {len(filepaths)} images\n")
-    metrics = eval_model(model, filepaths, args.entropy_estimation, args.recon_path)
+    try:
+        metrics = eval_model(model, filepaths, args.entropy_estimation, args.recon_path,
+                             metric_names=metric_names if args.metric else None)
+    except ValueError as e:
+        print(f"Error: {e}", file=sys.stderr)
+        return 4
     results = defaultdict(list)
     for k, v in metrics.items():
         results[k].append(v)

@@ -1,4 +1,5 @@
-"""RateDistortionLoss (train.py:44-76; loss form of train_czigzag.py:63,71) on the fused HIP reductions."""
+"""RateDistortionLoss (train.py:44-76; loss form of train_czigzag.py:63,71) on the fused HIP reductions, with the
+MS-SSIM distortion of upstream CompressAI's RateDistortionLoss(metric="ms-ssim") as an option."""
 from __future__ import annotations
 
 import torch
@@ -32,14 +33,28 @@ class _RDFn(torch.autograd.Function):
         return None, dxh * g, dly * g, dlz * g, None
 
 
-class RateDistortionLoss(nn.Module):
-    """loss = lmbda * 255^2 * mse + bpp; returns {"loss","bpp_loss","mse_loss"} like the reference."""
+METRICS = ("mse", "ms-ssim")
 
-    def __init__(self, lmbda=1e-2):
+
+class RateDistortionLoss(nn.Module):
+    """metric="mse" (default): loss = lmbda * 255^2 * mse + bpp; returns {"loss","bpp_loss","mse_loss"} like the
+    reference.  metric="ms-ssim" (CompressAI's form): loss = lmbda * (1 - ms_ssim(x_hat, target)) + bpp; returns
+    {"loss","bpp_loss","ms_ssim_loss"} with ms_ssim_loss = 1 - ms_ssim."""
+
+    def __init__(self, lmbda=1e-2, metric="mse"):
         super().__init__()
+        if metric not in METRICS:
+            raise NotImplementedError(f"{metric} is not implemented!")
         self.lmbda = float(lmbda)
+        self.metric = metric
 
     def forward(self, output, target):
         lik = output["likelihoods"]
-        loss, bpp, mse = _RDFn.apply(target, output["x_hat"], lik["y"], lik["z"], self.lmbda)
-        return {"loss": loss, "bpp_loss": bpp.detach(), "mse_loss": mse.detach()}
+        if self.metric == "mse":
+            loss, bpp, mse = _RDFn.apply(target, output["x_hat"], lik["y"], lik["z"], self.lmbda)
+            return {"loss": loss, "bpp_loss": bpp.detach(), "mse_loss": mse.detach()}
+        from .ops import ms_ssim
+        # the rate term from the same fused reduction (lmbda = 0: its loss output is bpp, with the bpp gradient)
+        rate, bpp, _ = _RDFn.apply(target, output["x_hat"], lik["y"], lik["z"], 0.0)
+        dist = 1.0 - ms_ssim(output["x_hat"], target, data_range=1.0)
+        return {"loss": self.lmbda * dist + rate, "bpp_loss": bpp.detach(), "ms_ssim_loss": dist.detach()}

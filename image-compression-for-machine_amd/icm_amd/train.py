@@ -11,7 +11,8 @@ loss (:438), best-only checkpoints ``<save_path><epoch>.ckpt`` holding epoch / s
   reference loop is a GPU test); the learning rate of ReduceLROnPlateau is applied through ``Trainer.lr``;
 * ``--split``/``--test-split`` replace the hard-coded ``val2017`` folder name (:404-405); ``--random-crop`` selects the
   ``RandomCrop(pad_if_needed)`` transform the reference has commented out (:393-395) instead of ``CenterCrop``;
-* the loss is the published ``lmbda * 255^2 * mse + bpp`` (train_czigzag.py:63,71; default 0.0067);
+* the loss is the published ``lmbda * 255^2 * mse + bpp`` (train_czigzag.py:63,71; default 0.0067); ``--metric ms-ssim``
+  selects ``lmbda * (1 - ms_ssim) + bpp`` instead (upstream CompressAI's ``RateDistortionLoss(metric="ms-ssim")``);
 * under ``torch.distributed.run`` (WORLD_SIZE > 1) every rank trains on its shard of each batch (DistributedSampler)
   and gradients are all-reduced over RCCL by the Trainer; the reference is single-process;
 * checkpoints are read with ``weights_only=True``."""
@@ -27,7 +28,7 @@ import torch
 from torch.utils.data import DataLoader
 
 from .datasets import CenterCrop, Compose, ImageFolder, RandomCrop, ToTensor
-from .losses import RateDistortionLoss
+from .losses import METRICS, RateDistortionLoss
 from .trainer import Trainer
 from .zoo import models
 
@@ -80,8 +81,9 @@ def train_one_epoch(trainer: Trainer, train_dataloader, epoch: int, log_every: i
         if i % log_every == 0 and trainer.rank == 0:
             v = s.tolist()   # the only host sync of the loop
             dt, start = time.time() - start, time.time()
+            dist = f"MS-SSIM loss: {v[7]:.4f}" if trainer.metric == "ms-ssim" else f"MSE loss: {v[1]:.3f}"
             print(f"Train epoch {epoch}: [{i * len(x)}/{len(train_dataloader.dataset)} "
-                  f"({100. * i / len(train_dataloader):.0f}%)]\tLoss: {v[2]:.3f} |\tMSE loss: {v[1]:.3f} |"
+                  f"({100. * i / len(train_dataloader):.0f}%)]\tLoss: {v[2]:.3f} |\t{dist} |"
                   f"\tBpp loss: {v[0]:.2f} |\tAux loss: {v[6]:.2f} |\ttime: {dt:.1f}", flush=True)
 
 
@@ -91,16 +93,22 @@ def test_epoch(epoch: int, test_dataloader, model, criterion, verbose: bool = Tr
     model.eval()
     device = next(model.parameters()).device
     loss, bpp_loss, mse_loss, aux_loss = AverageMeter(), AverageMeter(), AverageMeter(), AverageMeter()
+    ms_ssim_loss = AverageMeter()
     for d in test_dataloader:
         x = d.to(device)
         out = criterion(model(x), x)
         aux_loss.update(float(model.aux_loss()))
         bpp_loss.update(float(out["bpp_loss"]))
         loss.update(float(out["loss"]))
-        mse_loss.update(float(out["mse_loss"]))
+        if "ms_ssim_loss" in out:
+            ms_ssim_loss.update(float(out["ms_ssim_loss"]))
+        else:
+            mse_loss.update(float(out["mse_loss"]))
     model.train()
     if verbose:
-        print(f"Test epoch {epoch}: Average losses:\tLoss: {loss.avg:.3f} |\tMSE loss: {mse_loss.avg * 255 ** 2:.3f} |"
+        dist = (f"MS-SSIM loss: {ms_ssim_loss.avg:.4f}" if ms_ssim_loss.count
+                else f"MSE loss: {mse_loss.avg * 255 ** 2:.3f}")
+        print(f"Test epoch {epoch}: Average losses:\tLoss: {loss.avg:.3f} |\t{dist} |"
               f"\tBpp loss: {bpp_loss.avg:.2f} |\tAux loss: {aux_loss.avg:.2f}\n", flush=True)
     return loss.avg
 
@@ -121,6 +129,9 @@ def parse_args(argv):
     p.add_argument("-lr", "--learning-rate", default=1e-4, type=float, help="Learning rate (default: %(default)s)")
     p.add_argument("-n", "--num-workers", type=int, default=4, help="Dataloaders threads (default: %(default)s)")
     p.add_argument("--lambda", dest="lmbda", type=float, default=0.0067, help="Bit-rate distortion parameter (default: %(default)s)")
+    p.add_argument("--metric", type=str, default="mse", choices=list(METRICS),
+                   help="Distortion of the loss: mse = lmbda*255^2*mse + bpp, ms-ssim = lmbda*(1 - ms_ssim) + bpp "
+                        "(default: %(default)s)")
     p.add_argument("--batch-size", type=int, default=16, help="Batch size per GPU (default: %(default)s)")
     p.add_argument("--test-batch-size", type=int, default=16, help="Test batch size (default: %(default)s)")
     p.add_argument("--aux-learning-rate", default=1e-4, type=float, help="Auxiliary loss learning rate (default: %(default)s)")
@@ -193,9 +204,9 @@ def main(argv) -> int:
         last_epoch = int(ck["epoch"]) + 1
         net.load_state_dict(ck["state_dict"])
     trainer = Trainer(net, lr=args.learning_rate, aux_lr=args.aux_learning_rate, lmbda=args.lmbda,
-                      clip_max_norm=args.clip_max_norm, device=device, seed=int(args.seed or 0))
+                      clip_max_norm=args.clip_max_norm, device=device, seed=int(args.seed or 0), metric=args.metric)
     lr_scheduler = PlateauLR(trainer, factor=0.6, patience=6)
-    criterion = RateDistortionLoss(lmbda=args.lmbda)
+    criterion = RateDistortionLoss(lmbda=args.lmbda, metric=args.metric)
     if ck is not None and "optimizer" in ck and isinstance(ck["optimizer"], dict) and "m" in ck["optimizer"]:
         trainer.load_optimizer_state(ck["optimizer"], ck.get("aux_optimizer"))
         if "lr_scheduler" in ck:

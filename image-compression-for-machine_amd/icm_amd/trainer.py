@@ -151,7 +151,13 @@ class GradReducer:
 
 class Trainer:
     def __init__(self, model, lr: float = 1e-4, aux_lr: float = 1e-4, lmbda: float = 0.0067,
-                 clip_max_norm: float = 1.0, device="cuda:0", group=None, seed: int = 0):
+                 clip_max_norm: float = 1.0, device="cuda:0", group=None, seed: int = 0, metric: str = "mse"):
+        if metric not in ("mse", "ms-ssim"):
+            raise NotImplementedError(f"{metric} is not implemented!")
+        self.metric = metric
+        self.keep_loss_seed = False   # tests: keep (x_hat, dx_hat) of the last step in self.loss_seed
+        self.loss_seed = None
+        self._ms_ws = None   # ms-ssim: (input shape, workspace, per-plane values), allocated once per shape
         self.model = model.to(device).train()
         self.device = torch.device(device)
         self.flat = FlatParams(self.model, self.device)
@@ -169,7 +175,8 @@ class Trainer:
         self.gen.manual_seed(int(seed) + self.rank)
         self.step_no = 0
         self.names = [n for n, _ in self.flat.main] + [n for n, _ in self.flat.aux]
-        self.scal = torch.zeros(8, dtype=torch.float32, device=self.device)  # [0:5] rd loss, [5] sqnorm, [6] aux
+        # [0:5] rd loss, [5] sqnorm, [6] aux, [7] 1 - ms_ssim (metric="ms-ssim")
+        self.scal = torch.zeros(8, dtype=torch.float32, device=self.device)
         self.red_ws = torch.zeros(L.REDUCE_WS_FLOATS, dtype=torch.float32, device=self.device)  # fixed-order partial sums
         self.side = torch.cuda.Stream(device=self.device) if self.device.type == "cuda" else None
         self._side_ws = None
@@ -293,7 +300,8 @@ class Trainer:
     def step(self, x: torch.Tensor, noise: Optional[dict] = None, drops: Optional[dict] = None,
              _hyper: Optional[tuple] = None) -> torch.Tensor:
         """one training iteration on this rank's shard x [B,3,H,W]; returns the device tensor
-        [bpp, mse, loss, sumlog_y, sumlog_z, grad_sqnorm, aux_loss, -] (no host sync).
+        [bpp, mse, loss, sumlog_y, sumlog_z, grad_sqnorm, aux_loss, ms_ssim_loss] (no host sync; the last entry is
+        1 - ms_ssim with metric="ms-ssim" and 0 otherwise; loss is lmbda*255^2*mse + bpp or lmbda*(1 - ms_ssim) + bpp).
         _hyper (step_graphed only): device tensors holding Adam's step-dependent scalars for the two optimisers."""
         f, dev = self.flat, self.device
         st = L.stream()
@@ -338,11 +346,29 @@ class Trainer:
         else:
             x_hat, y_lik, z_lik = wacnn_forward(tape, P, x, nz, ny, bucket_marks=marks)
         # ---- R-D loss forward + seeds (train.py:53-76)
+        # metric="ms-ssim": the fused reduction runs with lmbda = 0, i.e. loss = bpp and dx_hat = 0, as the rate part
+        lm = self.lmbda if self.metric == "mse" else 0.0
         check(lib.icm_rd_loss_fwd(ptr(x), ptr(x_hat), x.numel(), ptr(y_lik), y_lik.numel(), ptr(z_lik), z_lik.numel(),
-                                  B * H * W, self.lmbda, ptr(self.scal), ptr(self.red_ws), st), "rd_loss_fwd")
+                                  B * H * W, lm, ptr(self.scal), ptr(self.red_ws), st), "rd_loss_fwd")
         dxh, dly, dlz = E.new(x_hat), E.new(y_lik), E.new(z_lik)
         check(lib.icm_rd_loss_bwd(ptr(x), ptr(x_hat), x.numel(), ptr(y_lik), y_lik.numel(), ptr(z_lik), z_lik.numel(),
-                                  B * H * W, self.lmbda, 1.0, ptr(dxh), ptr(dly), ptr(dlz), st), "rd_loss_bwd")
+                                  B * H * W, lm, 1.0, ptr(dxh), ptr(dly), ptr(dlz), st), "rd_loss_bwd")
+        if self.metric == "ms-ssim":
+            # loss += lmbda * (1 - ms_ssim(x_hat, x)) on the device; dx_hat = -lmbda * d ms_ssim / d x_hat overwrites
+            # the zero the rate part left there
+            if self._ms_ws is None or self._ms_ws[0] != tuple(x.shape):
+                from .ops import msssim_workspace
+                self._ms_ws = (tuple(x.shape), msssim_workspace(x),
+                               torch.empty(B * x.shape[1], dtype=torch.float32, device=dev))
+            _, mws, mpl = self._ms_ws
+            xc = x.contiguous()
+            # out = scal[6:8]: [7] keeps 1 - ms_ssim; [6] (the mean) is overwritten by the aux loss below
+            check(lib.icm_msssim_fwd(ptr(x_hat), ptr(xc), B, x.shape[1], H, W, 1.0, ptr(mpl), ptr(self.scal[6:8]),
+                                     self.lmbda, ptr(self.scal[2:3]), ptr(mws), mws.numel(), st), "msssim_fwd")
+            check(lib.icm_msssim_bwd(ptr(x_hat), ptr(xc), B, x.shape[1], H, W, 0, -self.lmbda, ptr(dxh), ptr(mws),
+                                     mws.numel(), st), "msssim_bwd")
+        if self.keep_loss_seed:
+            self.loss_seed = (x_hat.detach().clone(), dxh.clone())
         tape.bind_grad(x_hat, dxh, True)
         tape.bind_grad(y_lik, dly, True)
         tape.bind_grad(z_lik, dlz, True)

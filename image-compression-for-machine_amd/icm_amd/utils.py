@@ -4,7 +4,7 @@ from __future__ import annotations
 
 import math
 import time
-from typing import Dict, Tuple
+from typing import Dict, Optional, Sequence, Tuple
 
 import torch
 
@@ -58,10 +58,37 @@ def psnr(a: torch.Tensor, b: torch.Tensor) -> float:
     return -10.0 * math.log10(out[1].item())
 
 
+EVAL_METRICS = ("psnr", "ms-ssim")
+
+
+def ms_ssim(a: torch.Tensor, b: torch.Tensor) -> float:
+    """the "ms-ssim" entry the reference's evaluation loop has commented out (eval_model/__main__.py:135): mean MS-SSIM
+    of two [N,3,H,W] images in [0, 1]; sides of 160 pixels or fewer are a ValueError"""
+    from .ops import ms_ssim as _ms
+    with torch.no_grad():
+        return _ms(a.to(torch.float32).contiguous(), b.to(torch.float32).contiguous(), data_range=1.0).item()
+
+
+def _quality(x: torch.Tensor, x_hat: torch.Tensor, metrics: Optional[Sequence[str]]) -> Dict[str, float]:
+    """metrics=None: today's report ({"psnr"}); otherwise the listed ones, in EVAL_METRICS order"""
+    if metrics is None:
+        return {"psnr": psnr(x, x_hat)}
+    unknown = [m for m in metrics if m not in EVAL_METRICS]
+    if unknown:
+        raise ValueError(f"unknown metric(s) {unknown}; choose from {list(EVAL_METRICS)}")
+    out = {}
+    if "psnr" in metrics:
+        out["psnr"] = psnr(x, x_hat)
+    if "ms-ssim" in metrics:
+        out["ms-ssim"] = ms_ssim(x, x_hat)
+    return out
+
+
 @torch.no_grad()
-def inference(model, x: torch.Tensor, recon=None) -> Dict[str, float]:
+def inference(model, x: torch.Tensor, recon=None, metrics: Optional[Sequence[str]] = None) -> Dict[str, float]:
     """eval_model/__main__.py:96-139: actual bit-stream size and reconstruction quality of one image x [3,H,W] or
-    [1,3,H,W] in [0,1]; ``recon(x_hat)`` (optional) receives the cropped reconstruction (the reference saves it, :130)"""
+    [1,3,H,W] in [0,1]; ``recon(x_hat)`` (optional) receives the cropped reconstruction (the reference saves it, :130);
+    ``metrics`` (optional) lists the quality entries to report (EVAL_METRICS; default: "psnr" alone)"""
     if x.dim() == 3:
         x = x.unsqueeze(0)
     xp, pads = pad_to_multiple(x, 64)
@@ -77,11 +104,12 @@ def inference(model, x: torch.Tensor, recon=None) -> Dict[str, float]:
         recon(x_hat)
     num_pixels = x.size(0) * x.size(2) * x.size(3)
     bpp = sum(len(s[0]) for s in enc["strings"]) * 8.0 / num_pixels
-    return {"psnr": psnr(x, x_hat), "bpp": bpp, "encoding_time": t1 - t0, "decoding_time": t2 - t1}
+    return {**_quality(x, x_hat, metrics), "bpp": bpp, "encoding_time": t1 - t0, "decoding_time": t2 - t1}
 
 
 @torch.no_grad()
-def inference_entropy_estimation(model, x: torch.Tensor, recon=None) -> Dict[str, float]:
+def inference_entropy_estimation(model, x: torch.Tensor, recon=None,
+                                 metrics: Optional[Sequence[str]] = None) -> Dict[str, float]:
     """eval_model/__main__.py:143-225: forward pass with estimated rates (no entropy coder)"""
     if x.dim() == 3:
         x = x.unsqueeze(0)
@@ -95,4 +123,4 @@ def inference_entropy_estimation(model, x: torch.Tensor, recon=None) -> Dict[str
         recon(x_hat)
     num_pixels = x.size(0) * x.size(2) * x.size(3)
     bpp = sum((torch.log(l).sum() / (-math.log(2) * num_pixels)).item() for l in out["likelihoods"].values())
-    return {"psnr": psnr(x, x_hat), "bpp": bpp, "encoding_time": dt / 2.0, "decoding_time": dt / 2.0}
+    return {**_quality(x, x_hat, metrics), "bpp": bpp, "encoding_time": dt / 2.0, "decoding_time": dt / 2.0}

@@ -350,6 +350,26 @@ int icm_rd_loss_bwd(const float* x, const float* x_hat, int64_t n_img_elems, con
                     const float* lik_z, int64_t n_z, int64_t num_pixels, float lmbda, float gscale,
                     float* dx_hat, float* dlik_y, float* dlik_z, void* stream);
 
+/* ---- MS-SSIM (Wang, Simoncelli, Bovik 2003; the defaults of pytorch_msssim.ms_ssim, which the reference's evaluation
+ * CLI imports at compressai/utils/eval_model/__main__.py:32 and reports under the key "ms-ssim", :135) ------------
+ * x, y: contiguous [N,C,H,W] in [0, data_range]; 11-tap Gaussian window (sigma 1.5), valid filtering, five levels with
+ * weights {0.0448, 0.2856, 0.3001, 0.2363, 0.1333}, 2x2 average pooling (padding = size % 2) between levels,
+ * relu on every level value.  min(H, W) must exceed 160 (ICM_ERR_ARG otherwise, like the package's assert).
+ * ws: icm_msssim_workspace_floats(N, C, H, W) floats (0 = geometry refused); it holds the image pyramid, the
+ * per-workgroup partial sums (added in tile order: no float atomics, equal inputs give bit-identical results), the
+ * per-level upstream factors and the three coefficient maps per level the backward filters -- so icm_msssim_bwd must
+ * follow icm_msssim_fwd of the same inputs on the same ws, with no host read in between (graph-capture safe).
+ * fwd: ms[N*C] = prod_l v_l^w_l per plane; out[0] = mean(ms), out[1] = 1 - mean(ms);
+ *      loss_io != NULL: *loss_io += lmbda * (1 - mean(ms))   (the trainer's loss scalar, which holds bpp by then).
+ * bwd: dx = d(sum_p up[p] * ms[p]) / dx with up[p] = gscale * gplane[p], or gscale / (N*C) when gplane == NULL
+ *      (the gradient of gscale * mean(ms)); a plane with a non-positive level value gets an all-zero gradient.
+ *      Only x (the reconstruction) receives a gradient. */
+int64_t icm_msssim_workspace_floats(int N, int C, int H, int W);
+int icm_msssim_fwd(const float* x, const float* y, int N, int C, int H, int W, float data_range, float* ms, float* out,
+                   float lmbda, float* loss_io, float* ws, int64_t ws_floats, void* stream);
+int icm_msssim_bwd(const float* x, const float* y, int N, int C, int H, int W, const float* gplane, float gscale,
+                   float* dx, float* ws, int64_t ws_floats, void* stream);
+
 /* ---- optimiser (train.py:105-169,199-214) ---------------------------------------------------- */
 /* out[0] = sum g^2; ws: ICM_REDUCE_WS_FLOATS floats of scratch (fixed-order two-stage sum: every rank of a
  * data-parallel job derives the same clip coefficient from the same all-reduced gradient) */
