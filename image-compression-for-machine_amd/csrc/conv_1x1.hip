@@ -20,12 +20,7 @@ __global__ __launch_bounds__(256, 2) void conv1x1_kernel(const ConvDesc d) {
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
   const ConvPtrs P = d.g[blockIdx.y];
-  int bid;
-  {
-    const int nb = gridDim.x, hb = blockIdx.x;
-    const int xcd = hb & 7, q = hb >> 3;
-    bid = xcd * (nb >> 3) + min(xcd, nb & 7) + q;
-  }
+  int bid = xcd_block_id();
   const int cb = bid % d.ncb, ptile = bid / d.ncb;
   const int h = lane >> 5, l31 = lane & 31;
   const int HW = d.pg.H * d.pg.W;
@@ -162,31 +157,21 @@ int run_conv1x1(const icm_conv_args* arr, int ngroups, long long wp_off, int g_f
     }
   }
   {
-    static const int force = getenv("ICM_1X1_CFG") ? atoi(getenv("ICM_1X1_CFG")) : -1;   // measurement only
+    static const int force = env_int("ICM_1X1_CFG", -1);   // measurement only
     if (force >= 0 && force < (int)(sizeof(kCfgs1x1) / sizeof(kCfgs1x1[0]))) best = force;
   }
   const Cfg1x1& c = kCfgs1x1[best];
   const int ncb = cdiv(ncot, c.tco);
   const long long strips = (NP + 32 * c.tpx - 1) / (32 * c.tpx);
   // independent waves need >= one wave per SIMD to beat the split-K / co-resident tilings of the staged kernel
-  static const long long kMinWaves = getenv("ICM_1X1_MIN_WAVES") ? atoll(getenv("ICM_1X1_MIN_WAVES")) : 1024;
+  static const long long kMinWaves = env_ll("ICM_1X1_MIN_WAVES", 1024);
   // (short contractions pay less for a half-empty chip than the staged kernel pays for its barriers: 320 -> 160 at 16x16
   //  x 2 members, 640 waves: 24.9 us here against 29.7 us staged; 1 536 -> 384 on the same map is the other way round)
-  static const int kShortK = getenv("ICM_1X1_SHORT_K") ? atoi(getenv("ICM_1X1_SHORT_K")) : 384;
+  static const int kShortK = env_int("ICM_1X1_SHORT_K", 384);
   const long long need = a.Cin <= kShortK ? kMinWaves / 2 : kMinWaves;
   if (g_force_1x1 < 0 && strips * ncb * ngroups < need) return -1;
   ConvDesc d;
-  for (int gi = 0; gi < ICM_MAX_GROUPS; ++gi) {
-    const icm_conv_args& s = arr[gi < ngroups ? gi : 0];
-    d.g[gi].x = s.x;
-    d.g[gi].wp = s.wp + wp_off;
-    d.g[gi].bias = s.bias;
-    d.g[gi].y = s.y;
-    d.g[gi].res = s.res;
-    d.g[gi].aux = s.aux;
-    d.g[gi].aux2 = s.aux2;
-    d.g[gi].y2 = s.y2;
-  }
+  fill_conv_ptrs(d.g, arr, ngroups, wp_off);
   d.y_bs = a.y_bs; d.res_bs = a.res_bs; d.aux_bs = a.aux_bs; d.aux2_bs = a.aux2_bs; d.y2_bs = a.y2_bs;
   d.pg = PatchGeom{};
   d.pg.H = a.H; d.pg.W = a.W; d.pg.N = a.N; d.pg.C = a.Cin; d.pg.act = a.pro_act; d.pg.bs = a.x_bs;

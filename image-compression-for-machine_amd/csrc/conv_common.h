@@ -1,5 +1,9 @@
-// Shared by the convolution kernels (conv_igemm.hip, conv_1x1.hip): launch descriptor and the fused epilogues.
+// Shared by the convolution kernels (conv_igemm.hip, conv_1x1.hip, conv_ks8.hip, conv_wino.hip): launch descriptor
+// and THE definition of the fused-neighbour epilogue -- what each kind reads and writes (epi_reads_* / epi_writes_side
+// / epi_may_gelu), its per-element math (epi_apply, epi_materialise) and the kinds each kernel family is compiled for
+// (EpiAll / EpiKs8 / EpiWino: host eligibility test and device dispatch come from the same list).
 #pragma once
+#include <type_traits>
 #include "icm_common.h"
 
 namespace icm {
@@ -34,6 +38,79 @@ struct ConvDesc {
   int tapoff[ICM_MAX_TAPS];   // dword entries: read with s_load (a 16-bit entry forces a VMEM load + vmcnt(0))
 };
 
+// per-member pointers of a grouped launch; unused members repeat member 0 (every blockIdx.y finds valid pointers)
+inline void fill_conv_ptrs(ConvPtrs (&g)[ICM_MAX_GROUPS], const icm_conv_args* arr, int ngroups, long long wp_off) {
+  for (int gi = 0; gi < ICM_MAX_GROUPS; ++gi) {
+    const icm_conv_args& s = arr[gi < ngroups ? gi : 0];
+    g[gi] = ConvPtrs{s.x, s.wp + wp_off, s.bias, s.y, s.res, s.aux, s.aux2, s.y2};
+  }
+}
+
+// ---- the fused-neighbour epilogue (kinds: include/icm_hip.h): per output element
+//   v = acc + bias  ->  epi_apply<EPI>  ->  (+ old y if accum)  ->  epi_materialise (kinds with epi_may_gelu)  ->  y
+// Operands of a kind (host validation and the kernels' operand loads both ask these):
+constexpr bool epi_reads_res(int e) { return e == ICM_EPI_RES || e == ICM_EPI_RES_GELU || e == ICM_EPI_RES_MUL_DGELU; }
+constexpr bool epi_reads_aux(int e) {
+  return e == ICM_EPI_GDN || e == ICM_EPI_IGDN || e == ICM_EPI_MUL_DGELU || e == ICM_EPI_AXPY2 || e == ICM_EPI_LRP ||
+         e == ICM_EPI_RES_MUL_DGELU;
+}
+constexpr bool epi_reads_aux2(int e) { return e == ICM_EPI_AXPY2; }
+// y2 (when given) receives a side value of epi_apply: the GDN / IGDN norm before the root, the LRP tanh
+constexpr bool epi_writes_side(int e) { return e == ICM_EPI_GDN || e == ICM_EPI_IGDN || e == ICM_EPI_LRP; }
+// y2 (when given) receives gelu(y): the materialised activation for the consumers of this pre-activation (forward only)
+constexpr bool epi_may_gelu(int e) { return e == ICM_EPI_NONE || e == ICM_EPI_RES || e == ICM_EPI_RES_GELU; }
+
+// The math of a kind: v = accumulator + bias, rv = the res operand (AXPY2: the aux2 operand), av = the aux operand;
+// returns the value, `side` = what y2 receives for the kinds with epi_writes_side.  Operands a kind does not read are
+// ignored.  The callers keep their own load batching, accumulation order and store loops (their register budgets).
+template <int EPI>
+__device__ __forceinline__ float epi_apply(float v, float rv, float av, float& side) {
+  if constexpr (EPI == ICM_EPI_RES) v += rv;
+  if constexpr (EPI == ICM_EPI_RES_GELU) v += gelu_f(rv);
+  if constexpr (EPI == ICM_EPI_GDN || EPI == ICM_EPI_IGDN) {
+    side = v;
+    v = av * (EPI == ICM_EPI_GDN ? rsqrtf(v) : sqrtf(v));
+  }
+  if constexpr (EPI == ICM_EPI_MUL_DGELU) v *= dgelu_f(av);
+  if constexpr (EPI == ICM_EPI_RES_MUL_DGELU) v = (v + rv) * dgelu_f(av);
+  if constexpr (EPI == ICM_EPI_AXPY2) v = rv + 2.0f * av * v;
+  if constexpr (EPI == ICM_EPI_LRP) {
+    side = tanhf(v);
+    v = av + 0.5f * side;
+  }
+  return v;
+}
+// GELU materialisation of the value AFTER an accumulation (the launch that completes a partial sum materialises it);
+// y2 must be non-null.  v is what goes to y: with y2 == y (inference: nobody reads the pre-activation again) only
+// gelu(v) is stored, so v becomes it; otherwise y2[off] = gelu(v) and y keeps v.
+template <class Off>
+__device__ __forceinline__ void epi_materialise(float& v, const float* y, float* y2, Off off, bool ok) {
+  const float gv = gelu_f(v);
+  if (y2 == y) v = gv;
+  else if (ok) y2[off] = gv;
+}
+
+// The kinds a kernel family is compiled for, named once: has() is the host's eligibility test, dispatch() the device's
+// uniform branch -- f(std::integral_constant<int, K>{}) for the matching kind, the ICM_EPI_NONE instantiation for
+// anything else.  A kind outside the list costs no code object; a kind inside it is both accepted and instantiated.
+template <int... Kinds>
+struct EpiKinds {
+  static constexpr bool has(int epi) { return ((epi == Kinds) || ...); }
+  template <class F>
+  static __device__ __forceinline__ void dispatch(int epi, F&& f) {
+    static_assert(((Kinds == ICM_EPI_NONE) || ...), "ICM_EPI_NONE is the fallback of every kernel");
+    const bool hit = ((Kinds != ICM_EPI_NONE && epi == Kinds ? (f(std::integral_constant<int, Kinds>{}), true) : false) || ...);
+    if (!hit) f(std::integral_constant<int, ICM_EPI_NONE>{});
+  }
+};
+// LDS-staged (conv_igemm.hip) and direct 1x1 (conv_1x1.hip) kernels: every kind
+using EpiAll = EpiKinds<ICM_EPI_NONE, ICM_EPI_RES, ICM_EPI_RES_GELU, ICM_EPI_GDN, ICM_EPI_IGDN, ICM_EPI_MUL_DGELU,
+                        ICM_EPI_AXPY2, ICM_EPI_LRP, ICM_EPI_RES_MUL_DGELU>;
+// 8-wave K-split kernel (conv_ks8.hip): GDN / IGDN / AXPY2 belong to pointwise launches, which never take it
+using EpiKs8 = EpiKinds<ICM_EPI_NONE, ICM_EPI_RES, ICM_EPI_RES_GELU, ICM_EPI_MUL_DGELU, ICM_EPI_LRP, ICM_EPI_RES_MUL_DGELU>;
+// Winograd kernels (conv_wino.hip): the neighbours of the 3x3 stride-1 layers
+using EpiWino = EpiKinds<ICM_EPI_NONE, ICM_EPI_RES, ICM_EPI_RES_GELU, ICM_EPI_MUL_DGELU, ICM_EPI_RES_MUL_DGELU, ICM_EPI_LRP>;
+
 // Epilogue of one 32x32 accumulator tile.  The fused-neighbour kind is a template parameter so that the 16 rows
 // form ONE basic block: all operand loads (bias, residual, aux, old value) are issued back to back and waited for
 // once, instead of a load -> wait -> store chain per element.
@@ -41,13 +118,11 @@ template <int EPI, int half>
 __device__ __forceinline__ void store_half_e(const ConvDesc& d, const ConvPtrs& P, const f32x16 acc, int cot, int h,
                                              int n, int oy, int ox, bool pvalid) {
   const int plane = d.OHf * d.OWf;
-  constexpr bool kRes = EPI == ICM_EPI_RES || EPI == ICM_EPI_RES_GELU || EPI == ICM_EPI_RES_MUL_DGELU;
-  constexpr bool kAux = EPI == ICM_EPI_GDN || EPI == ICM_EPI_IGDN || EPI == ICM_EPI_MUL_DGELU ||
-                        EPI == ICM_EPI_AXPY2 || EPI == ICM_EPI_LRP || EPI == ICM_EPI_RES_MUL_DGELU;
+  constexpr bool kRes = epi_reads_res(EPI), kAux = epi_reads_aux(EPI), kAux2 = epi_reads_aux2(EPI);
   float* yb = P.y + n * d.y_bs;
   const float* resb = kRes ? P.res + n * d.res_bs : nullptr;
   const float* auxb = kAux ? P.aux + n * d.aux_bs : nullptr;
-  const float* aux2b = (EPI == ICM_EPI_AXPY2) ? P.aux2 + n * d.aux2_bs : nullptr;
+  const float* aux2b = kAux2 ? P.aux2 + n * d.aux2_bs : nullptr;
   float* y2b = P.y2 ? P.y2 + n * d.y2_bs : nullptr;
   const bool has_bias = P.bias != nullptr;
   // rows in two halves of 8: bounds the live registers of the load batch (the kernel's VGPR budget sets occupancy)
@@ -65,26 +140,15 @@ __device__ __forceinline__ void store_half_e(const ConvDesc& d, const ConvPtrs& 
       bv[q] = (has_bias && ok[q]) ? P.bias[co] : 0.0f;
       if constexpr (kRes) rv[q] = ok[q] ? resb[off[q]] : 0.0f;
       if constexpr (kAux) av[q] = ok[q] ? auxb[off[q]] : 0.0f;
-      if constexpr (EPI == ICM_EPI_AXPY2) rv[q] = ok[q] ? aux2b[off[q]] : 0.0f;
+      if constexpr (kAux2) rv[q] = ok[q] ? aux2b[off[q]] : 0.0f;
     }
     float v[8];
 #pragma unroll
     for (int q = 0; q < 8; ++q) {
-      v[q] = acc[half * 8 + q] + bv[q];
-      if constexpr (EPI == ICM_EPI_RES) v[q] += rv[q];
-      if constexpr (EPI == ICM_EPI_RES_GELU) v[q] += gelu_f(rv[q]);
-      if constexpr (EPI == ICM_EPI_GDN || EPI == ICM_EPI_IGDN) {
-        if (y2b && ok[q]) y2b[off[q]] = v[q];
-        v[q] = av[q] * (EPI == ICM_EPI_GDN ? rsqrtf(v[q]) : sqrtf(v[q]));
-      }
-      if constexpr (EPI == ICM_EPI_MUL_DGELU) v[q] *= dgelu_f(av[q]);
-      if constexpr (EPI == ICM_EPI_RES_MUL_DGELU) v[q] = (v[q] + rv[q]) * dgelu_f(av[q]);
-      if constexpr (EPI == ICM_EPI_AXPY2) v[q] = rv[q] + 2.0f * av[q] * v[q];
-      if constexpr (EPI == ICM_EPI_LRP) {
-        const float t = tanhf(v[q]);
-        if (y2b && ok[q]) y2b[off[q]] = t;
-        v[q] = av[q] + 0.5f * t;
-      }
+      float side;
+      v[q] = epi_apply<EPI>(acc[half * 8 + q] + bv[q], (kRes || kAux2) ? rv[q] : 0.0f, kAux ? av[q] : 0.0f, side);
+      if constexpr (epi_writes_side(EPI))
+        if (y2b && ok[q]) y2b[off[q]] = side;
     }
     if (d.accum) {   // accumulation (gradients; partial first-layer sums of the slice chains): one more batched read
       float old[8];
@@ -93,17 +157,10 @@ __device__ __forceinline__ void store_half_e(const ConvDesc& d, const ConvPtrs& 
 #pragma unroll
       for (int q = 0; q < 8; ++q) v[q] += old[q];
     }
-    if constexpr (EPI == ICM_EPI_NONE || EPI == ICM_EPI_RES || EPI == ICM_EPI_RES_GELU) {
-      // materialised activation for the consumers of this pre-activation (forward only): y2 = gelu(y), of the value
-      // AFTER an accumulation (the launch that completes a partial sum materialises it).  y2 == y (inference: nobody
-      // reads the pre-activation again): only gelu(y) is stored.
+    if constexpr (epi_may_gelu(EPI)) {
       if (y2b) {
 #pragma unroll
-        for (int q = 0; q < 8; ++q) {
-          const float gv = gelu_f(v[q]);
-          if (y2b == yb) v[q] = gv;
-          else if (ok[q]) y2b[off[q]] = gv;
-        }
+        for (int q = 0; q < 8; ++q) epi_materialise(v[q], yb, y2b, off[q], ok[q]);
       }
     }
 #pragma unroll
@@ -135,13 +192,11 @@ template <int EPI>
 __device__ __forceinline__ void epi_load(const ConvDesc& d, const ConvPtrs& P, int cot, int half, int h, int n, int oy,
                                          int ox, bool pvalid, EpiRegs& R) {
   const int plane = d.OHf * d.OWf;
-  constexpr bool kRes = EPI == ICM_EPI_RES || EPI == ICM_EPI_RES_GELU || EPI == ICM_EPI_RES_MUL_DGELU;
-  constexpr bool kAux = EPI == ICM_EPI_GDN || EPI == ICM_EPI_IGDN || EPI == ICM_EPI_MUL_DGELU ||
-                        EPI == ICM_EPI_AXPY2 || EPI == ICM_EPI_LRP || EPI == ICM_EPI_RES_MUL_DGELU;
+  constexpr bool kRes = epi_reads_res(EPI), kAux = epi_reads_aux(EPI), kAux2 = epi_reads_aux2(EPI);
   const float* yb = P.y + n * d.y_bs;
   const float* resb = kRes ? P.res + n * d.res_bs : nullptr;
   const float* auxb = kAux ? P.aux + n * d.aux_bs : nullptr;
-  const float* aux2b = (EPI == ICM_EPI_AXPY2) ? P.aux2 + n * d.aux2_bs : nullptr;
+  const float* aux2b = kAux2 ? P.aux2 + n * d.aux2_bs : nullptr;
   const bool has_bias = P.bias != nullptr;
   const bool tile_ok = pvalid && cot < d.ncot;
   R.n = n;
@@ -155,7 +210,7 @@ __device__ __forceinline__ void epi_load(const ConvDesc& d, const ConvPtrs& P, i
     R.bv[q] = (has_bias && R.ok[q]) ? P.bias[co] : 0.0f;
     if constexpr (kRes) R.rv[q] = R.ok[q] ? resb[R.off[q]] : 0.0f;
     if constexpr (kAux) R.av[q] = R.ok[q] ? auxb[R.off[q]] : 0.0f;
-    if constexpr (EPI == ICM_EPI_AXPY2) R.rv[q] = R.ok[q] ? aux2b[R.off[q]] : 0.0f;
+    if constexpr (kAux2) R.rv[q] = R.ok[q] ? aux2b[R.off[q]] : 0.0f;
   }
   if (d.accum) {   // gradient accumulation: one more batched read of the destination
 #pragma unroll
@@ -167,37 +222,23 @@ template <int EPI>
 __device__ __forceinline__ void epi_finish(const ConvDesc& d, const ConvPtrs& P, const float (&a8)[8], const EpiRegs& R) {
   float* yb = P.y + R.n * d.y_bs;
   float* y2b = P.y2 ? P.y2 + R.n * d.y2_bs : nullptr;
+  constexpr bool kRv = epi_reads_res(EPI) || epi_reads_aux2(EPI), kAux = epi_reads_aux(EPI);   // what epi_load filled
   float v[8];
 #pragma unroll
   for (int q = 0; q < 8; ++q) {
-    v[q] = a8[q] + R.bv[q];
-    if constexpr (EPI == ICM_EPI_RES) v[q] += R.rv[q];
-    if constexpr (EPI == ICM_EPI_RES_GELU) v[q] += gelu_f(R.rv[q]);
-    if constexpr (EPI == ICM_EPI_GDN || EPI == ICM_EPI_IGDN) {
-      if (y2b && R.ok[q]) y2b[R.off[q]] = v[q];
-      v[q] = R.av[q] * (EPI == ICM_EPI_GDN ? rsqrtf(v[q]) : sqrtf(v[q]));
-    }
-    if constexpr (EPI == ICM_EPI_MUL_DGELU) v[q] *= dgelu_f(R.av[q]);
-    if constexpr (EPI == ICM_EPI_RES_MUL_DGELU) v[q] = (v[q] + R.rv[q]) * dgelu_f(R.av[q]);
-    if constexpr (EPI == ICM_EPI_AXPY2) v[q] = R.rv[q] + 2.0f * R.av[q] * v[q];
-    if constexpr (EPI == ICM_EPI_LRP) {
-      const float t = tanhf(v[q]);
-      if (y2b && R.ok[q]) y2b[R.off[q]] = t;
-      v[q] = R.av[q] + 0.5f * t;
-    }
+    float side;
+    v[q] = epi_apply<EPI>(a8[q] + R.bv[q], kRv ? R.rv[q] : 0.0f, kAux ? R.av[q] : 0.0f, side);
+    if constexpr (epi_writes_side(EPI))
+      if (y2b && R.ok[q]) y2b[R.off[q]] = side;
   }
   if (d.accum) {
 #pragma unroll
     for (int q = 0; q < 8; ++q) v[q] += R.old[q];
   }
-  if constexpr (EPI == ICM_EPI_NONE || EPI == ICM_EPI_RES || EPI == ICM_EPI_RES_GELU) {
+  if constexpr (epi_may_gelu(EPI)) {
     if (y2b) {
 #pragma unroll
-      for (int q = 0; q < 8; ++q) {
-        const float gv = gelu_f(v[q]);
-        if (y2b == yb) v[q] = gv;   // y2 == y: only the activated value is stored (see store_half_e)
-        else if (R.ok[q]) y2b[R.off[q]] = gv;
-      }
+      for (int q = 0; q < 8; ++q) epi_materialise(v[q], yb, y2b, R.off[q], R.ok[q]);
     }
   }
 #pragma unroll
@@ -250,19 +291,10 @@ template <int TCO, int TPX, bool PIPE2 = false>
 __device__ __forceinline__ void epilogue_dispatch(const ConvDesc& d, const ConvPtrs& P, const f32x16 (&acc)[TCO][TPX],
                                                   int cot0, int h, const int (&pn)[TPX], const int (&poy)[TPX],
                                                   const int (&pox)[TPX], const bool (&pv)[TPX]) {
-  switch (d.epi) {
-    case ICM_EPI_RES: epilogue_tiles<ICM_EPI_RES, TCO, TPX, false>(d, P, acc, cot0, h, pn, poy, pox, pv); break;
-    case ICM_EPI_RES_GELU: epilogue_tiles<ICM_EPI_RES_GELU, TCO, TPX, false>(d, P, acc, cot0, h, pn, poy, pox, pv); break;
-    case ICM_EPI_GDN: epilogue_tiles<ICM_EPI_GDN, TCO, TPX, false>(d, P, acc, cot0, h, pn, poy, pox, pv); break;
-    case ICM_EPI_IGDN: epilogue_tiles<ICM_EPI_IGDN, TCO, TPX, false>(d, P, acc, cot0, h, pn, poy, pox, pv); break;
-    case ICM_EPI_MUL_DGELU: epilogue_tiles<ICM_EPI_MUL_DGELU, TCO, TPX, false>(d, P, acc, cot0, h, pn, poy, pox, pv); break;
-    case ICM_EPI_AXPY2: epilogue_tiles<ICM_EPI_AXPY2, TCO, TPX, PIPE2>(d, P, acc, cot0, h, pn, poy, pox, pv); break;
-    case ICM_EPI_LRP: epilogue_tiles<ICM_EPI_LRP, TCO, TPX, false>(d, P, acc, cot0, h, pn, poy, pox, pv); break;
-    case ICM_EPI_RES_MUL_DGELU:
-      epilogue_tiles<ICM_EPI_RES_MUL_DGELU, TCO, TPX, false>(d, P, acc, cot0, h, pn, poy, pox, pv);
-      break;
-    default: epilogue_tiles<ICM_EPI_NONE, TCO, TPX, false>(d, P, acc, cot0, h, pn, poy, pox, pv); break;
-  }
+  EpiAll::dispatch(d.epi, [&](auto kind) {
+    constexpr int EPI = decltype(kind)::value;
+    epilogue_tiles<EPI, TCO, TPX, EPI == ICM_EPI_AXPY2 && PIPE2>(d, P, acc, cot0, h, pn, poy, pox, pv);
+  });
 }
 
 // latency-bound problems (conv_ks8.hip): eight MFMA waves split K over one block of four tiles (tco = 2: 64 co x 64 px;

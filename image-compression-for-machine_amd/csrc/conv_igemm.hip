@@ -16,7 +16,7 @@
 //     stride-1 gather with its own tap subset -- no zero-stuffing, no atomics;
 //   * pointwise neighbours are fused: operand activation on the LDS staging path (virtual GELU,
 //     x^2 for GDN) and the epilogues listed in icm_hip.h (bias, residual, GDN rsqrt, GELU', LRP tanh,
-//     PixelShuffle store, gradient accumulation).
+//     PixelShuffle store, gradient accumulation), defined once for all conv kernels in conv_common.h.
 #include <cstdlib>
 #include <vector>
 #include "conv_common.h"
@@ -41,15 +41,9 @@ __global__ __launch_bounds__(512, (TCO * TPX <= 3) ? 4 : 2) void conv_igemm_kern
   const ConvPtrs P = d.g[blockIdx.y];
   const PatchGeom& pg = d.pg;
 
-  // XCD-aware tile order: workgroups are dealt round-robin to the 8 XCDs (each with its own L2), so hardware id b
-  // runs on XCD b % 8.  Give every XCD a CONTIGUOUS run of logical tiles: the co-blocks of one pixel tile and the
-  // vertically adjacent tiles (which share most of their halo rows) then meet in the same L2.
-  int bid;
-  {
-    const int nb = gridDim.x, hb = blockIdx.x;
-    const int xcd = hb & 7, q = hb >> 3;
-    bid = xcd * (nb >> 3) + min(xcd, nb & 7) + q;
-  }
+  // XCD-aware tile order: the co-blocks of one pixel tile and the vertically adjacent tiles (which share most of their
+  // halo rows) meet in the same L2
+  int bid = xcd_block_id();
   const int cb = bid % d.ncb;
   int pt = bid / d.ncb;
   const int tx_i = pt % d.tiles_x;
@@ -465,7 +459,7 @@ static const KernelCfg kCfgs[] = {
 };
 static int g_force_cfg = -1;
 
-static int g_force_1x1 = getenv("ICM_CONV_1X1") ? atoi(getenv("ICM_CONV_1X1")) : -1;   // -1 auto, 0 never, 1 whenever eligible
+static int g_force_1x1 = env_int("ICM_CONV_1X1", -1);   // -1 auto, 0 never, 1 whenever eligible
 
 struct Geometry {
   int lgTW, lgTH, lgTI, PH, PW, PWh, PWrow, PP, CS, tiles_x, tiles_y, tiles_n, ckm;
@@ -520,7 +514,7 @@ static int run_class(const icm_conv_args* arr, int ngroups, const ConvClass& cls
   // (tools/tune_conv.py; profiles/r01_tune_conv_v7.txt)
   static const double kEff[] = {0.75, 1.00, 0.80, 0.60, 1.10, 0.65, 0.80, 0.80, 0.75, 0.70, 0.70, 0.70, 0.65};
   static const int kOcc[] = {1, 1, 1, 2, 2, 1, 2, 2, 2, 2, 2, 2, 2};
-  static const double kCoResBoost = getenv("ICM_CONV_BOOST") ? atof(getenv("ICM_CONV_BOOST")) : 1.25;
+  static const double kCoResBoost = env_double("ICM_CONV_BOOST", 1.25);
   int best = -1, best1 = -1;
   double best_cost = 1e300, best1_cost = 1e300;
   Geometry bg{}, bg1{};
@@ -571,13 +565,11 @@ static int run_class(const icm_conv_args* arr, int ngroups, const ConvClass& cls
   // step (narrow outputs 64 -> 32: 17 -> 29 us, half-empty grids, second-round tails; same-box A/B).
   int ks8_tco = 0;
   {
-    static const int ks8_on = getenv("ICM_CONV_KS8") ? atoi(getenv("ICM_CONV_KS8")) : 1;
-    static const long long ks8_max = getenv("ICM_CONV_KS8_MAXWG") ? atoll(getenv("ICM_CONV_KS8_MAXWG")) : 256;
-    static const long long ks8_min = getenv("ICM_CONV_KS8_MINWG") ? atoll(getenv("ICM_CONV_KS8_MINWG")) : 160;
-    const bool epi_ok = a.epi == ICM_EPI_NONE || a.epi == ICM_EPI_RES || a.epi == ICM_EPI_RES_GELU ||
-                        a.epi == ICM_EPI_MUL_DGELU || a.epi == ICM_EPI_LRP || a.epi == ICM_EPI_RES_MUL_DGELU;
+    static const int ks8_on = env_int("ICM_CONV_KS8", 1);
+    static const long long ks8_max = env_ll("ICM_CONV_KS8_MAXWG", 256);
+    static const long long ks8_min = env_ll("ICM_CONV_KS8_MINWG", 160);
     if ((ks8_on && g_force_cfg < 0 || g_force_cfg == 100 || g_force_cfg == 101) && S_in == 1 && ntaps > 1 &&
-        a.pro_act == ICM_ACT_NONE && epi_ok && a.x_seg_len == 0) {
+        a.pro_act == ICM_ACT_NONE && EpiKs8::has(a.epi) && a.x_seg_len == 0) {
       const int tco = g_force_cfg == 101 ? 1 : (g_force_cfg == 100 ? 2 : (ncot >= 2 ? 2 : 1));
       const int bpx = tco == 2 ? 64 : 128;
       Geometry g = make_geometry(bpx, OHv, OWv, a.N, S_in, cls.ey, cls.ex, nchunks8, ntaps, 4);
@@ -597,17 +589,7 @@ static int run_class(const icm_conv_args* arr, int ngroups, const ConvClass& cls
   }
 
   ConvDesc d{};
-  for (int gi = 0; gi < ICM_MAX_GROUPS; ++gi) {
-    const icm_conv_args& s = arr[gi < ngroups ? gi : 0];
-    d.g[gi].x = s.x;
-    d.g[gi].wp = s.wp + wp_off;
-    d.g[gi].bias = s.bias;
-    d.g[gi].y = s.y;
-    d.g[gi].res = s.res;
-    d.g[gi].aux = s.aux;
-    d.g[gi].aux2 = s.aux2;
-    d.g[gi].y2 = s.y2;
-  }
+  fill_conv_ptrs(d.g, arr, ngroups, wp_off);
   d.y_bs = a.y_bs; d.res_bs = a.res_bs; d.aux_bs = a.aux_bs; d.aux2_bs = a.aux2_bs; d.y2_bs = a.y2_bs;
   PatchGeom& pg = d.pg;
   pg.PW = bg.PW; pg.PH = bg.PH; pg.PWrow = bg.PWrow; pg.PWh = bg.PWh; pg.PP = bg.PP; pg.CS = bg.CS; pg.S = S_in;
@@ -629,7 +611,7 @@ static int run_class(const icm_conv_args* arr, int ngroups, const ConvClass& cls
     pg.vec4 = v4 ? 1 : 0;
     // LDS-DMA staging: no activation to apply, linear patch layout (stride-1 input sampling: no column-parity split),
     // not the 16-byte halo-free path (4x the bytes per instruction)
-    static const int dma_on = getenv("ICM_CONV_DMA") ? atoi(getenv("ICM_CONV_DMA")) : 1;
+    static const int dma_on = env_int("ICM_CONV_DMA", 1);
     pg.dma = (dma_on && !v4 && S_in == 1 && a.pro_act == ICM_ACT_NONE && bg.PWrow == bg.PW && bg.PP == bg.PH * bg.PW) ? 1 : 0;
     pg.pipe = 0;
     set_v4_pack(pg);
@@ -675,11 +657,8 @@ static int validate(const icm_conv_args& a) {
     if (a.OH != (a.H + 2 * a.pad - a.KH) / a.stride + 1 || a.OW != (a.W + 2 * a.pad - a.KW) / a.stride + 1)
       return ICM_ERR_ARG;
   }
-  if ((a.epi == ICM_EPI_RES || a.epi == ICM_EPI_RES_GELU || a.epi == ICM_EPI_RES_MUL_DGELU) && !a.res) return ICM_ERR_ARG;
-  if ((a.epi == ICM_EPI_GDN || a.epi == ICM_EPI_IGDN || a.epi == ICM_EPI_MUL_DGELU || a.epi == ICM_EPI_LRP ||
-       a.epi == ICM_EPI_AXPY2 || a.epi == ICM_EPI_RES_MUL_DGELU) && !a.aux)
+  if ((epi_reads_res(a.epi) && !a.res) || (epi_reads_aux(a.epi) && !a.aux) || (epi_reads_aux2(a.epi) && !a.aux2))
     return ICM_ERR_ARG;
-  if (a.epi == ICM_EPI_AXPY2 && !a.aux2) return ICM_ERR_ARG;
   if (((long long)a.N * a.x_bs + 8LL * a.H * a.W) * 4 >= (1LL << 31)) return ICM_ERR_UNSUPPORTED;   // PlaneMap byte offsets are int32
   if (a.pixel_shuffle != 0 && a.pixel_shuffle != 2) return ICM_ERR_UNSUPPORTED;
   if (a.pixel_shuffle == 2 && (a.Cout % 4 != 0 || a.transposed)) return ICM_ERR_ARG;

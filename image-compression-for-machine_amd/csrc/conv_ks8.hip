@@ -29,12 +29,7 @@ __global__ __launch_bounds__(512, 2) void conv_ks8_kernel(const ConvDesc d) {
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const ConvPtrs P = d.g[blockIdx.y];
   const PatchGeom& pg = d.pg;
-  int bid;
-  {
-    const int nb = gridDim.x, hb = blockIdx.x;
-    const int xcd = hb & 7, q = hb >> 3;
-    bid = xcd * (nb >> 3) + min(xcd, nb & 7) + q;
-  }
+  int bid = xcd_block_id();
   const int cb = bid % d.ncb;
   int pt = bid / d.ncb;
   const int tx_i = pt % d.tiles_x;
@@ -177,14 +172,7 @@ __global__ __launch_bounds__(512, 2) void conv_ks8_kernel(const ConvDesc d) {
   const int n = n0 + ti, oyv = oy0 + ty, oxv = ox0 + tx;
   const bool pvalid = (n < pg.N) && (oyv < d.OHv) && (oxv < d.OWv) && cot < d.ncot;
   const int oy = oyv * d.out_sy + d.out_oy, ox = oxv * d.out_sx + d.out_ox;
-  switch (d.epi) {
-    case ICM_EPI_RES: ks8_store<ICM_EPI_RES>(d, P, v, cot, hf, h, n, oy, ox, pvalid); break;
-    case ICM_EPI_RES_GELU: ks8_store<ICM_EPI_RES_GELU>(d, P, v, cot, hf, h, n, oy, ox, pvalid); break;
-    case ICM_EPI_MUL_DGELU: ks8_store<ICM_EPI_MUL_DGELU>(d, P, v, cot, hf, h, n, oy, ox, pvalid); break;
-    case ICM_EPI_LRP: ks8_store<ICM_EPI_LRP>(d, P, v, cot, hf, h, n, oy, ox, pvalid); break;
-    case ICM_EPI_RES_MUL_DGELU: ks8_store<ICM_EPI_RES_MUL_DGELU>(d, P, v, cot, hf, h, n, oy, ox, pvalid); break;
-    default: ks8_store<ICM_EPI_NONE>(d, P, v, cot, hf, h, n, oy, ox, pvalid); break;
-  }
+  EpiKs8::dispatch(d.epi, [&](auto kind) { ks8_store<decltype(kind)::value>(d, P, v, cot, hf, h, n, oy, ox, pvalid); });
 }
 
 int launch_conv_ks8(const ConvDesc& d, int tco, long long nblk, int ngroups, size_t lds_bytes, hipStream_t stream) {

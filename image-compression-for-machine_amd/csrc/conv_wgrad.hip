@@ -181,11 +181,7 @@ __global__ __launch_bounds__(512, 2) void wgrad_t33_kernel(const WgDesc d) {
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const WgPtrs G = d.g[blockIdx.y];
   int bid = blockIdx.x;
-  if (d.xcd_order) {
-    const int nb = gridDim.x, hb = blockIdx.x;
-    const int xcd = hb & 7, q = hb >> 3;
-    bid = xcd * (nb >> 3) + min(xcd, nb & 7) + q;
-  }
+  if (d.xcd_order) bid = xcd_block_id();
   const int at = bid % d.natile; bid /= d.natile;
   const int bt = bid % d.nbtile; bid /= d.nbtile;
   const int tg = bid % d.ngroups;
@@ -323,11 +319,7 @@ __global__ __launch_bounds__(512, 2) void wgrad_tap9_kernel(const WgDesc d) {
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const WgPtrs G = d.g[blockIdx.y];
   int bid = blockIdx.x;
-  if (d.xcd_order) {
-    const int nb = gridDim.x, hb = blockIdx.x;
-    const int xcd = hb & 7, q = hb >> 3;
-    bid = xcd * (nb >> 3) + min(xcd, nb & 7) + q;
-  }
+  if (d.xcd_order) bid = xcd_block_id();
   const int at = bid % d.natile; bid /= d.natile;
   const int bt = bid % d.nbtile;
   const int split = bid / d.nbtile;
@@ -507,11 +499,7 @@ __global__ __launch_bounds__(512, 2) void wgrad_dma1_kernel(const WgDesc d) {
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const WgPtrs G = d.g[blockIdx.y];
   int bid = blockIdx.x;
-  if (d.xcd_order) {
-    const int nb = gridDim.x, hb = blockIdx.x;
-    const int xcd = hb & 7, q = hb >> 3;
-    bid = xcd * (nb >> 3) + min(xcd, nb & 7) + q;
-  }
+  if (d.xcd_order) bid = xcd_block_id();
   const int at = bid % d.natile; bid /= d.natile;
   const int bt = bid % d.nbtile;
   const int split = bid / d.nbtile;
@@ -689,15 +677,11 @@ __global__ __launch_bounds__(512, 2) void wgrad_kernel(const WgDesc d) {
   const bool loader = wave >= 4;
   const WgPtrs G = d.g[blockIdx.y];
 
-  // XCD-aware order (see conv_igemm.hip): hardware id b runs on XCD b % 8; every XCD gets a contiguous run of logical
+  // XCD-aware order (xcd_block_id): hardware id b runs on XCD b % 8; every XCD gets a contiguous run of logical
   // workgroups, so the (a-tile, b-tile, tap-group) workgroups of one pixel split read their pixels through one L2
   // (only for problems with many pixels: the 4 096-pixel slice-chain problems measured 3 % slower with it)
   int bid = blockIdx.x;
-  if (d.xcd_order) {
-    const int nb = gridDim.x, hb = blockIdx.x;
-    const int xcd = hb & 7, q = hb >> 3;
-    bid = xcd * (nb >> 3) + min(xcd, nb & 7) + q;
-  }
+  if (d.xcd_order) bid = xcd_block_id();
   const int at = bid % d.natile; bid /= d.natile;
   const int bt = bid % d.nbtile; bid /= d.nbtile;
   const int tg = bid % d.ngroups;
@@ -1062,7 +1046,7 @@ static int plan_wgrad(const icm_wgrad_args& a, WgPlan& p, int nproblems = 1) {
       // by padded area alone; among equal areas the four-way K split (96 x 192 / 192 x 96 blocks) measured best:
       // 192 -> 192 @128: <6,3> 75.8, <3,6> 73.4, <6,6> 68.3, <3,3> 63.9 TF against 58.7 for the loader-wave kernel
       // (profiles/r02_tune_wgrad_dma1.txt)
-      static const int dma1_on = getenv("ICM_WG_DMA1") ? atoi(getenv("ICM_WG_DMA1")) : 1;
+      static const int dma1_on = env_int("ICM_WG_DMA1", 1);
       if (ok && dma1_on && a.act_s == ICM_ACT_NONE && a.act_b == ICM_ACT_NONE && a.stride == 1 && a.pad == 0) {
         static const struct { int v, ta, tb; } dc[] = {{13, 6, 3}, {12, 3, 6}, {11, 6, 6}, {14, 3, 3}};
         double ba = 1e300;
@@ -1094,13 +1078,13 @@ static int plan_wgrad(const icm_wgrad_args& a, WgPlan& p, int nproblems = 1) {
       // single-staging kernel (96 -> 96 @ 64x64 x6: 92 TF against 65 for the tap-group kernel and 54 for <2,2,9>).  For
       // the 4 096-pixel slice-chain problems <2,2,9> (two workgroups per CU, 64 tiles per problem) stays ahead
       // (77 vs 71 TF at 480 -> 224 x10; profiles/r02_tune_wgrad_tap9.txt), as it does over the 64 x 64 tap9 form.
-      static const int tap9_on = getenv("ICM_WG_TAP9") ? atoi(getenv("ICM_WG_TAP9")) : 1;
+      static const int tap9_on = env_int("ICM_WG_TAP9", 1);
       const double p96 = (double)cdiv(a.Ca, 96) * 96 * cdiv(a.Cb, 96) * 96;
       ok = tap9_on && ntaps == 9 && p96 <= pad64 && (long long)a.N * a.OH * a.OW >= 16384 && variant(8);
       if (!ok) ok = (ntaps > 1 && pad96 * 1.1 < pad64 && variant(7)) || variant(1);
     }
     else {
-      static const int tap25_on = getenv("ICM_WG_TAP25") ? atoi(getenv("ICM_WG_TAP25")) : 1;
+      static const int tap25_on = env_int("ICM_WG_TAP25", 1);
       ok = tap25_on && ntaps == 25 && (long long)a.N * a.OH * a.OW >= 16384 && variant(10);
       if (ok && TI * p.PP > ICM_MAXJ * 64) ok = false;
       if (!ok) ok = variant(0);
@@ -1251,9 +1235,9 @@ static int wgrad_grouped(const icm_wgrad_args* arr, int n, hipStream_t stream) {
     d.gs_vec4 = g4 ? 1 : 0;
     // big-grid operand by LDS-DMA: no activation to apply and a halo patch (the halo-free 16-byte register path moves
     // 4x the bytes per instruction and is kept); wgrad patches are stored linearly (identity column map, PWrow = PW)
-    static const int dma_on = getenv("ICM_WG_DMA") ? atoi(getenv("ICM_WG_DMA")) : 1;
+    static const int dma_on = env_int("ICM_WG_DMA", 1);
     pg.dma = (dma_on && (a->act_b == ICM_ACT_NONE || dma_on > 1) && !v4) ? 1 : 0;   // ICM_WG_DMA=2: also with an activation (post-pass in LDS)
-    static const int pipe_on = getenv("ICM_WG_PIPE") ? atoi(getenv("ICM_WG_PIPE")) : 1;
+    static const int pipe_on = env_int("ICM_WG_PIPE", 1);
     pg.pipe = pipe_on;
   }
   d.Ca = a->Ca; d.OH = a->OH; d.OW = a->OW; d.act_s = a->act_s;
@@ -1277,7 +1261,7 @@ static int wgrad_grouped(const icm_wgrad_args* arr, int n, hipStream_t stream) {
   }
   const long long nblk = (long long)p.natile * p.nbtile * p.ngroups * p.nsplit;
   void (*fn)(const WgDesc) = nullptr;
-  static const bool dma1_v4_off = [] { const char* e = getenv("ICM_WG_DMA1_V4"); return e && atoi(e) == 0; }();   // measurement only
+  static const bool dma1_v4_off = env_int("ICM_WG_DMA1_V4", 1) == 0;   // measurement only
   bool v4dma = !dma1_v4_off && p.ws >= 11 && p.ws <= 14 && p.lgNPX == 6 && p.lgTW >= 2 && (a->OW % 4) == 0 &&
                (a->gs_bs % 4) == 0 && (a->gb_bs % 4) == 0;
   for (int i = 0; i < n && v4dma; ++i)

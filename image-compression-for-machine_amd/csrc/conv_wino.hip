@@ -20,10 +20,9 @@
 //     three units ahead;
 //   * epilogue: the column half of A^T M A happens in registers (each wave holds a whole row), the row half through
 //     LDS; every wave then finishes a quarter of the (channel, tile) elements: 2x2 pixels per lane with the fused
-//     neighbours of conv_common.h (bias, residual, GELU materialisation, GELU', LRP tanh, accumulation).
+//     neighbours (the epilogue definition of conv_common.h; the kinds compiled here are its EpiWino list).
 #include <cmath>
 #include <cstdlib>
-#include <type_traits>
 #include "conv_common.h"
 
 namespace icm {
@@ -47,26 +46,17 @@ struct WinoDesc {
 
 template <int EPI>
 __device__ __forceinline__ void wino_finish(const WinoDesc& d, const ConvPtrs& P, float v, int co, long long off, bool ok) {
-  // one output element: bias / fused neighbour / accumulate / materialise / store (conv_common.h semantics)
+  // one output element, scalar form of the epilogue of conv_common.h (epi_apply / epi_materialise): operands are loaded
+  // where they are used, the accumulation read follows the math
   if (!ok) return;
   if (P.bias) v += P.bias[co];
-  if constexpr (EPI == ICM_EPI_RES) v += P.res[off];
-  if constexpr (EPI == ICM_EPI_RES_GELU) v += gelu_f(P.res[off]);
-  if constexpr (EPI == ICM_EPI_MUL_DGELU) v *= dgelu_f(P.aux[off]);
-  if constexpr (EPI == ICM_EPI_RES_MUL_DGELU) v = (v + P.res[off]) * dgelu_f(P.aux[off]);
-  if constexpr (EPI == ICM_EPI_LRP) {
-    const float t = tanhf(v);
-    if (P.y2) P.y2[off] = t;
-    v = P.aux[off] + 0.5f * t;
-  }
+  float side;
+  v = epi_apply<EPI>(v, epi_reads_res(EPI) ? P.res[off] : 0.0f, epi_reads_aux(EPI) ? P.aux[off] : 0.0f, side);
+  if constexpr (epi_writes_side(EPI))
+    if (P.y2) P.y2[off] = side;
   if (d.accum) v += P.y[off];
-  if constexpr (EPI == ICM_EPI_NONE || EPI == ICM_EPI_RES || EPI == ICM_EPI_RES_GELU) {
-    if (P.y2) {
-      const float gv = gelu_f(v);
-      if (P.y2 == P.y) v = gv;   // y2 == y: only the activated value is stored (conv_common.h)
-      else P.y2[off] = gv;
-    }
-  }
+  if constexpr (epi_may_gelu(EPI))
+    if (P.y2) epi_materialise(v, P.y, P.y2, off, true);
   P.y[off] = v;
 }
 
@@ -76,12 +66,7 @@ __global__ __launch_bounds__(512, 2) void conv_wino_kernel(const WinoDesc d) {
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   ConvPtrs P = d.g[blockIdx.y];
-  int bid;
-  {
-    const int nb = gridDim.x, hb = blockIdx.x;
-    const int xcd = hb & 7, q = hb >> 3;
-    bid = xcd * (nb >> 3) + min(xcd, nb & 7) + q;
-  }
+  int bid = xcd_block_id();
   // Which operand should stay in the XCD's L2?  Consecutive logical blocks run together on one XCD.  Small weights
   // (chain layers: 2.5 MB): co-blocks fastest -- the co-blocks of a pixel block share its activations.  Wide first-layer
   // launches (87 MB of Winograd weights against 5 MB of activations): pixel blocks fastest, so each XCD streams only
@@ -307,14 +292,7 @@ __global__ __launch_bounds__(512, 2) void conv_wino_kernel(const WinoDesc d) {
     }
   };
   if (d.dbg & 4) return;
-  switch (d.epi) {
-    case ICM_EPI_RES: finish_all(std::integral_constant<int, ICM_EPI_RES>{}); break;
-    case ICM_EPI_RES_GELU: finish_all(std::integral_constant<int, ICM_EPI_RES_GELU>{}); break;
-    case ICM_EPI_MUL_DGELU: finish_all(std::integral_constant<int, ICM_EPI_MUL_DGELU>{}); break;
-    case ICM_EPI_RES_MUL_DGELU: finish_all(std::integral_constant<int, ICM_EPI_RES_MUL_DGELU>{}); break;
-    case ICM_EPI_LRP: finish_all(std::integral_constant<int, ICM_EPI_LRP>{}); break;
-    default: finish_all(std::integral_constant<int, ICM_EPI_NONE>{}); break;
-  }
+  EpiWino::dispatch(d.epi, finish_all);
 }
 
 
@@ -332,12 +310,7 @@ __global__ __launch_bounds__(512, 2) void conv_wino8_kernel(const WinoDesc d) {
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   ConvPtrs P = d.g[blockIdx.y];
-  int bid;
-  {
-    const int nb = gridDim.x, hb = blockIdx.x;
-    const int xcd = hb & 7, q = hb >> 3;
-    bid = xcd * (nb >> 3) + min(xcd, nb & 7) + q;
-  }
+  int bid = xcd_block_id();
   const int cb = d.px_fast ? bid / d.npx : bid % d.ncb;
   int pt = d.px_fast ? bid % d.npx : bid / d.ncb;
   const int pblk = pt;
@@ -476,14 +449,7 @@ __global__ __launch_bounds__(512, 2) void conv_wino8_kernel(const WinoDesc d) {
         }
       }
     };
-    switch (d.epi) {
-      case ICM_EPI_RES: finish_all(std::integral_constant<int, ICM_EPI_RES>{}); break;
-      case ICM_EPI_RES_GELU: finish_all(std::integral_constant<int, ICM_EPI_RES_GELU>{}); break;
-      case ICM_EPI_MUL_DGELU: finish_all(std::integral_constant<int, ICM_EPI_MUL_DGELU>{}); break;
-      case ICM_EPI_RES_MUL_DGELU: finish_all(std::integral_constant<int, ICM_EPI_RES_MUL_DGELU>{}); break;
-      case ICM_EPI_LRP: finish_all(std::integral_constant<int, ICM_EPI_LRP>{}); break;
-      default: finish_all(std::integral_constant<int, ICM_EPI_NONE>{}); break;
-    }
+    EpiWino::dispatch(d.epi, finish_all);
   }
 }
 
@@ -612,7 +578,7 @@ int run_wino_transform(const icm_conv_args* arr, int ngroups, hipStream_t stream
   d.dseg = make_fastdiv((uint32_t)std::max(1, a.x_seg_len));
   const long long nblk = (long long)g.tiles_x * g.tiles_y * g.tiles_n * d.nchunks;
   if (nblk <= 0 || nblk > 0x7fffffffLL) return ICM_ERR_ARG;
-  static const bool novec = [] { const char* e = getenv("ICM_WINO_XF_NOVEC"); return e && atoi(e) != 0; }();   // measurement only
+  static const bool novec = env_int("ICM_WINO_XF_NOVEC", 0) != 0;   // measurement only
   if (!novec && a.W % 2 == 0 && a.W >= 4)
     hipLaunchKernelGGL(wino_input_transform_kernel<true>, dim3((unsigned)nblk, ngroups), dim3(256), 0, stream, d);
   else
@@ -624,11 +590,7 @@ int run_wino_transform(const icm_conv_args* arr, int ngroups, hipStream_t stream
 bool wino_supported(const icm_conv_args& a) {
   if (a.KH != 3 || a.KW != 3 || a.stride != 1 || a.pad != 1 || a.pixel_shuffle) return false;
   if (a.OH != a.H || a.OW != a.W) return false;
-  switch (a.epi) {
-    case ICM_EPI_NONE: case ICM_EPI_RES: case ICM_EPI_RES_GELU: case ICM_EPI_MUL_DGELU: case ICM_EPI_RES_MUL_DGELU:
-    case ICM_EPI_LRP: break;
-    default: return false;
-  }
+  if (!EpiWino::has(a.epi)) return false;
   if (a.pro_act != ICM_ACT_NONE && a.pro_act != ICM_ACT_GELU && a.pro_act != ICM_ACT_SQUARE) return false;
   return true;
 }
@@ -637,11 +599,7 @@ int run_conv_wino(const icm_conv_args* arr, int ngroups, hipStream_t stream) {
   const icm_conv_args& a = arr[0];
   if (!wino_supported(a)) return ICM_ERR_UNSUPPORTED;
   WinoDesc d{};
-  for (int gi = 0; gi < ICM_MAX_GROUPS; ++gi) {
-    const icm_conv_args& s = arr[gi < ngroups ? gi : 0];
-    d.g[gi].x = s.x; d.g[gi].wp = s.wp; d.g[gi].bias = s.bias; d.g[gi].y = s.y;
-    d.g[gi].res = s.res; d.g[gi].aux = s.aux; d.g[gi].aux2 = nullptr; d.g[gi].y2 = s.y2;
-  }
+  fill_conv_ptrs(d.g, arr, ngroups, 0);
   d.x_bs = a.x_bs; d.y_bs = a.y_bs; d.res_bs = a.res_bs; d.aux_bs = a.aux_bs; d.y2_bs = a.y2_bs;
   d.N = a.N; d.Cin = a.Cin; d.Cout = a.Cout; d.H = a.H; d.W = a.W;
   {
@@ -662,7 +620,7 @@ int run_conv_wino(const icm_conv_args* arr, int ngroups, hipStream_t stream) {
   d.dseg = make_fastdiv((uint32_t)std::max(1, a.x_seg_len));
   const long long pblocks = (long long)d.tiles_x * d.tiles_y * d.tiles_n;
   // co tiles per workgroup: 2 halves the activation staging per output; 1 gives twice the workgroups (small launches)
-  static const int force_tco = getenv("ICM_WINO_TCO") ? atoi(getenv("ICM_WINO_TCO")) : 0;
+  static const int force_tco = env_int("ICM_WINO_TCO", 0);
   int tco = 2;
   {
     const long long b2 = pblocks * cdiv(d.ncot, 2) * ngroups, b1 = pblocks * d.ncot * ngroups;
@@ -672,7 +630,7 @@ int run_conv_wino(const icm_conv_args* arr, int ngroups, hipStream_t stream) {
     (void)b1;
   }
   // pre-transformed operand: the eight-MFMA-wave kernel, TCO in {2, 3, 4}: whole rounds of the chip, then wide co blocks
-  static const int w8_on = getenv("ICM_WINO8") ? atoi(getenv("ICM_WINO8")) : 1;
+  static const int w8_on = env_int("ICM_WINO8", 1);
   bool w8 = d.vpre && w8_on;
   if (w8) {
     int t8 = 2;
@@ -685,17 +643,17 @@ int run_conv_wino(const icm_conv_args* arr, int ngroups, hipStream_t stream) {
     if (force_tco >= 2 && force_tco <= 4) t8 = force_tco;
     // launches that cannot give the wide workgroups a (nearly) full round of the chip keep the 4 + 4 kernel with its
     // narrower co blocks (measured: 224 -> 176 single 46.6 vs 54.4 us, 176 -> 128 x2 41.9 vs 49.9 us, 3360 -> 160 607 vs 746 us)
-    static const long long w8_min = getenv("ICM_WINO8_MINWG") ? atoll(getenv("ICM_WINO8_MINWG")) : 150;
+    static const long long w8_min = env_ll("ICM_WINO8_MINWG", 150);
     if (pblocks * cdiv(d.ncot, t8) * ngroups >= w8_min || force_tco >= 2) tco = t8;
     else w8 = false;
   }
   d.ncb = cdiv(d.ncot, tco);
   d.npx = (int)pblocks;
-  static const int dbg = getenv("ICM_WINO_DEBUG") ? atoi(getenv("ICM_WINO_DEBUG")) : 0;
+  static const int dbg = env_int("ICM_WINO_DEBUG", 0);
   d.dbg = dbg;
   {
     const double wbytes = 64.0 * a.Cin * a.Cout, abytes = 4.0 * a.Cin * a.N * a.H * a.W;
-    static const int force_order = getenv("ICM_WINO_PXFAST") ? atoi(getenv("ICM_WINO_PXFAST")) : -1;
+    static const int force_order = env_int("ICM_WINO_PXFAST", -1);
     d.px_fast = (wbytes > 3.0e6 && wbytes > abytes) ? 1 : 0;
     if (force_order == 0 || force_order == 1) d.px_fast = force_order;
   }

@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <cstdlib>
 #include "../../include/icm_hip.h"
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
@@ -18,6 +19,31 @@ namespace icm {
 // Kernels that may use more than the default 64 KB of dynamic LDS get the attribute raised ONCE (first launch of
 // that kernel in the process), not on every launch.  Thread-safe; returns false if the runtime refuses.
 bool ensure_max_lds(const void* fn);
+
+// ICM_* environment switches (A/B and measurement knobs): unset means the default.  The call sites read them once
+// (static const).
+inline int env_int(const char* name, int def) {
+  const char* e = getenv(name);
+  return e ? atoi(e) : def;
+}
+inline long long env_ll(const char* name, long long def) {
+  const char* e = getenv(name);
+  return e ? atoll(e) : def;
+}
+inline double env_double(const char* name, double def) {
+  const char* e = getenv(name);
+  return e ? atof(e) : def;
+}
+
+// XCD-aware workgroup order: workgroups are dealt round-robin to the 8 XCDs (each with its own L2), so hardware id b
+// runs on XCD b % 8.  Give every XCD a CONTIGUOUS run of logical ids: neighbours in the logical order (the co-blocks
+// of one pixel tile, vertically adjacent tiles sharing halo rows, horizontally adjacent attention windows sharing
+// 128-B lines) then meet in the same L2.  Returns the logical id of this workgroup along grid x.
+__device__ __forceinline__ int xcd_block_id() {
+  const int nb = gridDim.x, hb = blockIdx.x;
+  const int xcd = hb & 7, q = hb >> 3;
+  return xcd * (nb >> 3) + min(xcd, nb & 7) + q;
+}
 
 // erf, branch-free.  libm's erff takes one of two polynomial paths behind a per-lane branch; inside the loaders (one wave
 // activating a batch of staged values) that control flow serialises the elements into ~40-instruction dependent

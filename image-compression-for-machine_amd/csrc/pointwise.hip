@@ -875,7 +875,7 @@ int icm_layernorm_bwd(const float* x, int64_t x_bs, const float* dy, int64_t dy_
     long long nblk = std::min<long long>(tiles, 256 * 16);
     // parameter gradients ride on the same pass when the workspace holds one partial row per workgroup
     float* pws = nullptr;
-    static const bool nofuse = [] { const char* e = getenv("ICM_LN_NOFUSE"); return e && atoi(e) != 0; }();   // measurement only
+    static const bool nofuse = env_int("ICM_LN_NOFUSE", 0) != 0;   // measurement only
     if (!nofuse && cached && C <= 192 && dgamma && dbeta && ws && ws_floats >= 2LL * 64 * C) {
       nblk = std::min<long long>(std::min<long long>(nblk, 1024), ws_floats / (2LL * C));
       pws = ws;

@@ -347,7 +347,7 @@ int launch_wgrad_wino(const icm_wgrad_args* arr, int n, int nsplit, int nchunks,
   const long long nblk = (long long)d.natile * d.nbtile * nsplit;
   if (nblk <= 0 || nblk > 0x7fffffffLL) return ICM_ERR_ARG;
   const size_t lds = (size_t)2 * WW_BUF * sizeof(float);
-  static const bool novec = [] { const char* e = getenv("ICM_WW_NOVEC"); return e && atoi(e) != 0; }();   // measurement only
+  static const bool novec = env_int("ICM_WW_NOVEC", 0) != 0;   // measurement only
   auto fn = (!novec && a.W % 2 == 0 && a.W >= 4) ? wgrad_wino_kernel<true> : wgrad_wino_kernel<false>;
   if (!ensure_max_lds(reinterpret_cast<const void*>(fn))) return ICM_ERR_LAUNCH;
   hipLaunchKernelGGL(fn, dim3((unsigned)nblk, n), dim3(512), lds, stream, d);

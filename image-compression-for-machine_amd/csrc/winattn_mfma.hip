@@ -204,12 +204,7 @@ __global__ __launch_bounds__(256, 2) void winattn_mfma_fwd_kernel(const WmDesc d
   float* Kt = Qt + LDS::kSlab;
   float* Vt = Kt + LDS::kSlab;
   float* bias = Vt + LDS::kSlab;
-  int bid;
-  {   // XCD-aware window order (see winattn.hip)
-    const int nb = gridDim.x, hb = blockIdx.x;
-    const int xcd = hb & 7, q = hb >> 3;
-    bid = xcd * (nb >> 3) + min(xcd, nb & 7) + q;
-  }
+  int bid = xcd_block_id();
   const int wx = bid % d.nwx; bid /= d.nwx;
   const int wy = bid % d.nwy;
   const int n = bid / d.nwy;
@@ -265,12 +260,7 @@ __global__ __launch_bounds__(256, 1) void winattn_mfma_bwd_kernel(const WmDesc d
   float* stat_m = dbias + 228;          // per query: max, 1 / sum, delta = sum_j P dP
   float* stat_l = stat_m + WM_T;
   float* stat_d = stat_l + WM_T;
-  int bid;
-  {
-    const int nb = gridDim.x, hb = blockIdx.x;
-    const int xcd = hb & 7, q = hb >> 3;
-    bid = xcd * (nb >> 3) + min(xcd, nb & 7) + q;
-  }
+  int bid = xcd_block_id();
   const int win = bid;
   const int wx = bid % d.nwx; bid /= d.nwx;
   const int wy = bid % d.nwy;
