@@ -14,6 +14,7 @@ Conventions
 from __future__ import annotations
 
 import ctypes as C
+import os as _os
 from typing import Callable, Dict, List, Optional, Sequence, Tuple
 
 import torch
@@ -23,7 +24,6 @@ from ._lib import (ACT_GELU, ACT_NONE, ACT_SQUARE, EPI_AXPY2, EPI_GDN, EPI_IGDN,
                    EPI_RES, EPI_RES_GELU, EPI_RES_MUL_DGELU, bs, check, ptr)
 
 PEDESTAL = 2.0 ** -36
-import os as _os
 _SKIP_WGRAD = _os.environ.get("ICM_DEBUG_SKIP_WGRAD", "0") == "1"
 PAIR_GATE_BRANCHES = _os.environ.get("ICM_PAIR_GATE_BRANCHES", "1") == "1"
 
@@ -55,7 +55,6 @@ WINO_PRE = _os.environ.get("ICM_WINO_PRE", "1") != "0"
 # (until the gathers of the Winograd weight-gradient kernel were vectorised and interleaved with its multiplies, problems
 # with many pixels kept the direct nine-tap kernel: 96 -> 96 @64x64 x6 was 716 us direct, 832 us Winograd; now 595 us)
 _WINO_WG_MAX_PIXELS = int(_os.environ.get("ICM_WINO_WG_MAX_PIXELS", "100000"))
-_WINO_EPIS = (EPI_NONE, EPI_RES, EPI_RES_GELU, EPI_MUL_DGELU, EPI_RES_MUL_DGELU, EPI_LRP)
 
 
 # the weight-gradient kernel has its own depth threshold (its contraction runs over the tiles, not the channels)
@@ -140,13 +139,31 @@ _MATERIALIZE = _os.environ.get("ICM_MATERIALIZE", "1") != "0"
 _MAT_MIN_PIXELS = int(_os.environ.get("ICM_MAT_MIN_PIXELS", "2048"))
 
 
+def _operands(tape, vts: Sequence["VT"]):
+    """(tensors, activation) ONE launch should read for the virtual tensors vts.  A launch has one activation flag: the
+    materialised tensors are read only if every member has one, otherwise every member reads its stored tensor with
+    the virtual activation."""
+    act = vts[0].act
+    if act == ACT_GELU and _MATERIALIZE:
+        ms = [tape.mat.get(_key(v.t)) for v in vts]
+        for m, v in zip(ms, vts):     # (plain loops: this runs once or twice per layer of a launch-bound step)
+            if m is None:
+                break
+        else:
+            return ms, ACT_NONE
+        for m, v in zip(ms, vts):
+            if m is v.t:
+                # unreachable today: in-place materialisation needs an inference tape and act_out, and then every
+                # member of every launch is materialised alike.  The virtual GELU would activate this member twice.
+                raise RuntimeError("a member stored activated in place shares a launch with one that has no "
+                                   "materialised activation (no caller builds such a group today)")
+    return [v.t for v in vts], act
+
+
 def _operand(tape, xv: "VT"):
-    """(tensor, activation) a kernel should read for the virtual tensor xv"""
-    if xv.act == ACT_GELU and _MATERIALIZE:
-        m = tape.mat.get(_key(xv.t))
-        if m is not None:
-            return m, ACT_NONE
-    return xv.t, xv.act
+    """(tensor, activation) a kernel should read for the virtual tensor xv: the one-member case of _operands"""
+    ts, act = _operands(tape, (xv,))
+    return ts[0], act
 
 
 class Tape:
@@ -365,7 +382,8 @@ class Tape:
 # ------------------------------------------------------------------------------------------------ raw launches
 
 def _wino_pretransform(tape, arr, xs):
-    """fill arr[i].xv: B^T d B of every distinct input tensor of a Winograd launch, computed by ONE transform launch"""
+    """fill arr[i].xv: B^T d B of every distinct input tensor of a Winograd launch, computed by ONE transform launch.
+    (The transform buffers are allocated and consumed on the tape's stream, so they need not outlive this call.)"""
     lib = L.lib()
     nfl = lib.icm_wino_transform_floats(C.byref(arr[0]))
     if nfl <= 0:
@@ -381,58 +399,108 @@ def _wino_pretransform(tape, arr, xs):
         part = firsts[j0:j0 + MAX_GROUP]
         tarr = (L.ConvArgs * len(part))(*[arr[i] for i in part])
         check(lib.icm_wino_transform(tarr, len(part), tape.st), "wino_transform")
-    return bufs
 
-def conv_launch(tape, x, wp, bias, y, *, Cin, Cout, KH, KW, stride, pad, transposed, OH, OW, pro_act=ACT_NONE,
-                epi=EPI_NONE, res=None, aux=None, aux2=None, y2=None, accum=0, ps=0, tag="fwd", seg=None, algo=0):
-    """seg = (run length, gap): blocked input-channel map (icm_conv_args.x_seg_len / x_seg_gap)"""
-    a = L.ConvArgs()
-    N, _, H, W = x.shape
+
+def _conv_launch(tape, single, xs, wps, biases, ys, *, Cin, Cout, KH, KW, stride, pad, transposed, OH, OW,
+                 pro_act=ACT_NONE, epi=EPI_NONE, auxs=None, y2s=None, ress=None, aux2s=None, accum=0, ps=0, tag="fwd",
+                 seg=None, algo=0):
+    """ONE launch over the members (xs[i], wps[i], ...) of one shared geometry; None = no such operand in any member.
+    seg = (run length, gap): blocked input-channel map (icm_conv_args.x_seg_len / x_seg_gap).
+    single: the member goes through icm_conv_run instead of icm_conv_run_grouped (the device does the same for both:
+    the host tests count the two entry points separately)."""
+    n = len(xs)
+    arr = (L.ConvArgs * n)()
     e0 = _prof_begin()
-    a.x, a.x_bs, a.N, a.Cin, a.H, a.W = ptr(x), bs(x), N, Cin, H, W
-    a.wp, a.bias = ptr(wp), ptr(bias)
-    a.y, a.y_bs, a.Cout, a.OH, a.OW = ptr(y), bs(y), Cout, OH, OW
-    a.KH, a.KW, a.stride, a.pad = KH, KW, stride, pad
-    a.transposed, a.pro_act, a.epi = int(transposed), pro_act, epi
-    a.res, a.res_bs = ptr(res), bs(res)
-    a.aux, a.aux_bs = ptr(aux), bs(aux)
-    a.aux2, a.aux2_bs = ptr(aux2), bs(aux2)
-    a.y2, a.y2_bs = ptr(y2), bs(y2)
-    a.accum, a.pixel_shuffle = accum, ps
-    if seg is not None:
-        a.x_seg_len, a.x_seg_gap = seg
-    a.algo = algo
-    keep = None
+    transposed = int(transposed)
+    for i, a in enumerate(arr):
+        x, y = xs[i], ys[i]
+        N, _, H, W = x.shape
+        a.x, a.x_bs, a.N, a.Cin, a.H, a.W = ptr(x), bs(x), N, Cin, H, W
+        a.wp, a.y, a.y_bs, a.Cout, a.OH, a.OW = ptr(wps[i]), ptr(y), bs(y), Cout, OH, OW
+        a.KH, a.KW, a.stride, a.pad = KH, KW, stride, pad
+        a.transposed, a.pro_act, a.epi = transposed, pro_act, epi
+        a.accum, a.pixel_shuffle, a.algo = accum, ps, algo
+        if biases is not None:
+            a.bias = ptr(biases[i])
+        if ress is not None:
+            a.res, a.res_bs = ptr(ress[i]), bs(ress[i])
+        if auxs is not None:
+            a.aux, a.aux_bs = ptr(auxs[i]), bs(auxs[i])
+        if aux2s is not None:
+            a.aux2, a.aux2_bs = ptr(aux2s[i]), bs(aux2s[i])
+        if y2s is not None:
+            a.y2, a.y2_bs = ptr(y2s[i]), bs(y2s[i])
+        if seg is not None:
+            a.x_seg_len, a.x_seg_gap = seg
+    if n > 1 and len({(m.x_bs, m.y_bs, m.res_bs, m.aux_bs, m.aux2_bs, m.y2_bs) for m in arr}) > 1:
+        raise ValueError("grouped conv: members must share strides")
     if algo and WINO_PRE:
-        arr1 = (L.ConvArgs * 1)(a)
-        keep = _wino_pretransform(tape, arr1, [x])
-        a = arr1[0]
-    check(L.lib().icm_conv_run(C.byref(a), tape.st), "conv_run")
+        _wino_pretransform(tape, arr, xs)
+    if single:
+        check(L.lib().icm_conv_run(C.byref(arr[0]), tape.st), "conv_run")
+    else:
+        check(L.lib().icm_conv_run_grouped(arr, n, tape.st), "conv_run_grouped")
     if e0 is not None:
+        N, _, H, W = xs[0].shape
         px = H * W if transposed else OH * OW
-        _prof_end(e0, _conv_label(tag + ("/wino" if algo else ""), transposed, KH, stride, Cin, Cout, H, W, N),
-                  2.0 * N * Cin * Cout * KH * KW * px)
+        _prof_end(e0, _conv_label(tag + ("/wino" if algo else ""), transposed, KH, stride, Cin, Cout, H, W, N, n),
+                  2.0 * n * N * Cin * Cout * KH * KW * px)
+
+
+def conv_launch_grouped(tape, xs, wps, biases, ys, **kw):
+    """one launch over several members; keywords: see _conv_launch"""
+    _conv_launch(tape, False, xs, wps, biases, ys, **kw)
+
+
+def conv_launch(tape, x, wp, bias, y, *, res=None, aux=None, aux2=None, y2=None, **kw):
+    """the launch of one member; geometry keywords as conv_launch_grouped"""
+    one = lambda t: None if t is None else (t,)
+    _conv_launch(tape, True, (x,), (wp,), one(bias), (y,), ress=one(res), auxs=one(aux), aux2s=one(aux2), y2s=one(y2),
+                 **kw)
+
+
+def _wgrad_args(a, gs, gb, dw, geom, accum, dbias, accum_bias, dw_ld=0, algo=0):
+    """fill one icm_wgrad_args (without its workspace); geom = the leading 15 fields of wgrad_defer's grouping key"""
+    Ca, Cb, KH, KW, stride, pad, act_s, act_b, N, OH, OW, H, W, gs_bs, gb_bs = geom
+    a.gs, a.gs_bs, a.Ca, a.OH, a.OW, a.act_s = ptr(gs), gs_bs, Ca, OH, OW, act_s
+    a.gb, a.gb_bs, a.Cb, a.H, a.W, a.act_b = ptr(gb), gb_bs, Cb, H, W, act_b
+    a.N, a.KH, a.KW, a.stride, a.pad = N, KH, KW, stride, pad
+    a.dw, a.accum = ptr(dw), accum
+    a.dbias, a.accum_bias = ptr(dbias), accum_bias
+    a.dw_ld, a.algo = dw_ld, algo
+
+
+def _wgrad_ws_floats(arr, grouped: bool) -> int:
+    """workspace floats per problem of the launch arr (immediate or grouped entry point)"""
+    lib = L.lib()
+    n = (lib.icm_wgrad_workspace_floats_grouped(C.byref(arr[0]), len(arr)) if grouped
+         else lib.icm_wgrad_workspace_floats(C.byref(arr[0])))
+    if n < 0:
+        raise ValueError("icm wgrad: invalid geometry")
+    return n
+
+
+def _wgrad_prof_end(e0, geom, algo, n, stream=None):
+    Ca, Cb, KH, KW, stride, pad, _, _, N, OH, OW, H, W = geom[:13]
+    _prof_end(e0, f"wgrad{'/wino' if algo else ''} {KH}x{KH}s{stride} {Cb}->{Ca} @{H}x{W} n{N}" + (f" x{n}" if n > 1 else ""),
+              2.0 * n * N * Ca * Cb * KH * KW * OH * OW, stream)
 
 
 def wgrad_launch(tape, gs, gb, dw, *, Ca, Cb, KH, KW, stride, pad, act_s=ACT_NONE, act_b=ACT_NONE, accum=0,
                  dbias=None, accum_bias=0):
-    a = L.WgradArgs()
+    """one weight-gradient problem at once on the main stream (GDN's gamma, the thin-output temporary weight)"""
     N, _, OH, OW = gs.shape
     _, _, H, W = gb.shape
-    a.gs, a.gs_bs, a.Ca, a.OH, a.OW, a.act_s = ptr(gs), bs(gs), Ca, OH, OW, act_s
-    a.gb, a.gb_bs, a.Cb, a.H, a.W, a.act_b = ptr(gb), bs(gb), Cb, H, W, act_b
-    a.N, a.KH, a.KW, a.stride, a.pad = N, KH, KW, stride, pad
-    a.dw, a.accum = ptr(dw), accum
-    a.dbias, a.accum_bias = ptr(dbias), accum_bias
-    a.ws = 0
-    n = L.lib().icm_wgrad_workspace_floats(C.byref(a))
-    if n < 0:
-        raise ValueError("icm wgrad: invalid geometry")
+    geom = (Ca, Cb, KH, KW, stride, pad, act_s, act_b, N, OH, OW, H, W, bs(gs), bs(gb))
+    arr = (L.WgradArgs * 1)()
+    a = arr[0]
+    _wgrad_args(a, gs, gb, dw, geom, accum, dbias, accum_bias)
+    n = _wgrad_ws_floats(arr, False)
     ws = tape.workspace(n, gs.device)
     a.ws, a.ws_floats = ptr(ws), n
     e0 = _prof_begin()
     check(L.lib().icm_conv_wgrad(C.byref(a), tape.st), "conv_wgrad")
-    _prof_end(e0, f"wgrad {KH}x{KH}s{stride} {Cb}->{Ca} @{H}x{W} n{N}", 2.0 * N * Ca * Cb * KH * KW * OH * OW)
+    _wgrad_prof_end(e0, geom, 0, 1)
 
 
 def wgrad_defer(tape, gs, gb, dw, *, Ca, Cb, KH, KW, stride, pad, act_s=ACT_NONE, act_b=ACT_NONE, accum=0,
@@ -476,22 +544,13 @@ def flush_wgrads(tape):
         st = side.cuda_stream
         tape._flushed.append(jobs_all)
     for key, jobs in groups.items():
-        Ca, Cb, KH, KW, stride, pad, act_s, act_b, N, OH, OW, H, W, gsb, gbb, _, algo = key
+        geom, algo = key[:15], key[-1]
         for i0 in range(0, len(jobs), 32):
             chunk = jobs[i0:i0 + 32]
             arr = (L.WgradArgs * len(chunk))()
             for a, (_, gs, gb, dw, accum, dbias, accum_bias, dw_ld) in zip(arr, chunk):
-                a.gs, a.gs_bs, a.Ca, a.OH, a.OW, a.act_s = ptr(gs), gsb, Ca, OH, OW, act_s
-                a.gb, a.gb_bs, a.Cb, a.H, a.W, a.act_b = ptr(gb), gbb, Cb, H, W, act_b
-                a.N, a.KH, a.KW, a.stride, a.pad = N, KH, KW, stride, pad
-                a.dw, a.accum = ptr(dw), accum
-                a.dbias, a.accum_bias = ptr(dbias), accum_bias
-                a.dw_ld = dw_ld
-                a.algo = algo
-            n = lib.icm_wgrad_workspace_floats_grouped(C.byref(arr[0]), len(chunk))
-            if n < 0:
-                raise ValueError("icm wgrad: invalid geometry")
-            n = (n + 63) // 64 * 64
+                _wgrad_args(a, gs, gb, dw, geom, accum, dbias, accum_bias, dw_ld, algo)
+            n = (_wgrad_ws_floats(arr, True) + 63) // 64 * 64
             if side is not None:
                 if tape._side_ws is None or tape._side_ws.numel() < n * len(chunk):
                     with torch.cuda.stream(side):
@@ -504,8 +563,7 @@ def flush_wgrads(tape):
                 a.ws, a.ws_floats = ptr(ws) + 4 * n * j, n
             e0 = _prof_begin(side)
             check(lib.icm_conv_wgrad_grouped(arr, len(chunk), st), "conv_wgrad_grouped")
-            _prof_end(e0, f"wgrad{'/wino' if algo else ''} {KH}x{KH}s{stride} {Cb}->{Ca} @{H}x{W} n{N}" + (f" x{len(chunk)}" if len(chunk) > 1 else ""),
-                      2.0 * len(chunk) * N * Ca * Cb * KH * KW * OH * OW, side)
+            _wgrad_prof_end(e0, key, algo, len(chunk), side)
 
 
 def accumulate(tape, dst_t, src, mul_dgelu_of=None):
@@ -537,6 +595,159 @@ def copy_into(tape, src, dst, accum=0):
 
 
 # ------------------------------------------------------------------------------------------------ conv family
+def _conv_layer(tape: Tape, single: bool, xvs, ws, bs_, outs, ress, lrp_auxs, *, stride=1, pad=0, transposed=False,
+                output_padding=0, pixel_shuffle=0, w_as=None, temp_weight=False, act_out=False):
+    """ONE convolution layer over a list of members (input xvs[i], weight ws[i], bias bs_[i] or None) that share shape
+    and options and run as one launch per direction; conv2d is the list of length one.  outs / ress / lrp_auxs: None or
+    one entry per member.  Members may share an input tensor (their input gradients are then summed).  single: the
+    launches go through the one-member entry point (_conv_launch).  Returns the list of output tensors."""
+    n = len(xvs)
+    if n > MAX_GROUP:
+        raise ValueError("conv2d_group: too many members")
+    if n > 1 and (transposed or stride != 1 or w_as is not None or temp_weight):
+        raise NotImplementedError("grouped layers are stride-1 Conv2d layers over their own weights")
+    x0, act = xvs[0].t, xvs[0].act
+    N, Cin, H, W = x0.shape
+    if w_as is not None:
+        w4s = [w.view(w_as[0], w_as[1], 1, 1) for w in ws]
+    else:
+        w4s = ws if ws[0].dim() == 4 else [w.view(w.shape[0], w.shape[1], 1, 1) for w in ws]
+    assert n == 1 or (all(v.act == act and v.t.shape == x0.shape for v in xvs) and
+                      all(w.shape == w4s[0].shape for w in w4s))
+    log = not temp_weight
+    wino = 0
+    if not transposed:
+        Cout, ci, KH, KW = w4s[0].shape
+        OH, OW = (H + 2 * pad - KH) // stride + 1, (W + 2 * pad - KW) // stride + 1
+        wino = 1 if (wino_ok(KH, KW, stride, pad, Cin, pixel_shuffle, work=float(n) * N * OH * OW * Cin * Cout)
+                     and w_as is None) else 0
+        wps = [tape.pack(w, Cout, Cin, KH, KW, 1, 0, stride, pad, wino=wino, log=log) for w in w4s]
+    else:
+        ci, Cout, KH, KW = w4s[0].shape
+        OH = (H - 1) * stride - 2 * pad + KH + output_padding
+        OW = (W - 1) * stride - 2 * pad + KW + output_padding
+        wps = [tape.pack(w, Cout, Cin, KH, KW, 0, 1, stride, pad, log=log) for w in w4s]
+    if ci != Cin:
+        raise ValueError(f"conv2d: weight expects {ci} input channels, got {Cin}")
+    oshape = (N, Cout // 4, OH * 2, OW * 2) if pixel_shuffle == 2 else (N, Cout, OH, OW)
+    ys = list(outs) if outs is not None else [new(oshape, x0.device) for _ in range(n)]
+    for y in ys:
+        assert tuple(y.shape) == oshape, (tuple(y.shape), oshape)
+    lrp = lrp_auxs is not None
+    assert not (lrp and ress is not None) and not (pixel_shuffle and (lrp or ress is not None))
+    xfs, actf = _operands(tape, xvs)     # what the forward kernel and the weight gradients read
+    epi, resf, y2s = EPI_NONE, None, None
+    if ress is not None:
+        assert ress[0].act in (ACT_NONE, ACT_GELU) and (n == 1 or all(r.act == ress[0].act for r in ress))
+        resf, ract = _operands(tape, ress)
+        epi = EPI_RES_GELU if ract == ACT_GELU else EPI_RES
+    if lrp:
+        epi, y2s = EPI_LRP, [new(oshape, x0.device) for _ in range(n)]
+    elif act_out and _MATERIALIZE and N * OH * OW >= _MAT_MIN_PIXELS:
+        if EVAL_INPLACE_ACT and not tape.need_grad and outs is None:
+            y2s = ys     # inference: y holds gelu(pre-activation); VT(y, GELU) consumers read it as is (tape.mat)
+        else:
+            y2s = [new(oshape, x0.device) for _ in range(n)]
+        for y, y2 in zip(ys, y2s):
+            tape.mat[_key(y)] = y2
+    _conv_launch(tape, single, xfs, wps, bs_, ys, Cin=Cin, Cout=Cout, KH=KH, KW=KW, stride=stride, pad=pad,
+                 transposed=transposed, OH=OH, OW=OW, pro_act=actf, epi=epi, ress=resf, auxs=lrp_auxs, y2s=y2s,
+                 ps=pixel_shuffle, algo=wino)
+    if not tape.need_grad:
+        return ys
+    # what the backward needs, as ONE object per member (absent operands: placeholders that are never read): the
+    # per-operand lists above die here -- every container a layer keeps alive until the backward is garbage-collector
+    # work in each of the several hundred layers of a launch-bound step
+    has_res = ress is not None
+    mem = list(zip(xvs, ws, w4s, bs_, ys, xfs, y2s or ys, ress or ys, lrp_auxs or ys))
+    del xvs, ws, w4s, bs_, xfs, y2s, ress, lrp_auxs
+
+    def bwd():
+        xvs, ws, w4s, bs_, ys, xfs, y2s, ress, lrp_auxs = zip(*mem)
+        dys = [tape.grad_of(y) for y in ys]
+        missing = 0
+        for d in dys:
+            missing += d is None
+        if missing == n:    # nothing downstream of this layer has a gradient
+            return
+        if missing:
+            raise RuntimeError("conv2d_group: every member needs a gradient")
+        if lrp:
+            for i, (dy, aux, y2) in enumerate(zip(dys, lrp_auxs, y2s)):
+                accumulate(tape, aux, dy)
+                dys[i] = dpre = new(oshape, x0.device)
+                check(L.lib().icm_lrp_bwd(ptr(dy), bs(dy), ptr(y2), bs(y2), ptr(dpre), bs(dpre), N, Cout, OH * OW, tape.st),
+                      "lrp_bwd")
+        if pixel_shuffle == 2:   # gradient of the fused PixelShuffle store
+            for i, dy in enumerate(dys):
+                dys[i] = du = new((N, Cout, OH, OW), x0.device)
+                dyc = dy if dy.is_contiguous() else dy.contiguous()
+                check(L.lib().icm_pixel_unshuffle2(ptr(dyc), ptr(du), N, Cout // 4, OH, OW, tape.st), "pixel_unshuffle2")
+        if has_res:
+            for r, dy in zip(ress, dys):
+                tape.defer_res_grad(r.t, dy, r.act == ACT_GELU)
+        wg = wgrad_launch if temp_weight else wgrad_defer
+        for xf, w, b, dy in zip(xfs, ws, bs_, dys):
+            want_w = tape.wants(w)
+            want_b = b is not None and tape.wants(b)
+            fuse_b = want_b and want_w and not transposed   # bias grad rides on the wgrad loaders
+            if want_b and not fuse_b:
+                gb_, acc = tape.grad_for_write(b)
+                channel_sum(tape, dy, gb_, acc)
+            if want_w:
+                gw, acc = tape.grad_for_write(w)
+                if not transposed:
+                    gb_, accb = tape.grad_for_write(b) if fuse_b else (None, 0)
+                    wg(tape, dy, xf, gw, Ca=Cout, Cb=Cin, KH=KH, KW=KW, stride=stride, pad=pad, act_b=actf, accum=acc,
+                       dbias=gb_, accum_bias=accb)
+                else:
+                    wg(tape, xf, dy, gw, Ca=Cin, Cb=Cout, KH=KH, KW=KW, stride=stride, pad=pad, act_s=actf, accum=acc)
+        # input gradients: one launch.  Members that share an input tensor (the fixed support of the late slices), or
+        # of which only some want a gradient, write private buffers which are then added to the gradients in member
+        # order; otherwise the gradients are written (or accumulated) in place.
+        want_x = [tape.wants(v.t) for v in xvs]
+        if not any(want_x):
+            return
+        if act not in (ACT_GELU, ACT_NONE):
+            raise NotImplementedError("dgrad through this virtual activation")
+        gelu = act == ACT_GELU
+        private = not all(want_x) or (n > 1 and len({_key(v.t) for v in xvs}) < n)
+        rgs = None   # identity-path terms ride on this dgrad if every member has a pending one of this activation
+        pend = tape._pending_res
+        if pend and not private and all(pend.get(_key(v.t), (0, 0, None))[2] == gelu for v in xvs):
+            rgs = [tape.take_res_grad(v.t, gelu) for v in xvs]
+        if private:
+            gxs, acc = [new((N, Cin, H, W), x0.device) for _ in range(n)], 0
+        else:
+            gws = [tape.grad_for_write(v.t) for v in xvs]
+            gxs, acc = [g for g, _ in gws], gws[0][1]
+            if n > 1 and len({ax for _, ax in gws}) > 1:   # one launch, one accumulate flag: zero the buffers that
+                for gx, ax in gws:                          # nobody has written yet
+                    if not ax:
+                        gx.zero_()
+                acc = 1
+        if not transposed:   # conv dgrad = scatter with W ([K=Cout][M=Cin])
+            wb = 2 if (wino_ok(KH, KW, stride, pad, Cout, pixel_shuffle, work=float(n) * N * H * W * Cin * Cout)
+                       and w_as is None) else 0
+            wpb = [tape.pack(w, Cin, Cout, KH, KW, 0, 1, stride, pad, wino=wb, log=log) for w in w4s]
+        else:                # convT dgrad = gather with Wt ([M=Cin][K=Cout])
+            wb = 0
+            wpb = [tape.pack(w, Cin, Cout, KH, KW, 1, 0, stride, pad, log=log) for w in w4s]
+        if gelu:
+            epi_b = EPI_RES_MUL_DGELU if rgs is not None else EPI_MUL_DGELU
+        else:
+            epi_b = EPI_RES if rgs is not None else EPI_NONE
+        _conv_launch(tape, single, dys, wpb, None, gxs, Cin=Cout, Cout=Cin, transposed=not transposed, OH=H, OW=W,
+                     epi=epi_b, auxs=[v.t for v in xvs] if gelu else None, ress=rgs, accum=acc, tag="dgrad",
+                     algo=1 if wb else 0, KH=KH, KW=KW, stride=stride, pad=pad)
+        if private:
+            for v, g in zip(xvs, gxs):
+                accumulate(tape, v.t, g)
+
+    tape.bw.append(bwd)
+    return ys
+
+
 def conv2d(tape: Tape, xv: VT, w, b, *, stride=1, pad=0, transposed=False, output_padding=0, res: Optional[VT] = None,
            out=None, pixel_shuffle=0, lrp_aux=None, w_as: Optional[Tuple[int, int]] = None, temp_weight: bool = False,
            act_out: bool = False) -> torch.Tensor:
@@ -547,106 +758,10 @@ def conv2d(tape: Tape, xv: VT, w, b, *, stride=1, pad=0, transposed=False, outpu
     temp_weight: w is a per-step temporary derived from a parameter (conv2d_thin_out): its packed copies are never
     produced ahead of time from a recorded sequence and its gradient is computed at once on the main stream (the caller
     carries it back into the parameter's layout right behind this layer's backward)."""
-    x, act = xv.t, xv.act
-    xf, actf = _operand(tape, xv)       # what the forward kernel and the weight gradient read
-    N, Cin, H, W = x.shape
-    w4 = w if w.dim() == 4 else w.view(w.shape[0], w.shape[1], 1, 1)
-    if w_as is not None:
-        w4 = w.view(w_as[0], w_as[1], 1, 1)
-    wino = 0
-    if not transposed:
-        Cout, ci, KH, KW = w4.shape
-        OH, OW = (H + 2 * pad - KH) // stride + 1, (W + 2 * pad - KW) // stride + 1
-        wino = 1 if wino_ok(KH, KW, stride, pad, Cin, pixel_shuffle, work=float(N) * OH * OW * Cin * Cout) and w_as is None else 0
-        wp = tape.pack(w4, Cout, Cin, KH, KW, 1, 0, stride, pad, wino=wino, log=not temp_weight)
-    else:
-        ci, Cout, KH, KW = w4.shape
-        OH = (H - 1) * stride - 2 * pad + KH + output_padding
-        OW = (W - 1) * stride - 2 * pad + KW + output_padding
-        wp = tape.pack(w4, Cout, Cin, KH, KW, 0, 1, stride, pad, log=not temp_weight)
-    if ci != Cin:
-        raise ValueError(f"conv2d: weight expects {ci} input channels, got {Cin}")
-    if pixel_shuffle == 2:
-        oshape = (N, Cout // 4, OH * 2, OW * 2)
-    else:
-        oshape = (N, Cout, OH, OW)
-    y = out if out is not None else torch.empty(oshape, dtype=torch.float32, device=x.device)
-    assert tuple(y.shape) == oshape, (tuple(y.shape), oshape)
-    epi, resv, aux, y2 = EPI_NONE, None, None, None
-    if res is not None:
-        assert res.act in (ACT_NONE, ACT_GELU)
-        resv, ract = _operand(tape, res)
-        epi = EPI_RES_GELU if ract == ACT_GELU else EPI_RES
-    if lrp_aux is not None:
-        assert res is None
-        epi, aux = EPI_LRP, lrp_aux
-        y2 = torch.empty(oshape, dtype=torch.float32, device=x.device)
-    elif act_out and _MATERIALIZE and N * OH * OW >= _MAT_MIN_PIXELS:
-        if EVAL_INPLACE_ACT and not tape.need_grad and out is None:
-            y2 = y     # inference: y holds gelu(pre-activation); VT(y, GELU) consumers read it as is (tape.mat)
-        else:
-            y2 = torch.empty(oshape, dtype=torch.float32, device=x.device)
-        tape.mat[_key(y)] = y2
-    conv_launch(tape, xf, wp, b, y, Cin=Cin, Cout=Cout, KH=KH, KW=KW, stride=stride, pad=pad, transposed=transposed,
-                OH=OH, OW=OW, pro_act=actf, epi=epi, res=resv, aux=aux, y2=y2, ps=pixel_shuffle, algo=wino)
-    if not tape.need_grad:
-        return y
-
-    def bwd():
-        dy = tape.grad_of(y)
-        if dy is None:
-            return
-        if lrp_aux is not None:
-            accumulate(tape, lrp_aux, dy)
-            dpre = torch.empty(oshape, dtype=torch.float32, device=x.device)
-            check(L.lib().icm_lrp_bwd(ptr(dy), bs(dy), ptr(y2), bs(y2), ptr(dpre), bs(dpre), N, Cout, OH * OW, tape.st),
-                  "lrp_bwd")
-            dy = dpre
-        if pixel_shuffle == 2:
-            du = torch.empty((N, Cout, OH, OW), dtype=torch.float32, device=x.device)
-            assert dy.is_contiguous()
-            check(L.lib().icm_pixel_unshuffle2(ptr(dy), ptr(du), N, Cout // 4, OH, OW, tape.st), "pixel_unshuffle2")
-            dy = du
-        if res is not None:
-            tape.defer_res_grad(res.t, dy, res.act == ACT_GELU)
-        want_b = b is not None and tape.wants(b)
-        fuse_b = want_b and not transposed and tape.wants(w)   # bias grad rides on the wgrad loaders
-        if want_b and not fuse_b:
-            gb_, acc = tape.grad_for_write(b)
-            channel_sum(tape, dy, gb_, acc)
-        if tape.wants(w):
-            gw, acc = tape.grad_for_write(w)
-            wg = wgrad_launch if temp_weight else wgrad_defer
-            if not transposed:
-                gb_, accb = tape.grad_for_write(b) if fuse_b else (None, 0)
-                wg(tape, dy, xf, gw, Ca=Cout, Cb=Cin, KH=KH, KW=KW, stride=stride, pad=pad, act_b=actf,
-                   accum=acc, dbias=gb_, accum_bias=accb)
-            else:
-                wg(tape, xf, dy, gw, Ca=Cin, Cb=Cout, KH=KH, KW=KW, stride=stride, pad=pad, act_s=actf,
-                   accum=acc)
-        if tape.wants(x):
-            rg = tape.take_res_grad(x, act == ACT_GELU) if act in (ACT_GELU, ACT_NONE) else None
-            gx, acc = tape.grad_for_write(x)
-            if act == ACT_GELU:
-                epi_b, aux_b = (EPI_RES_MUL_DGELU if rg is not None else EPI_MUL_DGELU), x
-            elif act == ACT_NONE:
-                epi_b, aux_b = (EPI_RES if rg is not None else EPI_NONE), None
-            else:
-                raise NotImplementedError("dgrad through this virtual activation")
-            if not transposed:   # conv dgrad = scatter with W ([K=Cout][M=Cin])
-                wb = 2 if (wino_ok(KH, KW, stride, pad, Cout, pixel_shuffle, work=float(N) * H * W * Cin * Cout)
-                           and w_as is None) else 0
-                wpb = tape.pack(w4, Cin, Cout, KH, KW, 0, 1, stride, pad, wino=wb, log=not temp_weight)
-                conv_launch(tape, dy, wpb, None, gx, Cin=Cout, Cout=Cin, KH=KH, KW=KW, stride=stride, pad=pad,
-                            transposed=1, OH=H, OW=W, epi=epi_b, aux=aux_b, res=rg, accum=acc, tag="dgrad",
-                            algo=1 if wb else 0)
-            else:                # convT dgrad = gather with Wt ([M=Cin][K=Cout])
-                wpb = tape.pack(w4, Cin, Cout, KH, KW, 1, 0, stride, pad, log=not temp_weight)
-                conv_launch(tape, dy, wpb, None, gx, Cin=Cout, Cout=Cin, KH=KH, KW=KW, stride=stride, pad=pad,
-                            transposed=0, OH=H, OW=W, epi=epi_b, aux=aux_b, res=rg, accum=acc, tag="dgrad")
-
-    tape.bw.append(bwd)
-    return y
+    return _conv_layer(tape, True, [xv], [w], [b], None if out is None else [out], None if res is None else [res],
+                       None if lrp_aux is None else [lrp_aux], stride=stride, pad=pad, transposed=transposed,
+                       output_padding=output_padding, pixel_shuffle=pixel_shuffle, w_as=w_as, temp_weight=temp_weight,
+                       act_out=act_out)[0]
 
 
 def conv2d_thin_in(tape: Tape, x, w, b, *, stride, pad) -> torch.Tensor:
@@ -740,165 +855,16 @@ def conv2d_thin_out(tape: Tape, xv: VT, w, b, *, pad) -> torch.Tensor:
     return convT2d_thin_out(tape, xv, wt, b, stride=1, pad=K - 1 - pad, output_padding=0, temp_weight=True)
 
 
-def conv_launch_grouped(tape, xs, wps, biases, ys, *, Cin, Cout, KH, KW, stride, pad, transposed, OH, OW,
-                        pro_act=ACT_NONE, epi=EPI_NONE, auxs=None, y2s=None, ress=None, accum=0, ps=0, tag="fwd", algo=0):
-    n = len(xs)
-    arr = (L.ConvArgs * n)()
-    e0 = _prof_begin()
-    for i, a in enumerate(arr):
-        x, y = xs[i], ys[i]
-        N, _, H, W = x.shape
-        a.x, a.x_bs, a.N, a.Cin, a.H, a.W = ptr(x), bs(x), N, Cin, H, W
-        a.wp, a.bias = ptr(wps[i]), ptr(biases[i]) if biases is not None else 0
-        a.y, a.y_bs, a.Cout, a.OH, a.OW = ptr(y), bs(y), Cout, OH, OW
-        a.KH, a.KW, a.stride, a.pad = KH, KW, stride, pad
-        a.transposed, a.pro_act, a.epi = int(transposed), pro_act, epi
-        aux = auxs[i] if auxs is not None else None
-        a.aux, a.aux_bs = ptr(aux), bs(aux)
-        y2 = y2s[i] if y2s is not None else None
-        a.y2, a.y2_bs = ptr(y2), bs(y2)
-        res = ress[i] if ress is not None else None
-        a.res, a.res_bs = ptr(res), bs(res)
-        a.accum, a.pixel_shuffle = accum, ps
-        a.algo = algo
-        if i and (bs(x) != bs(xs[0]) or bs(y) != bs(ys[0]) or bs(aux) != bs(auxs[0] if auxs else None)
-                  or bs(y2) != bs(y2s[0] if y2s else None) or bs(res) != bs(ress[0] if ress else None)):
-            raise ValueError("grouped conv: members must share strides")
-    keep = _wino_pretransform(tape, arr, xs) if (algo and WINO_PRE) else None
-    check(L.lib().icm_conv_run_grouped(arr, n, tape.st), "conv_run_grouped")
-    if e0 is not None:
-        N, _, H, W = xs[0].shape
-        px = H * W if transposed else OH * OW
-        _prof_end(e0, _conv_label(tag + ("/wino" if algo else ""), transposed, KH, stride, Cin, Cout, H, W, N, n),
-                  2.0 * n * N * Cin * Cout * KH * KW * px)
-
-
-
-
 def conv2d_group(tape: Tape, xvs, ws, bs_, *, pad=1, outs=None, lrp_auxs=None, ress=None, pixel_shuffle=0,
                  act_out: bool = False):
     """The same stride-1 convolution shape applied to several independent (input, weight) pairs in ONE launch:
     cc_mean_transforms[i] || cc_scale_transforms[i] (cnn.py:164-168), and -- because the support of slice i is
     y_hat_slices[:max_support] (cnn.py:161), i.e. the FIRST five slices -- all chains of the slices >= max_support at
-    once.  Members may share an input tensor (their input gradients are then summed).  outs / lrp_auxs: write into
-    the given tensors with the LRP tail (cnn.py:175-178) fused.  ress: per-member residual VT (identity or virtual
-    GELU) added in the epilogue (ResidualUnit tails of the two gate branches, layers.py:66-71).  Returns the outputs."""
-    n = len(xvs)
-    if n > MAX_GROUP:
-        raise ValueError("conv2d_group: too many members")
-    x0, act = xvs[0].t, xvs[0].act
-    N, Cin, H, W = x0.shape
-    Cout, ci, KH, KW = ws[0].shape
-    assert all(v.act == act and v.t.shape == x0.shape for v in xvs) and all(w.shape == ws[0].shape for w in ws)
-    if ci != Cin:
-        raise ValueError("conv2d_group: channel mismatch")
-    OH, OW = H + 2 * pad - KH + 1, W + 2 * pad - KW + 1
-    wino = 1 if wino_ok(KH, KW, 1, pad, Cin, pixel_shuffle, work=float(n) * N * OH * OW * Cin * Cout) else 0
-    wps = [tape.pack(w, Cout, Cin, KH, KW, 1, 0, 1, pad, wino=wino) for w in ws]
-    oshape = (N, Cout // 4, OH * 2, OW * 2) if pixel_shuffle == 2 else (N, Cout, OH, OW)
-    ys = list(outs) if outs is not None else [new(oshape, x0.device) for _ in range(n)]
-    assert all(tuple(y.shape) == oshape for y in ys)
-    lrp = lrp_auxs is not None
-    assert not (pixel_shuffle and (lrp or ress is not None))
-    y2s = [new((N, Cout, OH, OW), x0.device) for _ in range(n)] if lrp else None
-    epi = EPI_LRP if lrp else EPI_NONE
-    # materialised operands: used only when EVERY member has one (a launch has one activation flag)
-    ops = [_operand(tape, v) for v in xvs]
-    if all(a == ACT_NONE for _, a in ops):
-        xfs, actf = [t for t, _ in ops], ACT_NONE
-    else:
-        xfs, actf = [v.t for v in xvs], act
-    resf = None
-    if ress is not None:
-        assert not lrp and all(r.act == ress[0].act for r in ress) and ress[0].act in (ACT_NONE, ACT_GELU)
-        rops = [_operand(tape, r) for r in ress]
-        if all(a == ACT_NONE for _, a in rops):
-            resf, epi = [t for t, _ in rops], EPI_RES
-        else:
-            resf, epi = [r.t for r in ress], (EPI_RES_GELU if ress[0].act == ACT_GELU else EPI_RES)
-    if act_out and _MATERIALIZE and not lrp and N * OH * OW >= _MAT_MIN_PIXELS:
-        if EVAL_INPLACE_ACT and not tape.need_grad and outs is None:
-            y2s = list(ys)   # inference: only gelu(y) is stored (see conv2d)
-        else:
-            y2s = [new(oshape, x0.device) for _ in range(n)]
-        for y, y2 in zip(ys, y2s):
-            tape.mat[_key(y)] = y2
-    conv_launch_grouped(tape, xfs, wps, bs_, ys, Cin=Cin, Cout=Cout, KH=KH, KW=KW, stride=1, pad=pad,
-                        transposed=0, OH=OH, OW=OW, pro_act=actf, epi=epi,
-                        auxs=list(lrp_auxs) if lrp else None, y2s=y2s,
-                        ress=resf, ps=pixel_shuffle, algo=wino)
-    if not tape.need_grad:
-        return ys
-
-    def bwd():
-        dys = [tape.grad_of(y) for y in ys]
-        if any(d is None for d in dys):
-            raise RuntimeError("conv2d_group: every member needs a gradient")
-        if pixel_shuffle == 2:   # gradient of the fused PixelShuffle store
-            un = []
-            for dy in dys:
-                du = torch.empty((N, Cout, OH, OW), dtype=torch.float32, device=x0.device)
-                dyc = dy if dy.is_contiguous() else dy.contiguous()
-                check(L.lib().icm_pixel_unshuffle2(ptr(dyc), ptr(du), N, Cout // 4, OH, OW, tape.st), "pixel_unshuffle2")
-                un.append(du)
-            dys = un
-        if lrp:
-            pre = []
-            for dy, aux, y2 in zip(dys, lrp_auxs, y2s):
-                accumulate(tape, aux, dy)
-                dpre = torch.empty((N, Cout, OH, OW), dtype=torch.float32, device=x0.device)
-                check(L.lib().icm_lrp_bwd(ptr(dy), bs(dy), ptr(y2), bs(y2), ptr(dpre), bs(dpre), N, Cout, OH * OW, tape.st),
-                      "lrp_bwd")
-                pre.append(dpre)
-            dys = pre
-        if ress is not None:
-            for r, dy in zip(ress, dys):
-                tape.defer_res_grad(r.t, dy, r.act == ACT_GELU)
-        for xf_, w, b, dy in zip(xfs, ws, bs_, dys):
-            gw, acc = tape.grad_for_write(w)
-            gb_, accb = tape.grad_for_write(b)
-            wgrad_defer(tape, dy, xf_, gw, Ca=Cout, Cb=Cin, KH=KH, KW=KW, stride=1, pad=pad, act_b=actf, accum=acc,
-                        dbias=gb_, accum_bias=accb)
-        # input gradients: one grouped dgrad.  Members that share an input tensor (the fixed support of the late
-        # slices) write private buffers which are then summed into the shared gradient; distinct inputs are
-        # written (or accumulated) in place.
-        keys = [_key(v.t) for v in xvs]
-        shared = len(set(keys)) < n
-        rgs = None
-        if not shared and act in (ACT_GELU, ACT_NONE) and all(k in tape._pending_res and
-                                                              tape._pending_res[k][2] == (act == ACT_GELU) for k in keys):
-            rgs = [tape.take_res_grad(v.t, act == ACT_GELU) for v in xvs]   # identity-path terms ride on this dgrad
-        if not shared:
-            gxs, accs = [], []
-            for v in xvs:
-                gx, ax = tape.grad_for_write(v.t)
-                gxs.append(gx)
-                accs.append(ax)
-            if len(set(accs)) > 1:   # one launch, one accumulate flag: zero the buffers that nobody has written yet
-                for gx, ax in zip(gxs, accs):
-                    if not ax:
-                        gx.zero_()
-                accs = [1] * n
-            acc0 = accs[0]
-        else:
-            gxs = [torch.empty((N, Cin, H, W), dtype=torch.float32, device=x0.device) for _ in range(n)]
-            acc0 = 0
-        wb = 2 if wino_ok(KH, KW, 1, pad, Cout, pixel_shuffle, work=float(n) * N * H * W * Cin * Cout) else 0
-        wpb = [tape.pack(w, Cin, Cout, KH, KW, 0, 1, 1, pad, wino=wb) for w in ws]
-        if act == ACT_GELU:
-            epi_b = EPI_RES_MUL_DGELU if rgs is not None else EPI_MUL_DGELU
-        else:
-            epi_b = EPI_RES if rgs is not None else EPI_NONE
-        conv_launch_grouped(tape, dys, wpb, None, gxs, Cin=Cout, Cout=Cin, KH=KH, KW=KW, stride=1, pad=pad,
-                            transposed=1, OH=H, OW=W, epi=epi_b,
-                            auxs=[v.t for v in xvs] if act == ACT_GELU else None, ress=rgs, accum=acc0, tag="dgrad",
-                            algo=1 if wb else 0)
-        if shared:
-            for v, g in zip(xvs, gxs):
-                accumulate(tape, v.t, g)
-
-    tape.bw.append(bwd)
-    return ys
+    once.  Members may share an input tensor.  outs / lrp_auxs: write into the given tensors with the LRP tail
+    (cnn.py:175-178) fused.  ress: per-member residual VT (identity or virtual GELU) added in the epilogue (ResidualUnit
+    tails of the two gate branches, layers.py:66-71).  Returns the outputs."""
+    return _conv_layer(tape, False, xvs, ws, bs_, outs, ress, lrp_auxs, pad=pad, pixel_shuffle=pixel_shuffle,
+                       act_out=act_out)
 
 
 def gdn(tape: Tape, x, beta, gamma, inverse: bool, beta_min: float = 1e-6) -> torch.Tensor:

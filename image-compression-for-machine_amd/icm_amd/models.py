@@ -19,6 +19,7 @@ from .engine import VT
 from .entropy_models import EntropyBottleneck, GaussianConditional
 from .layers import (GDN, Conv2d, Win_noShift_Attention, WindowAttention, conv, conv3x3, deconv, subpel_conv3x3,
                      _named)
+from .slices import chain_layers
 
 SCALES_MIN, SCALES_MAX, SCALES_LEVELS = 0.11, 256, 64
 
@@ -128,11 +129,7 @@ def _chain(tape, P, p, xv: VT, strides=(1, 1, 1, 1, 1), out=None, lrp_aux=None):
 def _chain_pair(tape, P, p1, p2, xv1: VT, xv2: VT):
     """cc_mean_transforms[i] and cc_scale_transforms[i] are independent and shape-identical: run each of
     their five convolutions as one grouped launch (forward and dgrad)."""
-    for i in (0, 2, 4, 6, 8):
-        t1, t2 = E.conv2d_group(tape, [xv1, xv2], [P[f"{p1}.{i}.weight"], P[f"{p2}.{i}.weight"]],
-                                [P[f"{p1}.{i}.bias"], P[f"{p2}.{i}.bias"]], pad=1, act_out=i != 8)
-        xv1, xv2 = VT(t1, ACT_GELU), VT(t2, ACT_GELU)
-    return t1, t2
+    return chain_layers(tape, P, [p1, p2], [xv1, xv2], (0, 2, 4, 6, 8))
 
 
 def _h_s(tape, P, p, z_hat, out):
@@ -288,11 +285,7 @@ def hyper_slices(tape: E.Tape, P: Dict[str, torch.Tensor], y: torch.Tensor, nois
         ms, ss = MS[:, :M + sc_ * k], SS[:, :M + sc_ * k]
         # mean / scale chains of all tail slices: one grouped launch per layer
         names = [f"cc_mean_transforms.{i}" for i in idx] + [f"cc_scale_transforms.{i}" for i in idx]
-        xvs = [VT(ms)] * nt + [VT(ss)] * nt
-        for li in (0, 2, 4, 6, 8):
-            ts = E.conv2d_group(tape, xvs, [P[f"{p}.{li}.weight"] for p in names], [P[f"{p}.{li}.bias"] for p in names],
-                                pad=1, act_out=li != 8)
-            xvs = [VT(t, ACT_GELU) for t in ts]
+        ts = chain_layers(tape, P, names, [VT(ms)] * nt + [VT(ss)] * nt, (0, 2, 4, 6, 8))
         mu_t, sc_t = ts[:nt], ts[nt:]
         LSs, pres = [], []
         for j, i in enumerate(idx):
@@ -316,13 +309,8 @@ def hyper_slices(tape: E.Tape, P: Dict[str, torch.Tensor], y: torch.Tensor, nois
             pres.append(yh_pre)
         # lrp chains of all tail slices, LRP tail fused into the last grouped launch
         lnames = [f"lrp_transforms.{i}" for i in idx]
-        xvs = [VT(LS) for LS in LSs]
-        for li in (0, 2, 4, 6):
-            ts = E.conv2d_group(tape, xvs, [P[f"{p}.{li}.weight"] for p in lnames],
-                                [P[f"{p}.{li}.bias"] for p in lnames], pad=1, act_out=True)
-            xvs = [VT(t, ACT_GELU) for t in ts]
-        E.conv2d_group(tape, xvs, [P[f"{p}.8.weight"] for p in lnames], [P[f"{p}.8.bias"] for p in lnames], pad=1,
-                       outs=[Y_hat[:, i * sc_:(i + 1) * sc_] for i in idx], lrp_auxs=pres)
+        chain_layers(tape, P, lnames, [VT(LS) for LS in LSs], (0, 2, 4, 6, 8),
+                     outs=[Y_hat[:, i * sc_:(i + 1) * sc_] for i in idx], lrp_auxs=pres)
         if keep is not None:
             mus.extend(mu_t)
             scs.extend(sc_t)

@@ -42,10 +42,11 @@ KSPLIT_B = _os.environ.get("ICM_KSPLIT_B", "1") != "0"
 FAM = ("cc_mean_transforms", "lrp_transforms", "cc_scale_transforms")   # PRE0 family order: the two latent_means consumers adjacent
 
 
-def _tail_layers(tape, P, names, xvs, outs=None, lrp_auxs=None):
-    """layers 2, 4, 6, 8 of the given chains (first layers done), one grouped launch per layer (cnn.py:89-127)"""
+def chain_layers(tape, P, names, xvs, layers=(2, 4, 6, 8), outs=None, lrp_auxs=None):
+    """the given layers (default: all but the first) of the five-convolution chains ``names`` on the inputs xvs, one
+    grouped launch per layer with virtual GELUs between (cnn.py:89-127); outs / lrp_auxs belong to the last layer (8)"""
     ts = None
-    for li in (2, 4, 6, 8):
+    for li in layers:
         last = li == 8
         ts = E.conv2d_group(tape, xvs, [P[f"{p}.{li}.weight"] for p in names], [P[f"{p}.{li}.bias"] for p in names],
                             pad=1, outs=outs if last else None, lrp_auxs=lrp_auxs if last else None, act_out=not last)
@@ -301,11 +302,11 @@ def hyper_slices_split(tape: E.Tape, P: Dict[str, torch.Tensor], y, noise_z, noi
         names = [f"cc_mean_transforms.{i}" for i in idx] + [f"cc_scale_transforms.{i}" for i in idx]
         xvs = [VT(pre[(i, 0)], ACT_GELU) for i in idx] + [VT(pre[(i, 2)], ACT_GELU) for i in idx]
         outs = [MU[:, i * c:(i + 1) * c] for i in idx] + [SC[:, i * c:(i + 1) * c] for i in idx]
-        _tail_layers(tape, P, names, xvs, outs=outs)
+        chain_layers(tape, P, names, xvs, outs=outs)
         gauss(idx)
         own_block(idx, k)
         lnames = [f"lrp_transforms.{i}" for i in idx]
-        _tail_layers(tape, P, lnames, [VT(pre[(i, 1)], ACT_GELU) for i in idx],
+        chain_layers(tape, P, lnames, [VT(pre[(i, 1)], ACT_GELU) for i in idx],
                      outs=[Y_hat[:, i * c:(i + 1) * c] for i in idx], lrp_auxs=[YP[:, i * c:(i + 1) * c] for i in idx])
 
     # ---- serial slices 0 .. max_support-1, then the tail slices (all with the same, complete support) in batches

@@ -219,3 +219,24 @@ def test_trainer_step_plumbing_dry_run(dry, name):
     assert dry.calls["icm_rd_loss_fwd"] == 2 and dry.calls["icm_conv_wgrad_grouped"] > 40
     if name == "stf":   # thin-output end_conv[2]: W -> W' and dW' -> dW once per step, its gradient computed at once
         assert dry.calls.get("icm_permute_flip") == 4 and dry.calls.get("icm_conv_wgrad") == 2
+
+
+def test_group_with_mixed_inplace_materialisation_is_refused(dry):
+    """inference stores only gelu(y) for a layer whose consumers all apply GELU (tape.mat[y] is y).  A launch has one
+    activation flag: if such a member shared a launch with a member that has no materialised activation, the launch
+    would fall back to the virtual GELU and activate the in-place member twice.  No caller builds such a group; the
+    operand rule refuses it, for the input operands and for the residual operands alike."""
+    import icm_amd.engine as E
+    tape = E.Tape(need_grad=False)
+    a, b, x = (torch.zeros(1, 8, 4, 4) for _ in range(3))
+    tape.mat[E._key(a)] = a            # a holds gelu(pre-activation) in place; b is a plain pre-activation
+    ws, bias = [torch.zeros(8, 8, 3, 3) for _ in range(2)], [torch.zeros(8) for _ in range(2)]
+    mixed = [E.VT(a, E.ACT_GELU), E.VT(b, E.ACT_GELU)]
+    with pytest.raises(RuntimeError, match="in place"):
+        E.conv2d_group(tape, mixed, ws, bias, pad=1)
+    with pytest.raises(RuntimeError, match="in place"):
+        E.conv2d_group(tape, [E.VT(x), E.VT(x)], ws, bias, pad=1, ress=mixed)
+    assert "icm_conv_run_grouped" not in dry.calls
+    tape.mat[E._key(b)] = torch.zeros_like(b)   # every member materialised: one launch reading the stored activations
+    ys = E.conv2d_group(tape, mixed, ws, bias, pad=1)
+    assert len(ys) == 2 and dry.calls["icm_conv_run_grouped"] == 1
