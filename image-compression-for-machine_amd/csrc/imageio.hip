@@ -1,0 +1,300 @@
+// The 8-bit image boundary of the codec on the device, gfx950: what torchvision's ToTensor + F.pad do before compress()
+// and what crop + clamp + ToPILImage do after decompress(), so that an image crosses PCIe as bytes and the padded f32
+// planes are written / read once.
+//
+//   image_u8_to_f32_kernel   interleaved [H, W, 3] bytes -> planar [3, OH, OW] f32, image at (top, left), +0.0 around it
+//   image_f32_to_u8_kernel   planar [3, PH, PW] f32 -> interleaved [H, W, 3] bytes of the window at (top, left);
+//                            with a reference image also one partial sum of squared byte differences per workgroup
+//   image_sse_finish_kernel  adds the partial sums (64-bit integers: exact, whatever the order)
+//
+// Pure bandwidth work.  A thread owns a run of 16 pixels of one row: 48 interleaved bytes = three 16-byte accesses,
+// and 16 floats = four 16-byte accesses in each of the three planes.  Whether the 16-byte form may be used is decided
+// per run and per side (the run lies wholly inside the row and its first byte is 16-byte aligned); every other run --
+// row ends, widths that are not multiples of 16, odd pointers -- moves its pixels one at a time through the same
+// registers.  No scratch, no atomics.
+//
+// Values.  v / 255 must be the correctly rounded f32 quotient (ToTensor divides on the host); it is read from a
+// 256-entry table that the host compiler evaluates (IEEE division at compile time), staged in LDS once per workgroup.
+// The way back is clamp to [0, 1], one f32 multiplication by 255 (correctly rounded on every target) and truncation.
+// NaN input to image_f32_to_u8 is unspecified.
+#include "icm_common.h"
+
+namespace {
+
+constexpr int RUN = 16;        // pixels per thread
+constexpr int BLOCK = 256;
+constexpr int MAX_SIDE = 32768;
+
+typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+
+struct U8Table {
+  float v[256];
+};
+constexpr U8Table make_u8_table() {
+  U8Table t{};
+  for (int i = 0; i < 256; ++i) t.v[i] = (float)i / 255.0f;
+  return t;
+}
+static_assert(make_u8_table().v[0] == 0.0f && make_u8_table().v[255] == 1.0f && make_u8_table().v[51] == 0.2f, "u8 table");
+__device__ const U8Table u8_table = make_u8_table();
+
+__device__ __forceinline__ bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+
+// dvec: OW % 4 == 0 and a 16-byte aligned dst (host-checked), so every group of four floats at a column that is a
+// multiple of four lies wholly inside the row and is 16-byte aligned
+__global__ __launch_bounds__(BLOCK) void image_u8_to_f32_kernel(const uint8_t* __restrict__ src, int H, int W,
+                                                                 float* __restrict__ dst, int OH, int OW, int top,
+                                                                 int left, int runs_per_row, long long total_runs,
+                                                                 int dvec) {
+  __shared__ float lut[256];
+  lut[threadIdx.x] = u8_table.v[threadIdx.x];
+  __syncthreads();
+  const long long g = (long long)blockIdx.x * BLOCK + threadIdx.x;
+  if (g >= total_runs) return;
+  const int oy = (int)(g / runs_per_row);
+  const int ox0 = ((int)(g - (long long)oy * runs_per_row)) * RUN;
+  const int sy = oy - top, sx0 = ox0 - left;
+
+  uint32_t w[12];   // the run's 48 interleaved bytes, little-endian words; pixels outside the image are zero bytes
+#pragma unroll
+  for (int k = 0; k < 12; ++k) w[k] = 0u;
+  if ((unsigned)sy < (unsigned)H && sx0 + RUN > 0 && sx0 < W) {
+    const uint8_t* row = src + ((size_t)sy * W) * 3;
+    if (sx0 >= 0 && sx0 + RUN <= W && aligned16(row + (size_t)sx0 * 3)) {
+      const u32x4* p = reinterpret_cast<const u32x4*>(row + (size_t)sx0 * 3);
+#pragma unroll
+      for (int q = 0; q < 3; ++q) {
+        const u32x4 t = p[q];
+        w[4 * q] = t[0];
+        w[4 * q + 1] = t[1];
+        w[4 * q + 2] = t[2];
+        w[4 * q + 3] = t[3];
+      }
+    } else {
+#pragma unroll
+      for (int px = 0; px < RUN; ++px) {
+        const int sx = sx0 + px;
+        if ((unsigned)sx < (unsigned)W) {
+#pragma unroll
+          for (int c = 0; c < 3; ++c) {
+            const int b = 3 * px + c;
+            w[b >> 2] |= (uint32_t)row[(size_t)sx * 3 + c] << (8 * (b & 3));
+          }
+        }
+      }
+    }
+  }
+
+  const size_t plane = (size_t)OH * OW;
+  float* out = dst + (size_t)oy * OW + ox0;
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      f32x4 v;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const int b = 3 * (4 * q + j) + c;
+        v[j] = lut[(w[b >> 2] >> (8 * (b & 3))) & 255u];
+      }
+      float* o = out + c * plane + 4 * q;
+      const int ox = ox0 + 4 * q;
+      if (dvec) {
+        if (ox < OW) *reinterpret_cast<f32x4*>(o) = v;
+      } else {
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+          if (ox + j < OW) o[j] = v[j];
+      }
+    }
+  }
+}
+
+__device__ __forceinline__ uint32_t quantise_u8(float v) {
+  return (uint32_t)(int)(fminf(fmaxf(v, 0.0f), 1.0f) * 255.0f);   // clamp(0, 1).mul(255).to(uint8)
+}
+
+__global__ __launch_bounds__(BLOCK) void image_f32_to_u8_kernel(const float* __restrict__ src, int PH, int PW, int top,
+                                                                 int left, uint8_t* __restrict__ dst, int H, int W,
+                                                                 const uint8_t* __restrict__ ref,
+                                                                 unsigned long long* __restrict__ part,
+                                                                 int runs_per_row, long long total_runs) {
+  __shared__ unsigned long long red[BLOCK / 64];
+  const long long g = (long long)blockIdx.x * BLOCK + threadIdx.x;
+  uint32_t sse = 0u;   // 48 squared differences of at most 255^2 each
+  if (g < total_runs) {
+    const int y = (int)(g / runs_per_row);
+    const int x0 = ((int)(g - (long long)y * runs_per_row)) * RUN;
+    const bool full = x0 + RUN <= W;
+    const size_t plane = (size_t)PH * PW;
+    const float* in = src + (size_t)(top + y) * PW + left + x0;
+    const size_t obyte = ((size_t)y * W + x0) * 3;
+
+    uint32_t w[12];   // the run's 48 interleaved output bytes
+#pragma unroll
+    for (int k = 0; k < 12; ++k) w[k] = 0u;
+    // the three planes start a multiple of PH * PW floats apart: one alignment test serves them only if that is a
+    // multiple of four, so each plane is tested
+    if (full && aligned16(in) && aligned16(in + plane) && aligned16(in + 2 * plane)) {
+#pragma unroll
+      for (int c = 0; c < 3; ++c) {
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+          const f32x4 v = *reinterpret_cast<const f32x4*>(in + c * plane + 4 * q);
+#pragma unroll
+          for (int j = 0; j < 4; ++j) {
+            const int b = 3 * (4 * q + j) + c;
+            w[b >> 2] |= quantise_u8(v[j]) << (8 * (b & 3));
+          }
+        }
+      }
+    } else {
+#pragma unroll
+      for (int px = 0; px < RUN; ++px) {
+        if (x0 + px < W) {
+#pragma unroll
+          for (int c = 0; c < 3; ++c) {
+            const int b = 3 * px + c;
+            w[b >> 2] |= quantise_u8(in[c * plane + px]) << (8 * (b & 3));
+          }
+        }
+      }
+    }
+
+    if (ref) {
+      uint32_t r[12];
+#pragma unroll
+      for (int k = 0; k < 12; ++k) r[k] = w[k];   // pixels beyond the row end: equal bytes, no contribution
+      if (full && aligned16(ref + obyte)) {
+        const u32x4* p = reinterpret_cast<const u32x4*>(ref + obyte);
+#pragma unroll
+        for (int q = 0; q < 3; ++q) {
+          const u32x4 t = p[q];
+          r[4 * q] = t[0];
+          r[4 * q + 1] = t[1];
+          r[4 * q + 2] = t[2];
+          r[4 * q + 3] = t[3];
+        }
+      } else {
+#pragma unroll
+        for (int px = 0; px < RUN; ++px) {
+          if (x0 + px < W) {
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+              const int b = 3 * px + c, sh = 8 * (b & 3);
+              r[b >> 2] = (r[b >> 2] & ~(255u << sh)) | ((uint32_t)ref[obyte + b] << sh);
+            }
+          }
+        }
+      }
+#pragma unroll
+      for (int k = 0; k < 12; ++k) {
+#pragma unroll
+        for (int s = 0; s < 32; s += 8) {
+          const int d = (int)((w[k] >> s) & 255u) - (int)((r[k] >> s) & 255u);
+          sse += (uint32_t)(d * d);
+        }
+      }
+    }
+
+    if (full && aligned16(dst + obyte)) {
+      u32x4* p = reinterpret_cast<u32x4*>(dst + obyte);
+#pragma unroll
+      for (int q = 0; q < 3; ++q) {
+        const u32x4 t = {w[4 * q], w[4 * q + 1], w[4 * q + 2], w[4 * q + 3]};
+        p[q] = t;
+      }
+    } else {
+#pragma unroll
+      for (int px = 0; px < RUN; ++px) {
+        if (x0 + px < W) {
+#pragma unroll
+          for (int c = 0; c < 3; ++c) {
+            const int b = 3 * px + c;
+            dst[obyte + b] = (uint8_t)(w[b >> 2] >> (8 * (b & 3)));
+          }
+        }
+      }
+    }
+  }
+
+  if (ref) {   // kernel-uniform: every thread of the workgroup reaches the barrier
+    unsigned long long s = sse;
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) s += __shfl_xor(s, m, 64);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
+    __syncthreads();
+    if (threadIdx.x == 0) part[blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
+  }
+}
+
+// one workgroup: thread t adds partials t, t + 256, ... in index order, then the 256 sums are added in a fixed tree
+__global__ __launch_bounds__(BLOCK) void image_sse_finish_kernel(const unsigned long long* __restrict__ part, int n,
+                                                                  long long* __restrict__ out) {
+  __shared__ unsigned long long red[BLOCK / 64];
+  unsigned long long s = 0ull;
+  for (int i = threadIdx.x; i < n; i += BLOCK) s += part[i];
+#pragma unroll
+  for (int m = 32; m >= 1; m >>= 1) s += __shfl_xor(s, m, 64);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
+  __syncthreads();
+  if (threadIdx.x == 0) *out = (long long)((red[0] + red[1]) + (red[2] + red[3]));
+}
+
+// runs of a rows x cols image and the workgroups that cover them; false = geometry out of range
+bool run_grid(int rows, int cols, int& runs_per_row, long long& total_runs, int& blocks) {
+  if (rows <= 0 || cols <= 0 || rows > MAX_SIDE || cols > MAX_SIDE) return false;
+  runs_per_row = (cols + RUN - 1) / RUN;
+  total_runs = (long long)rows * runs_per_row;
+  blocks = (int)((total_runs + BLOCK - 1) / BLOCK);
+  return true;
+}
+
+}  // namespace
+
+#define ST ((hipStream_t)stream)
+
+extern "C" {
+
+int64_t icm_image_workspace_bytes(int H, int W) {
+  int rpr, blocks;
+  long long total;
+  return run_grid(H, W, rpr, total, blocks) ? (int64_t)blocks * 8 : 0;
+}
+
+int icm_image_u8_to_f32(const uint8_t* src, int H, int W, float* dst, int OH, int OW, int top, int left, void* stream) {
+  int rpr, blocks, srpr, sblocks;
+  long long total, stotal;
+  if (!src || !dst || top < 0 || left < 0) return ICM_ERR_ARG;
+  if (!run_grid(H, W, srpr, stotal, sblocks) || !run_grid(OH, OW, rpr, total, blocks)) return ICM_ERR_ARG;
+  if ((long long)top + H > OH || (long long)left + W > OW) return ICM_ERR_ARG;
+  const int dvec = OW % 4 == 0 && (reinterpret_cast<uintptr_t>(dst) & 15) == 0;
+  hipLaunchKernelGGL(image_u8_to_f32_kernel, dim3(blocks), dim3(BLOCK), 0, ST, src, H, W, dst, OH, OW, top, left, rpr,
+                     total, dvec);
+  ICM_CHECK_LAUNCH();
+  return ICM_OK;
+}
+
+int icm_image_f32_to_u8(const float* src, int PH, int PW, int top, int left, uint8_t* dst, int H, int W,
+                        const uint8_t* ref, int64_t* sse, void* ws, int64_t ws_bytes, void* stream) {
+  int rpr, blocks, prpr, pblocks;
+  long long total, ptotal;
+  if (!src || !dst || top < 0 || left < 0) return ICM_ERR_ARG;
+  if (!run_grid(H, W, rpr, total, blocks) || !run_grid(PH, PW, prpr, ptotal, pblocks)) return ICM_ERR_ARG;
+  if ((long long)top + H > PH || (long long)left + W > PW) return ICM_ERR_ARG;
+  if (ref) {
+    if (!sse || !ws || ws_bytes < (int64_t)blocks * 8) return ICM_ERR_ARG;
+    if ((reinterpret_cast<uintptr_t>(ws) | reinterpret_cast<uintptr_t>(sse)) & 7) return ICM_ERR_ARG;
+  }
+  unsigned long long* part = ref ? static_cast<unsigned long long*>(ws) : nullptr;
+  hipLaunchKernelGGL(image_f32_to_u8_kernel, dim3(blocks), dim3(BLOCK), 0, ST, src, PH, PW, top, left, dst, H, W, ref,
+                     part, rpr, total);
+  ICM_CHECK_LAUNCH();
+  if (ref) {
+    hipLaunchKernelGGL(image_sse_finish_kernel, dim3(1), dim3(BLOCK), 0, ST, part, blocks, reinterpret_cast<long long*>(sse));
+    ICM_CHECK_LAUNCH();
+  }
+  return ICM_OK;
+}
+
+}  // extern "C"

@@ -81,6 +81,7 @@ SYMBOLS = [
     "icm_eb_table_bounds", "icm_eb_pmf_table", "icm_gc_table_centers", "icm_gc_pmf_table", "icm_gc_build_indexes",
     "icm_quantize", "icm_dequantize", "icm_clamp", "icm_pad2d",
     "icm_msssim_workspace_floats", "icm_msssim_fwd", "icm_msssim_bwd",
+    "icm_image_workspace_bytes", "icm_image_u8_to_f32", "icm_image_f32_to_u8",
 ]
 REDUCE_WS_FLOATS = 8192   # ICM_REDUCE_WS_FLOATS
 
@@ -183,6 +184,10 @@ def lib():
         L.icm_dequantize.argtypes = [vp, vp, i64, i64, i64, vp, i64, i32, i32, i32, vp]
         L.icm_clamp.argtypes = [vp, i64, f32, f32, vp]
         L.icm_pad2d.argtypes = [vp, i32, i32, i32, i32, vp, i32, i32, i32, i32, f32, vp]
+        L.icm_image_workspace_bytes.argtypes = [i32, i32]
+        L.icm_image_workspace_bytes.restype = i64
+        L.icm_image_u8_to_f32.argtypes = [vp, i32, i32, vp, i32, i32, i32, i32, vp]
+        L.icm_image_f32_to_u8.argtypes = [vp, i32, i32, i32, i32, vp, i32, i32, vp, vp, vp, i64, vp]
         L.icm_zigzag_order.argtypes = [i32, i32, i32, vp, i32]
         L.icm_zigzag_splits.argtypes = [vp, i64, vp, i32, i32, i32, i32, i32, i32, i32, vp]
         L.icm_zigzag_reverse.argtypes = [vp, vp, i64, i32, i32, i32, i32, i32, i32, i32, vp]

@@ -391,6 +391,25 @@ int icm_clamp(float* p, int64_t n, float lo, float hi, void* stream);
 int icm_pad2d(const float* src, int N, int C, int H, int W, float* dst, int OH, int OW, int top, int left, float value,
               void* stream);
 
+/* ---- 8-bit image boundary of the codec (icm_amd/codec.py; no counterpart in the reference, whose evaluation loop does
+ * this work on the host: torchvision ToTensor + F.pad before compress(), crop + clamp + ToPILImage after decompress(),
+ * utils/eval_model/__main__.py:83-117,89-94,129-131).  Images are single, RGB, at most 32768 pixels a side.
+ * u8_to_f32: src = interleaved [H, W, 3] bytes; dst = planar [1, 3, OH, OW] f32 with dst[c][top + y][left + x] =
+ *   src[y][x][c] / 255 (the correctly rounded quotient, ToTensor's value bit for bit) and +0.0 everywhere else: every
+ *   element of dst is written exactly once, the caller does not clear it.  Needs top, left >= 0, top + H <= OH,
+ *   left + W <= OW.
+ * f32_to_u8: src = planar [1, 3, PH, PW] f32; dst = interleaved [H, W, 3] bytes of the window at (top, left),
+ *   dst[y][x][c] = (uint8)(min(max(src[c][top + y][left + x], 0), 1) * 255), truncated (ToPILImage); NaN input is
+ *   unspecified.  ref != NULL (interleaved [H, W, 3] bytes): the same pass leaves one 64-bit partial sum of
+ *   (dst - ref)^2 per workgroup in ws (icm_image_workspace_bytes(H, W) bytes, 8-byte aligned) and a second launch adds
+ *   them in index order into *sse (device memory, 8-byte aligned).  Integer sums: exact and order-independent; no
+ *   atomics, no host read in between.  ref == NULL: sse / ws are not touched and may be NULL.
+ * No pointer needs more than its natural alignment: runs whose bytes are not 16-byte aligned take a per-pixel path. */
+int64_t icm_image_workspace_bytes(int H, int W);   /* 0 = bad geometry */
+int icm_image_u8_to_f32(const uint8_t* src, int H, int W, float* dst, int OH, int OW, int top, int left, void* stream);
+int icm_image_f32_to_u8(const float* src, int PH, int PW, int top, int left, uint8_t* dst, int H, int W,
+                        const uint8_t* ref, int64_t* sse, void* ws, int64_t ws_bytes, void* stream);
+
 /* ---- test hooks (process-global; used by the parity tests and tools/tune_conv.py only) ----------------------
  * force the implicit-GEMM tile configuration (index into the kernel table; 100 / 101 = the 8-wave K-split kernel of
  * conv_ks8.hip with 64 co x 64 px / 32 co x 128 px blocks where it is eligible; -1 = automatic) / the weight-gradient
