@@ -3,6 +3,8 @@
 // planes are written / read once.
 //
 //   image_u8_to_f32_kernel   interleaved [H, W, 3] bytes -> planar [3, OH, OW] f32, image at (top, left), +0.0 around it
+//   image_batch_u8_to_f32_kernel   the same conversion for a training batch: B crop windows cut out of an arena of
+//                            images (icm_crop_desc each) -> planar [B, 3, CH, CW] f32, +0.0 outside the image
 //   image_f32_to_u8_kernel   planar [3, PH, PW] f32 -> interleaved [H, W, 3] bytes of the window at (top, left);
 //                            with a reference image also one partial sum of squared byte differences per workgroup
 //   image_sse_finish_kernel  adds the partial sums (64-bit integers: exact, whatever the order)
@@ -40,53 +42,39 @@ __device__ const U8Table u8_table = make_u8_table();
 
 __device__ __forceinline__ bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
-// dvec: OW % 4 == 0 and a 16-byte aligned dst (host-checked), so every group of four floats at a column that is a
-// multiple of four lies wholly inside the row and is 16-byte aligned
-__global__ __launch_bounds__(BLOCK) void image_u8_to_f32_kernel(const uint8_t* __restrict__ src, int H, int W,
-                                                                 float* __restrict__ dst, int OH, int OW, int top,
-                                                                 int left, int runs_per_row, long long total_runs,
-                                                                 int dvec) {
-  __shared__ float lut[256];
-  lut[threadIdx.x] = u8_table.v[threadIdx.x];
-  __syncthreads();
-  const long long g = (long long)blockIdx.x * BLOCK + threadIdx.x;
-  if (g >= total_runs) return;
-  const int oy = (int)(g / runs_per_row);
-  const int ox0 = ((int)(g - (long long)oy * runs_per_row)) * RUN;
-  const int sy = oy - top, sx0 = ox0 - left;
+// the 48 bytes of a run from three 16-byte loads (p is 16-byte aligned)
+__device__ __forceinline__ void load_run16(const uint8_t* p, uint32_t (&w)[12]) {
+  const u32x4* q4 = reinterpret_cast<const u32x4*>(p);
+#pragma unroll
+  for (int q = 0; q < 3; ++q) {
+    const u32x4 t = q4[q];
+    w[4 * q] = t[0];
+    w[4 * q + 1] = t[1];
+    w[4 * q + 2] = t[2];
+    w[4 * q + 3] = t[3];
+  }
+}
 
-  uint32_t w[12];   // the run's 48 interleaved bytes, little-endian words; pixels outside the image are zero bytes
+// the pixels sx0 .. sx0 + 15 of a row of W pixels, one byte at a time; pixels outside the row stay zero bytes
+__device__ __forceinline__ void gather_run(const uint8_t* row, int sx0, int W, uint32_t (&w)[12]) {
 #pragma unroll
-  for (int k = 0; k < 12; ++k) w[k] = 0u;
-  if ((unsigned)sy < (unsigned)H && sx0 + RUN > 0 && sx0 < W) {
-    const uint8_t* row = src + ((size_t)sy * W) * 3;
-    if (sx0 >= 0 && sx0 + RUN <= W && aligned16(row + (size_t)sx0 * 3)) {
-      const u32x4* p = reinterpret_cast<const u32x4*>(row + (size_t)sx0 * 3);
+  for (int px = 0; px < RUN; ++px) {
+    const int sx = sx0 + px;
+    if ((unsigned)sx < (unsigned)W) {
 #pragma unroll
-      for (int q = 0; q < 3; ++q) {
-        const u32x4 t = p[q];
-        w[4 * q] = t[0];
-        w[4 * q + 1] = t[1];
-        w[4 * q + 2] = t[2];
-        w[4 * q + 3] = t[3];
-      }
-    } else {
-#pragma unroll
-      for (int px = 0; px < RUN; ++px) {
-        const int sx = sx0 + px;
-        if ((unsigned)sx < (unsigned)W) {
-#pragma unroll
-          for (int c = 0; c < 3; ++c) {
-            const int b = 3 * px + c;
-            w[b >> 2] |= (uint32_t)row[(size_t)sx * 3 + c] << (8 * (b & 3));
-          }
-        }
+      for (int c = 0; c < 3; ++c) {
+        const int b = 3 * px + c;
+        w[b >> 2] |= (uint32_t)row[(size_t)sx * 3 + c] << (8 * (b & 3));
       }
     }
   }
+}
 
-  const size_t plane = (size_t)OH * OW;
-  float* out = dst + (size_t)oy * OW + ox0;
+// a run's 48 interleaved bytes -> 16 floats in each of the three planes, out = the run's first element of plane 0.
+// dvec: OW % 4 == 0 and a 16-byte aligned dst (host-checked), so every group of four floats at a column that is a
+// multiple of four lies wholly inside the row and is 16-byte aligned
+__device__ __forceinline__ void store_run(const float* lut, const uint32_t (&w)[12], float* out, size_t plane, int ox0,
+                                          int OW, int dvec) {
 #pragma unroll
   for (int c = 0; c < 3; ++c) {
 #pragma unroll
@@ -108,6 +96,82 @@ __global__ __launch_bounds__(BLOCK) void image_u8_to_f32_kernel(const uint8_t* _
       }
     }
   }
+}
+
+__global__ __launch_bounds__(BLOCK) void image_u8_to_f32_kernel(const uint8_t* __restrict__ src, int H, int W,
+                                                                 float* __restrict__ dst, int OH, int OW, int top,
+                                                                 int left, int runs_per_row, long long total_runs,
+                                                                 int dvec) {
+  __shared__ float lut[256];
+  lut[threadIdx.x] = u8_table.v[threadIdx.x];
+  __syncthreads();
+  const long long g = (long long)blockIdx.x * BLOCK + threadIdx.x;
+  if (g >= total_runs) return;
+  const int oy = (int)(g / runs_per_row);
+  const int ox0 = ((int)(g - (long long)oy * runs_per_row)) * RUN;
+  const int sy = oy - top, sx0 = ox0 - left;
+
+  uint32_t w[12];   // the run's 48 interleaved bytes, little-endian words; pixels outside the image are zero bytes
+#pragma unroll
+  for (int k = 0; k < 12; ++k) w[k] = 0u;
+  if ((unsigned)sy < (unsigned)H && sx0 + RUN > 0 && sx0 < W) {
+    const uint8_t* row = src + ((size_t)sy * W) * 3;
+    if (sx0 >= 0 && sx0 + RUN <= W && aligned16(row + (size_t)sx0 * 3))
+      load_run16(row + (size_t)sx0 * 3, w);
+    else
+      gather_run(row, sx0, W, w);
+  }
+  store_run(lut, w, dst + (size_t)oy * OW + ox0, (size_t)OH * OW, ox0, OW, dvec);
+}
+
+// Batch of crops out of an arena of images: block-uniform sample b, one thread per run of 16 output pixels.  The
+// window's x0 is arbitrary, so the 48 source bytes of a run start at any byte residue and a 16-byte aligned access is
+// the exception.  A run that lies wholly inside its image row reads the dword-aligned window around its bytes -- 12
+// dwords, 13 when the residue mod 4 is not zero, which need dword alignment only and which the compiler merges into
+// three 16-byte loads and one dword load -- and moves the bytes down by the residue with one v_alignbyte per word.  The
+// window may begin up to 3 bytes before the run and end up to 3 bytes after it, so it is used only where it lies inside
+// [image, image + 3 H W): a first or last run of an image that fails this, and every run that crosses a row end,
+// takes the byte path.
+__global__ __launch_bounds__(BLOCK) void image_batch_u8_to_f32_kernel(const uint8_t* __restrict__ arena,
+                                                                       const icm_crop_desc* __restrict__ desc,
+                                                                       float* __restrict__ dst, int CH, int CW,
+                                                                       int runs_per_row, int runs_per_image,
+                                                                       int blocks_per_image, int dvec) {
+  __shared__ float lut[256];
+  lut[threadIdx.x] = u8_table.v[threadIdx.x];
+  __syncthreads();
+  const int b = blockIdx.x / blocks_per_image;
+  const int r = (blockIdx.x - b * blocks_per_image) * BLOCK + threadIdx.x;
+  if (r >= runs_per_image) return;
+  const icm_crop_desc d = desc[b];
+  const int oy = r / runs_per_row;
+  const int ox0 = (r - oy * runs_per_row) * RUN;
+  const int sy = d.y0 + oy, sx0 = d.x0 + ox0;
+
+  uint32_t w[12];
+#pragma unroll
+  for (int k = 0; k < 12; ++k) w[k] = 0u;
+  if ((unsigned)sy < (unsigned)d.H && sx0 + RUN > 0 && sx0 < d.W) {
+    const uint8_t* img = arena + d.offset;
+    const uint8_t* row = img + ((size_t)sy * d.W) * 3;
+    const uint8_t* p = row + (size_t)sx0 * 3;
+    const uint32_t res = (uint32_t)(reinterpret_cast<uintptr_t>(p) & 3);
+    const uint32_t* a = reinterpret_cast<const uint32_t*>(p - res);
+    const uint8_t* end = img + (size_t)d.H * d.W * 3;
+    if (sx0 >= 0 && sx0 + RUN <= d.W && reinterpret_cast<const uint8_t*>(a) >= img &&
+        reinterpret_cast<const uint8_t*>(a) + (res ? 52 : 48) <= end) {
+      uint32_t t[13];
+#pragma unroll
+      for (int k = 0; k < 12; ++k) t[k] = a[k];
+      t[12] = res ? a[12] : 0u;
+#pragma unroll
+      for (int k = 0; k < 12; ++k) w[k] = __builtin_amdgcn_alignbyte(t[k + 1], t[k], res);
+    } else {
+      gather_run(row, sx0, d.W, w);
+    }
+  }
+  const size_t plane = (size_t)CH * CW;
+  store_run(lut, w, dst + (size_t)b * 3 * plane + (size_t)oy * CW + ox0, plane, ox0, CW, dvec);
 }
 
 __device__ __forceinline__ uint32_t quantise_u8(float v) {
@@ -271,6 +335,19 @@ int icm_image_u8_to_f32(const uint8_t* src, int H, int W, float* dst, int OH, in
   const int dvec = OW % 4 == 0 && (reinterpret_cast<uintptr_t>(dst) & 15) == 0;
   hipLaunchKernelGGL(image_u8_to_f32_kernel, dim3(blocks), dim3(BLOCK), 0, ST, src, H, W, dst, OH, OW, top, left, rpr,
                      total, dvec);
+  ICM_CHECK_LAUNCH();
+  return ICM_OK;
+}
+
+int icm_image_batch_u8_to_f32(const uint8_t* arena, const icm_crop_desc* desc, int B, float* dst, int CH, int CW,
+                              void* stream) {
+  int rpr, bpi;
+  long long rpi;
+  if (!arena || !desc || !dst || B < 1 || !run_grid(CH, CW, rpr, rpi, bpi)) return ICM_ERR_ARG;
+  if ((long long)bpi * B > 0x7fffffffLL) return ICM_ERR_ARG;
+  const int dvec = CW % 4 == 0 && (reinterpret_cast<uintptr_t>(dst) & 15) == 0;
+  hipLaunchKernelGGL(image_batch_u8_to_f32_kernel, dim3((unsigned)(bpi * B)), dim3(BLOCK), 0, ST, arena, desc, dst, CH,
+                     CW, rpr, (int)rpi, bpi, dvec);
   ICM_CHECK_LAUNCH();
   return ICM_OK;
 }

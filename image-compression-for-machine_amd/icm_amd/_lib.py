@@ -82,6 +82,7 @@ SYMBOLS = [
     "icm_quantize", "icm_dequantize", "icm_clamp", "icm_pad2d",
     "icm_msssim_workspace_floats", "icm_msssim_fwd", "icm_msssim_bwd",
     "icm_image_workspace_bytes", "icm_image_u8_to_f32", "icm_image_f32_to_u8",
+    "icm_image_batch_u8_to_f32",
 ]
 REDUCE_WS_FLOATS = 8192   # ICM_REDUCE_WS_FLOATS
 
@@ -188,6 +189,7 @@ def lib():
         L.icm_image_workspace_bytes.restype = i64
         L.icm_image_u8_to_f32.argtypes = [vp, i32, i32, vp, i32, i32, i32, i32, vp]
         L.icm_image_f32_to_u8.argtypes = [vp, i32, i32, i32, i32, vp, i32, i32, vp, vp, vp, i64, vp]
+        L.icm_image_batch_u8_to_f32.argtypes = [vp, vp, i32, vp, i32, i32, vp]
         L.icm_zigzag_order.argtypes = [i32, i32, i32, vp, i32]
         L.icm_zigzag_splits.argtypes = [vp, i64, vp, i32, i32, i32, i32, i32, i32, i32, vp]
         L.icm_zigzag_reverse.argtypes = [vp, vp, i64, i32, i32, i32, i32, i32, i32, i32, vp]

@@ -15,6 +15,9 @@ loss (:438), best-only checkpoints ``<save_path><epoch>.ckpt`` holding epoch / s
   selects ``lmbda * (1 - ms_ssim) + bpp`` instead (upstream CompressAI's ``RateDistortionLoss(metric="ms-ssim")``);
 * under ``torch.distributed.run`` (WORLD_SIZE > 1) every rank trains on its shard of each batch (DistributedSampler)
   and gradients are all-reduced over RCCL by the Trainer; the reference is single-process;
+* ``--device-cache GB`` keeps both splits on the device as 8-bit images (decoded once, ``datasets.DeviceImageCache``)
+  and cuts every batch there with one kernel launch; the per-step host work left is drawing the crop positions.  The
+  crops are the transforms' own (same ``random`` draws); the epoch order comes from ``datasets.EpochSampler``;
 * checkpoints are read with ``weights_only=True``."""
 from __future__ import annotations
 
@@ -27,7 +30,8 @@ import time
 import torch
 from torch.utils.data import DataLoader
 
-from .datasets import CenterCrop, Compose, ImageFolder, RandomCrop, ToTensor
+from .datasets import (CenterCrop, Compose, DeviceCacheLoader, DeviceImageCache, EpochSampler, ImageFolder, RandomCrop,
+                       ToTensor)
 from .losses import METRICS, RateDistortionLoss
 from .trainer import Trainer
 from .zoo import models
@@ -144,6 +148,9 @@ def parse_args(argv):
     p.add_argument("--checkpoint", type=str, default=None, help="Path to a checkpoint")
     p.add_argument("--test-every", type=int, default=5, help="test / checkpoint every N epochs (train.py:505; default: %(default)s)")
     p.add_argument("--max-steps", type=int, default=0, help="stop each epoch after N iterations (0 = full epoch)")
+    p.add_argument("--device-cache", type=float, default=0.0, metavar="GB",
+                   help="keep both splits on the device as 8-bit images, at most GB gigabytes (10^9 bytes), and crop "
+                        "batches there (default: 0 = off, DataLoader workers decode every step)")
     return p.parse_args(argv)
 
 
@@ -180,17 +187,37 @@ def main(argv) -> int:
         import torch.distributed as dist
         dist.init_process_group("nccl", device_id=torch.device(device))
 
-    crop = RandomCrop(args.patch_size, pad_if_needed=True) if args.random_crop else CenterCrop(args.patch_size)
-    train_dataset = ImageFolder(args.dataset, split=args.split, transform=Compose([crop, ToTensor()]))
-    test_dataset = ImageFolder(args.dataset, split=args.test_split, transform=Compose([CenterCrop(args.patch_size), ToTensor()]))
     sampler = None
-    if world > 1:
-        from torch.utils.data.distributed import DistributedSampler
-        sampler = DistributedSampler(train_dataset, num_replicas=world, rank=rank, shuffle=True, drop_last=True)
-    train_dataloader = DataLoader(train_dataset, batch_size=args.batch_size, num_workers=args.num_workers,
-                                  shuffle=sampler is None, sampler=sampler, pin_memory=True, drop_last=world > 1)
-    test_dataloader = DataLoader(test_dataset, batch_size=args.test_batch_size, num_workers=args.num_workers,
-                                 shuffle=False, pin_memory=True)
+    if args.device_cache > 0:
+        budget = int(args.device_cache * 1e9)
+        seed = int(args.seed or 0)
+        try:
+            train_cache = DeviceImageCache(args.dataset, args.split, device, budget, num_workers=args.num_workers)
+            test_cache = DeviceImageCache(args.dataset, args.test_split, device, budget - train_cache.nbytes,
+                                          num_workers=args.num_workers)
+        except ValueError as e:
+            print(f"Error: {e}", file=sys.stderr)
+            if world > 1:
+                dist.destroy_process_group()
+            return 2
+        if rank == 0:
+            print(f"device cache: {len(train_cache) + len(test_cache)} images, "
+                  f"{(train_cache.nbytes + test_cache.nbytes) / 1e9:.2f} GB", flush=True)
+        sampler = EpochSampler(len(train_cache), args.batch_size, seed, rank=rank, world=world)
+        train_dataloader = DeviceCacheLoader(train_cache, sampler, "random" if args.random_crop else "center", args.patch_size)
+        test_dataloader = DeviceCacheLoader(test_cache, EpochSampler(len(test_cache), args.test_batch_size, seed, shuffle=False),
+                                            "center", args.patch_size)
+    else:
+        crop = RandomCrop(args.patch_size, pad_if_needed=True) if args.random_crop else CenterCrop(args.patch_size)
+        train_dataset = ImageFolder(args.dataset, split=args.split, transform=Compose([crop, ToTensor()]))
+        test_dataset = ImageFolder(args.dataset, split=args.test_split, transform=Compose([CenterCrop(args.patch_size), ToTensor()]))
+        if world > 1:
+            from torch.utils.data.distributed import DistributedSampler
+            sampler = DistributedSampler(train_dataset, num_replicas=world, rank=rank, shuffle=True, drop_last=True)
+        train_dataloader = DataLoader(train_dataset, batch_size=args.batch_size, num_workers=args.num_workers,
+                                      shuffle=sampler is None, sampler=sampler, pin_memory=True, drop_last=world > 1)
+        test_dataloader = DataLoader(test_dataset, batch_size=args.test_batch_size, num_workers=args.num_workers,
+                                     shuffle=False, pin_memory=True)
     if args.max_steps > 0:
         train_dataloader = _Limited(train_dataloader, args.max_steps)
 

@@ -410,6 +410,20 @@ int icm_image_u8_to_f32(const uint8_t* src, int H, int W, float* dst, int OH, in
 int icm_image_f32_to_u8(const float* src, int PH, int PW, int top, int left, uint8_t* dst, int H, int W,
                         const uint8_t* ref, int64_t* sse, void* ws, int64_t ws_bytes, void* stream);
 
+/* ---- device-resident training data (icm_amd/datasets.py DeviceImageCache; stands in for the reference's per-step
+ * CenterCrop / RandomCrop(pad_if_needed) + ToTensor + collate on the host, train.py:393-425).  A training batch cut out
+ * of an arena of 8-bit images in one launch: sample b is the interleaved [H, W, 3] byte image at arena + offset, and
+ *   dst[b][c][y][x] = src[y0 + y][x0 + x][c] / 255   (the same table as icm_image_u8_to_f32: ToTensor's value)
+ * with +0.0 wherever (y0 + y, x0 + x) lies outside the image; y0 / x0 are signed (padding crops start at negative
+ * coordinates) and lie in [-2^30, 2^30].  dst = planar [B, 3, CH, CW] f32, every element written exactly once, the
+ * caller does not clear it.  desc = B descriptors in DEVICE memory, produced and checked by the caller: the kernel
+ * trusts them and reads only inside [offset, offset + 3 H W) of each image.  One launch, no atomics, no allocation, no
+ * synchronisation (graph-capturable).  No pointer needs more than its natural alignment (desc: 8 bytes).
+ * ICM_ERR_ARG before any launch: null pointers, B < 1, CH or CW outside 1..32768 (or more than 2^31 - 1 workgroups). */
+typedef struct { int64_t offset; int32_t H, W, y0, x0; } icm_crop_desc;   /* 24 bytes */
+int icm_image_batch_u8_to_f32(const uint8_t* arena, const icm_crop_desc* desc, int B, float* dst /* [B,3,CH,CW] */,
+                              int CH, int CW, void* stream);
+
 /* ---- test hooks (process-global; used by the parity tests and tools/tune_conv.py only) ----------------------
  * force the implicit-GEMM tile configuration (index into the kernel table; 100 / 101 = the 8-wave K-split kernel of
  * conv_ks8.hip with 64 co x 64 px / 32 co x 128 px blocks where it is eligible; -1 = automatic) / the weight-gradient
