@@ -933,19 +933,86 @@ __global__ __launch_bounds__(256) void wgrad_reduce_kernel(const RedDesc d) {
   }
 }
 
-// test hooks (icm_debug_force_wgrad_cfg): kernel variant 0 = <2,1,7>, 1 = <2,2,9>, 2 = <4,4,4> (general kernel);
-// 3 = t33<3,3,1,1>, 4 = t33<6,6,2,2>, 5 = t33<3,6,1,2>, 6 = t33<6,3,2,1> (3 x 3 tiles per wave, one tap per workgroup);
-// XCD-aware workgroup order 0 / 1; -1 = automatic choice
-#define WG_NVARIANTS 15  /* 7 = t33<3,3,1,1,tap-per-wave>: 96 x 96 x 4 taps per workgroup (3x3 problems);
-                          * 8 / 9 = tap9<3,3> / tap9<2,2>: all nine taps from one DMA staging (3x3 s1 p1, no activation) */
+// ---- kernel variants: one row each; the row index is the variant id (icm_debug_force_wgrad_cfg, icm_debug_wgrad_plan,
+// WG_CASES of tests/test_gpu_ops.py).  Everything the planner and the launch need to know about a variant is its row.
+enum WgFamily {
+  WG_GENERAL,    // wgrad_kernel<TA,TB,NACC>: 4 MFMA + 4 loader waves, NACC accumulator tiles per wave
+  WG_T33,        // wgrad_t33_kernel: 3 x 3 tiles per wave, one tap per workgroup, spare waves split K (folded through LDS)
+  WG_T33_TAPW,   // its tap-per-wave form: 96 x 96 x 4 taps per workgroup (one per MFMA wave), no K split
+  WG_TAP9,       // wgrad_tap9_kernel: all nine taps of a 3x3 stride-1 pad-1 problem from one DMA staging (no activation)
+  WG_TAP25,      // its 25-tap form for 5x5 pad-2 problems (stride 1 or 2): 96 x 32 blocks, three taps per wave
+  WG_DMA1,       // wgrad_dma1_kernel: 1x1, activation-free: 8 MFMA waves, DMA-only staging, K split folded through LDS
+};
+typedef void (*WgKernel)(const WgDesc);
+struct WgVariant {
+  WgFamily fam;
+  int ta, tb, nacc;   // (a, b) block of 32 ta x 32 tb channels; accumulator tiles per wave
+  int tpg;            // taps per tap-group: min(taps, tpg) ...
+  bool halves;        // ... or, with more taps than tpg, two groups of half the taps each (refused if still > tpg)
+  int lds_kb;         // LDS budget the variant is admitted under (150 for the general kernel, 160 for the later ones: kept)
+  WgKernel fn, fn_v4;   // kernel; WG_DMA1: its 16-byte-DMA form (aligned operands, 64-pixel tiles)
+};
+static const WgVariant kWgVariants[] = {
+    /*  0 */ {WG_GENERAL, 2, 1, 7, 14, true, 150, wgrad_kernel<2, 1, 7>, nullptr},   // <=14 taps x 2 a-tiles = 28 tiles = 7 per MFMA wave
+    /*  1 */ {WG_GENERAL, 2, 2, 9, 9, false, 150, wgrad_kernel<2, 2, 9>, nullptr},
+    /*  2 */ {WG_GENERAL, 4, 4, 4, 1, false, 150, wgrad_kernel<4, 4, 4>, nullptr},
+    /*  3 */ {WG_T33, 3, 3, 9, 1, false, 160, wgrad_t33_kernel<3, 3, 1, 1>, nullptr},
+    /*  4 */ {WG_T33, 6, 6, 9, 1, false, 160, wgrad_t33_kernel<6, 6, 2, 2>, nullptr},
+    /*  5 */ {WG_T33, 3, 6, 9, 1, false, 160, wgrad_t33_kernel<3, 6, 1, 2>, nullptr},
+    /*  6 */ {WG_T33, 6, 3, 9, 1, false, 160, wgrad_t33_kernel<6, 3, 2, 1>, nullptr},
+    /*  7 */ {WG_T33_TAPW, 3, 3, 9, 4, false, 160, wgrad_t33_kernel<3, 3, 1, 1, true>, nullptr},
+    /*  8 */ {WG_TAP9, 3, 3, 9, 9, false, 160, wgrad_tap9_kernel<3, 3>, nullptr},   // 96 x 96 blocks
+    /*  9 */ {WG_TAP9, 2, 2, 9, 9, false, 160, wgrad_tap9_kernel<2, 2>, nullptr},   // 64 x 64 blocks
+    /* 10 */ {WG_TAP25, 3, 1, 10, 25, false, 160, wgrad_tap9_kernel<3, 1, 3>, nullptr},
+    /* 11 */ {WG_DMA1, 6, 6, 9, 1, false, 160, wgrad_dma1_kernel<6, 6, 2, 2, false>, wgrad_dma1_kernel<6, 6, 2, 2, true>},
+    /* 12 */ {WG_DMA1, 3, 6, 9, 1, false, 160, wgrad_dma1_kernel<3, 6, 1, 2, false>, wgrad_dma1_kernel<3, 6, 1, 2, true>},
+    /* 13 */ {WG_DMA1, 6, 3, 9, 1, false, 160, wgrad_dma1_kernel<6, 3, 2, 1, false>, wgrad_dma1_kernel<6, 3, 2, 1, true>},
+    /* 14 */ {WG_DMA1, 3, 3, 9, 1, false, 160, wgrad_dma1_kernel<3, 3, 1, 1, false>, wgrad_dma1_kernel<3, 3, 1, 1, true>},
+};
+constexpr int WG_NVARIANTS = sizeof(kWgVariants) / sizeof(kWgVariants[0]);
+// test hooks (icm_debug_force_wgrad_cfg): kernel variant (-1 = automatic choice), XCD-aware workgroup order 0 / 1 / -1
 static int g_force_variant = -1, g_force_xcd = -1;
 
 struct WgPlan {
-  int ta, tb, nacc, tpg, ws;
+  int variant, tpg;   // row of kWgVariants; taps per tap-group
   int lgTW, lgTH, lgTI, lgNPX, PH, PW, PP, CS;
   int tiles_x, tiles_y, tiles_n, ntiles, nsplit, natile, nbtile, ngroups;
   size_t lds;
 };
+
+// the two LDS buffers of a block: small-grid tile [32 ta][pixels + 1] + big-grid patch [32 tb][CS] each
+static size_t wg_staging_bytes(int ta, int tb, int lgNPX, int CS) {
+  return (size_t)2 * (ta * 32 * ((1 << lgNPX) + 1) + tb * 32 * CS) * 4;
+}
+// the fold of the K-split waves parks up to two accumulator sets per (wa, wb) group in the staging LDS
+static size_t wg_fold_bytes(const WgVariant& v) {
+  const int waves = v.fam == WG_T33 ? 4 : (v.fam == WG_DMA1 ? 8 : 0);
+  if (!waves) return 0;
+  const int groups = (v.ta / 3) * (v.tb / 3), wk = waves / groups;
+  return wk > 1 ? (size_t)groups * std::min(wk - 1, 2) * 9 * 16 * 64 * 4 : 0;
+}
+// Does variant vi take problem a at the pixel-tile size of p (lgNPX, CS)?  If so p.variant, p.tpg and p.lds (the
+// dynamic LDS of the launch) are set; p is untouched otherwise.
+static bool wg_admit(int vi, const icm_wgrad_args& a, WgPlan& p) {
+  const WgVariant& v = kWgVariants[vi];
+  const int ntaps = a.KH * a.KW;
+  const bool plain = a.act_s == ICM_ACT_NONE && a.act_b == ICM_ACT_NONE;   // DMA-only staging applies no activation
+  if (v.fam == WG_DMA1 && !(ntaps == 1 && a.stride == 1 && a.pad == 0 && plain)) return false;
+  if (v.fam == WG_TAP9 && !(a.KH == 3 && a.KW == 3 && a.stride == 1 && a.pad == 1 && plain)) return false;
+  if (v.fam == WG_TAP25 && !(a.KH == 5 && a.KW == 5 && a.pad == 2 && plain)) return false;
+  const size_t need = std::max(wg_staging_bytes(v.ta, v.tb, p.lgNPX, p.CS), wg_fold_bytes(v));
+  if (need > (size_t)v.lds_kb * 1024) return false;
+  const int tpg = v.halves && ntaps > v.tpg ? (ntaps + 1) / 2 : std::min(ntaps, v.tpg);
+  if (tpg > v.tpg) return false;
+  p.variant = vi; p.tpg = tpg; p.lds = need;
+  return true;
+}
+// (a, b) area of the problem padded to whole blocks of 32 ta x 32 tb channels, times an optional cost factor
+static double wg_padded_area(const icm_wgrad_args& a, int ta, int tb, double factor = 1.0) {
+  return (double)cdiv(a.Ca, 32 * ta) * 32 * ta * cdiv(a.Cb, 32 * tb) * 32 * tb * factor;
+}
+// staging factor of the 1x1 cost model (plan_wgrad): max(1, kappa x staged bytes per MAC)
+static double wg_staging_factor(int ta, int tb) { return std::max(1.0, 5.2 * (1.0 / ta + 1.0 / tb)); }
 
 static int plan_wgrad(const icm_wgrad_args& a, WgPlan& p, int nproblems = 1) {
   if (!a.gs || !a.gb || a.N <= 0 || a.Ca <= 0 || a.Cb <= 0 || a.KH * a.KW > WG_MAX_TAPS) return ICM_ERR_ARG;
@@ -969,77 +1036,19 @@ static int plan_wgrad(const icm_wgrad_args& a, WgPlan& p, int nproblems = 1) {
     p.PP = p.PH * p.PW;
     p.CS = TI * p.PP;
     if ((p.CS & 1) == 0) p.CS += 1;
-    auto lds_of = [&](int ta, int tb) {
-      return (size_t)2 * (ta * 32 * ((1 << lg) + 1) + tb * 32 * p.CS) * 4;
-    };
-    p.ws = 0;
-    auto t33 = [&](int v, int ta, int tb) -> bool {
-      // the fold of the K-split waves parks up to two accumulator sets per (wa, wb) group in the staging LDS
-      const int wk = 4 / ((ta / 3) * (tb / 3));
-      const size_t fold = wk > 1 ? (size_t)(ta / 3) * (tb / 3) * std::min(wk - 1, 2) * 9 * 16 * 64 * 4 : 0;
-      const size_t need = std::max(lds_of(ta, tb), fold);
-      if (need > 160 * 1024) return false;
-      p.ta = ta; p.tb = tb; p.nacc = 9; p.tpg = 1; p.ws = v;
-      return true;
-    };
-    auto dma1 = [&](int v, int ta, int tb) -> bool {   // 1x1, activation-free: 8 MFMA waves, DMA-only staging
-      if (!(ntaps == 1 && a.stride == 1 && a.pad == 0 && a.act_s == ICM_ACT_NONE && a.act_b == ICM_ACT_NONE)) return false;
-      const int groups = (ta / 3) * (tb / 3), wk = 8 / groups;
-      const size_t fold = (size_t)groups * std::min(wk - 1, 2) * 9 * 16 * 64 * 4;
-      if (std::max(lds_of(ta, tb), fold) > 160 * 1024) return false;
-      p.ta = ta; p.tb = tb; p.nacc = 9; p.tpg = 1; p.ws = v;
-      return true;
-    };
-    auto variant = [&](int v) -> bool {   // kernel variant v for this tile size; false if its LDS does not fit
-      switch (v) {
-        case 11: return dma1(11, 6, 6);
-        case 12: return dma1(12, 3, 6);
-        case 13: return dma1(13, 6, 3);
-        case 14: return dma1(14, 3, 3);
-        case 3: return t33(3, 3, 3);
-        case 4: return t33(4, 6, 6);
-        case 5: return t33(5, 3, 6);
-        case 6: return t33(6, 6, 3);
-        case 8:
-        case 9: {   // all nine taps of a 3x3 stride-1 problem from one DMA staging: 96 x 96 (8) or 64 x 64 (9) blocks
-          const int t = v == 8 ? 3 : 2;
-          if (!(a.KH == 3 && a.KW == 3 && a.stride == 1 && a.pad == 1 && a.act_s == ICM_ACT_NONE &&
-                a.act_b == ICM_ACT_NONE) || lds_of(t, t) > 160 * 1024)
-            return false;
-          p.ta = t; p.tb = t; p.nacc = 9; p.tpg = 9; p.ws = v;
-          return true;
-        }
-        case 10:   // all 25 taps of a 5x5 problem (stride 1 or 2) from one DMA staging: 96 x 32 blocks, three taps per wave
-          if (!(a.KH == 5 && a.KW == 5 && a.pad == 2 && a.act_s == ICM_ACT_NONE && a.act_b == ICM_ACT_NONE) ||
-              lds_of(3, 1) > 160 * 1024)
-            return false;
-          p.ta = 3; p.tb = 1; p.nacc = 10; p.tpg = 25; p.ws = v;
-          return true;
-        case 7:   // 96 x 96 (a, b) block, four taps per workgroup (one per MFMA wave), no K split
-          if (lds_of(3, 3) > 160 * 1024) return false;
-          p.ta = 3; p.tb = 3; p.nacc = 9; p.tpg = std::min(ntaps, 4); p.ws = 7;
-          return true;
-        case 2: if (lds_of(4, 4) > 150 * 1024) return false; p.ta = 4; p.tb = 4; p.nacc = 4; p.tpg = 1; return true;
-        case 1: if (lds_of(2, 2) > 150 * 1024) return false; p.ta = 2; p.tb = 2; p.nacc = 9; p.tpg = std::min(ntaps, 9); return true;
-        default:   // <=14 taps per group x 2 a-tiles = 28 tiles = 7 per MFMA wave
-          if (lds_of(2, 1) > 150 * 1024) return false;
-          p.ta = 2; p.tb = 1; p.nacc = 7; p.tpg = ntaps <= 14 ? ntaps : (ntaps + 1) / 2;
-          return p.tpg <= 14;
-      }
-    };
+    auto variant = [&](int v) { return wg_admit(v, a, p); };   // kernel variant v for this tile size; false if it does not fit
     if (g_force_variant >= 0) ok = variant(g_force_variant);
     else if (ntaps == 1) {
       // 1x1 problems: the loaders are latency-bound, so time ~ padded MACs x max(1, kappa x staged bytes per MAC);
       // kappa from the measured 45 TF of the 96 x 96 tile (0.29 of the MFMA peak; profiles/r02_*)
-      static const struct { int v, ta, tb; } cand[] = {{4, 6, 6}, {5, 3, 6}, {6, 6, 3}, {3, 3, 3}, {2, 4, 4}};
+      static const int cand[] = {4, 5, 6, 3, 2};
       double bestc = 1e300;
       int bestv = -1;
-      for (const auto& c : cand) {
-        const size_t need = c.v == 2 ? lds_of(4, 4) : lds_of(c.ta, c.tb);
-        if (need > 160 * 1024) continue;
-        const double area = (double)cdiv(a.Ca, 32 * c.ta) * 32 * c.ta * cdiv(a.Cb, 32 * c.tb) * 32 * c.tb;
-        const double cost = area * std::max(1.0, 5.2 * (1.0 / c.ta + 1.0 / c.tb));
-        if (cost < bestc - 1e-9) { bestc = cost; bestv = c.v; }
+      for (const int v : cand) {
+        const WgVariant& c = kWgVariants[v];
+        if (wg_staging_bytes(c.ta, c.tb, lg, p.CS) > 160 * 1024) continue;
+        const double cost = wg_padded_area(a, c.ta, c.tb, wg_staging_factor(c.ta, c.tb));
+        if (cost < bestc - 1e-9) { bestc = cost; bestv = v; }
       }
       ok = bestv >= 0 && variant(bestv);
       // activation-free operands: the DMA-only kernel (8 MFMA waves).  Staging costs it little, so the block is chosen
@@ -1048,38 +1057,38 @@ static int plan_wgrad(const icm_wgrad_args& a, WgPlan& p, int nproblems = 1) {
       // (profiles/r02_tune_wgrad_dma1.txt)
       static const int dma1_on = env_int("ICM_WG_DMA1", 1);
       if (ok && dma1_on && a.act_s == ICM_ACT_NONE && a.act_b == ICM_ACT_NONE && a.stride == 1 && a.pad == 0) {
-        static const struct { int v, ta, tb; } dc[] = {{13, 6, 3}, {12, 3, 6}, {11, 6, 6}, {14, 3, 3}};
+        static const int dc[] = {13, 12, 11, 14};
         double ba = 1e300;
         int bv = -1;
-        for (const auto& c : dc) {
-          const double area = (double)cdiv(a.Ca, 32 * c.ta) * 32 * c.ta * cdiv(a.Cb, 32 * c.tb) * 32 * c.tb;
+        for (const int v : dc) {
+          const double area = wg_padded_area(a, kWgVariants[v].ta, kWgVariants[v].tb);
           if (area < ba - 1e-9) {
             WgPlan keep = p;
-            if (variant(c.v)) { ba = area; bv = c.v; }
+            if (variant(v)) { ba = area; bv = v; }
             p = keep;
           }
         }
         if (bv >= 0) variant(bv);
       }
       // a smaller pixel tile is only worth it for the big tiles that need it (<6,6> does not fit 64 pixels)
-      if (ok && lg == 6 && p.ws < 11) {
-        const double area6 = (double)cdiv(a.Ca, 32 * p.ta) * 32 * p.ta * cdiv(a.Cb, 32 * p.tb) * 32 * p.tb *
-                             std::max(1.0, 5.2 * (1.0 / p.ta + 1.0 / p.tb));
-        const double area66 = (double)cdiv(a.Ca, 192) * 192 * cdiv(a.Cb, 192) * 192 * std::max(1.0, 5.2 / 3.0);
+      if (ok && lg == 6 && kWgVariants[p.variant].fam != WG_DMA1) {
+        const WgVariant& c = kWgVariants[p.variant];
+        const double area6 = wg_padded_area(a, c.ta, c.tb, wg_staging_factor(c.ta, c.tb));
+        const double area66 = wg_padded_area(a, 6, 6, std::max(1.0, 5.2 / 3.0));
         if (area66 < area6 - 1e-9) ok = false;   // retry at lg = 5, where <6,6> fits
       }
     }
-    else if (ntaps <= 9 && lds_of(2, 2) <= 150 * 1024) {
+    else if (ntaps <= 9 && wg_staging_bytes(2, 2, lg, p.CS) <= 150 * 1024) {
       // 3x3: 64 x 64 x 9-tap tiles, unless 96-wide tiles fit the channel counts so much better (96 / 192 channels:
       // 100 % against 56 %) that idling the waves without a tap in the last tap group (9 taps = 4 + 4 + 1) still wins
-      const double pad64 = (double)cdiv(a.Ca, 64) * 64 * cdiv(a.Cb, 64) * 64;
-      const double pad96 = (double)cdiv(a.Ca, 96) * 96 * cdiv(a.Cb, 96) * 96 * (4.0 * cdiv(ntaps, 4) / ntaps);
+      const double pad64 = wg_padded_area(a, 2, 2);
+      const double pad96 = wg_padded_area(a, 3, 3, 4.0 * cdiv(ntaps, 4) / ntaps);
       // activation-free 3x3 stride-1 problems whose channels fit 96-wide blocks, with many pixels: the nine-tap
       // single-staging kernel (96 -> 96 @ 64x64 x6: 92 TF against 65 for the tap-group kernel and 54 for <2,2,9>).  For
       // the 4 096-pixel slice-chain problems <2,2,9> (two workgroups per CU, 64 tiles per problem) stays ahead
       // (77 vs 71 TF at 480 -> 224 x10; profiles/r02_tune_wgrad_tap9.txt), as it does over the 64 x 64 tap9 form.
       static const int tap9_on = env_int("ICM_WG_TAP9", 1);
-      const double p96 = (double)cdiv(a.Ca, 96) * 96 * cdiv(a.Cb, 96) * 96;
+      const double p96 = wg_padded_area(a, 3, 3);
       ok = tap9_on && ntaps == 9 && p96 <= pad64 && (long long)a.N * a.OH * a.OW >= 16384 && variant(8);
       if (!ok) ok = (ntaps > 1 && pad96 * 1.1 < pad64 && variant(7)) || variant(1);
     }
@@ -1090,23 +1099,13 @@ static int plan_wgrad(const icm_wgrad_args& a, WgPlan& p, int nproblems = 1) {
       if (!ok) ok = variant(0);
     }
     if (ok && TI * p.PP > ICM_MAXJ * 64) ok = false;   // PlaneMap capacity
-    if (ok) {
-      p.lds = lds_of(p.ta, p.tb);
-      if (p.ws && p.ws < 7) {
-        const int wk = 4 / ((p.ta / 3) * (p.tb / 3));
-        if (wk > 1) p.lds = std::max(p.lds, (size_t)(p.ta / 3) * (p.tb / 3) * std::min(wk - 1, 2) * 9 * 16 * 64 * 4);
-      }
-      if (p.ws >= 11) {
-        const int groups = (p.ta / 3) * (p.tb / 3), wk = 8 / groups;
-        p.lds = std::max(p.lds, (size_t)groups * std::min(wk - 1, 2) * 9 * 16 * 64 * 4);
-      }
-    }
   }
   if (!ok) return ICM_ERR_UNSUPPORTED;
+  const WgVariant& v = kWgVariants[p.variant];
   const int TW = 1 << p.lgTW, TH = 1 << p.lgTH, TI = 1 << p.lgTI;
   p.tiles_x = cdiv(a.OW, TW); p.tiles_y = cdiv(a.OH, TH); p.tiles_n = cdiv(a.N, TI);
   p.ntiles = p.tiles_x * p.tiles_y * p.tiles_n;
-  p.natile = cdiv(a.Ca, 32 * p.ta); p.nbtile = cdiv(a.Cb, 32 * p.tb); p.ngroups = cdiv(ntaps, p.tpg);
+  p.natile = cdiv(a.Ca, 32 * v.ta); p.nbtile = cdiv(a.Cb, 32 * v.tb); p.ngroups = cdiv(ntaps, p.tpg);
   const int base = p.natile * p.nbtile * p.ngroups * std::max(1, nproblems);
   // pixel splits: minimise (rounds of workgroups over the CUs) x (pixel tiles per workgroup + un-overlapped
   // prologue), with a small charge per split for the extra slab traffic
@@ -1123,93 +1122,100 @@ static int plan_wgrad(const icm_wgrad_args& a, WgPlan& p, int nproblems = 1) {
   return ICM_OK;
 }
 
-}  // namespace icm
-
-extern "C" {
-
-int64_t icm_wgrad_workspace_floats_grouped(const icm_wgrad_args* a, int n) {
-  icm::WgPlan p;
-  if (a && n >= 1 && a->algo == ICM_ALGO_WINOGRAD) {
-    int nsplit = 0, nchunks = 0;
-    if (!a->gs || !a->gb || a->N <= 0 || a->Ca <= 0 || a->Cb <= 0 || icm::wgrad_wino_plan(*a, n, &nsplit, &nchunks)) return -1;
-    return (int64_t)nsplit * 16 * a->Ca * a->Cb + (int64_t)nsplit * a->Ca;
-  }
-  if (!a || n < 1 || icm::plan_wgrad(*a, p, n)) return -1;
-  return (int64_t)p.nsplit * a->KH * a->KW * a->Ca * a->Cb + (int64_t)p.nsplit * a->Ca;
+// ---- host-side rules shared by the direct and the Winograd (16 transform points as "taps") form
+// workspace of one problem: nsplit slabs [taps][Ca][Cb], then the bias partials [nsplit][Ca]
+static long long slab_floats(int nsplit, int taps_in_slab, int Ca, int Cb) { return (long long)nsplit * taps_in_slab * Ca * Cb; }
+static long long workspace_floats(int nsplit, int taps_in_slab, int Ca, int Cb) {
+  return slab_floats(nsplit, taps_in_slab, Ca, Cb) + (long long)nsplit * Ca;
 }
-int64_t icm_wgrad_workspace_floats(const icm_wgrad_args* a) { return icm_wgrad_workspace_floats_grouped(a, 1); }
-
-static int wgrad_grouped(const icm_wgrad_args* arr, int n, hipStream_t stream) {
-  using namespace icm;
-  if (!arr || n < 1 || n > WG_MAXG) return ICM_ERR_ARG;
-  const icm_wgrad_args* a = &arr[0];
-  if (a->algo == ICM_ALGO_WINOGRAD) {
-    int nsplit = 0, nchunks = 0;
-    if (!a->gs || !a->gb || a->N <= 0 || a->Ca <= 0 || a->Cb <= 0) return ICM_ERR_ARG;
-    int rcw = wgrad_wino_plan(*a, n, &nsplit, &nchunks);
-    if (rcw) return rcw;
-    if ((long long)a->N * ((a->W + 1) / 2) * ((a->H + 1) / 2) >= 65536) return ICM_ERR_UNSUPPORTED;   // tile index fits the fast division
-    const long long slab_all = (long long)nsplit * 16 * a->Ca * a->Cb;
-    float* wsp[WG_MAXG];
-    float* dbp[WG_MAXG];
-    RedDesc r{};
-    for (int i = 0; i < n; ++i) {
-      const icm_wgrad_args& b = arr[i];
-      if (!b.gs || !b.gb || !b.dw || !b.ws) return ICM_ERR_ARG;
-      if (b.Ca != a->Ca || b.Cb != a->Cb || b.OH != a->OH || b.OW != a->OW || b.H != a->H || b.W != a->W || b.N != a->N ||
-          b.KH != a->KH || b.KW != a->KW || b.stride != a->stride || b.pad != a->pad || b.act_s != a->act_s ||
-          b.act_b != a->act_b || b.gs_bs != a->gs_bs || b.gb_bs != a->gb_bs || b.algo != a->algo)
-        return ICM_ERR_ARG;
-      if (b.ws_floats > 0 && b.ws_floats < slab_all + (long long)nsplit * a->Ca) return ICM_ERR_ARG;
-      wsp[i] = b.ws;
-      dbp[i] = b.dbias ? b.ws + slab_all : nullptr;
-    }
-    rcw = launch_wgrad_wino(arr, n, nsplit, nchunks, wsp, dbp, stream);
-    if (rcw) return rcw;
-    bool any_bias = false;
-    for (int i = 0; i < WG_MAXG; ++i) {
-      const icm_wgrad_args& b = arr[i < n ? i : 0];
-      r.g[i].ws = b.ws; r.g[i].dw = b.dw; r.g[i].dbias_ws = b.dbias ? b.ws + slab_all : nullptr; r.g[i].dbias = b.dbias;
-      r.g[i].accum = b.accum; r.g[i].accum_bias = b.accum_bias;
-      r.g[i].dw_ld = b.dw_ld > 0 ? b.dw_ld : a->Cb;
-      if (r.g[i].dw_ld < a->Cb) return ICM_ERR_ARG;
-      if (i < n) any_bias |= b.dbias != nullptr;
-    }
-    r.Ca = a->Ca; r.Cb = a->Cb; r.ntaps = 16; r.nsplit = nsplit; r.nsplit_bias = nsplit; r.vec4 = 0; r.wino = 1;
-    r.nwblocks = (int)(((long long)a->Ca * a->Cb + 63) / 64);
-    const int rblocks = r.nwblocks + (any_bias ? cdiv(a->Ca, 16) : 0);
-    hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(rblocks, n), dim3(256), 0, stream, r);
-    ICM_CHECK_LAUNCH();
-    return ICM_OK;
+// every problem of a grouped launch has its pointers and the geometry of problem 0
+static bool members_agree(const icm_wgrad_args* arr, int n) {
+  const icm_wgrad_args& a = arr[0];
+  for (int i = 0; i < n; ++i) {
+    const icm_wgrad_args& b = arr[i];
+    if (!b.gs || !b.gb || !b.dw || !b.ws) return false;
+    if (b.Ca != a.Ca || b.Cb != a.Cb || b.OH != a.OH || b.OW != a.OW || b.H != a.H || b.W != a.W || b.N != a.N ||
+        b.KH != a.KH || b.KW != a.KW || b.stride != a.stride || b.pad != a.pad || b.act_s != a.act_s ||
+        b.act_b != a.act_b || b.gs_bs != a.gs_bs || b.gb_bs != a.gb_bs || b.algo != a.algo)
+      return false;
   }
-  if (a->algo != ICM_ALGO_DIRECT) return ICM_ERR_ARG;
+  return true;
+}
+// the slabs (+ bias partials) of this launch's split count must fit every caller's workspace
+static bool workspaces_fit(const icm_wgrad_args* arr, int n, long long need) {
+  for (int i = 0; i < n; ++i)
+    if (arr[i].ws_floats > 0 && arr[i].ws_floats < need) return false;
+  return true;
+}
+// descriptor of the reduction over the nsplit slabs of [taps][Ca][Cb] each problem's kernel leaves in its workspace
+static int fill_reduce(RedDesc& r, const icm_wgrad_args* arr, int n, int nsplit, int taps_in_slab, int wino) {
+  const icm_wgrad_args& a = arr[0];
+  const long long slab_all = slab_floats(nsplit, taps_in_slab, a.Ca, a.Cb), CaCb = (long long)a.Ca * a.Cb;
+  bool v4 = taps_in_slab == 1 && (CaCb % 4) == 0;
+  for (int i = 0; i < WG_MAXG; ++i) {   // unused members repeat member 0
+    const icm_wgrad_args& b = arr[i < n ? i : 0];
+    r.g[i].ws = b.ws; r.g[i].dw = b.dw; r.g[i].dbias_ws = b.dbias ? b.ws + slab_all : nullptr; r.g[i].dbias = b.dbias;
+    r.g[i].accum = b.accum; r.g[i].accum_bias = b.accum_bias;
+    r.g[i].dw_ld = b.dw_ld > 0 ? b.dw_ld : a.Cb;
+    if (r.g[i].dw_ld < a.Cb) return ICM_ERR_ARG;
+    v4 = v4 && ((reinterpret_cast<uintptr_t>(b.ws) & 15) == 0) && ((reinterpret_cast<uintptr_t>(b.dw) & 15) == 0);
+    if (r.g[i].dw_ld != a.Cb) v4 = v4 && (a.Cb % 4) == 0 && (r.g[i].dw_ld % 4) == 0;
+  }
+  r.Ca = a.Ca; r.Cb = a.Cb; r.ntaps = taps_in_slab; r.nsplit = nsplit; r.nsplit_bias = nsplit; r.wino = wino;
+  r.vec4 = v4 ? 1 : 0;
+  r.nwblocks = (int)((CaCb + 63) / 64);   // 16 float4 positions (1x1) or 64 positions (multi-tap) per workgroup
+  return ICM_OK;
+}
+static int launch_reduce(const RedDesc& r, const icm_wgrad_args* arr, int n, hipStream_t stream) {
+  bool any_bias = false;
+  for (int i = 0; i < n; ++i) any_bias |= arr[i].dbias != nullptr;
+  const int rblocks = r.nwblocks + (any_bias ? cdiv(r.Ca, 16) : 0);
+  hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(rblocks, n), dim3(256), 0, stream, r);
+  ICM_CHECK_LAUNCH();
+  return ICM_OK;
+}
+
+static int wgrad_wino_grouped(const icm_wgrad_args* arr, int n, hipStream_t stream) {
+  const icm_wgrad_args* a = &arr[0];
+  int nsplit = 0, nchunks = 0;
+  if (!a->gs || !a->gb || a->N <= 0 || a->Ca <= 0 || a->Cb <= 0) return ICM_ERR_ARG;
+  int rc = wgrad_wino_plan(*a, n, &nsplit, &nchunks);
+  if (rc) return rc;
+  if ((long long)a->N * ((a->W + 1) / 2) * ((a->H + 1) / 2) >= 65536) return ICM_ERR_UNSUPPORTED;   // tile index fits the fast division
+  if (!members_agree(arr, n) || !workspaces_fit(arr, n, workspace_floats(nsplit, 16, a->Ca, a->Cb))) return ICM_ERR_ARG;
+  const long long slab_all = slab_floats(nsplit, 16, a->Ca, a->Cb);
+  float* wsp[WG_MAXG];
+  float* dbp[WG_MAXG];
+  for (int i = 0; i < n; ++i) {
+    wsp[i] = arr[i].ws;
+    dbp[i] = arr[i].dbias ? arr[i].ws + slab_all : nullptr;
+  }
+  rc = launch_wgrad_wino(arr, n, nsplit, nchunks, wsp, dbp, stream);
+  if (rc) return rc;
+  RedDesc r{};
+  rc = fill_reduce(r, arr, n, nsplit, 16, 1);
+  return rc ? rc : launch_reduce(r, arr, n, stream);
+}
+
+static int wgrad_direct_grouped(const icm_wgrad_args* arr, int n, hipStream_t stream) {
+  const icm_wgrad_args* a = &arr[0];
   WgPlan p;
   int rc = plan_wgrad(*a, p, n);
   if (rc) return rc;
-  for (int i = 0; i < n; ++i) {
-    const icm_wgrad_args& b = arr[i];
-    if (!b.gs || !b.gb || !b.dw || !b.ws) return ICM_ERR_ARG;
-    if (b.Ca != a->Ca || b.Cb != a->Cb || b.OH != a->OH || b.OW != a->OW || b.H != a->H || b.W != a->W ||
-        b.N != a->N || b.KH != a->KH || b.KW != a->KW || b.stride != a->stride || b.pad != a->pad ||
-        b.act_s != a->act_s || b.act_b != a->act_b || b.gs_bs != a->gs_bs || b.gb_bs != a->gb_bs || b.algo != a->algo)
-      return ICM_ERR_ARG;
-  }
+  if (!members_agree(arr, n)) return ICM_ERR_ARG;
   if (((long long)a->N * a->gb_bs + 8LL * a->H * a->W) * 4 >= (1LL << 31)) return ICM_ERR_UNSUPPORTED;   // PlaneMap byte offsets are int32
+  const WgVariant& v = kWgVariants[p.variant];
   const int ntaps = a->KH * a->KW;
-  const int nslab = p.nsplit;   // (wave-split mode folds its four waves through LDS: still one slab per pixel split)
-  const long long slab_all = (long long)nslab * ntaps * a->Ca * a->Cb;
-  for (int i = 0; i < n; ++i)   // the slabs (+ bias partials) of this launch's split count must fit the caller's workspace
-    if (arr[i].ws_floats > 0 && arr[i].ws_floats < slab_all + (long long)p.nsplit * a->Ca) return ICM_ERR_ARG;
+  // (wave-split mode folds its waves through LDS: still one slab per pixel split)
+  if (!workspaces_fit(arr, n, workspace_floats(p.nsplit, ntaps, a->Ca, a->Cb))) return ICM_ERR_ARG;
   WgDesc d{};
   RedDesc r{};
+  rc = fill_reduce(r, arr, n, p.nsplit, ntaps, 0);
+  if (rc) return rc;
+  const long long slab_all = slab_floats(p.nsplit, ntaps, a->Ca, a->Cb);
   for (int i = 0; i < WG_MAXG; ++i) {
     const icm_wgrad_args& b = arr[i < n ? i : 0];
-    d.g[i].gs = b.gs; d.g[i].gb = b.gb; d.g[i].ws = b.ws;
-    d.g[i].dbias_ws = b.dbias ? b.ws + slab_all : nullptr;
-    r.g[i].ws = b.ws; r.g[i].dw = b.dw; r.g[i].dbias_ws = d.g[i].dbias_ws; r.g[i].dbias = b.dbias;
-    r.g[i].accum = b.accum; r.g[i].accum_bias = b.accum_bias;
-    r.g[i].dw_ld = b.dw_ld > 0 ? b.dw_ld : a->Cb;
-    if (r.g[i].dw_ld < a->Cb) return ICM_ERR_ARG;
+    d.g[i].gs = b.gs; d.g[i].gb = b.gb; d.g[i].ws = b.ws; d.g[i].dbias_ws = b.dbias ? b.ws + slab_all : nullptr;
   }
   d.gs_bs = a->gs_bs;
   PatchGeom& pg = d.pg;
@@ -1242,7 +1248,7 @@ static int wgrad_grouped(const icm_wgrad_args* arr, int n, hipStream_t stream) {
   }
   d.Ca = a->Ca; d.OH = a->OH; d.OW = a->OW; d.act_s = a->act_s;
   d.xcd_order = ((long long)a->N * a->OH * a->OW >= 16384) ? 1 : 0;
-  if (icm::g_force_xcd >= 0) d.xcd_order = icm::g_force_xcd;
+  if (g_force_xcd >= 0) d.xcd_order = g_force_xcd;
   d.S = a->stride; d.pad = a->pad; d.ntaps = ntaps; d.tpg = p.tpg;
   d.lgTW = p.lgTW; d.lgTH = p.lgTH; d.lgTI = p.lgTI; d.lgNPX = p.lgNPX;
   d.tiles_x = p.tiles_x; d.tiles_y = p.tiles_y; d.tiles_n = p.tiles_n; d.ntiles = p.ntiles; d.nsplit = p.nsplit;
@@ -1260,52 +1266,55 @@ static int wgrad_grouped(const icm_wgrad_args* arr, int n, hipStream_t stream) {
     d.po_h = off(1) - off(0);
   }
   const long long nblk = (long long)p.natile * p.nbtile * p.ngroups * p.nsplit;
-  void (*fn)(const WgDesc) = nullptr;
   static const bool dma1_v4_off = env_int("ICM_WG_DMA1_V4", 1) == 0;   // measurement only
-  bool v4dma = !dma1_v4_off && p.ws >= 11 && p.ws <= 14 && p.lgNPX == 6 && p.lgTW >= 2 && (a->OW % 4) == 0 &&
+  bool v4dma = !dma1_v4_off && v.fam == WG_DMA1 && p.lgNPX == 6 && p.lgTW >= 2 && (a->OW % 4) == 0 &&
                (a->gs_bs % 4) == 0 && (a->gb_bs % 4) == 0;
   for (int i = 0; i < n && v4dma; ++i)
     v4dma = ((reinterpret_cast<uintptr_t>(arr[i].gs) | reinterpret_cast<uintptr_t>(arr[i].gb)) & 15) == 0;
-  if (p.ws == 11) fn = v4dma ? wgrad_dma1_kernel<6, 6, 2, 2, true> : wgrad_dma1_kernel<6, 6, 2, 2, false>;
-  else if (p.ws == 12) fn = v4dma ? wgrad_dma1_kernel<3, 6, 1, 2, true> : wgrad_dma1_kernel<3, 6, 1, 2, false>;
-  else if (p.ws == 13) fn = v4dma ? wgrad_dma1_kernel<6, 3, 2, 1, true> : wgrad_dma1_kernel<6, 3, 2, 1, false>;
-  else if (p.ws == 14) fn = v4dma ? wgrad_dma1_kernel<3, 3, 1, 1, true> : wgrad_dma1_kernel<3, 3, 1, 1, false>;
-  else if (p.ws == 10) fn = wgrad_tap9_kernel<3, 1, 3>;
-  else if (p.ws == 8) fn = wgrad_tap9_kernel<3, 3>;
-  else if (p.ws == 9) fn = wgrad_tap9_kernel<2, 2>;
-  else if (p.ws == 7) fn = wgrad_t33_kernel<3, 3, 1, 1, true>;
-  else if (p.ws == 3) fn = wgrad_t33_kernel<3, 3, 1, 1>;
-  else if (p.ws == 4) fn = wgrad_t33_kernel<6, 6, 2, 2>;
-  else if (p.ws == 5) fn = wgrad_t33_kernel<3, 6, 1, 2>;
-  else if (p.ws == 6) fn = wgrad_t33_kernel<6, 3, 2, 1>;
-  else if (p.ta == 4) fn = wgrad_kernel<4, 4, 4>;
-  else if (p.tb == 2) fn = wgrad_kernel<2, 2, 9>;
-  else fn = wgrad_kernel<2, 1, 7>;
+  const WgKernel fn = v4dma ? v.fn_v4 : v.fn;
   if (p.lds > 64 * 1024 && !ensure_max_lds(reinterpret_cast<const void*>(fn))) return ICM_ERR_LAUNCH;
   hipLaunchKernelGGL(fn, dim3((unsigned)nblk, n), dim3(512), p.lds, stream, d);
   ICM_CHECK_LAUNCH();
-  r.Ca = a->Ca; r.Cb = a->Cb; r.ntaps = ntaps; r.nsplit = nslab; r.nsplit_bias = p.nsplit;
-  {
-    const long long CaCb = (long long)a->Ca * a->Cb;
-    bool v4 = ntaps == 1 && (CaCb % 4) == 0;
-    for (int i = 0; i < n; ++i) {
-      v4 = v4 && ((reinterpret_cast<uintptr_t>(arr[i].ws) & 15) == 0) && ((reinterpret_cast<uintptr_t>(arr[i].dw) & 15) == 0);
-      if (r.g[i].dw_ld != a->Cb) v4 = v4 && (a->Cb % 4) == 0 && (r.g[i].dw_ld % 4) == 0;
-    }
-    r.vec4 = v4 ? 1 : 0;
-    r.nwblocks = (int)((CaCb + 63) / 64);   // 16 float4 positions (1x1) or 64 positions (multi-tap) per workgroup
+  return launch_reduce(r, arr, n, stream);
+}
+
+}  // namespace icm
+
+extern "C" {
+
+int64_t icm_wgrad_workspace_floats_grouped(const icm_wgrad_args* a, int n) {
+  if (a && n >= 1 && a->algo == ICM_ALGO_WINOGRAD) {
+    int nsplit = 0, nchunks = 0;
+    if (!a->gs || !a->gb || a->N <= 0 || a->Ca <= 0 || a->Cb <= 0 || icm::wgrad_wino_plan(*a, n, &nsplit, &nchunks)) return -1;
+    return icm::workspace_floats(nsplit, 16, a->Ca, a->Cb);
   }
-  bool any_bias = false;
-  for (int i = 0; i < n; ++i) any_bias |= arr[i].dbias != nullptr;
-  const int rblocks = r.nwblocks + (any_bias ? cdiv(a->Ca, 16) : 0);
-  hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(rblocks, n), dim3(256), 0, stream, r);
-  ICM_CHECK_LAUNCH();
-  return ICM_OK;
+  icm::WgPlan p;
+  if (!a || n < 1 || icm::plan_wgrad(*a, p, n)) return -1;
+  return icm::workspace_floats(p.nsplit, a->KH * a->KW, a->Ca, a->Cb);
+}
+int64_t icm_wgrad_workspace_floats(const icm_wgrad_args* a) { return icm_wgrad_workspace_floats_grouped(a, 1); }
+
+static int wgrad_grouped(const icm_wgrad_args* arr, int n, hipStream_t stream) {
+  if (!arr || n < 1 || n > WG_MAXG) return ICM_ERR_ARG;
+  if (arr[0].algo == ICM_ALGO_WINOGRAD) return icm::wgrad_wino_grouped(arr, n, stream);
+  if (arr[0].algo != ICM_ALGO_DIRECT) return ICM_ERR_ARG;
+  return icm::wgrad_direct_grouped(arr, n, stream);
 }
 
 void icm_debug_force_wgrad_cfg(int variant, int xcd_order) {
-  icm::g_force_variant = (variant >= 0 && variant < WG_NVARIANTS) ? variant : -1;
+  icm::g_force_variant = (variant >= 0 && variant < icm::WG_NVARIANTS) ? variant : -1;
   icm::g_force_xcd = (xcd_order == 0 || xcd_order == 1) ? xcd_order : -1;
+}
+
+int icm_debug_wgrad_plan(const icm_wgrad_args* a, int n, int32_t out[8]) {
+  for (int i = 0; i < 8; ++i) out[i] = 0;
+  if (!a || n < 1) return ICM_ERR_ARG;
+  icm::WgPlan p;
+  const int rc = icm::plan_wgrad(*a, p, n);
+  if (rc) return rc;
+  const int32_t vals[8] = {p.variant, p.lgNPX, p.lgTW, p.lgTH, p.lgTI, p.tpg, p.nsplit, (int32_t)p.lds};
+  for (int i = 0; i < 8; ++i) out[i] = vals[i];
+  return ICM_OK;
 }
 
 int icm_conv_wgrad(const icm_wgrad_args* a, void* stream_) {

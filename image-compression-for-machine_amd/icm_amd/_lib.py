@@ -73,7 +73,7 @@ SYMBOLS = [
     "icm_eb_likelihood_fwd", "icm_eb_likelihood_bwd", "icm_eb_aux_loss", "icm_gc_likelihood_ste_fwd",
     "icm_gc_likelihood_ste_bwd", "icm_rd_loss_fwd", "icm_rd_loss_bwd", "icm_grad_sqnorm", "icm_adam_step", "icm_adam_step_hyper", "icm_fill",
     "icm_winattn_bwd_workspace_floats", "icm_debug_force_conv_cfg", "icm_debug_forced_conv_cfg", "icm_debug_force_conv1x1",
-    "icm_debug_force_wgrad_cfg",
+    "icm_debug_force_wgrad_cfg", "icm_debug_wgrad_plan",
     "icm_debug_force_winattn_valu",
     "icm_zigzag_order", "icm_zigzag_splits", "icm_zigzag_reverse",
     "icm_pmf_to_quantized_cdf", "icm_rans_encode_with_indexes", "icm_rans_decode_with_indexes",
@@ -145,6 +145,7 @@ def lib():
         L.icm_debug_force_conv1x1.restype = None
         L.icm_debug_force_wgrad_cfg.argtypes = [i32, i32]
         L.icm_debug_force_wgrad_cfg.restype = None
+        L.icm_debug_wgrad_plan.argtypes = [C.POINTER(WgradArgs), i32, C.POINTER(C.c_int32)]
         L.icm_debug_force_winattn_valu.argtypes = [i32]
         L.icm_debug_force_winattn_valu.restype = None
         L.icm_eb_likelihood_fwd.argtypes = [vp, vp, C.POINTER(EbParams), vp, vp, i32, i32, i32, f32, vp]

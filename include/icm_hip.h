@@ -439,6 +439,10 @@ int icm_debug_forced_conv_cfg(void);
  * launch has >= 1024 waves), 0 = always the LDS-staged kernel, 1 = the direct kernel whenever eligible */
 void icm_debug_force_conv1x1(int mode);
 void icm_debug_force_wgrad_cfg(int variant, int xcd_order);
+/* what the planner of the direct weight-gradient kernels decides for n problems of geometry *a (pure host code; honours
+ * the forced variant): returns its code and fills out = {variant, lgNPX, lgTW, lgTH, lgTI, taps per group, pixel
+ * splits, dynamic LDS bytes} (all 0 unless ICM_OK) */
+int icm_debug_wgrad_plan(const icm_wgrad_args* a, int n, int32_t out[8]);
 /* 1: window attention always runs the generic VALU kernels (the matrix-core kernels cover 8x8 windows) */
 void icm_debug_force_winattn_valu(int on);
 

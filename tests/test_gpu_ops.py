@@ -524,10 +524,8 @@ def _wgrad_ref(x, w, b, g, k, s, tr):
 
 
 WG_CASES = [
-    # name, N, Cin, H, W, Cout, k, stride, transposed, variants to force (conv_wgrad.hip: 0-2 general kernel <2,1,7> /
-    # <2,2,9> / <4,4,4>; 3-6 the 3x3-tiles-per-wave kernel <3,3,1,1> / <6,6,2,2> / <3,6,1,2> / <6,3,2,1>; 7 its
-    # tap-per-wave form; 8 / 9 the nine-tap single-staging DMA kernel tap9<3,3> / tap9<2,2>; 10 its 25-tap 5x5 form;
-    # 11-14 the DMA-only 1x1 kernel dma1<6,6> / <3,6> / <6,3> / <3,3>)
+    # name, N, Cin, H, W, Cout, k, stride, transposed, variants to force: row indices of kWgVariants in
+    # csrc/conv_wgrad.hip, the one description of the ids (-1 = the automatic choice)
     ("wg_c5s2", 3, 40, 36, 20, 72, 5, 2, False, (0, 1, 3, 7, 10)),   # <4,4,4> and the 192-wide tiles need > 160 KB of LDS here
     ("wg_t5s2", 2, 48, 10, 12, 40, 5, 2, True, (0, 1, 10)),
     ("wg_c5s2_192_100", 2, 192, 24, 40, 100, 5, 2, False, (10,)),    # 25 taps from one staging: several blocks, channel tails
@@ -546,8 +544,10 @@ WG_CASES = [
 
 @pytest.mark.parametrize("case", WG_CASES, ids=[c[0] for c in WG_CASES])
 def test_wgrad_every_variant(case):
-    """each of wgrad_kernel<2,1,7>, <2,2,9>, <4,4,4> and <3,3,9,wave-split>, with the plain and the XCD-aware
-    workgroup order, against torch.autograd.grad of F.conv2d / F.conv_transpose2d on CPU (weight AND fused bias grads)"""
+    """each of the fifteen weight-gradient kernel variants (kWgVariants in csrc/conv_wgrad.hip: the general kernel, the
+    3x3-tiles-per-wave kernel and its tap-per-wave form, the nine- and 25-tap single-staging kernels, the DMA-only 1x1
+    kernel) forced on the shapes that admit it, with the plain and the XCD-aware workgroup order, against
+    torch.autograd.grad of F.conv2d / F.conv_transpose2d on CPU (weight AND fused bias grads)"""
     from icm_amd import _lib, layers
     name, N, Cin, H, Wd, Cout, k, s, tr, variants = case
     d = dev()

@@ -63,6 +63,39 @@ def test_host_planning_entry_points():
         _lib.check(2, "x")
 
 
+def test_wgrad_plans_match_the_recorded_planner(golden_dir):
+    """every row of tests/golden/wgrad_plans.npz (make_wgrad_plans.py: automatic choices over a cross of geometries, and
+    every variant id forced on every WG_CASES shape) replayed through icm_debug_wgrad_plan: the return code and all
+    eight plan values {variant, lgNPX, lgTW, lgTH, lgTI, taps per group, pixel splits, LDS bytes} are exactly the
+    recorded ones, and the workspace query agrees with the plan's split count"""
+    import numpy as np
+    L = _lib.lib()
+    z = np.load(os.path.join(golden_dir, "wgrad_plans.npz"), allow_pickle=False)
+    args, want = z["args"].tolist(), z["plan"].tolist()
+    assert len(args) == len(want) > 9000
+    fields = ("Ca", "OH", "OW", "act_s", "Cb", "H", "W", "act_b", "N", "KH", "KW", "stride", "pad")
+    a = _lib.WgradArgs()
+    a.gs, a.gb = 1, 1   # never dereferenced by the planner
+    out = (ctypes.c_int32 * 8)()
+    bad = []
+    try:
+        for row, exp in zip(args, want):
+            forced, n = row[:2]
+            for f, v in zip(fields, row[2:]):
+                setattr(a, f, v)
+            L.icm_debug_force_wgrad_cfg(forced, -1)
+            got = [L.icm_debug_wgrad_plan(ctypes.byref(a), n, out)] + list(out)
+            if got != exp:
+                bad.append((row, exp, got))
+            elif forced < 0 and got[0] == 0:
+                ws = L.icm_wgrad_workspace_floats_grouped(ctypes.byref(a), n)
+                if ws != got[7] * (a.KH * a.KW * a.Ca * a.Cb + a.Ca):
+                    bad.append((row, "workspace", ws))
+    finally:
+        L.icm_debug_force_wgrad_cfg(-1, -1)
+    assert not bad, (len(bad), bad[:5])
+
+
 class _FakeLib:
     """real host-side planners, no-op launches"""
 
