@@ -131,8 +131,8 @@ static const Cfg1x1 kCfgs1x1[] = {
     {3, 1, conv1x1_kernel<3, 1>, 0.95f}, {2, 1, conv1x1_kernel<2, 1>, 0.6f},   // more, smaller wave tiles
 };
 
-int run_conv1x1(const icm_conv_args* arr, int ngroups, long long wp_off, int g_force_1x1, hipStream_t stream) {
-  const icm_conv_args& a = arr[0];
+// The pointwise kernel's table row for this launch, or -1 (not a pointwise launch, or too few waves).  No HIP call.
+int plan_conv1x1(const icm_conv_args& a, int ngroups, int g_force_1x1, ConvPlan& p) {
   if (g_force_1x1 == 0) return -1;
   if (a.KH != 1 || a.KW != 1 || a.stride != 1 || a.pad != 0 || a.pixel_shuffle || (a.Cin % 8) != 0) return -1;
   if (a.OH != a.H || a.OW != a.W) return -1;
@@ -158,7 +158,7 @@ int run_conv1x1(const icm_conv_args* arr, int ngroups, long long wp_off, int g_f
   }
   {
     static const int force = env_int("ICM_1X1_CFG", -1);   // measurement only
-    if (force >= 0 && force < (int)(sizeof(kCfgs1x1) / sizeof(kCfgs1x1[0]))) best = force;
+    if (force >= 0 && force < ncfg) best = force;
   }
   const Cfg1x1& c = kCfgs1x1[best];
   const int ncb = cdiv(ncot, c.tco);
@@ -170,24 +170,22 @@ int run_conv1x1(const icm_conv_args* arr, int ngroups, long long wp_off, int g_f
   static const int kShortK = env_int("ICM_1X1_SHORT_K", 384);
   const long long need = a.Cin <= kShortK ? kMinWaves / 2 : kMinWaves;
   if (g_force_1x1 < 0 && strips * ncb * ngroups < need) return -1;
-  ConvDesc d;
-  fill_conv_ptrs(d.g, arr, ngroups, wp_off);
-  d.y_bs = a.y_bs; d.res_bs = a.res_bs; d.aux_bs = a.aux_bs; d.aux2_bs = a.aux2_bs; d.y2_bs = a.y2_bs;
-  d.pg = PatchGeom{};
-  d.pg.H = a.H; d.pg.W = a.W; d.pg.N = a.N; d.pg.C = a.Cin; d.pg.act = a.pro_act; d.pg.bs = a.x_bs;
-  d.Cout = a.Cout;
-  d.ps2 = 0;
-  d.OHf = a.H; d.OWf = a.W; d.OHv = a.H; d.OWv = a.W;
-  d.out_sy = d.out_sx = 1; d.out_oy = d.out_ox = 0; d.iy0 = d.ix0 = 0;
-  d.ntaps = 1;
-  d.lgTW = d.lgTH = d.lgTI = 0;
-  d.tiles_x = d.tiles_y = d.tiles_n = 1;
-  d.ncot = ncot; d.nchunks8 = a.Cin / 8; d.ckm = 1; d.ncb = ncb;
-  d.epi = a.epi; d.accum = a.accum;
-  for (int t = 0; t < ICM_MAX_TAPS; ++t) d.tapoff[t] = 0;
   const long long nblk = ((strips + 3) / 4) * ncb;
   if (nblk <= 0 || nblk > 0x7fffffffLL) return ICM_ERR_ARG;
-  hipLaunchKernelGGL(c.fn, dim3((unsigned)nblk, ngroups, 1), dim3(256), 0, stream, d);
+  p = ConvPlan{};
+  p.family = kFam1x1; p.row = best; p.g.ckm = 1; p.ncb = ncb; p.nblk = nblk; p.block = 256;
+  return ICM_OK;
+}
+
+// the flat geometry of a pointwise launch: one tap, no tiles, the pixels of all images as one strip
+int launch_conv1x1(ConvDesc& d, const icm_conv_args& a, const ConvPlan& p, int ngroups, hipStream_t stream) {
+  d.pg.H = a.H; d.pg.W = a.W; d.pg.N = a.N; d.pg.C = a.Cin; d.pg.act = a.pro_act; d.pg.bs = a.x_bs;
+  d.OHf = a.H; d.OWf = a.W; d.OHv = a.H; d.OWv = a.W;
+  d.out_sy = d.out_sx = 1;
+  d.ntaps = 1;
+  d.tiles_x = d.tiles_y = d.tiles_n = 1;
+  d.nchunks8 = a.Cin / 8; d.ckm = p.g.ckm;
+  hipLaunchKernelGGL(kCfgs1x1[p.row].fn, dim3((unsigned)p.nblk, ngroups, 1), dim3(p.block), 0, stream, d);
   ICM_CHECK_LAUNCH();
   return ICM_OK;
 }

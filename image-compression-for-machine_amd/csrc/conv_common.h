@@ -38,13 +38,45 @@ struct ConvDesc {
   int tapoff[ICM_MAX_TAPS];   // dword entries: read with s_load (a 16-bit entry forces a VMEM load + vmcnt(0))
 };
 
-// per-member pointers of a grouped launch; unused members repeat member 0 (every blockIdx.y finds valid pointers)
+// What every conv kernel family's launch takes straight from the arguments: per-member pointers (unused members repeat
+// member 0: every blockIdx.y finds valid pointers), batch strides, GEMM-M size and the epilogue.  d arrives zeroed.
 inline void fill_conv_ptrs(ConvPtrs (&g)[ICM_MAX_GROUPS], const icm_conv_args* arr, int ngroups, long long wp_off) {
   for (int gi = 0; gi < ICM_MAX_GROUPS; ++gi) {
     const icm_conv_args& s = arr[gi < ngroups ? gi : 0];
     g[gi] = ConvPtrs{s.x, s.wp + wp_off, s.bias, s.y, s.res, s.aux, s.aux2, s.y2};
   }
 }
+inline void fill_conv_desc(ConvDesc& d, const icm_conv_args* arr, int ngroups, long long wp_off) {
+  const icm_conv_args& a = arr[0];
+  fill_conv_ptrs(d.g, arr, ngroups, wp_off);
+  d.y_bs = a.y_bs; d.res_bs = a.res_bs; d.aux_bs = a.aux_bs; d.aux2_bs = a.aux2_bs; d.y2_bs = a.y2_bs;
+  d.Cout = a.Cout; d.ncot = (a.Cout + 31) / 32;
+  d.epi = a.epi; d.accum = a.accum;
+}
+
+// ---- launch plans: everything a launch decides, by pure host code, before any HIP call (icm_debug_conv_plan shows them)
+enum ConvFamily { kFamStaged = 0, kFamKs8 = 1, kFam1x1 = 2, kFamWino44 = 3, kFamWino8 = 4 };
+struct Geometry {   // pixel tile, LDS patch and grid of the LDS-staged kernels
+  int lgTW, lgTH, lgTI, PH, PW, PWh, PWrow, PP, CS, tiles_x, tiles_y, tiles_n, ckm;
+  size_t lds_bytes;
+};
+struct ConvPlan {   // one tap class of a direct launch
+  int family;       // kFamStaged / kFamKs8 / kFam1x1
+  int row;          // row of the family's kernel table (conv_igemm.hip kCfgs, conv_1x1.hip kCfgs1x1); K-split: co tiles per block
+  Geometry g;       // the pointwise kernel has none: zeros, ckm = 1
+  int ncb;          // co blocks
+  long long nblk;   // workgroups per member; 0: nothing to launch
+  int block, vec4, dma;
+};
+struct WinoGeom {
+  int lgTX, lgTY, lgTI, tiles_x, tiles_y, tiles_n, nchunks8, nsteps;
+};
+struct WinoPlan {
+  WinoGeom g;
+  int tco, w8, px_fast, ncb;   // co tiles per workgroup; 0: the 4 + 4 wave kernel, 1: the eight-MFMA-wave kernel
+  long long nblk;
+  size_t lds_bytes;
+};
 
 // ---- the fused-neighbour epilogue (kinds: include/icm_hip.h): per output element
 //   v = acc + bias  ->  epi_apply<EPI>  ->  (+ old y if accum)  ->  epi_materialise (kinds with epi_may_gelu)  ->  y
@@ -303,11 +335,14 @@ int launch_conv_ks8(const ConvDesc& d, int tco, long long nblk, int ngroups, siz
 
 // Winograd F(2x2, 3x3) path (conv_wino.hip): 3x3 stride-1 pad-1 launches whose weights were packed with wino != 0
 bool wino_supported(const icm_conv_args& a);
+int plan_conv_wino(const icm_conv_args& a, int ngroups, WinoPlan& p);
 int run_conv_wino(const icm_conv_args* arr, int ngroups, hipStream_t stream);
 long long wino_transform_floats(const icm_conv_args& a);
 int run_wino_transform(const icm_conv_args* arr, int ngroups, hipStream_t stream);
 
-// pointwise path (conv_1x1.hip): ICM_OK after launching, -1 when the launch should take the LDS-staged kernel
-int run_conv1x1(const icm_conv_args* arr, int ngroups, long long wp_off, int force_mode, hipStream_t stream);
+// pointwise path (conv_1x1.hip).  plan: ICM_OK with p filled, -1 when the launch should take the LDS-staged kernel (p
+// untouched); launch: d holds what fill_conv_desc and the plan's ncb gave it
+int plan_conv1x1(const icm_conv_args& a, int ngroups, int force_mode, ConvPlan& p);
+int launch_conv1x1(ConvDesc& d, const icm_conv_args& a, const ConvPlan& p, int ngroups, hipStream_t stream);
 
 }  // namespace icm

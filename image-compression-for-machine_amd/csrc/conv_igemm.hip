@@ -437,34 +437,38 @@ static std::vector<ConvClass> build_classes(int KH, int KW, int stride, int pad,
   return out;
 }
 
+// One row per instantiation; the index is the id of icm_debug_force_conv_cfg.  Cost model inputs: eff = efficiency measured
+// on MI355X (tools/tune_conv.py; profiles/r01_tune_conv_v7.txt), occ = 2 where the kernel fits 128 VGPRs (launch bounds)
 struct KernelCfg {
   int wco, wpx, tco, tpx;
   void (*fn)(const ConvDesc);
-  int ks = 1;
+  int ks;   // intra-workgroup K split
+  double eff;
+  int occ;
 };
 static const KernelCfg kCfgs[] = {
-    {1, 4, 3, 2, conv_igemm_kernel<1, 4, 3, 2>},  // 96 co x 256 px
-    {1, 4, 6, 1, conv_igemm_kernel<1, 4, 6, 1>},  // 192 x 128
-    {1, 4, 2, 2, conv_igemm_kernel<1, 4, 2, 2>},  // 64 x 256
-    {1, 4, 1, 2, conv_igemm_kernel<1, 4, 1, 2>},  // 32 x 256
-    {1, 4, 3, 1, conv_igemm_kernel<1, 4, 3, 1>},  // 96 x 128
-    {1, 4, 5, 1, conv_igemm_kernel<1, 4, 5, 1>},  // 160 x 128
-    {2, 2, 2, 1, conv_igemm_kernel<2, 2, 2, 1>},  // 128 x 64
-    {2, 2, 1, 1, conv_igemm_kernel<2, 2, 1, 1>},  // 64 x 64
-    {4, 1, 1, 1, conv_igemm_kernel<4, 1, 1, 1>},  // 128 x 32
-    {1, 4, 1, 1, conv_igemm_kernel<1, 4, 1, 1>},  // 32 x 128
-    {2, 1, 1, 1, conv_igemm_kernel<2, 1, 1, 1, 2>, 2},  // 64 x 32, K split in 2
-    {1, 2, 1, 1, conv_igemm_kernel<1, 2, 1, 1, 2>, 2},  // 32 x 64, K split in 2
-    {1, 1, 1, 1, conv_igemm_kernel<1, 1, 1, 1, 4>, 4},  // 32 x 32, K split in 4
+    {1, 4, 3, 2, conv_igemm_kernel<1, 4, 3, 2>, 1, 0.75, 1},     // 96 co x 256 px
+    {1, 4, 6, 1, conv_igemm_kernel<1, 4, 6, 1>, 1, 1.00, 1},     // 192 x 128
+    {1, 4, 2, 2, conv_igemm_kernel<1, 4, 2, 2>, 1, 0.80, 1},     // 64 x 256
+    {1, 4, 1, 2, conv_igemm_kernel<1, 4, 1, 2>, 1, 0.60, 2},     // 32 x 256
+    {1, 4, 3, 1, conv_igemm_kernel<1, 4, 3, 1>, 1, 1.10, 2},     // 96 x 128
+    {1, 4, 5, 1, conv_igemm_kernel<1, 4, 5, 1>, 1, 0.65, 1},     // 160 x 128
+    {2, 2, 2, 1, conv_igemm_kernel<2, 2, 2, 1>, 1, 0.80, 2},     // 128 x 64
+    {2, 2, 1, 1, conv_igemm_kernel<2, 2, 1, 1>, 1, 0.80, 2},     // 64 x 64
+    {4, 1, 1, 1, conv_igemm_kernel<4, 1, 1, 1>, 1, 0.75, 2},     // 128 x 32
+    {1, 4, 1, 1, conv_igemm_kernel<1, 4, 1, 1>, 1, 0.70, 2},     // 32 x 128
+    {2, 1, 1, 1, conv_igemm_kernel<2, 1, 1, 1, 2>, 2, 0.70, 2},  // 64 x 32, K split in 2
+    {1, 2, 1, 1, conv_igemm_kernel<1, 2, 1, 1, 2>, 2, 0.70, 2},  // 32 x 64, K split in 2
+    {1, 1, 1, 1, conv_igemm_kernel<1, 1, 1, 1, 4>, 4, 0.65, 2},  // 32 x 32, K split in 4
 };
-static int g_force_cfg = -1;
+constexpr int kNumCfgs = (int)(sizeof(kCfgs) / sizeof(kCfgs[0]));
+static_assert(kNumCfgs <= ICM_CONV_CFG_KS8_64X64, "the K-split ids lie above the table rows");
 
+static int g_force_cfg = ICM_CONV_CFG_AUTO;
+static bool cfg_forced() { return g_force_cfg != ICM_CONV_CFG_AUTO; }
+static bool ks8_forced() { return g_force_cfg == ICM_CONV_CFG_KS8_64X64 || g_force_cfg == ICM_CONV_CFG_KS8_32X128; }
+static bool row_forced() { return cfg_forced() && g_force_cfg < ICM_CONV_CFG_KS8_64X64; }
 static int g_force_1x1 = env_int("ICM_CONV_1X1", -1);   // -1 auto, 0 never, 1 whenever eligible
-
-struct Geometry {
-  int lgTW, lgTH, lgTI, PH, PW, PWh, PWrow, PP, CS, tiles_x, tiles_y, tiles_n, ckm;
-  size_t lds_bytes;
-};
 
 static Geometry make_geometry(int bpx, int OHv, int OWv, int N, int S, int ey, int ex, int nchunks8, int ntaps,
                               int tiles_per_wave) {
@@ -493,51 +497,42 @@ static Geometry make_geometry(int bpx, int OHv, int OWv, int N, int S, int ey, i
   g.lds_bytes = (size_t)2 * ckm * 8 * g.CS * sizeof(float);
   return g;
 }
+static bool fits_plane_map(const Geometry& g) { return (1 << g.lgTI) * g.PH * g.PW <= ICM_MAXJ * 64; }
+static bool linear_patch(const Geometry& g) { return g.PWrow == g.PW && g.PP == g.PH * g.PW; }
+static long long tile_count(const Geometry& g) { return (long long)g.tiles_x * g.tiles_y * g.tiles_n; }
 
-static int run_class(const icm_conv_args* arr, int ngroups, const ConvClass& cls, long long wp_off, int S_in,
-                     int out_s, hipStream_t stream) {
-  const icm_conv_args& a = arr[0];
-  const int OHv = a.transposed ? cdiv(a.OH - cls.cy, out_s) : a.OH;
-  const int OWv = a.transposed ? cdiv(a.OW - cls.cx, out_s) : a.OW;
-  if (OHv <= 0 || OWv <= 0) return ICM_OK;
-  const int ncot = cdiv(a.Cout, 32), nchunks8 = cdiv(a.Cin, 8);
-  const int ntaps = (int)cls.taps.size();
-  if (ntaps > ICM_MAX_TAPS) return ICM_ERR_UNSUPPORTED;
-  if (ntaps == 1 && S_in == 1 && out_s == 1 && cls.iy0 == 0 && cls.ix0 == 0 && a.x_seg_len == 0) {
-    const int rc = (g_force_cfg >= 0) ? -1 : run_conv1x1(arr, ngroups, wp_off, g_force_1x1, stream);
-    if (rc >= 0) return rc;
-  }
+struct ClassShape { int OHv, OWv, ncot, nchunks8, ntaps; };   // virtual output grid (a scatter class writes every out_s-th row / column)
+static ClassShape class_shape(const icm_conv_args& a, const ConvClass& cls, int out_s) {
+  return {a.transposed ? cdiv(a.OH - cls.cy, out_s) : a.OH, a.transposed ? cdiv(a.OW - cls.cx, out_s) : a.OW,
+          cdiv(a.Cout, 32), cdiv(a.Cin, 8), (int)cls.taps.size()};
+}
 
-  // pick the tile configuration: time ~ rounds x (co-resident workgroups share the MFMA pipes: occ x MFMAs per wave /
-  // efficiency + one fixed prologue/epilogue overhead per round), rounds = ceil(workgroups / (256 CUs x occ)); occ = 2
-  // for the configurations whose kernels fit 128 VGPRs (launch bounds above), efficiencies measured on MI355X
-  // (tools/tune_conv.py; profiles/r01_tune_conv_v7.txt)
-  static const double kEff[] = {0.75, 1.00, 0.80, 0.60, 1.10, 0.65, 0.80, 0.80, 0.75, 0.70, 0.70, 0.70, 0.65};
-  static const int kOcc[] = {1, 1, 1, 2, 2, 1, 2, 2, 2, 2, 2, 2, 2};
+// Tile configuration of the staged kernel: time ~ rounds x (co-resident workgroups share the MFMA pipes: occ x MFMAs per
+// wave / efficiency + one fixed prologue/epilogue overhead per round), rounds = ceil(workgroups / (256 CUs x occ)).
+static int search_staged(const icm_conv_args& a, int ngroups, const ConvClass& cls, const ClassShape& s, int S_in,
+                         Geometry& bg) {
   static const double kCoResBoost = env_double("ICM_CONV_BOOST", 1.25);
   int best = -1, best1 = -1;
   double best_cost = 1e300, best1_cost = 1e300;
-  Geometry bg{}, bg1{};
-  const int ncfg = (int)(sizeof(kCfgs) / sizeof(kCfgs[0]));
-  for (int i = 0; i < ncfg; ++i) {
-    if (g_force_cfg >= 0 && g_force_cfg < 100 && i != g_force_cfg) continue;
+  Geometry bg1{};
+  for (int i = 0; i < kNumCfgs; ++i) {
+    if (row_forced() && i != g_force_cfg) continue;
     const KernelCfg& c = kCfgs[i];
     const int bpx = c.wpx * c.tpx * 32, bco_t = c.wco * c.tco;
-    Geometry g = make_geometry(bpx, OHv, OWv, a.N, S_in, cls.ey, cls.ex, nchunks8, ntaps, c.tco * c.tpx);
+    Geometry g = make_geometry(bpx, s.OHv, s.OWv, a.N, S_in, cls.ey, cls.ex, s.nchunks8, s.ntaps, c.tco * c.tpx);
     if (c.ks > 1) g.lds_bytes = std::max<size_t>(g.lds_bytes, (size_t)(c.ks - 1) * c.wco * c.wpx * 4096);
-    if (g.lds_bytes > 160 * 1024) continue;
-    if ((1 << g.lgTI) * g.PH * g.PW > ICM_MAXJ * 64) continue;   // PlaneMap capacity
-    const long long blocks = (long long)cdiv(ncot, bco_t) * g.tiles_x * g.tiles_y * g.tiles_n * ngroups;
-    const int occ_max = (g.lds_bytes * 2 <= 160 * 1024) ? kOcc[i] : 1;
+    if (g.lds_bytes > 160 * 1024 || !fits_plane_map(g)) continue;
+    const long long blocks = cdiv(s.ncot, bco_t) * tile_count(g) * ngroups;
+    const int occ_max = (g.lds_bytes * 2 <= 160 * 1024) ? c.occ : 1;
     const int occ = (int)std::min<long long>(occ_max, (blocks + 255) / 256);   // workgroups actually co-resident
     const double rounds = (double)((blocks + 256 * occ - 1) / (256 * occ));
-    const double mfma = (double)c.tco * c.tpx * nchunks8 * ntaps * 4 / c.ks + (c.ks > 1 ? 24.0 : 0.0);   // per MFMA wave
+    const double mfma = (double)c.tco * c.tpx * s.nchunks8 * s.ntaps * 4 / c.ks + (c.ks > 1 ? 24.0 : 0.0);   // per MFMA wave
     // two co-resident workgroups interleave their MFMA streams: the issue gaps of one wave per SIMD are filled
     // (the interleaving gain fades for long K loops, whose steady state already keeps the matrix pipe busy)
     const double boost = occ > 1 ? 1.0 + (kCoResBoost - 1.0) * std::min(1.0, 1500.0 / mfma) : 1.0;
-    double cost = rounds * (occ * mfma / (kEff[i] * boost) + 200.0);
+    const double cost = rounds * (occ * mfma / (c.eff * boost) + 200.0);
     // a configuration whose co-tile covers all output channels stages every halo patch exactly once
-    if (ntaps >= 9 && (long long)OHv * OWv * a.N >= 16384 && cdiv(ncot, bco_t) == 1 && cost < best1_cost) {
+    if (s.ntaps >= 9 && (long long)s.OHv * s.OWv * a.N >= 16384 && cdiv(s.ncot, bco_t) == 1 && cost < best1_cost) {
       best1_cost = cost;
       best1 = i;
       bg1 = g;
@@ -548,7 +543,6 @@ static int run_class(const icm_conv_args* arr, int ngroups, const ConvClass& cls
       bg = g;
     }
   }
-  if (best < 0) return ICM_ERR_UNSUPPORTED;
   // halo convolutions with many pixels: within 20 % of the cheapest estimate, take the single-pass-over-activations
   // tiling (every extra co-block re-stages the whole halo patch from L2 / HBM: 1.85x FETCH_SIZE measured on g_a.2
   // for 3 % of MFMA time)
@@ -556,41 +550,84 @@ static int run_class(const icm_conv_args* arr, int ngroups, const ConvClass& cls
     best = best1;
     bg = bg1;
   }
-  const KernelCfg& c = kCfgs[best];
-  // Latency-bound launches: the 8-wave K-split kernel (conv_ks8.hip).  Needs stride-1 sampling, no operand activation,
-  // the GDN / AXPY2 epilogues excluded (they belong to pointwise launches), and the step table in one VGPR
-  // (ckm * ntaps <= 64, as here).  It runs one workgroup per CU, so it is taken only when its grid is ONE nearly full
-  // round of the chip (160..256 workgroups): there it cuts the critical path of the serial slice-chain layers by ~15 %
-  // (224 -> 176 @16x16: 60 -> 51 us, 480 -> 224: 116 -> 100 us); applied to every small launch it lost 1.3 % on the
-  // step (narrow outputs 64 -> 32: 17 -> 29 us, half-empty grids, second-round tails; same-box A/B).
-  int ks8_tco = 0;
-  {
-    static const int ks8_on = env_int("ICM_CONV_KS8", 1);
-    static const long long ks8_max = env_ll("ICM_CONV_KS8_MAXWG", 256);
-    static const long long ks8_min = env_ll("ICM_CONV_KS8_MINWG", 160);
-    if ((ks8_on && g_force_cfg < 0 || g_force_cfg == 100 || g_force_cfg == 101) && S_in == 1 && ntaps > 1 &&
-        a.pro_act == ICM_ACT_NONE && EpiKs8::has(a.epi) && a.x_seg_len == 0) {
-      const int tco = g_force_cfg == 101 ? 1 : (g_force_cfg == 100 ? 2 : (ncot >= 2 ? 2 : 1));
-      const int bpx = tco == 2 ? 64 : 128;
-      Geometry g = make_geometry(bpx, OHv, OWv, a.N, S_in, cls.ey, cls.ex, nchunks8, ntaps, 4);
-      // more K per barrier than the staged kernel needs: every wave should find >= 2 of its sub-steps in a chunk
-      int ckm = std::max(1, std::min(nchunks8, 64 / ntaps));
-      while (ckm > 1 && (size_t)2 * ckm * 8 * g.CS * sizeof(float) > 96 * 1024) --ckm;
-      g.ckm = ckm;
-      g.lds_bytes = std::max((size_t)2 * ckm * 8 * g.CS * sizeof(float), (size_t)8 * 4 * 16 * 64 * sizeof(float));
-      const long long blocks = (long long)cdiv(ncot, tco) * g.tiles_x * g.tiles_y * g.tiles_n * ngroups;
-      const bool fits = g.lds_bytes <= 160 * 1024 && (1 << g.lgTI) * g.PH * g.PW <= ICM_MAXJ * 64 && g.PWrow == g.PW &&
-                        g.PP == g.PH * g.PW;
-      if (fits && (g_force_cfg >= 100 || (blocks <= ks8_max && blocks >= ks8_min && tco == 2))) {
-        ks8_tco = tco;
-        bg = g;
-      }
-    }
-  }
+  return best;
+}
 
+// Latency-bound launches: the 8-wave K-split kernel (conv_ks8.hip).  Needs stride-1 sampling, no operand activation,
+// the GDN / AXPY2 epilogues excluded (they belong to pointwise launches), and the step table in one VGPR
+// (ckm * ntaps <= 64, as here).  It runs one workgroup per CU, so it is taken only when its grid is ONE nearly full
+// round of the chip (160..256 workgroups): there it cuts the critical path of the serial slice-chain layers by ~15 %
+// (224 -> 176 @16x16: 60 -> 51 us, 480 -> 224: 116 -> 100 us); applied to every small launch it lost 1.3 % on the
+// step (narrow outputs 64 -> 32: 17 -> 29 us, half-empty grids, second-round tails; same-box A/B).
+// Returns its co tiles per block; 0: the launch keeps the staged kernel.
+static int plan_ks8(const icm_conv_args& a, int ngroups, const ConvClass& cls, const ClassShape& s, int S_in, Geometry& g) {
+  static const int ks8_on = env_int("ICM_CONV_KS8", 1);
+  static const long long ks8_max = env_ll("ICM_CONV_KS8_MAXWG", 256);
+  static const long long ks8_min = env_ll("ICM_CONV_KS8_MINWG", 160);
+  if (!(ks8_forced() || (ks8_on && !cfg_forced())) || S_in != 1 || s.ntaps <= 1 || a.pro_act != ICM_ACT_NONE ||
+      !EpiKs8::has(a.epi) || a.x_seg_len != 0)
+    return 0;
+  const int tco = g_force_cfg == ICM_CONV_CFG_KS8_32X128 ? 1 : (g_force_cfg == ICM_CONV_CFG_KS8_64X64 ? 2 : (s.ncot >= 2 ? 2 : 1));
+  g = make_geometry(tco == 2 ? 64 : 128, s.OHv, s.OWv, a.N, S_in, cls.ey, cls.ex, s.nchunks8, s.ntaps, 4);
+  // more K per barrier than the staged kernel needs: every wave should find >= 2 of its sub-steps in a chunk
+  int ckm = std::max(1, std::min(s.nchunks8, 64 / s.ntaps));
+  while (ckm > 1 && (size_t)2 * ckm * 8 * g.CS * sizeof(float) > 96 * 1024) --ckm;
+  g.ckm = ckm;
+  g.lds_bytes = std::max((size_t)2 * ckm * 8 * g.CS * sizeof(float), (size_t)8 * 4 * 16 * 64 * sizeof(float));
+  const long long blocks = cdiv(s.ncot, tco) * tile_count(g) * ngroups;
+  const bool fits = g.lds_bytes <= 160 * 1024 && fits_plane_map(g) && linear_patch(g);
+  return (fits && (ks8_forced() || (blocks <= ks8_max && blocks >= ks8_min && tco == 2))) ? tco : 0;
+}
+
+// Everything one tap class's launch decides; no HIP call, no pointer read.  Precedence: the pointwise kernel unless a
+// configuration is forced, the cost search, the K-split override (its own geometry).  p.nblk == 0: an empty class.
+static int plan_class(const icm_conv_args& a, int ngroups, const ConvClass& cls, int S_in, int out_s, bool x_aligned16,
+                      ConvPlan& p) {
+  p = ConvPlan{};
+  const ClassShape s = class_shape(a, cls, out_s);
+  if (s.OHv <= 0 || s.OWv <= 0) return ICM_OK;
+  if (s.ntaps > ICM_MAX_TAPS) return ICM_ERR_UNSUPPORTED;
+  if (s.ntaps == 1 && S_in == 1 && out_s == 1 && cls.iy0 == 0 && cls.ix0 == 0 && a.x_seg_len == 0 && !cfg_forced()) {
+    const int rc = plan_conv1x1(a, ngroups, g_force_1x1, p);
+    if (rc >= 0) return rc;
+  }
+  p.row = search_staged(a, ngroups, cls, s, S_in, p.g);
+  if (p.row < 0) return ICM_ERR_UNSUPPORTED;
+  p.block = 512;
+  Geometry kg;
+  if (const int tco = plan_ks8(a, ngroups, cls, s, S_in, kg)) {
+    p.family = kFamKs8;
+    p.row = tco;
+    p.g = kg;
+    p.dma = 1;
+  } else {
+    const Geometry& g = p.g;
+    const int plane4 = (1 << g.lgTI) * g.PH * (g.PW / 4);
+    // 16-byte halo-free staging (the packed vec4 form moves several channels per instruction: keep segments simple)
+    p.vec4 = S_in == 1 && cls.ex == 1 && cls.ey == 1 && cls.ix0 == 0 && (g.PW % 4) == 0 && ((1 << g.lgTW) % 4) == 0 &&
+             (a.W % 4) == 0 && (a.x_bs % 4) == 0 && ((long long)a.H * a.W % 4) == 0 && plane4 <= 4 * 64 &&
+             (g.CS % 4) == 0 && (g.PWrow % 4) == 0 && (g.PP % 4) == 0 && x_aligned16 && a.x_seg_len == 0;
+    // LDS-DMA staging: no activation to apply, linear patch layout (stride-1 input sampling: no column-parity split),
+    // not the 16-byte halo-free path (4x the bytes per instruction)
+    static const int dma_on = env_int("ICM_CONV_DMA", 1);
+    p.dma = dma_on && !p.vec4 && S_in == 1 && a.pro_act == ICM_ACT_NONE && linear_patch(g);
+  }
+  p.ncb = cdiv(s.ncot, p.family == kFamKs8 ? p.row : kCfgs[p.row].wco * kCfgs[p.row].tco);
+  p.nblk = p.ncb * tile_count(p.g);
+  if (p.nblk <= 0 || p.nblk > 0x7fffffffLL) return ICM_ERR_ARG;
+  return ICM_OK;
+}
+
+static int launch_class(const icm_conv_args* arr, int ngroups, const ConvClass& cls, long long wp_off, int S_in,
+                        int out_s, const ConvPlan& p, hipStream_t stream) {
+  if (p.nblk == 0) return ICM_OK;
+  const icm_conv_args& a = arr[0];
   ConvDesc d{};
-  fill_conv_ptrs(d.g, arr, ngroups, wp_off);
-  d.y_bs = a.y_bs; d.res_bs = a.res_bs; d.aux_bs = a.aux_bs; d.aux2_bs = a.aux2_bs; d.y2_bs = a.y2_bs;
+  fill_conv_desc(d, arr, ngroups, wp_off);
+  d.ncb = p.ncb;
+  if (p.family == kFam1x1) return launch_conv1x1(d, a, p, ngroups, stream);
+  const ClassShape s = class_shape(a, cls, out_s);
+  const Geometry& bg = p.g;
   PatchGeom& pg = d.pg;
   pg.PW = bg.PW; pg.PH = bg.PH; pg.PWrow = bg.PWrow; pg.PWh = bg.PWh; pg.PP = bg.PP; pg.CS = bg.CS; pg.S = S_in;
   pg.TIPH = (1 << bg.lgTI) * bg.PH;
@@ -600,50 +637,28 @@ static int run_class(const icm_conv_args* arr, int ngroups, const ConvClass& cls
   pg.H = a.H; pg.W = a.W; pg.N = a.N; pg.C = a.Cin; pg.act = a.pro_act; pg.bs = a.x_bs;
   pg.seg_len = a.x_seg_len; pg.seg_gap = a.x_seg_len ? a.x_seg_gap : 0;
   pg.dseg = make_fastdiv((uint32_t)std::max(1, a.x_seg_len));
-  {
-    const int TW = 1 << bg.lgTW;
-    const int plane4 = (1 << bg.lgTI) * bg.PH * (bg.PW / 4);
-    bool v4 = S_in == 1 && cls.ex == 1 && cls.ey == 1 && cls.ix0 == 0 && (bg.PW % 4) == 0 && (TW % 4) == 0 &&
-              (a.W % 4) == 0 && (a.x_bs % 4) == 0 && ((long long)a.H * a.W % 4) == 0 && plane4 <= 4 * 64 &&
-              (bg.CS % 4) == 0 && (bg.PWrow % 4) == 0 && (bg.PP % 4) == 0;
-    for (int gi = 0; gi < ngroups; ++gi) v4 = v4 && ((reinterpret_cast<uintptr_t>(arr[gi].x) & 15) == 0);
-    if (a.x_seg_len) v4 = false;   // (the packed vec4 form moves several channels per instruction: keep segments simple)
-    pg.vec4 = v4 ? 1 : 0;
-    // LDS-DMA staging: no activation to apply, linear patch layout (stride-1 input sampling: no column-parity split),
-    // not the 16-byte halo-free path (4x the bytes per instruction)
-    static const int dma_on = env_int("ICM_CONV_DMA", 1);
-    pg.dma = (dma_on && !v4 && S_in == 1 && a.pro_act == ICM_ACT_NONE && bg.PWrow == bg.PW && bg.PP == bg.PH * bg.PW) ? 1 : 0;
-    pg.pipe = 0;
-    set_v4_pack(pg);
-  }
-  d.Cout = a.Cout;
+  pg.vec4 = p.vec4; pg.dma = p.dma; pg.pipe = 0;
+  set_v4_pack(pg);
   d.ps2 = a.pixel_shuffle == 2;
   d.OHf = d.ps2 ? a.OH * 2 : a.OH;
   d.OWf = d.ps2 ? a.OW * 2 : a.OW;
-  d.OHv = OHv; d.OWv = OWv;
+  d.OHv = s.OHv; d.OWv = s.OWv;
   d.out_sy = d.out_sx = out_s;
   d.out_oy = cls.cy; d.out_ox = cls.cx;
   d.iy0 = cls.iy0; d.ix0 = cls.ix0;
-  d.ntaps = ntaps;
+  d.ntaps = s.ntaps;
   d.lgTW = bg.lgTW; d.lgTH = bg.lgTH; d.lgTI = bg.lgTI;
   d.tiles_x = bg.tiles_x; d.tiles_y = bg.tiles_y; d.tiles_n = bg.tiles_n;
-  d.ncot = ncot; d.nchunks8 = nchunks8; d.ckm = bg.ckm; d.ncb = cdiv(ncot, ks8_tco ? ks8_tco : c.wco * c.tco);
-  d.epi = a.epi; d.accum = a.accum;
-  for (int t = 0; t < ICM_MAX_TAPS; ++t) d.tapoff[t] = 0;
-  for (int t = 0; t < ntaps; ++t) {
+  d.nchunks8 = s.nchunks8; d.ckm = bg.ckm;
+  for (int t = 0; t < s.ntaps; ++t) {
     const Tap& tp = cls.taps[t];
     const int col = (S_in == 2) ? ((tp.dx & 1) * bg.PWh + (tp.dx >> 1)) : tp.dx;
     d.tapoff[t] = tp.dy * bg.PWrow + col;
   }
-  const long long nblk = (long long)d.ncb * d.tiles_x * d.tiles_y * d.tiles_n;
-  if (nblk <= 0 || nblk > 0x7fffffffLL) return ICM_ERR_ARG;
-  if (ks8_tco) {
-    d.pg.vec4 = 0;
-    d.pg.dma = 1;
-    return launch_conv_ks8(d, ks8_tco, nblk, ngroups, bg.lds_bytes, stream);
-  }
+  if (p.family == kFamKs8) return launch_conv_ks8(d, p.row, p.nblk, ngroups, bg.lds_bytes, stream);
+  const KernelCfg& c = kCfgs[p.row];
   if (bg.lds_bytes > 64 * 1024 && !ensure_max_lds(reinterpret_cast<const void*>(c.fn))) return ICM_ERR_LAUNCH;
-  hipLaunchKernelGGL(c.fn, dim3((unsigned)nblk, ngroups, 1), dim3(512), bg.lds_bytes, stream, d);
+  hipLaunchKernelGGL(c.fn, dim3((unsigned)p.nblk, ngroups, 1), dim3(p.block), bg.lds_bytes, stream, d);
   ICM_CHECK_LAUNCH();
   return ICM_OK;
 }
@@ -666,7 +681,7 @@ static int validate(const icm_conv_args& a) {
   return ICM_OK;
 }
 
-static int conv_run_grouped(const icm_conv_args* arr, int ngroups, hipStream_t stream) {
+static int check_group(const icm_conv_args* arr, int ngroups) {
   if (!arr || ngroups < 1 || ngroups > ICM_MAX_GROUPS) return ICM_ERR_ARG;
   for (int i = 0; i < ngroups; ++i) {
     int rc = validate(arr[i]);
@@ -687,17 +702,46 @@ static int conv_run_grouped(const icm_conv_args* arr, int ngroups, hipStream_t s
         (b.bias != nullptr) != (a.bias != nullptr) || (b.xv != nullptr) != (a.xv != nullptr))
       return ICM_ERR_ARG;
   }
+  return (a.algo == ICM_ALGO_WINOGRAD || a.algo == ICM_ALGO_DIRECT) ? ICM_OK : ICM_ERR_ARG;
+}
+
+// floats of one tap class in a packed weight buffer whose (chunk, tap) steps hold ncot 32-row tiles
+static long long class_packed_floats(int Cin, int ntaps, int ncot) { return (long long)cdiv(Cin, 8) * ntaps * ncot * 256; }
+
+static bool x_aligned16(const icm_conv_args* arr, int ngroups) {
+  bool ok = true;
+  for (int gi = 0; gi < ngroups; ++gi) ok = ok && (reinterpret_cast<uintptr_t>(arr[gi].x) & 15) == 0;
+  return ok;
+}
+
+static int conv_run_grouped(const icm_conv_args* arr, int ngroups, hipStream_t stream) {
+  if (int rc = check_group(arr, ngroups)) return rc;
+  const icm_conv_args& a = arr[0];
   if (a.algo == ICM_ALGO_WINOGRAD) return run_conv_wino(arr, ngroups, stream);
-  if (a.algo != ICM_ALGO_DIRECT) return ICM_ERR_ARG;
-  std::vector<ConvClass> classes = build_classes(a.KH, a.KW, a.stride, a.pad, a.transposed);
-  const int ncot = cdiv(a.Cout, 32), nchunks = cdiv(a.Cin, 8);
+  const int S_in = a.transposed ? 1 : a.stride, out_s = a.transposed ? a.stride : 1;
   long long off = 0;
-  for (const ConvClass& cls : classes) {
-    int rc = run_class(arr, ngroups, cls, off, a.transposed ? 1 : a.stride, a.transposed ? a.stride : 1, stream);
+  for (const ConvClass& cls : build_classes(a.KH, a.KW, a.stride, a.pad, a.transposed)) {
+    ConvPlan p;
+    int rc = plan_class(a, ngroups, cls, S_in, out_s, x_aligned16(arr, ngroups), p);
+    if (!rc) rc = launch_class(arr, ngroups, cls, off, S_in, out_s, p, stream);
     if (rc) return rc;
-    off += (long long)nchunks * (long long)cls.taps.size() * ncot * 256;
+    off += class_packed_floats(a.Cin, (int)cls.taps.size(), cdiv(a.Cout, 32));
   }
   return ICM_OK;
+}
+
+static PackDesc make_pack_desc(const icm_pack_job& J, const ConvClass& cls, long long off) {
+  const int ntaps = (int)cls.taps.size(), ncot = cdiv(J.Cout, 32);
+  PackDesc d{};
+  d.w = J.w;
+  d.wp = J.wp + off;
+  d.Co = J.Cout; d.Ci = J.Cin; d.KHW = J.KH * J.KW; d.src_out_major = J.src_out_major;
+  d.ntaps = ntaps; d.ncot = ncot; d.nchunks = cdiv(J.Cin, 8); d.nonneg = J.nonneg;
+  d.bound = J.bound; d.pedestal = J.pedestal;
+  d.src_ld = J.src_ld > 0 ? J.src_ld : (J.src_out_major ? J.Cin : J.Cout); d.src_off = J.src_off;
+  d.dst_ncot = J.dst_ncot > 0 ? J.dst_ncot : ncot; d.dst_cot_off = J.dst_cot_off; d.wino = J.wino;
+  for (int t = 0; t < ntaps; ++t) d.tapidx[t] = (short)cls.taps[t].kidx;
+  return d;
 }
 
 }  // namespace icm
@@ -741,42 +785,59 @@ int icm_wino_transform(const icm_conv_args* arr, int ngroups, void* stream) {
   return icm::run_wino_transform(arr, ngroups, (hipStream_t)stream);
 }
 
-void icm_debug_force_conv_cfg(int idx) { icm::g_force_cfg = idx; }
+void icm_debug_force_conv_cfg(int idx) { icm::g_force_cfg = idx < 0 ? ICM_CONV_CFG_AUTO : idx; }
 int icm_debug_forced_conv_cfg(void) { return icm::g_force_cfg; }
 void icm_debug_force_conv1x1(int mode) { icm::g_force_1x1 = mode; }
 
+int icm_debug_conv_plan(const icm_conv_args* arr, int ngroups, int cls, int64_t out[16]) {
+  using namespace icm;
+  std::fill(out, out + 16, 0);
+  int rc = check_group(arr, ngroups);
+  if (rc) return rc;
+  const icm_conv_args& a = arr[0];
+  if (a.algo == ICM_ALGO_WINOGRAD) {
+    WinoPlan w{};
+    if (cls != 0) return ICM_ERR_ARG;
+    if ((rc = plan_conv_wino(a, ngroups, w))) return rc;
+    const int64_t v[13] = {1, w.w8 ? kFamWino8 : kFamWino44, w.tco, w.g.lgTX, w.g.lgTY, w.g.lgTI, w.g.nsteps, w.ncb, w.nblk,
+                           (int64_t)w.lds_bytes, 512, a.xv != nullptr, w.px_fast};
+    std::copy(v, v + 13, out);
+    return ICM_OK;
+  }
+  const std::vector<ConvClass> classes = build_classes(a.KH, a.KW, a.stride, a.pad, a.transposed);
+  if (cls < 0 || cls >= (int)classes.size()) return ICM_ERR_ARG;
+  long long off = 0;
+  for (int i = 0; i < cls; ++i) off += class_packed_floats(a.Cin, (int)classes[i].taps.size(), cdiv(a.Cout, 32));
+  ConvPlan p;
+  rc = plan_class(a, ngroups, classes[cls], a.transposed ? 1 : a.stride, a.transposed ? a.stride : 1, x_aligned16(arr, ngroups), p);
+  if (rc) return rc;
+  const int64_t v[14] = {(int64_t)classes.size(), p.family, p.row, p.g.lgTW, p.g.lgTH, p.g.lgTI, p.g.ckm, p.ncb, p.nblk,
+                         (int64_t)p.g.lds_bytes, p.block, p.vec4, p.dma, off};
+  std::copy(v, v + 14, out);
+  return ICM_OK;
+}
+
 int64_t icm_packed_weight_floats(int Cout, int Cin, int KH, int KW) {
-  return (int64_t)icm::cdiv(Cin, 8) * KH * KW * icm::cdiv(Cout, 32) * 256;
+  return icm::class_packed_floats(Cin, KH * KW, icm::cdiv(Cout, 32));
 }
 
 int icm_pack_weights(const float* w, float* wp, int Cout, int Cin, int KH, int KW, int src_out_major,
                      int transposed, int stride, int pad, int nonneg, float bound, float pedestal, void* stream) {
   using namespace icm;
   if (!w || !wp || Cout <= 0 || Cin <= 0 || KH * KW > ICM_MAX_TAPS || (stride != 1 && stride != 2)) return ICM_ERR_ARG;
-  std::vector<ConvClass> classes = build_classes(KH, KW, stride, pad, transposed);
-  const int ncot = cdiv(Cout, 32), nchunks = cdiv(Cin, 8);
+  icm_pack_job J{};   // natural source row length and destination tiling, spatial taps
+  J.w = w; J.wp = wp; J.Cout = Cout; J.Cin = Cin; J.KH = KH; J.KW = KW; J.src_out_major = src_out_major; J.nonneg = nonneg;
+  J.bound = bound; J.pedestal = pedestal;
   long long off = 0;
-  for (const ConvClass& cls : classes) {
-    const int ntaps = (int)cls.taps.size();
-    if (ntaps == 0) continue;
-    PackDesc d{};
-    d.w = w;
-    d.wp = wp + off;
-    d.Co = Cout; d.Ci = Cin; d.KHW = KH * KW; d.src_out_major = src_out_major;
-    d.ntaps = ntaps; d.ncot = ncot; d.nchunks = nchunks; d.nonneg = nonneg;
-    d.bound = bound; d.pedestal = pedestal;
-    d.src_ld = src_out_major ? Cin : Cout; d.src_off = 0; d.dst_ncot = ncot; d.dst_cot_off = 0; d.wino = 0;
-    for (int t = 0; t < ICM_MAX_TAPS; ++t) d.tapidx[t] = 0;
-    for (int t = 0; t < ntaps; ++t) d.tapidx[t] = (short)cls.taps[t].kidx;
-    const long long total = (long long)nchunks * ntaps * ncot * 256;
-    const int blocks = std::min(nchunks * ncot, 2048);
-    hipLaunchKernelGGL(pack_weights_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, d);
+  for (const ConvClass& cls : build_classes(KH, KW, stride, pad, transposed)) {
+    if (cls.taps.empty()) continue;
+    const PackDesc d = make_pack_desc(J, cls, off);
+    hipLaunchKernelGGL(pack_weights_kernel, dim3(std::min(d.nchunks * d.ncot, 2048)), dim3(256), 0, (hipStream_t)stream, d);
     ICM_CHECK_LAUNCH();
-    off += total;
+    off += class_packed_floats(Cin, d.ntaps, d.dst_ncot);
   }
   return ICM_OK;
 }
-
 
 int icm_pack_weights_batch(const icm_pack_job* jobs, int n, void* stream) {
   using namespace icm;
@@ -804,25 +865,15 @@ int icm_pack_weights_batch(const icm_pack_job* jobs, int n, void* stream) {
       for (int t = 0; t < 16; ++t) wc.taps.push_back({0, 0, 0});
       classes.assign(1, wc);
     }
-    const int ncot = cdiv(J.Cout, 32), nchunks = cdiv(J.Cin, 8);
-    const int inner = J.src_out_major ? J.Cin : J.Cout;
-    const int src_ld = J.src_ld > 0 ? J.src_ld : inner;
-    const int dst_ncot = J.dst_ncot > 0 ? J.dst_ncot : ncot;
-    if (J.src_off < 0 || J.src_off + inner > src_ld || J.dst_cot_off < 0 || J.dst_cot_off + ncot > dst_ncot) return ICM_ERR_ARG;
+    const int ncot = cdiv(J.Cout, 32), inner = J.src_out_major ? J.Cin : J.Cout;
+    if (J.src_off < 0 || J.src_off + inner > (J.src_ld > 0 ? J.src_ld : inner) || J.dst_cot_off < 0 ||
+        J.dst_cot_off + ncot > (J.dst_ncot > 0 ? J.dst_ncot : ncot))
+      return ICM_ERR_ARG;
     long long off = 0;
     for (const ConvClass& cls : classes) {
-      const int ntaps = (int)cls.taps.size();
-      if (ntaps == 0) continue;
-      PackDesc& d = m.g[nb];
-      d.w = J.w;
-      d.wp = J.wp + off;
-      d.Co = J.Cout; d.Ci = J.Cin; d.KHW = J.KH * J.KW; d.src_out_major = J.src_out_major;
-      d.ntaps = ntaps; d.ncot = ncot; d.nchunks = nchunks; d.nonneg = J.nonneg;
-      d.bound = J.bound; d.pedestal = J.pedestal;
-      d.src_ld = src_ld; d.src_off = J.src_off; d.dst_ncot = dst_ncot; d.dst_cot_off = J.dst_cot_off; d.wino = J.wino;
-      for (int t = 0; t < ICM_MAX_TAPS; ++t) d.tapidx[t] = 0;
-      for (int t = 0; t < ntaps; ++t) d.tapidx[t] = (short)cls.taps[t].kidx;
-      off += (long long)nchunks * ntaps * dst_ncot * 256;   // class stride of the (possibly concatenated) destination
+      if (cls.taps.empty()) continue;
+      const PackDesc& d = m.g[nb] = make_pack_desc(J, cls, off);
+      off += class_packed_floats(J.Cin, d.ntaps, d.dst_ncot);   // class stride of the (possibly concatenated) destination
       if (++nb == ICM_PACK_NB) {
         int rc = flush();
         if (rc) return rc;

@@ -542,9 +542,6 @@ __global__ __launch_bounds__(256) void wino_input_transform_kernel(const WinoXfD
   }
 }
 
-struct WinoGeom {
-  int lgTX, lgTY, lgTI, tiles_x, tiles_y, tiles_n, nchunks8, nsteps;
-};
 static WinoGeom wino_geometry(const icm_conv_args& a) {
   WinoGeom g;
   const int tw = cdiv(a.W, 2), th = cdiv(a.H, 2);   // tiles per image row / column
@@ -595,18 +592,60 @@ bool wino_supported(const icm_conv_args& a) {
   return true;
 }
 
+// Co tiles per workgroup, the 4 + 4 or the eight-MFMA-wave kernel, the workgroup order and the grid.  No HIP call.
+int plan_conv_wino(const icm_conv_args& a, int ngroups, WinoPlan& p) {
+  if (!wino_supported(a)) return ICM_ERR_UNSUPPORTED;
+  p.g = wino_geometry(a);
+  const int ncot = cdiv(a.Cout, 32);
+  const long long pblocks = (long long)p.g.tiles_x * p.g.tiles_y * p.g.tiles_n;
+  // co tiles per workgroup: 2 halves the activation staging per output; 1 gives twice the workgroups (small launches)
+  static const int force_tco = env_int("ICM_WINO_TCO", 0);
+  int tco = 2;
+  {
+    const long long b2 = pblocks * cdiv(ncot, 2) * ngroups, b1 = pblocks * ncot * ngroups;
+    const double t2 = std::ceil(b2 / 256.0) * 2.0, t1 = std::ceil(b1 / 256.0) * 1.0 * 1.08;
+    if (ncot == 1 || t1 < t2) tco = 1;
+    if (force_tco == 1 || force_tco == 2) tco = force_tco;
+  }
+  // pre-transformed operand: the eight-MFMA-wave kernel, TCO in {2, 3, 4}: whole rounds of the chip, then wide co blocks
+  static const int w8_on = env_int("ICM_WINO8", 1);
+  bool w8 = a.xv != nullptr && w8_on;
+  if (w8) {
+    int t8 = 2;
+    double bestc = 1e300;
+    for (int t = 4; t >= 2; --t) {
+      const long long b = pblocks * cdiv(ncot, t) * ngroups;
+      const double c = std::ceil(b / 256.0) * (t + 0.6);
+      if (c < bestc - 1e-9) { bestc = c; t8 = t; }
+    }
+    if (force_tco >= 2 && force_tco <= 4) t8 = force_tco;
+    // launches that cannot give the wide workgroups a (nearly) full round of the chip keep the 4 + 4 kernel with its
+    // narrower co blocks (measured: 224 -> 176 single 46.6 vs 54.4 us, 176 -> 128 x2 41.9 vs 49.9 us, 3360 -> 160 607 vs 746 us)
+    static const long long w8_min = env_ll("ICM_WINO8_MINWG", 150);
+    if (pblocks * cdiv(ncot, t8) * ngroups >= w8_min || force_tco >= 2) tco = t8;
+    else w8 = false;
+  }
+  p.tco = tco; p.w8 = w8; p.ncb = cdiv(ncot, tco);
+  const double wbytes = 64.0 * a.Cin * a.Cout, abytes = 4.0 * a.Cin * a.N * a.H * a.W;
+  static const int force_order = env_int("ICM_WINO_PXFAST", -1);
+  p.px_fast = (force_order == 0 || force_order == 1) ? force_order : ((wbytes > 3.0e6 && wbytes > abytes) ? 1 : 0);
+  p.nblk = pblocks * p.ncb;
+  if (p.nblk <= 0 || p.nblk > 0x7fffffffLL) return ICM_ERR_ARG;
+  // 64 KB: two staging steps, the output transform reuses it / 128 KB: one output-transform pass of two co tiles
+  p.lds_bytes = w8 ? (size_t)2 * 4 * 2 * 2 * 16 * 64 * sizeof(float) : (size_t)2 * WINO_STEP_FLOATS * sizeof(float);
+  return ICM_OK;
+}
+
 int run_conv_wino(const icm_conv_args* arr, int ngroups, hipStream_t stream) {
   const icm_conv_args& a = arr[0];
-  if (!wino_supported(a)) return ICM_ERR_UNSUPPORTED;
+  WinoPlan p;
+  if (int rc = plan_conv_wino(a, ngroups, p)) return rc;
   WinoDesc d{};
   fill_conv_ptrs(d.g, arr, ngroups, 0);
   d.x_bs = a.x_bs; d.y_bs = a.y_bs; d.res_bs = a.res_bs; d.aux_bs = a.aux_bs; d.y2_bs = a.y2_bs;
   d.N = a.N; d.Cin = a.Cin; d.Cout = a.Cout; d.H = a.H; d.W = a.W;
-  {
-    const WinoGeom g = wino_geometry(a);
-    d.lgTX = g.lgTX; d.lgTY = g.lgTY; d.lgTI = g.lgTI; d.tiles_x = g.tiles_x; d.tiles_y = g.tiles_y; d.tiles_n = g.tiles_n;
-    d.nchunks8 = g.nchunks8; d.nsteps = g.nsteps;
-  }
+  d.lgTX = p.g.lgTX; d.lgTY = p.g.lgTY; d.lgTI = p.g.lgTI; d.tiles_x = p.g.tiles_x; d.tiles_y = p.g.tiles_y; d.tiles_n = p.g.tiles_n;
+  d.nchunks8 = p.g.nchunks8; d.nsteps = p.g.nsteps;
   d.ncot = cdiv(a.Cout, 32);
   d.vpre = a.xv != nullptr ? 1 : 0;
   if (d.vpre)   // the operand of every member is its pre-transformed buffer
@@ -618,55 +657,15 @@ int run_conv_wino(const icm_conv_args* arr, int ngroups, hipStream_t stream) {
   d.epi = a.epi; d.accum = a.accum; d.act = a.pro_act;
   d.seg_len = a.x_seg_len; d.seg_gap = a.x_seg_len ? a.x_seg_gap : 0;
   d.dseg = make_fastdiv((uint32_t)std::max(1, a.x_seg_len));
-  const long long pblocks = (long long)d.tiles_x * d.tiles_y * d.tiles_n;
-  // co tiles per workgroup: 2 halves the activation staging per output; 1 gives twice the workgroups (small launches)
-  static const int force_tco = env_int("ICM_WINO_TCO", 0);
-  int tco = 2;
-  {
-    const long long b2 = pblocks * cdiv(d.ncot, 2) * ngroups, b1 = pblocks * d.ncot * ngroups;
-    const double t2 = std::ceil(b2 / 256.0) * 2.0, t1 = std::ceil(b1 / 256.0) * 1.0 * 1.08;
-    if (d.ncot == 1 || t1 < t2) tco = 1;
-    if (force_tco == 1 || force_tco == 2) tco = force_tco;
-    (void)b1;
-  }
-  // pre-transformed operand: the eight-MFMA-wave kernel, TCO in {2, 3, 4}: whole rounds of the chip, then wide co blocks
-  static const int w8_on = env_int("ICM_WINO8", 1);
-  bool w8 = d.vpre && w8_on;
-  if (w8) {
-    int t8 = 2;
-    double bestc = 1e300;
-    for (int t = 4; t >= 2; --t) {
-      const long long b = pblocks * cdiv(d.ncot, t) * ngroups;
-      const double c = std::ceil(b / 256.0) * (t + 0.6);
-      if (c < bestc - 1e-9) { bestc = c; t8 = t; }
-    }
-    if (force_tco >= 2 && force_tco <= 4) t8 = force_tco;
-    // launches that cannot give the wide workgroups a (nearly) full round of the chip keep the 4 + 4 kernel with its
-    // narrower co blocks (measured: 224 -> 176 single 46.6 vs 54.4 us, 176 -> 128 x2 41.9 vs 49.9 us, 3360 -> 160 607 vs 746 us)
-    static const long long w8_min = env_ll("ICM_WINO8_MINWG", 150);
-    if (pblocks * cdiv(d.ncot, t8) * ngroups >= w8_min || force_tco >= 2) tco = t8;
-    else w8 = false;
-  }
-  d.ncb = cdiv(d.ncot, tco);
-  d.npx = (int)pblocks;
+  d.ncb = p.ncb; d.npx = (int)(p.nblk / p.ncb); d.px_fast = p.px_fast;
   static const int dbg = env_int("ICM_WINO_DEBUG", 0);
   d.dbg = dbg;
-  {
-    const double wbytes = 64.0 * a.Cin * a.Cout, abytes = 4.0 * a.Cin * a.N * a.H * a.W;
-    static const int force_order = env_int("ICM_WINO_PXFAST", -1);
-    d.px_fast = (wbytes > 3.0e6 && wbytes > abytes) ? 1 : 0;
-    if (force_order == 0 || force_order == 1) d.px_fast = force_order;
-  }
-  const long long nblk = pblocks * d.ncb;
-  if (nblk <= 0 || nblk > 0x7fffffffLL) return ICM_ERR_ARG;
-  void (*fn)(const WinoDesc) = tco == 2 ? conv_wino_kernel<2> : conv_wino_kernel<1>;
-  size_t lds = (size_t)2 * WINO_STEP_FLOATS * sizeof(float);   // 64 KB: two staging steps; the output transform reuses it
-  if (w8) {
-    fn = tco == 4 ? conv_wino8_kernel<4> : (tco == 3 ? conv_wino8_kernel<3> : conv_wino8_kernel<2>);
-    lds = (size_t)2 * 4 * 2 * 2 * 16 * 64 * sizeof(float);      // 128 KB: one output-transform pass of two co tiles
+  void (*fn)(const WinoDesc) = p.tco == 2 ? conv_wino_kernel<2> : conv_wino_kernel<1>;
+  if (p.w8) {
+    fn = p.tco == 4 ? conv_wino8_kernel<4> : (p.tco == 3 ? conv_wino8_kernel<3> : conv_wino8_kernel<2>);
     if (!ensure_max_lds(reinterpret_cast<const void*>(fn))) return ICM_ERR_LAUNCH;
   }
-  hipLaunchKernelGGL(fn, dim3((unsigned)nblk, ngroups, 1), dim3(512), lds, stream, d);
+  hipLaunchKernelGGL(fn, dim3((unsigned)p.nblk, ngroups, 1), dim3(512), p.lds_bytes, stream, d);
   ICM_CHECK_LAUNCH();
   return ICM_OK;
 }

@@ -13,6 +13,8 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("ICM_LIB", os.path.join(os.path.dirname(_HERE), "lib", "libicm_hip.so"))
 
 ACT_NONE, ACT_GELU, ACT_SQUARE = 0, 1, 2
+# icm_debug_force_conv_cfg values that are no row of the tile table (ICM_CONV_CFG_* of include/icm_hip.h)
+CONV_CFG_AUTO, CONV_CFG_KS8_64X64, CONV_CFG_KS8_32X128 = -1, 100, 101
 EPI_NONE, EPI_RES, EPI_RES_GELU, EPI_GDN, EPI_IGDN, EPI_MUL_DGELU, EPI_AXPY2, EPI_LRP, EPI_RES_MUL_DGELU = range(9)
 
 _f = C.POINTER(C.c_float)
@@ -73,7 +75,7 @@ SYMBOLS = [
     "icm_eb_likelihood_fwd", "icm_eb_likelihood_bwd", "icm_eb_aux_loss", "icm_gc_likelihood_ste_fwd",
     "icm_gc_likelihood_ste_bwd", "icm_rd_loss_fwd", "icm_rd_loss_bwd", "icm_grad_sqnorm", "icm_adam_step", "icm_adam_step_hyper", "icm_fill",
     "icm_winattn_bwd_workspace_floats", "icm_debug_force_conv_cfg", "icm_debug_forced_conv_cfg", "icm_debug_force_conv1x1",
-    "icm_debug_force_wgrad_cfg", "icm_debug_wgrad_plan",
+    "icm_debug_force_wgrad_cfg", "icm_debug_wgrad_plan", "icm_debug_conv_plan",
     "icm_debug_force_winattn_valu",
     "icm_zigzag_order", "icm_zigzag_splits", "icm_zigzag_reverse",
     "icm_pmf_to_quantized_cdf", "icm_rans_encode_with_indexes", "icm_rans_decode_with_indexes",
@@ -143,6 +145,7 @@ def lib():
         L.icm_debug_force_conv_cfg.restype = None
         L.icm_debug_force_conv1x1.argtypes = [i32]
         L.icm_debug_force_conv1x1.restype = None
+        L.icm_debug_conv_plan.argtypes = [C.POINTER(ConvArgs), i32, i32, C.POINTER(i64)]
         L.icm_debug_force_wgrad_cfg.argtypes = [i32, i32]
         L.icm_debug_force_wgrad_cfg.restype = None
         L.icm_debug_wgrad_plan.argtypes = [C.POINTER(WgradArgs), i32, C.POINTER(C.c_int32)]

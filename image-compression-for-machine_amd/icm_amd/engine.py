@@ -66,7 +66,7 @@ def wino_ok(KH, KW, stride, pad, Cin, ps=0, conv_transposed=False, work: float =
     directions of a 3x3 stride-1 layer are all supported: icm_conv_winograd_ok).  work = N * H * W * Cin * Cout * members."""
     return (USE_WINO and KH == 3 and KW == 3 and stride == 1 and pad == 1 and not ps and not conv_transposed and
             Cin >= (_WINO_MIN_CIN if min_c is None else min_c) and work >= _WINO_MIN_WORK and
-            L.lib().icm_debug_forced_conv_cfg() < 0)
+            L.lib().icm_debug_forced_conv_cfg() == L.CONV_CFG_AUTO)
 
 
 # In-place HIP updates (icm_adam_step) do not bump torch's tensor version counters: the trainer bumps this generation

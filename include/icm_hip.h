@@ -424,20 +424,36 @@ typedef struct { int64_t offset; int32_t H, W, y0, x0; } icm_crop_desc;   /* 24 
 int icm_image_batch_u8_to_f32(const uint8_t* arena, const icm_crop_desc* desc, int B, float* dst /* [B,3,CH,CW] */,
                               int CH, int CW, void* stream);
 
-/* ---- test hooks (process-global; used by the parity tests and tools/tune_conv.py only) ----------------------
- * force the implicit-GEMM tile configuration (index into the kernel table; 100 / 101 = the 8-wave K-split kernel of
- * conv_ks8.hip with 64 co x 64 px / 32 co x 128 px blocks where it is eligible; -1 = automatic) / the weight-gradient
+/* ---- test hooks (process-global; used by the parity tests, the recorded-plan tests and tools/tune_conv.py only) ----
+ * force the implicit-GEMM tile configuration: a row of the kernel table of conv_igemm.hip (0-12), one of the two block
+ * shapes of the 8-wave K-split kernel of conv_ks8.hip where it is eligible (ICM_CONV_CFG_KS8_*), or
+ * ICM_CONV_CFG_AUTO (any negative value).  While a configuration is forced no launch takes the pointwise kernel.
+ * icm_debug_force_wgrad_cfg: the weight-gradient
  * kernel variant (0-2 general kernel <2,1,7> / <2,2,9> / <4,4,4>; 3-6 three-by-three tiles per wave <3,3> / <6,6> /
  * <3,6> / <6,3>; 7 its tap-per-wave form; 8 / 9 nine taps from one DMA staging, 96 / 64-wide blocks; 10 the 25-tap
  * 5x5 form; 11-14 the DMA-only 1x1 kernel <6,6> / <3,6> / <6,3> / <3,3>; -1 = automatic) and its XCD-aware
  * workgroup order (0 / 1, -1 = automatic) */
+#define ICM_CONV_CFG_AUTO (-1)
+#define ICM_CONV_CFG_KS8_64X64 100    /* 64 co x 64 px blocks */
+#define ICM_CONV_CFG_KS8_32X128 101   /* 32 co x 128 px blocks */
 void icm_debug_force_conv_cfg(int idx);
-/* the value last set (-1 = automatic): callers that choose between the direct and the Winograd form keep the direct
- * one while a tile configuration is forced */
+/* the value in force (ICM_CONV_CFG_AUTO = automatic): callers that choose between the direct and the Winograd form keep
+ * the direct one while a tile configuration is forced */
 int icm_debug_forced_conv_cfg(void);
 /* pointwise (1x1 stride-1, Cin % 8 == 0) convolutions: -1 = automatic (the barrier-free direct-operand kernel when the
  * launch has >= 1024 waves), 0 = always the LDS-staged kernel, 1 = the direct kernel whenever eligible */
 void icm_debug_force_conv1x1(int mode);
+/* what a forward / input-gradient launch of these ngroups members would be, for tap class cls (a transposed stride-2
+ * launch has four classes, every other launch one): validation, the member-agreement check and the plan step of
+ * icm_conv_run_grouped, and nothing else -- pure host code, pointers are looked at for null-ness and alignment only.
+ * Honours icm_debug_force_conv_cfg, icm_debug_force_conv1x1 and a->algo.  Returns the code the launch would return and
+ * fills (all 0 unless ICM_OK)
+ *   out = {classes, family, cfg row or co tiles per block, lgTW|lgTX, lgTH|lgTY, lgTI, ckm|nsteps, co blocks, workgroups
+ *          per member (0: an empty class, nothing launched), dynamic LDS bytes, block threads, vec4|vpre, dma|px_fast,
+ *          offset of the class in the packed weights in floats, 0, 0}
+ * family: 0 LDS-staged implicit GEMM (cfg row of its table), 1 8-wave K-split (co tiles per block), 2 pointwise (row of
+ * its table), 3 Winograd 4 + 4 waves, 4 Winograd eight MFMA waves (both: co tiles per workgroup; the | alternatives). */
+int icm_debug_conv_plan(const icm_conv_args* a, int ngroups, int cls, int64_t out[16]);
 void icm_debug_force_wgrad_cfg(int variant, int xcd_order);
 /* what the planner of the direct weight-gradient kernels decides for n problems of geometry *a (pure host code; honours
  * the forced variant): returns its code and fills out = {variant, lgNPX, lgTW, lgTH, lgTI, taps per group, pixel

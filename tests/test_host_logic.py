@@ -96,6 +96,38 @@ def test_wgrad_plans_match_the_recorded_planner(golden_dir):
     assert not bad, (len(bad), bad[:5])
 
 
+def test_conv_plans_match_the_recorded_planner(golden_dir):
+    """every row of tests/golden/conv_plans.npz (make_conv_plans.py: automatic choices over a cross of geometries,
+    operand / epilogue kinds, alignment and algo, and every forced configuration and pointwise mode on the conv shapes of
+    test_gpu_ops.py) replayed through icm_debug_conv_plan: the return code and all sixteen values are exactly the
+    recorded ones.  For every ICM_OK row, the family is a Winograd one exactly when algo is, and for direct rows the
+    last tap class ends where icm_packed_weight_floats says the packed weights end."""
+    import importlib.util
+    import numpy as np
+    spec = importlib.util.spec_from_file_location("make_conv_plans", os.path.join(golden_dir, "make_conv_plans.py"))
+    G = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(G)   # the row layout and the argument builder have one definition: the generator's
+    L = _lib.lib()
+    z = np.load(os.path.join(golden_dir, "conv_plans.npz"), allow_pickle=False)
+    args, want = z["args"].tolist(), z["plan"].tolist()
+    assert len(args) == len(want) > 50000
+    bad = []
+    for row, exp in zip(args, want):
+        got = G.plan(L, row)
+        if got != exp:
+            bad.append((row, exp, got))
+        elif got[0] == 0:
+            r = dict(zip(G.ARG_FIELDS, row))
+            if (got[2] in (G.WINO44, G.WINO8)) != (r["algo"] == 1):
+                bad.append((row, "family", got))
+            elif r["algo"] == 0 and r["cls"] == got[1] - 1:
+                size = -(-r["Cin"] // 8) * G.class_taps(r["KH"], r["stride"], r["pad"], r["transposed"], r["cls"]) * \
+                    -(-r["Cout"] // 32) * 256
+                if got[14] + size != L.icm_packed_weight_floats(r["Cout"], r["Cin"], r["KH"], r["KW"]):
+                    bad.append((row, "packed size", got))
+    assert not bad, (len(bad), bad[:5])
+
+
 class _FakeLib:
     """real host-side planners, no-op launches"""
 
