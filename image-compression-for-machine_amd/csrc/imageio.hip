@@ -8,6 +8,8 @@
 //   image_f32_to_u8_kernel   planar [3, PH, PW] f32 -> interleaved [H, W, 3] bytes of the window at (top, left);
 //                            with a reference image also one partial sum of squared byte differences per workgroup
 //   image_sse_finish_kernel  adds the partial sums (64-bit integers: exact, whatever the order)
+//   image_tile_blend_kernel  adds one decoded tile's window, weighted by its seam ramps, into the f32 canvas of a
+//                            tiled image (planar [3, PH, PW] -> planar [3, H, W]); a thread owns four pixels of a row
 //
 // Pure bandwidth work.  A thread owns a run of 16 pixels of one row: 48 interleaved bytes = three 16-byte accesses,
 // and 16 floats = four 16-byte accesses in each of the three planes.  Whether the 16-byte form may be used is decided
@@ -305,6 +307,93 @@ __global__ __launch_bounds__(BLOCK) void image_sse_finish_kernel(const unsigned 
   if (threadIdx.x == 0) *out = (long long)((red[0] + red[1]) + (red[2] + red[3]));
 }
 
+// Tile assembly of a tiled image: canvas[c][y0 + y][x0 + x] += (wy(y) * wx(x)) * src[c][top + y][left + x] over the
+// h x w window.  w?(i) is ramp[i] within m pixels of a side that has a neighbour (ramp[n - 1 - i] at the far side) and 1
+// elsewhere; where both bands reach a pixel the near (left / top) side decides.  The two products and the sum are
+// single IEEE operations in that association (no contraction into an FMA), so a host restatement agrees bit for bit
+// and a pixel under one tile keeps 0 + 1 * v = v.  A thread owns BLEND_RUN adjacent pixels of one row in all three
+// planes and shares the weights among them; each side (source, canvas) of each plane moves as one 16-byte access when
+// its address is 16-byte aligned and the run lies inside the window, and float by float otherwise.  Plane offsets are
+// 64-bit: the canvas of a large image exceeds 2^31 elements.
+constexpr int BLEND_RUN = 4;
+constexpr int EDGE_LEFT = ICM_TILE_EDGE_LEFT, EDGE_RIGHT = ICM_TILE_EDGE_RIGHT, EDGE_TOP = ICM_TILE_EDGE_TOP,
+              EDGE_BOTTOM = ICM_TILE_EDGE_BOTTOM;
+
+// One rounding each, never fused: the headers' __fmul_rn / __fadd_rn are a plain * and + that carry the contraction
+// flag of their own translation context, and hipcc folds a pair of them into v_pk_fma_f32.  The same operators under
+// contract(off) stay a v_mul / v_add pair.
+__device__ __forceinline__ float mul_rn(float a, float b) {
+#pragma clang fp contract(off)
+  return a * b;
+}
+__device__ __forceinline__ float add_rn(float a, float b) {
+#pragma clang fp contract(off)
+  return a + b;
+}
+
+__device__ __forceinline__ float blend_weight(const float* __restrict__ ramp, int i, int n, int m, bool near, bool far) {
+  if (near && i < m) return ramp[i];
+  if (far && n - 1 - i < m) return ramp[n - 1 - i];
+  return 1.0f;
+}
+
+__global__ __launch_bounds__(BLOCK) void image_tile_blend_kernel(const float* __restrict__ src, int PH, int PW, int top,
+                                                                  int left, int h, int w, float* __restrict__ canvas,
+                                                                  int H, int W, int y0, int x0,
+                                                                  const float* __restrict__ ramp, int m, int edges,
+                                                                  int runs_per_row, long long total_runs) {
+  const long long g = (long long)blockIdx.x * BLOCK + threadIdx.x;
+  if (g >= total_runs) return;
+  const int y = (int)(g / runs_per_row);
+  const int x = ((int)(g - (long long)y * runs_per_row)) * BLEND_RUN;
+  const bool full = x + BLEND_RUN <= w;
+
+  const float wy = blend_weight(ramp, y, h, m, edges & EDGE_TOP, edges & EDGE_BOTTOM);
+  float k[BLEND_RUN];   // wy * wx of the run's pixels
+#pragma unroll
+  for (int j = 0; j < BLEND_RUN; ++j) {
+    const float wx = x + j < w ? blend_weight(ramp, x + j, w, m, edges & EDGE_LEFT, edges & EDGE_RIGHT) : 1.0f;
+    k[j] = mul_rn(wy, wx);
+  }
+
+  const size_t splane = (size_t)PH * PW, cplane = (size_t)H * W;
+  const float* in = src + (size_t)(top + y) * PW + left + x;
+  float* out = canvas + (size_t)(y0 + y) * W + x0 + x;
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    const float* ip = in + c * splane;
+    float* op = out + c * cplane;
+    const bool ovec = full && aligned16(op);
+    float s[BLEND_RUN], a[BLEND_RUN];
+    if (full && aligned16(ip)) {
+      const f32x4 v = *reinterpret_cast<const f32x4*>(ip);
+#pragma unroll
+      for (int j = 0; j < BLEND_RUN; ++j) s[j] = v[j];
+    } else {
+#pragma unroll
+      for (int j = 0; j < BLEND_RUN; ++j) s[j] = x + j < w ? ip[j] : 0.0f;
+    }
+    if (ovec) {
+      const f32x4 v = *reinterpret_cast<const f32x4*>(op);
+#pragma unroll
+      for (int j = 0; j < BLEND_RUN; ++j) a[j] = v[j];
+    } else {
+#pragma unroll
+      for (int j = 0; j < BLEND_RUN; ++j) a[j] = x + j < w ? op[j] : 0.0f;
+    }
+#pragma unroll
+    for (int j = 0; j < BLEND_RUN; ++j) a[j] = add_rn(a[j], mul_rn(k[j], s[j]));
+    if (ovec) {
+      const f32x4 v = {a[0], a[1], a[2], a[3]};
+      *reinterpret_cast<f32x4*>(op) = v;
+    } else {
+#pragma unroll
+      for (int j = 0; j < BLEND_RUN; ++j)
+        if (x + j < w) op[j] = a[j];
+    }
+  }
+}
+
 // runs of a rows x cols image and the workgroups that cover them; false = geometry out of range
 bool run_grid(int rows, int cols, int& runs_per_row, long long& total_runs, int& blocks) {
   if (rows <= 0 || cols <= 0 || rows > MAX_SIDE || cols > MAX_SIDE) return false;
@@ -371,6 +460,23 @@ int icm_image_f32_to_u8(const float* src, int PH, int PW, int top, int left, uin
     hipLaunchKernelGGL(image_sse_finish_kernel, dim3(1), dim3(BLOCK), 0, ST, part, blocks, reinterpret_cast<long long*>(sse));
     ICM_CHECK_LAUNCH();
   }
+  return ICM_OK;
+}
+
+int icm_image_tile_blend(const float* src, int PH, int PW, int top, int left, int h, int w, float* canvas, int H, int W,
+                         int y0, int x0, const float* ramp, int m, int edges, void* stream) {
+  if (!src || !canvas || top < 0 || left < 0 || y0 < 0 || x0 < 0 || m < 0 || (m > 0 && !ramp)) return ICM_ERR_ARG;
+  if (edges < 0 || edges > 15) return ICM_ERR_ARG;
+  for (int v : {PH, PW, h, w, H, W})
+    if (v <= 0 || v > MAX_SIDE) return ICM_ERR_ARG;
+  if ((long long)top + h > PH || (long long)left + w > PW) return ICM_ERR_ARG;   // the window inside src
+  if ((long long)y0 + h > H || (long long)x0 + w > W) return ICM_ERR_ARG;       // and inside the canvas
+  if (((edges & (EDGE_LEFT | EDGE_RIGHT)) && m > w) || ((edges & (EDGE_TOP | EDGE_BOTTOM)) && m > h)) return ICM_ERR_ARG;
+  const int rpr = (w + BLEND_RUN - 1) / BLEND_RUN;
+  const long long total = (long long)h * rpr;                                    // <= 32768 * 8192
+  hipLaunchKernelGGL(image_tile_blend_kernel, dim3((unsigned)((total + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, ST, src, PH,
+                     PW, top, left, h, w, canvas, H, W, y0, x0, ramp, m, edges, rpr, total);
+  ICM_CHECK_LAUNCH();
   return ICM_OK;
 }
 

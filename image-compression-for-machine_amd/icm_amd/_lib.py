@@ -15,6 +15,7 @@ LIB_PATH = os.environ.get("ICM_LIB", os.path.join(os.path.dirname(_HERE), "lib",
 ACT_NONE, ACT_GELU, ACT_SQUARE = 0, 1, 2
 # icm_debug_force_conv_cfg values that are no row of the tile table (ICM_CONV_CFG_* of include/icm_hip.h)
 CONV_CFG_AUTO, CONV_CFG_KS8_64X64, CONV_CFG_KS8_32X128 = -1, 100, 101
+TILE_EDGE_LEFT, TILE_EDGE_RIGHT, TILE_EDGE_TOP, TILE_EDGE_BOTTOM = 1, 2, 4, 8   # ICM_TILE_EDGE_*
 EPI_NONE, EPI_RES, EPI_RES_GELU, EPI_GDN, EPI_IGDN, EPI_MUL_DGELU, EPI_AXPY2, EPI_LRP, EPI_RES_MUL_DGELU = range(9)
 
 _f = C.POINTER(C.c_float)
@@ -84,7 +85,7 @@ SYMBOLS = [
     "icm_quantize", "icm_dequantize", "icm_clamp", "icm_pad2d",
     "icm_msssim_workspace_floats", "icm_msssim_fwd", "icm_msssim_bwd",
     "icm_image_workspace_bytes", "icm_image_u8_to_f32", "icm_image_f32_to_u8",
-    "icm_image_batch_u8_to_f32",
+    "icm_image_batch_u8_to_f32", "icm_image_tile_blend",
 ]
 REDUCE_WS_FLOATS = 8192   # ICM_REDUCE_WS_FLOATS
 
@@ -194,6 +195,7 @@ def lib():
         L.icm_image_u8_to_f32.argtypes = [vp, i32, i32, vp, i32, i32, i32, i32, vp]
         L.icm_image_f32_to_u8.argtypes = [vp, i32, i32, i32, i32, vp, i32, i32, vp, vp, vp, i64, vp]
         L.icm_image_batch_u8_to_f32.argtypes = [vp, vp, i32, vp, i32, i32, vp]
+        L.icm_image_tile_blend.argtypes = [vp, i32, i32, i32, i32, i32, i32, vp, i32, i32, i32, i32, vp, i32, i32, vp]
         L.icm_zigzag_order.argtypes = [i32, i32, i32, vp, i32]
         L.icm_zigzag_splits.argtypes = [vp, i64, vp, i32, i32, i32, i32, i32, i32, i32, vp]
         L.icm_zigzag_reverse.argtypes = [vp, vp, i64, i32, i32, i32, i32, i32, i32, i32, vp]

@@ -23,6 +23,27 @@ Layout -- fixed-width little-endian integers, no padding between fields:
 A stream of two strings therefore carries ``HEADER_BYTES_2`` = 46 bytes besides its payloads, and the file size is
 what ``bpp`` is computed from.  ``unpack`` raises ``ValueError`` -- and nothing else -- for anything that is not
 exactly one such stream; each message names the condition that failed.
+
+A tiled image is a second container with its own magic: a grid of independently coded tiles (``tile_grid`` below gives
+the grid), each of them one complete ``ICMB`` stream.  ``ICMB`` and ``unpack`` are unchanged by it, and each reader
+refuses the other's files for their magic.
+
+    offset  size  field
+         0     4  magic, the bytes ``ICMT``
+         4     2  format version (u16), ``TILED_VERSION`` = 1
+         6     2  architecture id (u16), index into ``ARCHS``
+         8     4  image height (u32, >= 1)
+        12     4  image width (u32, >= 1)
+        16     2  tile extent (u16): a multiple of 64 in 64..32768
+        18     2  overlap of neighbouring tiles in pixels (u16), 2 x overlap <= extent
+        20     2  rows of the tile grid (u16)
+        22     2  cols of the tile grid (u16)
+        24     4  model fingerprint (u32)
+        28  4 rows cols  length of each tile stream (u32), row-major
+       ...   ...  the tile streams, back to back
+       end-4     4  CRC-32 of every byte before it
+
+rows / cols are redundant with the four numbers before them, and a reader refuses a file in which they disagree.
 """
 from __future__ import annotations
 
@@ -133,3 +154,108 @@ def fingerprint(model) -> int:
                 raise ValueError("fingerprint: the entropy tables are empty; call model.update(force=True) first")
             crc = zlib.crc32(t.detach().cpu().numpy().astype("<i4").tobytes(), crc)
     return crc & U32_MAX
+
+
+# ------------------------------------------------------------------------------------------------- tiled images
+TILED_MAGIC = b"ICMT"
+TILED_VERSION = 1
+TILE_MIN, TILE_MAX = 64, 32768              # extents: multiples of TILE_MIN (the codec pads every tile to one)
+_TFIXED = struct.Struct("<4sHHIIHHHHI")     # magic .. fingerprint
+TILED_FIXED_BYTES = _TFIXED.size            # 28
+assert TILED_FIXED_BYTES == 28
+TILED_HEADER_KEYS = ("arch", "height", "width", "tile", "overlap", "fingerprint")
+
+
+def tile_grid(height: int, width: int, tile: int, overlap: int) -> Tuple[int, int]:
+    """(rows, cols) of the tile plan.  Per axis of length L, with extent E = tile, overlap m and stride S = E - m:
+    n = max(1, ceil((L - m) / S)) tiles at origins k S with sizes min(E, L - k S).  Neighbours share exactly m pixels,
+    every tile is wider than m and a pixel lies in at most two tiles per axis.  ValueError unless tile is a multiple of
+    64 in 64..32768 and 0 <= 2 overlap <= tile."""
+    height, width = _uint("height", height, U32_MAX, 1), _uint("width", width, U32_MAX, 1)
+    tile, overlap = _uint("tile", tile, TILE_MAX, TILE_MIN), _uint("overlap", overlap, TILE_MAX)
+    if tile % TILE_MIN:
+        raise ValueError(f"bitstream: tile = {tile} is not a multiple of {TILE_MIN}")
+    if 2 * overlap > tile:
+        raise ValueError(f"bitstream: overlap = {overlap} is more than half the tile extent {tile}")
+    stride = tile - overlap
+    return tuple(max(1, -(-(length - overlap) // stride)) for length in (height, width))
+
+
+def pack_tiled(header: Dict, streams: Sequence[bytes]) -> bytes:
+    """``header``: {"arch", "height", "width", "tile", "overlap", "fingerprint"} ("rows" / "cols", if given, must be
+    those of ``tile_grid``); ``streams``: one complete ICMB stream per tile, row-major."""
+    missing = [k for k in TILED_HEADER_KEYS if k not in header]
+    if missing:
+        raise ValueError(f"bitstream: tiled header lacks {missing}")
+    if header["arch"] not in ARCHS:
+        raise ValueError(f"bitstream: unknown architecture {header['arch']!r}; the format knows {list(ARCHS)}")
+    rows, cols = tile_grid(header["height"], header["width"], header["tile"], header["overlap"])
+    if (header.get("rows", rows), header.get("cols", cols)) != (rows, cols):
+        raise ValueError(f"bitstream: header says {header.get('rows')}x{header.get('cols')} tiles, the plan has {rows}x{cols}")
+    rows, cols = _uint("rows", rows, U16_MAX), _uint("cols", cols, U16_MAX)
+    streams = [bytes(s) for s in streams]
+    if len(streams) != rows * cols:
+        raise ValueError(f"bitstream: {len(streams)} tile streams for a plan of {rows}x{cols} tiles")
+    out = bytearray(_TFIXED.pack(TILED_MAGIC, TILED_VERSION, ARCHS.index(header["arch"]), int(header["height"]),
+                                 int(header["width"]), int(header["tile"]), int(header["overlap"]), rows, cols,
+                                 _uint("fingerprint", header["fingerprint"], U32_MAX)))
+    for s in streams:
+        out += _U32.pack(_uint("tile stream length", len(s), U32_MAX))
+    for s in streams:
+        out += s
+    out += _U32.pack(zlib.crc32(bytes(out)) & U32_MAX)
+    return bytes(out)
+
+
+def is_tiled(data) -> bool:
+    """True if ``data`` begins with the magic of a tiled stream (says nothing else about it)"""
+    return isinstance(data, (bytes, bytearray, memoryview)) and bytes(data[:4]) == TILED_MAGIC
+
+
+def unpack_tiled(data: bytes) -> Tuple[Dict, List[bytes]]:
+    """inverse of ``pack_tiled``: (header with "rows" and "cols", tile streams).  ValueError for a bad magic, an unknown
+    version or architecture id, a tile geometry ``tile_grid`` refuses or whose rows / cols are not the stored ones, a
+    declared length that runs past the data, trailing bytes or a CRC mismatch.  The tile streams are returned as they
+    lie; ``unpack`` checks each."""
+    if not isinstance(data, (bytes, bytearray, memoryview)):
+        raise ValueError(f"bitstream: expected bytes, got {type(data).__name__}")
+    data = bytes(data)
+    if not TILED_MAGIC.startswith(data[:4]):
+        raise ValueError("bitstream: bad magic (not an ICMT stream)")
+    if len(data) < TILED_FIXED_BYTES + CRC_BYTES:
+        raise ValueError(f"bitstream: truncated: {len(data)} bytes, the fixed tiled header and CRC need "
+                         f"{TILED_FIXED_BYTES + CRC_BYTES}")
+    (_, version, arch_id, height, width, tile, overlap, rows, cols, fp) = _TFIXED.unpack_from(data, 0)
+    if version != TILED_VERSION:
+        raise ValueError(f"bitstream: unknown tiled format version {version} (this reader knows {TILED_VERSION})")
+    if arch_id >= len(ARCHS):
+        raise ValueError(f"bitstream: unknown architecture id {arch_id} (this reader knows 0..{len(ARCHS) - 1})")
+    if height < 1 or width < 1:
+        raise ValueError(f"bitstream: empty image {height}x{width}")
+    try:
+        plan = tile_grid(height, width, tile, overlap)
+    except ValueError as e:
+        raise ValueError(f"bitstream: bad tile geometry: {e}")
+    if plan != (rows, cols):
+        raise ValueError(f"bitstream: tile grid mismatch: the header says {rows}x{cols} tiles, a {height}x{width} image "
+                         f"in tiles of {tile} overlapping by {overlap} has {plan[0]}x{plan[1]}")
+    n = rows * cols
+    pos = TILED_FIXED_BYTES + 4 * n
+    if pos + CRC_BYTES > len(data):
+        raise ValueError(f"bitstream: truncated: the length table of {n} tiles runs past the data")
+    lengths = [_U32.unpack_from(data, TILED_FIXED_BYTES + 4 * i)[0] for i in range(n)]
+    end = pos + sum(lengths)
+    if end + CRC_BYTES > len(data):
+        raise ValueError(f"bitstream: truncated: declared tile stream lengths run past the data ({len(data)} bytes, "
+                         f"{end + CRC_BYTES} needed)")
+    if end + CRC_BYTES < len(data):
+        raise ValueError(f"bitstream: {len(data) - end - CRC_BYTES} trailing bytes after the CRC")
+    if _U32.unpack_from(data, end)[0] != zlib.crc32(data[:end]) & U32_MAX:
+        raise ValueError("bitstream: CRC mismatch (corrupt stream)")
+    streams = []
+    for ln in lengths:
+        streams.append(data[pos:pos + ln])
+        pos += ln
+    header = {"arch": ARCHS[arch_id], "height": height, "width": width, "tile": tile, "overlap": overlap, "rows": rows,
+              "cols": cols, "fingerprint": fp}
+    return header, streams

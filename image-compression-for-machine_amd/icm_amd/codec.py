@@ -1,7 +1,7 @@
 """``python -m icm_amd.codec`` -- image file to bit-stream file and back, in two processes that share a checkpoint.
 
-    python -m icm_amd.codec encode IMAGE -o FILE -a cnn -p CKPT
-    python -m icm_amd.codec decode FILE -o IMAGE.png -p CKPT [--reference IMAGE]
+    python -m icm_amd.codec encode IMAGE -o FILE -a cnn -p CKPT [--tile N [--overlap M]]
+    python -m icm_amd.codec decode FILE -o IMAGE.png -p CKPT [--reference IMAGE] [--region Y0,X0,H,W]
 
 Parity unpinned: no counterpart in the reference (upstream CompressAI's ``examples/codec.py`` is not in its tree).  The
 conventions are those of ``icm_amd.eval_model``: ``-a`` architecture, ``-p`` checkpoint (``weights_only=True``), exit
@@ -12,7 +12,13 @@ checkpoint's.  Both commands print one JSON line.
 The image boundary runs on the device: the 8-bit image crosses PCIe as bytes, ``icm_image_u8_to_f32`` converts and
 pads in one pass (``ToTensor`` + ``utils.pad_to_multiple``, bit for bit), and ``icm_image_f32_to_u8`` crops, quantises
 (``datasets.to_pil_image``) and, given the original, sums the squared 8-bit differences that the PSNR is formed from.
-The container is ``icm_amd.bitstream``; one image per stream."""
+The container is ``icm_amd.bitstream``; one image per stream.
+
+Large images are coded as a grid of independently coded tiles (``--tile``): the convolution kernels address a plane
+set with 32-bit offsets, which bounds one ``compress()`` call near 11 megapixels, and activation memory grows with the
+image.  Each tile is a complete single-image stream of its crop, all of them wrapped in an ``ICMT`` container; the
+decoder adds the decoded tiles into an f32 canvas, their overlap bands weighted by a linear ramp
+(``icm_image_tile_blend``), and quantises the canvas once.  ``--region`` decodes only the tiles a region touches."""
 from __future__ import annotations
 
 import argparse
@@ -112,49 +118,167 @@ def _ready(model) -> str:
     return arch
 
 
-@torch.no_grad()
-def encode_image(model, img) -> bytes:
-    """8-bit [H, W, 3] image (tensor on any device, or anything ``numpy.asarray`` accepts) -> one bit-stream"""
-    arch = _ready(model)
-    device = next(model.parameters()).device
-    u8 = _as_u8_image(img, device)
+def plan_tiles(H: int, W: int, tile: int, overlap: int):
+    """(rows, cols, [(y0, x0, h, w), ...] row-major) of ``bitstream.tile_grid``: tiles of extent ``tile`` at a stride
+    of ``tile - overlap``, the last of each axis cut at the image.  Host-only."""
+    rows, cols = B.tile_grid(H, W, tile, overlap)
+    S = tile - overlap
+    return rows, cols, [(r * S, c * S, min(tile, H - r * S), min(tile, W - c * S))
+                        for r in range(rows) for c in range(cols)]
+
+
+def tile_edges(r: int, c: int, rows: int, cols: int) -> int:
+    """the sides of tile (r, c) that have a neighbour, as ``icm_image_tile_blend`` takes them"""
+    return ((L.TILE_EDGE_LEFT if c > 0 else 0) | (L.TILE_EDGE_RIGHT if c < cols - 1 else 0) |
+            (L.TILE_EDGE_TOP if r > 0 else 0) | (L.TILE_EDGE_BOTTOM if r < rows - 1 else 0))
+
+
+def blend_ramp(m: int) -> np.ndarray:
+    """weights across an overlap band of m pixels, (i + 0.5) / m in f32: i + 0.5 is exact and the quotient is rounded
+    once, on the host, so nothing depends on how the device divides"""
+    return (np.arange(m, dtype=np.float32) + np.float32(0.5)) / np.float32(max(m, 1))
+
+
+def image_tile_blend(x: torch.Tensor, pads: Tuple[int, int, int, int], canvas: torch.Tensor, y0: int, x0: int,
+                     ramp: Optional[torch.Tensor], edges: int) -> None:
+    """canvas [3, H, W] += weights x the window of the f32 [1, 3, PH, PW] tile ``x`` inside ``pads``, at (y0, x0)"""
+    left, right, top, bottom = pads
+    h, w = x.size(2) - top - bottom, x.size(3) - left - right
+    m = 0 if ramp is None else ramp.numel()
+    check(L.lib().icm_image_tile_blend(x.data_ptr(), x.size(2), x.size(3), top, left, h, w, canvas.data_ptr(),
+                                       canvas.size(1), canvas.size(2), y0, x0, L.ptr(ramp), m, edges, L.stream()),
+          "image_tile_blend")
+
+
+def _encode_one(model, arch: str, fp: int, u8: torch.Tensor) -> bytes:
     H, W = u8.size(0), u8.size(1)
     pads = center_pads(H, W)
     enc = model.compress(image_u8_to_f32(u8, pads))
     header = {"arch": arch, "height": H, "width": W, "pads": pads, "shape": tuple(int(s) for s in enc["shape"]),
-              "fingerprint": B.fingerprint(model)}
+              "fingerprint": fp}
     return B.pack(header, [s for part in enc["strings"] for s in part])
 
 
 @torch.no_grad()
-def decode_image(model, data: bytes, reference=None) -> Tuple[torch.Tensor, Dict]:
-    """one bit-stream -> (8-bit [H, W, 3] host tensor, info); ``info``: "bpp" = 8 x the whole stream length / (H W),
-    header included, and, given ``reference`` (the original 8-bit image), "psnr" of the two 8-bit images"""
+def encode_image(model, img, tile: Optional[int] = None, overlap: int = 0) -> bytes:
+    """8-bit [H, W, 3] image (tensor on any device, or anything ``numpy.asarray`` accepts) -> one bit-stream.  With
+    ``tile``, an image of more than one tile (``plan_tiles``) becomes an ICMT stream whose tile k is
+    ``encode_image(model, crop k)``, the tiles coded one after another; an image of one tile is written untiled."""
     arch = _ready(model)
-    header, strings = B.unpack(data)
-    if header["arch"] != arch:
-        raise ValueError(f"codec: the stream was written by architecture {header['arch']!r}, the model is {arch!r}")
-    fp = B.fingerprint(model)
-    if header["fingerprint"] != fp:
-        raise ValueError(f"codec: model fingerprint mismatch: the stream was written with entropy tables "
-                         f"{header['fingerprint']:#010x}, this checkpoint has {fp:#010x}")
-    H, W, pads = header["height"], header["width"], header["pads"]
-    if len(strings) != 2:
-        raise ValueError(f"codec: {arch} streams hold two strings, this one holds {len(strings)}")
     device = next(model.parameters()).device
-    ref = None if reference is None else _as_u8_image(reference, device, "reference")
-    if ref is not None and tuple(ref.shape) != (H, W, 3):
-        raise ValueError(f"codec: the reference is {ref.size(0)}x{ref.size(1)}, the stream holds a {H}x{W} image")
+    u8 = _as_u8_image(img, device)
+    H, W = u8.size(0), u8.size(1)
+    if tile is None:
+        if overlap:
+            raise ValueError("codec: overlap needs a tile extent")
+        plan = [(0, 0, H, W)]
+    else:
+        plan = plan_tiles(H, W, tile, overlap)[2]
+    fp = B.fingerprint(model)
+    if len(plan) == 1:
+        return _encode_one(model, arch, fp, u8)
+    streams = [_encode_one(model, arch, fp, u8[y0:y0 + h, x0:x0 + w].contiguous()) for y0, x0, h, w in plan]
+    return B.pack_tiled({"arch": arch, "height": H, "width": W, "tile": tile, "overlap": overlap, "fingerprint": fp},
+                        streams)
+
+
+def _check_model(header: Dict, arch: str, fp: int, what: str = "the stream") -> None:
+    if header["arch"] != arch:
+        raise ValueError(f"codec: {what} was written by architecture {header['arch']!r}, the model is {arch!r}")
+    if header["fingerprint"] != fp:
+        raise ValueError(f"codec: model fingerprint mismatch: {what} was written with entropy tables "
+                         f"{header['fingerprint']:#010x}, this checkpoint has {fp:#010x}")
+
+
+def _check_strings(arch: str, strings, what: str = "this one") -> None:
+    if len(strings) != 2:
+        raise ValueError(f"codec: {arch} streams hold two strings, {what} holds {len(strings)}")
+
+
+def _decompress_one(model, arch: str, header: Dict, strings) -> torch.Tensor:
+    H, W, pads = header["height"], header["width"], header["pads"]
     x_hat = model.decompress([[strings[0]], [strings[1]]], header["shape"])["x_hat"]
     left, right, top, bottom = pads
     if tuple(x_hat.shape) != (1, 3, top + H + bottom, left + W + right):
         raise ValueError(f"codec: latent shape {header['shape']} decodes to {tuple(x_hat.shape)}, not to a padded "
                          f"{H}x{W} image")
-    out, sse = image_f32_to_u8(x_hat, pads, ref)
+    return x_hat
+
+
+def _check_region(region, H: int, W: int) -> Tuple[int, int, int, int]:
+    if region is None:
+        return 0, 0, H, W
+    try:
+        y0, x0, h, w = region
+        if any(isinstance(v, bool) or not hasattr(v, "__index__") for v in region):
+            raise TypeError
+        y0, x0, h, w = int(y0), int(x0), int(h), int(w)
+    except (TypeError, ValueError):
+        raise ValueError(f"codec: region must be four integers (y0, x0, h, w), got {region!r}")
+    if y0 < 0 or x0 < 0 or h < 1 or w < 1 or y0 + h > H or x0 + w > W:
+        raise ValueError(f"codec: region {(y0, x0, h, w)} is not inside the {H}x{W} image")
+    return y0, x0, h, w
+
+
+@torch.no_grad()
+def decode_image(model, data: bytes, reference=None, region=None) -> Tuple[torch.Tensor, Dict]:
+    """one bit-stream, ICMB or ICMT -> (8-bit [H, W, 3] host tensor, info); ``info``: "bpp" = 8 x the whole stream
+    length / (H W), header included, and, given ``reference`` (the original 8-bit image), "psnr" of the two 8-bit
+    images.  ``region`` = (y0, x0, h, w): only that window is returned ([h, w, 3]; "sse" / "psnr" are over it, against
+    the same window of ``reference``); of a tiled stream only the tiles that touch it are decoded
+    (``info["tiles_decoded"]``), and the result is bit for bit the same crop of the full decode."""
+    arch = _ready(model)
+    fp = B.fingerprint(model)
+    device = next(model.parameters()).device
+    tiled = B.is_tiled(data)
+    if tiled:
+        outer, streams = B.unpack_tiled(data)
+        _check_model(outer, arch, fp)
+        H, W = outer["height"], outer["width"]
+        rows, cols, plan = plan_tiles(H, W, outer["tile"], outer["overlap"])
+        inner = [B.unpack(s) for s in streams]          # every header checked before any payload is decoded
+        for k, ((y0, x0, h, w), (hd, tile_strings)) in enumerate(zip(plan, inner)):
+            _check_model(hd, arch, fp, f"tile {k}")
+            _check_strings(arch, tile_strings, f"tile {k}")
+            if (hd["height"], hd["width"]) != (h, w):
+                raise ValueError(f"codec: tile {k} holds a {hd['height']}x{hd['width']} image, the plan has {h}x{w}")
+    else:
+        header, strings = B.unpack(data)
+        _check_model(header, arch, fp)
+        H, W = header["height"], header["width"]
+        _check_strings(arch, strings)
+    ry, rx, rh, rw = _check_region(region, H, W)
+    ref = None if reference is None else _as_u8_image(reference, device, "reference")
+    if ref is not None and tuple(ref.shape) != (H, W, 3):
+        raise ValueError(f"codec: the reference is {ref.size(0)}x{ref.size(1)}, the stream holds a {H}x{W} image")
+    if ref is not None and region is not None:
+        ref = ref[ry:ry + rh, rx:rx + rw].contiguous()
     info = {"arch": arch, "height": H, "width": W, "bytes": len(data), "bpp": 8.0 * len(data) / (H * W)}
+    if tiled:
+        sel = [k for k, (y0, x0, h, w) in enumerate(plan)
+               if y0 < ry + rh and ry < y0 + h and x0 < rx + rw and rx < x0 + w]
+        by, bx = min(plan[k][0] for k in sel), min(plan[k][1] for k in sel)      # the canvas: their bounding box
+        bh = max(plan[k][0] + plan[k][2] for k in sel) - by
+        bw = max(plan[k][1] + plan[k][3] for k in sel) - bx
+        canvas = torch.zeros((3, bh, bw), dtype=torch.float32, device=device)
+        m = outer["overlap"]
+        ramp = torch.from_numpy(blend_ramp(m)).to(device) if m else None
+        for k in sel:                                    # plan order, one stream: a fixed order of additions per pixel
+            hd, strings = inner[k]
+            x_hat = _decompress_one(model, arch, hd, strings)
+            image_tile_blend(x_hat, hd["pads"], canvas, plan[k][0] - by, plan[k][1] - bx, ramp,
+                             tile_edges(k // cols, k % cols, rows, cols))
+        x_hat, top, left = canvas[None], ry - by, rx - bx
+        info.update(tile=outer["tile"], overlap=m, tiles=rows * cols, tiles_decoded=len(sel))
+    else:
+        x_hat = _decompress_one(model, arch, header, strings)
+        top, left = header["pads"][2] + ry, header["pads"][0] + rx
+    if region is not None:
+        info["region"] = [ry, rx, rh, rw]
+    out, sse = image_f32_to_u8(x_hat, (left, x_hat.size(3) - left - rw, top, x_hat.size(2) - top - rh), ref)
     if sse is not None:
         info["sse"] = int(sse.item())
-        info["psnr"] = 10.0 * math.log10(255.0 ** 2 / (info["sse"] / (H * W * 3))) if info["sse"] else math.inf
+        info["psnr"] = 10.0 * math.log10(255.0 ** 2 / (info["sse"] / (rh * rw * 3))) if info["sse"] else math.inf
     return out.cpu(), info
 
 
@@ -169,6 +293,16 @@ def read_image_u8(path: str) -> np.ndarray:
         raise ValueError(f"{path}: not an image ({e})")
 
 
+def _region(text: str) -> Tuple[int, int, int, int]:
+    try:
+        v = tuple(int(t) for t in text.split(","))
+    except ValueError:
+        v = ()
+    if len(v) != 4:
+        raise argparse.ArgumentTypeError(f"expected Y0,X0,H,W, got {text!r}")
+    return v
+
+
 def setup_args() -> argparse.ArgumentParser:
     p = argparse.ArgumentParser(prog="icm_amd.codec")
     sub = p.add_subparsers(dest="command", required=True)
@@ -180,6 +314,12 @@ def setup_args() -> argparse.ArgumentParser:
     dec.add_argument("-a", "--architecture", default=None, type=str,
                      help="model architecture (default: the stream's; must agree with it)")
     dec.add_argument("--reference", default=None, help="the original image: report the PSNR of the reconstruction")
+    dec.add_argument("--region", default=None, type=_region, metavar="Y0,X0,H,W",
+                     help="decode only this window of the image (of a tiled stream: only the tiles it touches)")
+    enc.add_argument("--tile", default=None, type=int, metavar="N",
+                     help="code the image as tiles of N x N pixels (a multiple of 64); one tile: the untiled stream")
+    enc.add_argument("--overlap", default=0, type=int, metavar="M",
+                     help="pixels neighbouring tiles share, blended by the decoder (needs --tile; at most N / 2)")
     for s in (enc, dec):
         s.add_argument("-o", "--output", required=True, help="file to write")
         s.add_argument("-p", "--path", dest="paths", required=True, type=str, help="checkpoint path")
@@ -202,6 +342,14 @@ def main(argv) -> int:
         why = "has no bit-stream codec" if arch in models else "is not an architecture"
         print(f"Error: -a {arch}: {why}; {known}.", file=sys.stderr)
         return 2
+    if args.command == "encode" and (args.tile is not None or args.overlap):
+        try:
+            if args.tile is None:
+                raise ValueError("--overlap needs --tile")
+            B.tile_grid(1, 1, args.tile, args.overlap)
+        except ValueError as e:
+            print(f"Error: {e}", file=sys.stderr)
+            return 2
     try:
         if args.command == "encode":
             payload = read_image_u8(args.input)
@@ -210,7 +358,7 @@ def main(argv) -> int:
                 raise ValueError(f"{args.input}: no such file")
             with open(args.input, "rb") as f:
                 payload = f.read()
-            header, _ = B.unpack(payload)
+            header, _ = B.unpack_tiled(payload) if B.is_tiled(payload) else B.unpack(payload)
             if arch is not None and arch != header["arch"]:
                 print(f"Error: -a {arch} disagrees with the stream, written by {header['arch']!r}.", file=sys.stderr)
                 return 2
@@ -227,7 +375,7 @@ def main(argv) -> int:
         torch.cuda.synchronize()
         t0 = time.perf_counter()
         if args.command == "encode":
-            data = encode_image(model, payload)
+            data = encode_image(model, payload, args.tile, args.overlap)
             torch.cuda.synchronize()
             dt = time.perf_counter() - t0
             h, w = payload.shape[:2]
@@ -236,7 +384,7 @@ def main(argv) -> int:
             report = {"command": "encode", "arch": arch, "height": h, "width": w, "bytes": len(data),
                       "bpp": 8.0 * len(data) / (h * w), "encode_time": dt}
         else:
-            img, info = decode_image(model, payload, reference)
+            img, info = decode_image(model, payload, reference, args.region)
             torch.cuda.synchronize()
             dt = time.perf_counter() - t0
             from PIL import Image

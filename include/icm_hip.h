@@ -410,6 +410,27 @@ int icm_image_u8_to_f32(const uint8_t* src, int H, int W, float* dst, int OH, in
 int icm_image_f32_to_u8(const float* src, int PH, int PW, int top, int left, uint8_t* dst, int H, int W,
                         const uint8_t* ref, int64_t* sse, void* ws, int64_t ws_bytes, void* stream);
 
+/* ---- assembly of a tiled image (icm_amd/codec.py, ICMT streams; no counterpart in the reference).  One decoded tile
+ * is added into the zero-filled f32 canvas of the image, its overlap bands weighted by a ramp:
+ *   canvas[c][y0 + y][x0 + x] = canvas[c][y0 + y][x0 + x] + (wy(y) * wx(x)) * src[c][top + y][left + x]
+ * for 0 <= y < h, 0 <= x < w, c < 3; src = planar [3, PH, PW], canvas = planar [3, H, W].  The two products and the sum
+ * are evaluated in that association, each rounded once (no FMA).  edges names the sides of the window that have a
+ * neighbouring tile (ICM_TILE_EDGE_*).  wx(x) = ramp[x] if the left side has a neighbour and x < m; otherwise
+ * ramp[w - 1 - x] if the right side has one and w - 1 - x < m; otherwise 1.  wy(y) likewise with top / bottom / h.
+ * ramp = m floats in device memory, by convention (i + 0.5) / m formed in f32 on the host; m = 0: ramp is not read.
+ * Elements outside the window are not touched.  Tiles issued on one stream add in issue order: no atomics, two runs
+ * are bit-identical.  Plane offsets are 64-bit (3 H W may exceed 2^31); no pointer needs more than float alignment.
+ * ICM_ERR_ARG before any launch: null src / canvas, a size outside 1..32768, negative top / left / y0 / x0, a window
+ * outside src or outside the canvas, m < 0, m > 0 with a null ramp, edges outside 0..15, m > w with a left or right
+ * neighbour, m > h with a top or bottom one. */
+#define ICM_TILE_EDGE_LEFT 1
+#define ICM_TILE_EDGE_RIGHT 2
+#define ICM_TILE_EDGE_TOP 4
+#define ICM_TILE_EDGE_BOTTOM 8
+int icm_image_tile_blend(const float* src, int PH, int PW, int top, int left, int h, int w,
+                         float* canvas, int H, int W, int y0, int x0,
+                         const float* ramp, int m, int edges, void* stream);
+
 /* ---- device-resident training data (icm_amd/datasets.py DeviceImageCache; stands in for the reference's per-step
  * CenterCrop / RandomCrop(pad_if_needed) + ToTensor + collate on the host, train.py:393-425).  A training batch cut out
  * of an arena of 8-bit images in one launch: sample b is the interleaved [H, W, 3] byte image at arena + offset, and
