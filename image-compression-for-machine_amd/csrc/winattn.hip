@@ -17,7 +17,10 @@
 
 namespace icm {
 
-// matrix-core kernels for 8x8 windows (winattn_mfma.hip): ICM_OK = launched, -1 = geometry not covered
+// matrix-core kernels for 8x8 and 4x4 windows (winattn_mfma.hip): *_takes = the family serves this geometry in this
+// direction (host arithmetic only); launches: ICM_OK = launched, -1 = geometry not covered
+bool winattn_mfma_takes(int N, int C, int H, int W, int heads, int ws, int shift, int backward);
+bool winattn_mfma16_takes(int N, int C, int H, int W, int heads, int ws, int shift, int backward);
 int winattn_mfma_fwd(const float* qkv, const float* table, float* out, int N, int C, int H, int W, int heads, int ws,
                      int shift, hipStream_t stream);
 int winattn_mfma_bwd(const float* qkv, const float* table, const float* dout, float* dqkv, float* dtable_ws, int N, int C,
@@ -371,6 +374,47 @@ static int fill_desc(WaDesc& d, int N, int C, int H, int W, int heads, int ws, i
   return ICM_OK;
 }
 
+// launch shape of the generic kernels, or why they cannot serve d
+struct ValuPlan {
+  WaFn fn;
+  int waves;
+  size_t lds;
+};
+static int valu_plan(const WaDesc& d, int backward, ValuPlan& p) {
+  WaFn f, b;
+  if (!pick(d.hd, f, b)) return ICM_ERR_UNSUPPORTED;
+  const int tw = 2 * d.ws - 1, wave_tasks = (d.heads + d.G - 1) / d.G;
+  if (!backward) {
+    p.fn = f;
+    p.waves = std::min(4, wave_tasks);
+    p.lds = (size_t)p.waves * d.G * (2 * d.T * d.hd + d.T * (d.T + 1)) * 4;
+  } else {
+    if (tw * tw > d.T * d.hd) return ICM_ERR_UNSUPPORTED;   // the table gradient is accumulated in the dO region
+    p.fn = b;
+    p.waves = std::min(2, wave_tasks);
+    p.lds = (size_t)p.waves * d.G * ((3 * d.T * d.hd + d.T * (d.T + 1) + 3) & ~3) * 4;
+  }
+  return p.lds > 160 * 1024 ? ICM_ERR_UNSUPPORTED : ICM_OK;
+}
+
+enum { WA_ROUTE_VALU = 0, WA_ROUTE_MFMA = 1, WA_ROUTE_MFMA16 = 2 };
+// Which kernel family serves a checked geometry (route), or rc = the code the call returns without launching.  The
+// one decision behind icm_winattn_fwd, icm_winattn_bwd and icm_debug_winattn_route; no HIP call.
+static int winattn_route(const WaDesc& d, int backward, int& route, ValuPlan& vp) {
+  if (!g_force_valu) {
+    if (winattn_mfma_takes(d.N, d.C, d.H, d.W, d.heads, d.ws, d.shift, backward)) {
+      route = WA_ROUTE_MFMA;
+      return ICM_OK;
+    }
+    if (winattn_mfma16_takes(d.N, d.C, d.H, d.W, d.heads, d.ws, d.shift, backward)) {
+      route = WA_ROUTE_MFMA16;
+      return ICM_OK;
+    }
+  }
+  route = WA_ROUTE_VALU;
+  return valu_plan(d, backward, vp);
+}
+
 }  // namespace icm
 
 using namespace icm;
@@ -378,36 +422,50 @@ extern "C" {
 
 void icm_debug_force_winattn_valu(int on) { icm::g_force_valu = on ? 1 : 0; }
 
+int icm_debug_winattn_route(int N, int C, int H, int W, int heads, int ws, int shift, int backward) {
+  WaDesc d{};
+  int rc = fill_desc(d, N, C, H, W, heads, ws, shift);
+  if (rc) return -rc;
+  int route;
+  ValuPlan vp;
+  rc = winattn_route(d, backward ? 1 : 0, route, vp);
+  return rc ? -rc : route;
+}
+
 int icm_winattn_fwd(const float* qkv, const float* table, float* out, int N, int C, int H, int W, int heads, int ws,
                     int shift, void* stream) {
   if (!qkv || !table || !out) return ICM_ERR_ARG;
   WaDesc d{};
   int rc = fill_desc(d, N, C, H, W, heads, ws, shift);
   if (rc) return rc;
-  d.qkv = qkv; d.table = table; d.out = out;
-  if (!g_force_valu) {
-    int rm = winattn_mfma_fwd(qkv, table, out, N, C, H, W, heads, ws, shift, (hipStream_t)stream);
-    if (rm < 0) rm = winattn_mfma16_fwd(qkv, table, out, N, C, H, W, heads, ws, shift, (hipStream_t)stream);
-    if (rm >= 0) return rm;
+  int route;
+  ValuPlan vp;
+  rc = winattn_route(d, 0, route, vp);
+  if (rc) return rc;
+  if (route != WA_ROUTE_VALU) {
+    const hipStream_t st = (hipStream_t)stream;
+    const int rm = route == WA_ROUTE_MFMA ? winattn_mfma_fwd(qkv, table, out, N, C, H, W, heads, ws, shift, st)
+                                          : winattn_mfma16_fwd(qkv, table, out, N, C, H, W, heads, ws, shift, st);
+    return rm < 0 ? ICM_ERR_UNSUPPORTED : rm;   // < 0 cannot happen: the launch repeats the test the route passed
   }
-  WaFn f, b;
-  if (!pick(d.hd, f, b)) return ICM_ERR_UNSUPPORTED;
-  const int waves = std::min(4, (heads + d.G - 1) / d.G);
-  const size_t lds = (size_t)waves * d.G * (2 * d.T * d.hd + d.T * (d.T + 1)) * 4;
-  if (lds > 160 * 1024) return ICM_ERR_UNSUPPORTED;
-  if (lds > 64 * 1024 && !ensure_max_lds(reinterpret_cast<const void*>(f))) return ICM_ERR_LAUNCH;
-  hipLaunchKernelGGL(f, dim3(N * d.nwy * d.nwx), dim3(64 * waves), lds, (hipStream_t)stream, d);
+  d.qkv = qkv; d.table = table; d.out = out;
+  if (vp.lds > 64 * 1024 && !ensure_max_lds(reinterpret_cast<const void*>(vp.fn))) return ICM_ERR_LAUNCH;
+  hipLaunchKernelGGL(vp.fn, dim3(N * d.nwy * d.nwx), dim3(64 * vp.waves), vp.lds, (hipStream_t)stream, d);
   ICM_CHECK_LAUNCH();
   return ICM_OK;
 }
 
+// reduction plan of nwin table-gradient slabs: S partial sums over chunks of `chunk` slabs, S <= 64
+static void dtable_chunks(int nwin, int& S, int& chunk) {
+  S = std::max(1, std::min(64, nwin / 16));
+  chunk = (nwin + S - 1) / S;
+  S = (nwin + chunk - 1) / chunk;
+}
 static void dtable_plan(int N, int H, int W, int heads, int ws, int& nwin, int& E, int& S, int& chunk) {
   const int tw = 2 * ws - 1;
   nwin = N * (H / ws) * (W / ws);
   E = heads * tw * tw;
-  S = std::max(1, std::min(64, nwin / 16));
-  chunk = (nwin + S - 1) / S;
-  S = (nwin + chunk - 1) / chunk;
+  dtable_chunks(nwin, S, chunk);
 }
 
 int64_t icm_winattn_bwd_workspace_floats(int N, int C, int H, int W, int heads, int ws) {
@@ -427,35 +485,26 @@ int icm_winattn_bwd(const float* qkv, const float* table, const float* dout, flo
   int nwin, E, S, chunk;
   dtable_plan(N, H, W, heads, ws, nwin, E, S, chunk);
   if (ws_floats < (int64_t)nwin * E + (int64_t)S * E) return ICM_ERR_ARG;
-  d.qkv = qkv; d.table = table; d.dout = dout; d.dqkv = dqkv; d.dtable_ws = wsp;
+  int route;
+  ValuPlan vp;
+  rc = winattn_route(d, 1, route, vp);
+  if (rc) return rc;
   const int tw = 2 * ws - 1;
-  int rm = -1;
-  if (!g_force_valu) {
-    rm = winattn_mfma_bwd(qkv, table, dout, dqkv, wsp, N, C, H, W, heads, ws, shift, (hipStream_t)stream);
-    if (rm < 0) {
-      // 4x4 windows: one table-gradient slab per wave task (four windows), fewer than the per-window slabs planned for
-      const int slabs = winattn_mfma16_slabs(N, C, H, W, heads, ws, shift);
-      if (slabs > 0) {
-        rm = winattn_mfma16_bwd(qkv, table, dout, dqkv, wsp, N, C, H, W, heads, ws, shift, (hipStream_t)stream);
-        if (rm == ICM_OK) {
-          nwin = slabs;
-          S = std::max(1, std::min(64, nwin / 16));
-          chunk = (nwin + S - 1) / S;
-          S = (nwin + chunk - 1) / chunk;
-        }
-      }
-    }
-  }
-  if (rm > 0) return rm;
-  if (rm < 0) {
-    WaFn f, b;
-    if (!pick(d.hd, f, b)) return ICM_ERR_UNSUPPORTED;
-    const int waves = std::min(2, (heads + d.G - 1) / d.G);
-    if (tw * tw > d.T * d.hd) return ICM_ERR_UNSUPPORTED;   // the table gradient is accumulated in the dO region
-    const size_t lds = (size_t)waves * d.G * ((3 * d.T * d.hd + d.T * (d.T + 1) + 3) & ~3) * 4;
-    if (lds > 160 * 1024) return ICM_ERR_UNSUPPORTED;
-    if (lds > 64 * 1024 && !ensure_max_lds(reinterpret_cast<const void*>(b))) return ICM_ERR_LAUNCH;
-    hipLaunchKernelGGL(b, dim3(N * d.nwy * d.nwx), dim3(64 * waves), lds, (hipStream_t)stream, d);
+  if (route == WA_ROUTE_MFMA) {
+    const int rm = winattn_mfma_bwd(qkv, table, dout, dqkv, wsp, N, C, H, W, heads, ws, shift, (hipStream_t)stream);
+    if (rm) return rm < 0 ? ICM_ERR_UNSUPPORTED : rm;
+  } else if (route == WA_ROUTE_MFMA16) {
+    // 4x4 windows: one table-gradient slab per wave task (four windows), fewer than the per-window slabs planned for
+    const int slabs = winattn_mfma16_slabs(N, C, H, W, heads, ws, shift);
+    const int rm =
+        slabs > 0 ? winattn_mfma16_bwd(qkv, table, dout, dqkv, wsp, N, C, H, W, heads, ws, shift, (hipStream_t)stream) : -1;
+    if (rm) return rm < 0 ? ICM_ERR_UNSUPPORTED : rm;
+    nwin = slabs;
+    dtable_chunks(nwin, S, chunk);
+  } else {
+    d.qkv = qkv; d.table = table; d.dout = dout; d.dqkv = dqkv; d.dtable_ws = wsp;
+    if (vp.lds > 64 * 1024 && !ensure_max_lds(reinterpret_cast<const void*>(vp.fn))) return ICM_ERR_LAUNCH;
+    hipLaunchKernelGGL(vp.fn, dim3(N * d.nwy * d.nwx), dim3(64 * vp.waves), vp.lds, (hipStream_t)stream, d);
     ICM_CHECK_LAUNCH();
   }
   float* part = wsp + (long long)nwin * E;

@@ -416,14 +416,32 @@ static bool wm_fill(WmDesc& d, int N, int C, int H, int W, int heads, int ws, in
   return true;
 }
 
+// does the 8x8 family take this geometry (window size, a head dim of its table, LDS of the direction within the
+// 160 KB a workgroup may ask for)?  The one test behind the launches below and icm_debug_winattn_route: pure host code
+static bool wm_plan(WmDesc& d, WmFn& fn, size_t& lds, int N, int C, int H, int W, int heads, int ws, int shift,
+                    int backward) {
+  WmFn f, b;
+  size_t lf, lb;
+  if (!wm_fill(d, N, C, H, W, heads, ws, shift) || !wm_pick(C / heads, f, b, lf, lb)) return false;
+  fn = backward ? b : f;
+  lds = backward ? lb : lf;
+  return lds <= 160 * 1024;
+}
+bool winattn_mfma_takes(int N, int C, int H, int W, int heads, int ws, int shift, int backward) {
+  WmDesc d{};
+  WmFn fn;
+  size_t lds;
+  return wm_plan(d, fn, lds, N, C, H, W, heads, ws, shift, backward);
+}
+
 // returns ICM_OK when the MFMA path took the launch, -1 when this geometry is not covered (caller falls through to
 // the generic kernel of winattn.hip), an ICM_ERR_* code on failure
 int winattn_mfma_fwd(const float* qkv, const float* table, float* out, int N, int C, int H, int W, int heads, int ws,
                      int shift, hipStream_t stream) {
   WmDesc d{};
-  WmFn f, b;
-  size_t lf, lb;
-  if (!wm_fill(d, N, C, H, W, heads, ws, shift) || !wm_pick(C / heads, f, b, lf, lb)) return -1;
+  WmFn f;
+  size_t lf;
+  if (!wm_plan(d, f, lf, N, C, H, W, heads, ws, shift, 0)) return -1;
   d.qkv = qkv; d.table = table; d.out = out;
   if (lf > 64 * 1024 && !ensure_max_lds(reinterpret_cast<const void*>(f))) return ICM_ERR_LAUNCH;
   hipLaunchKernelGGL(f, dim3(N * d.nwy * d.nwx), dim3(256), lf, stream, d);
@@ -434,11 +452,10 @@ int winattn_mfma_fwd(const float* qkv, const float* table, float* out, int N, in
 int winattn_mfma_bwd(const float* qkv, const float* table, const float* dout, float* dqkv, float* dtable_ws, int N, int C,
                      int H, int W, int heads, int ws, int shift, hipStream_t stream) {
   WmDesc d{};
-  WmFn f, b;
-  size_t lf, lb;
-  if (!wm_fill(d, N, C, H, W, heads, ws, shift) || !wm_pick(C / heads, f, b, lf, lb)) return -1;
+  WmFn b;
+  size_t lb;
+  if (!wm_plan(d, b, lb, N, C, H, W, heads, ws, shift, 1)) return -1;
   d.qkv = qkv; d.table = table; d.dout = dout; d.dqkv = dqkv; d.dtable_ws = dtable_ws;
-  if (lb > 160 * 1024) return -1;
   if (lb > 64 * 1024 && !ensure_max_lds(reinterpret_cast<const void*>(b))) return ICM_ERR_LAUNCH;
   hipLaunchKernelGGL(b, dim3(N * d.nwy * d.nwx), dim3(256), lb, stream, d);
   ICM_CHECK_LAUNCH();
@@ -780,21 +797,38 @@ static bool w4_fill(W4Desc& d, int N, int C, int H, int W, int heads, int ws, in
   return true;
 }
 
+// does the 4x4 family take this geometry?  Same role as wm_plan
+static bool w4_plan(W4Desc& d, W4Fn& fn, size_t& lds, int N, int C, int H, int W, int heads, int ws, int shift,
+                    int backward) {
+  W4Fn f, b;
+  size_t lf, lb;
+  if (!w4_fill(d, N, C, H, W, heads, ws, shift) || !w4_pick(C / heads, f, b, lf, lb)) return false;
+  fn = backward ? b : f;
+  lds = backward ? lb : lf;
+  return lds <= 160 * 1024;
+}
+bool winattn_mfma16_takes(int N, int C, int H, int W, int heads, int ws, int shift, int backward) {
+  W4Desc d{};
+  W4Fn fn;
+  size_t lds;
+  return w4_plan(d, fn, lds, N, C, H, W, heads, ws, shift, backward);
+}
+
 // number of table-gradient slabs the 4x4 backward writes (one per wave task = group of four windows), or -1
 int winattn_mfma16_slabs(int N, int C, int H, int W, int heads, int ws, int shift) {
   W4Desc d{};
-  W4Fn f, b;
-  size_t lf, lb;
-  if (!w4_fill(d, N, C, H, W, heads, ws, shift) || !w4_pick(C / heads, f, b, lf, lb) || lb > 160 * 1024) return -1;
+  W4Fn b;
+  size_t lb;
+  if (!w4_plan(d, b, lb, N, C, H, W, heads, ws, shift, 1)) return -1;
   return N * d.nwy * d.ngx;
 }
 
 int winattn_mfma16_fwd(const float* qkv, const float* table, float* out, int N, int C, int H, int W, int heads, int ws,
                        int shift, hipStream_t stream) {
   W4Desc d{};
-  W4Fn f, b;
-  size_t lf, lb;
-  if (!w4_fill(d, N, C, H, W, heads, ws, shift) || !w4_pick(C / heads, f, b, lf, lb) || lf > 160 * 1024) return -1;
+  W4Fn f;
+  size_t lf;
+  if (!w4_plan(d, f, lf, N, C, H, W, heads, ws, shift, 0)) return -1;
   d.qkv = qkv; d.table = table; d.out = out;
   if (lf > 64 * 1024 && !ensure_max_lds(reinterpret_cast<const void*>(f))) return ICM_ERR_LAUNCH;
   const int nwt = N * d.nwy * d.ngx * heads;
@@ -805,9 +839,9 @@ int winattn_mfma16_fwd(const float* qkv, const float* table, float* out, int N, 
 int winattn_mfma16_bwd(const float* qkv, const float* table, const float* dout, float* dqkv, float* dtable_ws, int N,
                        int C, int H, int W, int heads, int ws, int shift, hipStream_t stream) {
   W4Desc d{};
-  W4Fn f, b;
-  size_t lf, lb;
-  if (!w4_fill(d, N, C, H, W, heads, ws, shift) || !w4_pick(C / heads, f, b, lf, lb) || lb > 160 * 1024) return -1;
+  W4Fn b;
+  size_t lb;
+  if (!w4_plan(d, b, lb, N, C, H, W, heads, ws, shift, 1)) return -1;
   d.qkv = qkv; d.table = table; d.dout = dout; d.dqkv = dqkv; d.dtable_ws = dtable_ws;
   if (lb > 64 * 1024 && !ensure_max_lds(reinterpret_cast<const void*>(b))) return ICM_ERR_LAUNCH;
   const int nwt = N * d.nwy * d.ngx * heads;

@@ -77,7 +77,7 @@ SYMBOLS = [
     "icm_gc_likelihood_ste_bwd", "icm_rd_loss_fwd", "icm_rd_loss_bwd", "icm_grad_sqnorm", "icm_adam_step", "icm_adam_step_hyper", "icm_fill",
     "icm_winattn_bwd_workspace_floats", "icm_debug_force_conv_cfg", "icm_debug_forced_conv_cfg", "icm_debug_force_conv1x1",
     "icm_debug_force_wgrad_cfg", "icm_debug_wgrad_plan", "icm_debug_conv_plan",
-    "icm_debug_force_winattn_valu",
+    "icm_debug_force_winattn_valu", "icm_debug_winattn_route",
     "icm_zigzag_order", "icm_zigzag_splits", "icm_zigzag_reverse",
     "icm_pmf_to_quantized_cdf", "icm_rans_encode_with_indexes", "icm_rans_decode_with_indexes",
     "icm_rans_decoder_create", "icm_rans_decoder_decode", "icm_rans_decoder_destroy",
@@ -152,6 +152,7 @@ def lib():
         L.icm_debug_wgrad_plan.argtypes = [C.POINTER(WgradArgs), i32, C.POINTER(C.c_int32)]
         L.icm_debug_force_winattn_valu.argtypes = [i32]
         L.icm_debug_force_winattn_valu.restype = None
+        L.icm_debug_winattn_route.argtypes = [i32, i32, i32, i32, i32, i32, i32, i32]
         L.icm_eb_likelihood_fwd.argtypes = [vp, vp, C.POINTER(EbParams), vp, vp, i32, i32, i32, f32, vp]
         L.icm_eb_likelihood_bwd.argtypes = [vp, vp, C.POINTER(EbParams), vp, vp, C.POINTER(EbGrads), i32, i32, i32,
                                             f32, i32, vp]

@@ -482,6 +482,12 @@ void icm_debug_force_wgrad_cfg(int variant, int xcd_order);
 int icm_debug_wgrad_plan(const icm_wgrad_args* a, int n, int32_t out[8]);
 /* 1: window attention always runs the generic VALU kernels (the matrix-core kernels cover 8x8 windows) */
 void icm_debug_force_winattn_valu(int on);
+/* which kernel family icm_winattn_fwd (backward = 0) / icm_winattn_bwd (backward = 1) gives this geometry to: 0 the
+ * generic VALU kernels, 1 the matrix-core kernels for 8x8 windows, 2 the matrix-core kernels for 4x4 windows; or, for a
+ * geometry the call refuses, minus its ICM_ERR_* code (the codes are small positive integers too, so they come back
+ * negated: -ICM_ERR_ARG, -ICM_ERR_UNSUPPORTED).  The decision the launches use, not a restatement; pure host code, no
+ * HIP call; honours icm_debug_force_winattn_valu. */
+int icm_debug_winattn_route(int N, int C, int H, int W, int heads, int ws, int shift, int backward);
 
 #ifdef __cplusplus
 }
