@@ -12,59 +12,16 @@
 // cross-lane shuffles.  Relative-position-bias gradients are reduced per wave in LDS (all lanes of one
 // instruction hit distinct table entries); every (window, head) writes its partial table to a workspace slab
 // and two small kernels add the slabs in window order: bitwise reproducible, no float atomics.
+//
+// Host side: fill_desc (winattn_common.h) checks the geometry, winattn_route walks the family table (matrix cores 8x8,
+// matrix cores 4x4, the VALU kernels of this file) for the first family whose plan takes it, launch() starts the
+// planned kernel; icm_winattn_fwd, icm_winattn_bwd and icm_debug_winattn_route are those three steps.
 #include <algorithm>
-#include "icm_common.h"
+#include "winattn_common.h"
 
 namespace icm {
 
-// matrix-core kernels for 8x8 and 4x4 windows (winattn_mfma.hip): *_takes = the family serves this geometry in this
-// direction (host arithmetic only); launches: ICM_OK = launched, -1 = geometry not covered
-bool winattn_mfma_takes(int N, int C, int H, int W, int heads, int ws, int shift, int backward);
-bool winattn_mfma16_takes(int N, int C, int H, int W, int heads, int ws, int shift, int backward);
-int winattn_mfma_fwd(const float* qkv, const float* table, float* out, int N, int C, int H, int W, int heads, int ws,
-                     int shift, hipStream_t stream);
-int winattn_mfma_bwd(const float* qkv, const float* table, const float* dout, float* dqkv, float* dtable_ws, int N, int C,
-                     int H, int W, int heads, int ws, int shift, hipStream_t stream);
-int winattn_mfma16_fwd(const float* qkv, const float* table, float* out, int N, int C, int H, int W, int heads, int ws,
-                       int shift, hipStream_t stream);
-int winattn_mfma16_bwd(const float* qkv, const float* table, const float* dout, float* dqkv, float* dtable_ws, int N,
-                       int C, int H, int W, int heads, int ws, int shift, hipStream_t stream);
-int winattn_mfma16_slabs(int N, int C, int H, int W, int heads, int ws, int shift);
 static int g_force_valu = 0;   // test hook: 1 = always take the generic (VALU) kernels below
-
-struct WaDesc {
-  const float* qkv;
-  const float* table;
-  float* out;          // fwd
-  const float* dout;   // bwd
-  float* dqkv;         // bwd
-  float* dtable_ws;    // bwd: per-(window, head) partial tables [nwin][heads][(2ws-1)^2]
-  int N, C, H, W, heads, ws, shift, hd, T, nwx, nwy, G;
-  float scale;
-};
-
-__device__ __forceinline__ int region(int s, int L, int ws, int shift) {
-  return s < L - ws ? 0 : (s < L - shift ? 1 : 2);
-}
-
-// Common per-token geometry
-struct Tok {
-  int pix;   // oy*W + ox in the original (un-shifted) image
-  int lab;   // shift-mask region label
-  int r, c;  // row / col inside the window
-};
-__device__ __forceinline__ Tok token(const WaDesc& d, int wy, int wx, int j) {
-  Tok t;
-  t.r = j / d.ws;
-  t.c = j - t.r * d.ws;
-  const int sy = wy * d.ws + t.r, sx = wx * d.ws + t.c;
-  int oy = sy + d.shift, ox = sx + d.shift;
-  if (oy >= d.H) oy -= d.H;
-  if (ox >= d.W) ox -= d.W;
-  t.pix = oy * d.W + ox;
-  t.lab = d.shift > 0 ? region(sy, d.H, d.ws, d.shift) * 3 + region(sx, d.W, d.ws, d.shift) : 0;
-  return t;
-}
 
 // s = sum_d a[d] * row[d]; row is an LDS row shared by all lanes (broadcast): 16-byte reads when HD % 4 == 0
 template <int HD>
@@ -123,7 +80,7 @@ __global__ __launch_bounds__(256) void winattn_fwd_kernel(const WaDesc d) {
   const int n = bid / d.nwy;
   const long long HW = (long long)d.H * d.W;
   const float* base = d.qkv + (long long)n * 3 * d.C * HW;
-  const Tok me = token(d, wy, wx, lane);
+  const Tok me = token(d, d.ws, wy, wx, lane);
   const int tw = 2 * d.ws - 1;
 
   for (int head0 = wave * G; head0 < d.heads; head0 += nwaves * G) {
@@ -147,7 +104,7 @@ __global__ __launch_bounds__(256) void winattn_fwd_kernel(const WaDesc d) {
     if (active) {
       for (int j = 0; j < T; ++j) {
         float s = dot_row<HD>(q, Ksh + j * HD);
-        const Tok tj = token(d, wy, wx, j);
+        const Tok tj = token(d, d.ws, wy, wx, j);
         const int idx = (me.r - tj.r + d.ws - 1) * tw + (me.c - tj.c + d.ws - 1);
         s += d.table[idx * d.heads + head];
         if (d.shift > 0 && tj.lab != me.lab) s += -100.0f;
@@ -203,7 +160,7 @@ __global__ __launch_bounds__(128) void winattn_bwd_kernel(const WaDesc d) {
   const long long HW = (long long)d.H * d.W;
   const float* base = d.qkv + (long long)n * 3 * d.C * HW;
   float* dbase = d.dqkv + (long long)n * 3 * d.C * HW;
-  const Tok me = token(d, wy, wx, lane);
+  const Tok me = token(d, d.ws, wy, wx, lane);
 
   for (int head0 = wave * G; head0 < d.heads; head0 += nwaves * G) {
     const int head = min(head0 + grp, d.heads - 1);
@@ -231,7 +188,7 @@ __global__ __launch_bounds__(128) void winattn_bwd_kernel(const WaDesc d) {
       float m = -3.0e38f;
       for (int j = 0; j < T; ++j) {
         float s = dot_row<HD>(q, Ksh + j * HD);
-        const Tok tj = token(d, wy, wx, j);
+        const Tok tj = token(d, d.ws, wy, wx, j);
         const int idx = (me.r - tj.r + d.ws - 1) * tw + (me.c - tj.c + d.ws - 1);
         s += d.table[idx * d.heads + head];
         if (d.shift > 0 && tj.lab != me.lab) s += -100.0f;
@@ -283,7 +240,7 @@ __global__ __launch_bounds__(128) void winattn_bwd_kernel(const WaDesc d) {
         const float ds = Ssh[lane * TS + j] * (dp - delta);
         Ssh[lane * TS + j] = ds;
         axpy_row<HD>(dq, ds, Ksh + j * HD);
-        const Tok tj = token(d, wy, wx, j);
+        const Tok tj = token(d, d.ws, wy, wx, j);
         const int idx = (me.r - tj.r + d.ws - 1) * tw + (me.c - tj.c + d.ws - 1);
         Bsh[idx] += ds;  // distinct idx across the active lanes of this instruction
       }
@@ -348,71 +305,68 @@ __global__ void dtable_reduce2_kernel(const float* __restrict__ part, float* __r
   *o = accum ? *o + acc : acc;
 }
 
-typedef void (*WaFn)(const WaDesc);
-template <int HD> struct WaK {
-  static WaFn fwd() { return winattn_fwd_kernel<HD>; }
-  static WaFn bwd() { return winattn_bwd_kernel<HD>; }
-};
-static bool pick(int hd, WaFn& f, WaFn& b) {
+
+static bool pick(int hd, int backward, void (*&fn)(const WaDesc)) {
   switch (hd) {
-#define C_(n) case n: f = WaK<n>::fwd(); b = WaK<n>::bwd(); return true;
+#define C_(n) case n: fn = backward ? winattn_bwd_kernel<n> : winattn_fwd_kernel<n>; return true;
     C_(8) C_(10) C_(16) C_(24) C_(32) C_(40) C_(48)
 #undef C_
     default: return false;
   }
 }
 
-static int fill_desc(WaDesc& d, int N, int C, int H, int W, int heads, int ws, int shift) {
-  if (N <= 0 || C <= 0 || heads <= 0 || C % heads != 0 || ws <= 0) return ICM_ERR_ARG;
-  if (shift < 0 || shift >= ws) return ICM_ERR_ARG;            // assert at win_attention.py:144
-  if (H % ws != 0 || W % ws != 0) return ICM_ERR_ARG;          // view() would raise in window_partition
-  if (ws * ws > 64) return ICM_ERR_UNSUPPORTED;
-  d.N = N; d.C = C; d.H = H; d.W = W; d.heads = heads; d.ws = ws; d.shift = shift; d.hd = C / heads;
-  d.T = ws * ws; d.nwx = W / ws; d.nwy = H / ws;
-  d.G = 64 / d.T;   // heads per wave (1 for 8x8 windows, 4 for 4x4)
-  d.scale = 1.0f / sqrtf((float)d.hd);
+// the generic kernels: every window size fill_desc admits, one workgroup per window
+static int valu_plan(const WaDesc& d, int backward, WaPlan& p) {
+  if (!pick(d.hd, backward, p.fn)) return ICM_ERR_UNSUPPORTED;
+  const int tw = 2 * d.ws - 1, wave_tasks = (d.heads + d.G - 1) / d.G;
+  int waves;
+  if (!backward) {
+    waves = std::min(4, wave_tasks);
+    p.lds = (size_t)waves * d.G * (2 * d.T * d.hd + d.T * (d.T + 1)) * 4;
+  } else {
+    if (tw * tw > d.T * d.hd) return ICM_ERR_UNSUPPORTED;   // the table gradient is accumulated in the dO region
+    waves = std::min(2, wave_tasks);
+    p.lds = (size_t)waves * d.G * ((3 * d.T * d.hd + d.T * (d.T + 1) + 3) & ~3) * 4;
+  }
+  p.grid = p.slabs = d.N * d.nwy * d.nwx;
+  p.block = 64 * waves;
+  return p.lds > kWaLdsLimit ? ICM_ERR_UNSUPPORTED : ICM_OK;
+}
+
+// The kernel families in trial order; the route code is what icm_debug_winattn_route reports.
+enum { WA_ROUTE_VALU = 0, WA_ROUTE_MFMA = 1, WA_ROUTE_MFMA16 = 2 };
+static const struct {
+  int route;
+  WaPlanFn plan;
+} kWaFamilies[] = {{WA_ROUTE_MFMA, winattn_mfma_plan}, {WA_ROUTE_MFMA16, winattn_mfma16_plan}, {WA_ROUTE_VALU, valu_plan}};
+
+// Which family serves a checked geometry (route) and how (p), or the code the call returns without launching: that of
+// the last family tried.  The one decision behind icm_winattn_fwd, icm_winattn_bwd and icm_debug_winattn_route; no
+// HIP call.
+static int winattn_route(const WaDesc& d, int backward, int& route, WaPlan& p) {
+  int rc = ICM_ERR_UNSUPPORTED;
+  for (const auto& f : kWaFamilies) {
+    if (g_force_valu && f.route != WA_ROUTE_VALU) continue;
+    route = f.route;
+    rc = f.plan(d, backward, p);
+    if (rc == ICM_OK) break;
+  }
+  return rc;
+}
+
+// the only launch site of the attention kernels
+static int launch(const WaDesc& d, const WaPlan& p, hipStream_t stream) {
+  if (p.lds > 64 * 1024 && !ensure_max_lds(reinterpret_cast<const void*>(p.fn))) return ICM_ERR_LAUNCH;
+  hipLaunchKernelGGL(p.fn, dim3(p.grid), dim3(p.block), p.lds, stream, d);
+  ICM_CHECK_LAUNCH();
   return ICM_OK;
 }
 
-// launch shape of the generic kernels, or why they cannot serve d
-struct ValuPlan {
-  WaFn fn;
-  int waves;
-  size_t lds;
-};
-static int valu_plan(const WaDesc& d, int backward, ValuPlan& p) {
-  WaFn f, b;
-  if (!pick(d.hd, f, b)) return ICM_ERR_UNSUPPORTED;
-  const int tw = 2 * d.ws - 1, wave_tasks = (d.heads + d.G - 1) / d.G;
-  if (!backward) {
-    p.fn = f;
-    p.waves = std::min(4, wave_tasks);
-    p.lds = (size_t)p.waves * d.G * (2 * d.T * d.hd + d.T * (d.T + 1)) * 4;
-  } else {
-    if (tw * tw > d.T * d.hd) return ICM_ERR_UNSUPPORTED;   // the table gradient is accumulated in the dO region
-    p.fn = b;
-    p.waves = std::min(2, wave_tasks);
-    p.lds = (size_t)p.waves * d.G * ((3 * d.T * d.hd + d.T * (d.T + 1) + 3) & ~3) * 4;
-  }
-  return p.lds > 160 * 1024 ? ICM_ERR_UNSUPPORTED : ICM_OK;
-}
-
-enum { WA_ROUTE_VALU = 0, WA_ROUTE_MFMA = 1, WA_ROUTE_MFMA16 = 2 };
-// Which kernel family serves a checked geometry (route), or rc = the code the call returns without launching.  The
-// one decision behind icm_winattn_fwd, icm_winattn_bwd and icm_debug_winattn_route; no HIP call.
-static int winattn_route(const WaDesc& d, int backward, int& route, ValuPlan& vp) {
-  if (!g_force_valu) {
-    if (winattn_mfma_takes(d.N, d.C, d.H, d.W, d.heads, d.ws, d.shift, backward)) {
-      route = WA_ROUTE_MFMA;
-      return ICM_OK;
-    }
-    if (winattn_mfma16_takes(d.N, d.C, d.H, d.W, d.heads, d.ws, d.shift, backward)) {
-      route = WA_ROUTE_MFMA16;
-      return ICM_OK;
-    }
-  }
-  route = WA_ROUTE_VALU;
-  return valu_plan(d, backward, vp);
+// reduction plan of nslab table-gradient slabs: S partial sums over chunks of `chunk` slabs, S <= 64
+static void dtable_chunks(int nslab, int& S, int& chunk) {
+  S = std::max(1, std::min(64, nslab / 16));
+  chunk = (nslab + S - 1) / S;
+  S = (nslab + chunk - 1) / chunk;
 }
 
 }  // namespace icm
@@ -427,8 +381,8 @@ int icm_debug_winattn_route(int N, int C, int H, int W, int heads, int ws, int s
   int rc = fill_desc(d, N, C, H, W, heads, ws, shift);
   if (rc) return -rc;
   int route;
-  ValuPlan vp;
-  rc = winattn_route(d, backward ? 1 : 0, route, vp);
+  WaPlan p;
+  rc = winattn_route(d, backward ? 1 : 0, route, p);
   return rc ? -rc : route;
 }
 
@@ -439,39 +393,19 @@ int icm_winattn_fwd(const float* qkv, const float* table, float* out, int N, int
   int rc = fill_desc(d, N, C, H, W, heads, ws, shift);
   if (rc) return rc;
   int route;
-  ValuPlan vp;
-  rc = winattn_route(d, 0, route, vp);
+  WaPlan p;
+  rc = winattn_route(d, 0, route, p);
   if (rc) return rc;
-  if (route != WA_ROUTE_VALU) {
-    const hipStream_t st = (hipStream_t)stream;
-    const int rm = route == WA_ROUTE_MFMA ? winattn_mfma_fwd(qkv, table, out, N, C, H, W, heads, ws, shift, st)
-                                          : winattn_mfma16_fwd(qkv, table, out, N, C, H, W, heads, ws, shift, st);
-    return rm < 0 ? ICM_ERR_UNSUPPORTED : rm;   // < 0 cannot happen: the launch repeats the test the route passed
-  }
   d.qkv = qkv; d.table = table; d.out = out;
-  if (vp.lds > 64 * 1024 && !ensure_max_lds(reinterpret_cast<const void*>(vp.fn))) return ICM_ERR_LAUNCH;
-  hipLaunchKernelGGL(vp.fn, dim3(N * d.nwy * d.nwx), dim3(64 * vp.waves), vp.lds, (hipStream_t)stream, d);
-  ICM_CHECK_LAUNCH();
-  return ICM_OK;
+  return launch(d, p, (hipStream_t)stream);
 }
 
-// reduction plan of nwin table-gradient slabs: S partial sums over chunks of `chunk` slabs, S <= 64
-static void dtable_chunks(int nwin, int& S, int& chunk) {
-  S = std::max(1, std::min(64, nwin / 16));
-  chunk = (nwin + S - 1) / S;
-  S = (nwin + chunk - 1) / chunk;
-}
-static void dtable_plan(int N, int H, int W, int heads, int ws, int& nwin, int& E, int& S, int& chunk) {
-  const int tw = 2 * ws - 1;
-  nwin = N * (H / ws) * (W / ws);
-  E = heads * tw * tw;
-  dtable_chunks(nwin, S, chunk);
-}
-
+// one slab per window (the 4x4 matrix-core kernels write fewer: callers size for any family) + the S partial sums
 int64_t icm_winattn_bwd_workspace_floats(int N, int C, int H, int W, int heads, int ws) {
   if (N <= 0 || heads <= 0 || ws <= 0 || H % ws || W % ws) return -1;
-  int nwin, E, S, chunk;
-  dtable_plan(N, H, W, heads, ws, nwin, E, S, chunk);
+  const int tw = 2 * ws - 1, nwin = N * (H / ws) * (W / ws), E = heads * tw * tw;
+  int S, chunk;
+  dtable_chunks(nwin, S, chunk);
   return (int64_t)nwin * E + (int64_t)S * E;
 }
 
@@ -482,34 +416,20 @@ int icm_winattn_bwd(const float* qkv, const float* table, const float* dout, flo
   WaDesc d{};
   int rc = fill_desc(d, N, C, H, W, heads, ws, shift);
   if (rc) return rc;
-  int nwin, E, S, chunk;
-  dtable_plan(N, H, W, heads, ws, nwin, E, S, chunk);
-  if (ws_floats < (int64_t)nwin * E + (int64_t)S * E) return ICM_ERR_ARG;
+  if (ws_floats < icm_winattn_bwd_workspace_floats(N, C, H, W, heads, ws)) return ICM_ERR_ARG;
   int route;
-  ValuPlan vp;
-  rc = winattn_route(d, 1, route, vp);
+  WaPlan p;
+  rc = winattn_route(d, 1, route, p);
   if (rc) return rc;
-  const int tw = 2 * ws - 1;
-  if (route == WA_ROUTE_MFMA) {
-    const int rm = winattn_mfma_bwd(qkv, table, dout, dqkv, wsp, N, C, H, W, heads, ws, shift, (hipStream_t)stream);
-    if (rm) return rm < 0 ? ICM_ERR_UNSUPPORTED : rm;
-  } else if (route == WA_ROUTE_MFMA16) {
-    // 4x4 windows: one table-gradient slab per wave task (four windows), fewer than the per-window slabs planned for
-    const int slabs = winattn_mfma16_slabs(N, C, H, W, heads, ws, shift);
-    const int rm =
-        slabs > 0 ? winattn_mfma16_bwd(qkv, table, dout, dqkv, wsp, N, C, H, W, heads, ws, shift, (hipStream_t)stream) : -1;
-    if (rm) return rm < 0 ? ICM_ERR_UNSUPPORTED : rm;
-    nwin = slabs;
-    dtable_chunks(nwin, S, chunk);
-  } else {
-    d.qkv = qkv; d.table = table; d.dout = dout; d.dqkv = dqkv; d.dtable_ws = wsp;
-    if (vp.lds > 64 * 1024 && !ensure_max_lds(reinterpret_cast<const void*>(vp.fn))) return ICM_ERR_LAUNCH;
-    hipLaunchKernelGGL(vp.fn, dim3(N * d.nwy * d.nwx), dim3(64 * vp.waves), vp.lds, (hipStream_t)stream, d);
-    ICM_CHECK_LAUNCH();
-  }
-  float* part = wsp + (long long)nwin * E;
+  d.qkv = qkv; d.table = table; d.dout = dout; d.dqkv = dqkv; d.dtable_ws = wsp;
+  rc = launch(d, p, (hipStream_t)stream);
+  if (rc) return rc;
+  const int tw = 2 * ws - 1, E = heads * tw * tw;
+  int S, chunk;
+  dtable_chunks(p.slabs, S, chunk);
+  float* part = wsp + (long long)p.slabs * E;
   hipLaunchKernelGGL(dtable_reduce1_kernel, dim3((E + 63) / 64, S), dim3(256), 0, (hipStream_t)stream, wsp, part, E,
-                     nwin, chunk);
+                     p.slabs, chunk);
   ICM_CHECK_LAUNCH();
   hipLaunchKernelGGL(dtable_reduce2_kernel, dim3((E + 255) / 256), dim3(256), 0, (hipStream_t)stream, part, dtable, E, S,
                      tw * tw, heads, accum_table);

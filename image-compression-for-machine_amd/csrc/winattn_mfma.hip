@@ -17,40 +17,16 @@
 // Relative-position-bias gradients: each lane adds its dS entries into the head's LDS table, lanes 0-31 first, then
 // lanes 32-63 (within a half all table entries of one register are distinct), so the sum order is fixed; the
 // per-(window, head) tables go to the same workspace slabs winattn.hip reduces in window order.
-#include "icm_common.h"
+// This file exports winattn_mfma_plan and winattn_mfma16_plan (winattn_common.h); winattn.hip validates, routes and
+// launches.
+#include "winattn_common.h"
 
 namespace icm {
-
-struct WaDesc;   // winattn.hip
-
-struct WmDesc {
-  const float* qkv;
-  const float* table;
-  float* out;          // fwd
-  const float* dout;   // bwd
-  float* dqkv;         // bwd
-  float* dtable_ws;    // bwd
-  int N, C, H, W, heads, shift, nwx, nwy;
-  float scale;
-};
 
 #define WM_WS 8
 #define WM_T 64
 #define WM_TS 65
 #define WM_NTAB 225   // (2 * 8 - 1)^2
-
-__device__ __forceinline__ int wm_region(int s, int L, int shift) { return s < L - WM_WS ? 0 : (s < L - shift ? 1 : 2); }
-
-// pixel offset (oy * W + ox) and shift-mask label of token t of window (wy, wx)
-__device__ __forceinline__ void wm_token(const WmDesc& d, int wy, int wx, int t, int& pix, int& lab) {
-  const int r = t >> 3, c = t & 7;
-  const int sy = wy * WM_WS + r, sx = wx * WM_WS + c;
-  int oy = sy + d.shift, ox = sx + d.shift;
-  if (oy >= d.H) oy -= d.H;
-  if (ox >= d.W) ox -= d.W;
-  pix = oy * d.W + ox;
-  lab = d.shift > 0 ? wm_region(sy, d.H, d.shift) * 3 + wm_region(sx, d.W, d.shift) : 0;
-}
 
 // rows of a 32x32 accumulator tile held by register r of a lane in half h: (r & 3) + 8 (r >> 2) + 4 h
 __device__ __forceinline__ int wm_row(int r) { return (r & 3) + 8 * (r >> 2); }
@@ -193,7 +169,7 @@ struct WmLds {
 };
 
 template <int HD>
-__global__ __launch_bounds__(256, 2) void winattn_mfma_fwd_kernel(const WmDesc d) {
+__global__ __launch_bounds__(256, 2) void winattn_mfma_fwd_kernel(const WaDesc d) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   constexpr int ND = (HD + 31) / 32;
   using LDS = WmLds<HD, 3>;
@@ -210,10 +186,9 @@ __global__ __launch_bounds__(256, 2) void winattn_mfma_fwd_kernel(const WmDesc d
   const int n = bid / d.nwy;
   const long long HW = (long long)d.H * d.W;
   if (tid < WM_T) {
-    int px, lb;
-    wm_token(d, wy, wx, tid, px, lb);
-    pixs[tid] = px;
-    labs[tid] = (unsigned char)lb;
+    const Tok tk = token(d, WM_WS, wy, wx, tid);
+    pixs[tid] = tk.pix;
+    labs[tid] = (unsigned char)tk.lab;
   }
   __syncthreads();
   const int l31 = lane & 31;
@@ -244,7 +219,7 @@ __global__ __launch_bounds__(256, 2) void winattn_mfma_fwd_kernel(const WmDesc d
 }
 
 template <int HD>
-__global__ __launch_bounds__(256, 1) void winattn_mfma_bwd_kernel(const WmDesc d) {
+__global__ __launch_bounds__(256, 1) void winattn_mfma_bwd_kernel(const WaDesc d) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   constexpr int ND = (HD + 31) / 32;
   using LDS = WmLds<HD, 4>;
@@ -267,10 +242,9 @@ __global__ __launch_bounds__(256, 1) void winattn_mfma_bwd_kernel(const WmDesc d
   const int n = bid / d.nwy;
   const long long HW = (long long)d.H * d.W;
   if (tid < WM_T) {
-    int px, lb;
-    wm_token(d, wy, wx, tid, px, lb);
-    pixs[tid] = px;
-    labs[tid] = (unsigned char)lb;
+    const Tok tk = token(d, WM_WS, wy, wx, tid);
+    pixs[tid] = tk.pix;
+    labs[tid] = (unsigned char)tk.lab;
   }
   __syncthreads();
   const int l31 = lane & 31, h = lane >> 5;
@@ -392,15 +366,13 @@ __global__ __launch_bounds__(256, 1) void winattn_mfma_bwd_kernel(const WmDesc d
   }
 }
 
-typedef void (*WmFn)(const WmDesc);
-static bool wm_pick(int hd, WmFn& f, WmFn& b, size_t& lf, size_t& lb) {
+static bool wm_pick(int hd, int backward, WaPlan& p) {
   switch (hd) {
-#define C_(n)                                               \
-  case n:                                                   \
-    f = winattn_mfma_fwd_kernel<n>;                         \
-    b = winattn_mfma_bwd_kernel<n>;                         \
-    lf = ((size_t)4 * WmLds<n, 3>::kFloats + WM_T + WM_T / 4) * sizeof(float);  \
-    lb = ((size_t)4 * WmLds<n, 4>::kFloats + WM_T + WM_T / 4) * sizeof(float);  \
+#define C_(n)                                                                           \
+  case n:                                                                               \
+    p.fn = backward ? winattn_mfma_bwd_kernel<n> : winattn_mfma_fwd_kernel<n>;          \
+    p.lds = (size_t)4 * (backward ? WmLds<n, 4>::kFloats : WmLds<n, 3>::kFloats);       \
+    p.lds = (p.lds + WM_T + WM_T / 4) * sizeof(float); /* + pixel offsets and labels */ \
     return true;
     C_(8) C_(16) C_(24) C_(32) C_(48)
 #undef C_
@@ -408,58 +380,12 @@ static bool wm_pick(int hd, WmFn& f, WmFn& b, size_t& lf, size_t& lb) {
   }
 }
 
-static bool wm_fill(WmDesc& d, int N, int C, int H, int W, int heads, int ws, int shift) {
-  if (ws != WM_WS || heads <= 0 || C % heads || H % ws || W % ws || shift < 0 || shift >= ws) return false;
-  d.N = N; d.C = C; d.H = H; d.W = W; d.heads = heads; d.shift = shift;
-  d.nwx = W / ws; d.nwy = H / ws;
-  d.scale = 1.0f / sqrtf((float)(C / heads));
-  return true;
-}
-
-// does the 8x8 family take this geometry (window size, a head dim of its table, LDS of the direction within the
-// 160 KB a workgroup may ask for)?  The one test behind the launches below and icm_debug_winattn_route: pure host code
-static bool wm_plan(WmDesc& d, WmFn& fn, size_t& lds, int N, int C, int H, int W, int heads, int ws, int shift,
-                    int backward) {
-  WmFn f, b;
-  size_t lf, lb;
-  if (!wm_fill(d, N, C, H, W, heads, ws, shift) || !wm_pick(C / heads, f, b, lf, lb)) return false;
-  fn = backward ? b : f;
-  lds = backward ? lb : lf;
-  return lds <= 160 * 1024;
-}
-bool winattn_mfma_takes(int N, int C, int H, int W, int heads, int ws, int shift, int backward) {
-  WmDesc d{};
-  WmFn fn;
-  size_t lds;
-  return wm_plan(d, fn, lds, N, C, H, W, heads, ws, shift, backward);
-}
-
-// returns ICM_OK when the MFMA path took the launch, -1 when this geometry is not covered (caller falls through to
-// the generic kernel of winattn.hip), an ICM_ERR_* code on failure
-int winattn_mfma_fwd(const float* qkv, const float* table, float* out, int N, int C, int H, int W, int heads, int ws,
-                     int shift, hipStream_t stream) {
-  WmDesc d{};
-  WmFn f;
-  size_t lf;
-  if (!wm_plan(d, f, lf, N, C, H, W, heads, ws, shift, 0)) return -1;
-  d.qkv = qkv; d.table = table; d.out = out;
-  if (lf > 64 * 1024 && !ensure_max_lds(reinterpret_cast<const void*>(f))) return ICM_ERR_LAUNCH;
-  hipLaunchKernelGGL(f, dim3(N * d.nwy * d.nwx), dim3(256), lf, stream, d);
-  ICM_CHECK_LAUNCH();
-  return ICM_OK;
-}
-
-int winattn_mfma_bwd(const float* qkv, const float* table, const float* dout, float* dqkv, float* dtable_ws, int N, int C,
-                     int H, int W, int heads, int ws, int shift, hipStream_t stream) {
-  WmDesc d{};
-  WmFn b;
-  size_t lb;
-  if (!wm_plan(d, b, lb, N, C, H, W, heads, ws, shift, 1)) return -1;
-  d.qkv = qkv; d.table = table; d.dout = dout; d.dqkv = dqkv; d.dtable_ws = dtable_ws;
-  if (lb > 64 * 1024 && !ensure_max_lds(reinterpret_cast<const void*>(b))) return ICM_ERR_LAUNCH;
-  hipLaunchKernelGGL(b, dim3(N * d.nwy * d.nwx), dim3(256), lb, stream, d);
-  ICM_CHECK_LAUNCH();
-  return ICM_OK;
+// one workgroup of four waves per window, each wave walks heads
+int winattn_mfma_plan(const WaDesc& d, int backward, WaPlan& p) {
+  if (d.ws != WM_WS || !wm_pick(d.hd, backward, p)) return ICM_ERR_UNSUPPORTED;
+  p.grid = p.slabs = d.N * d.nwy * d.nwx;
+  p.block = 256;
+  return p.lds > kWaLdsLimit ? ICM_ERR_UNSUPPORTED : ICM_OK;
 }
 
 }  // namespace icm
@@ -478,20 +404,7 @@ namespace icm {
 #define W4_TS 17
 #define W4_NTAB 49   // (2 * 4 - 1)^2
 
-struct W4Desc {
-  const float* qkv;
-  const float* table;
-  float* out;
-  const float* dout;
-  float* dqkv;
-  float* dtable_ws;
-  int N, C, H, W, heads, shift, ngx, nwy;   // ngx = groups of 4 windows per row
-  float scale;
-};
-
 typedef float f32x4v __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ int w4_region(int s, int L, int shift) { return s < L - 4 ? 0 : (s < L - shift ? 1 : 2); }
 
 // acc (+)= sum_d rowT[d][row token] * colT[d][col token] for ONE window slab pair ([HD][17] each)
 template <int HD>
@@ -563,20 +476,16 @@ __device__ __forceinline__ void w4_load_all(const float* const (&src)[NS], long 
 }
 
 // geometry of the wave's four windows: pixel / mask label of (window w, token t) for the lane's own (w, t)
-__device__ __forceinline__ void w4_token(const W4Desc& d, int wy, int gx, int w, int t, int& pix, int& lab, bool& valid) {
+__device__ __forceinline__ void w4_token(const WaDesc& d, int wy, int gx, int w, int t, int& pix, int& lab, bool& valid) {
   const int wx = gx * 4 + w;
-  valid = wx * 4 < d.W;
-  const int r = t >> 2, c = t & 3;
-  const int sy = wy * 4 + r, sx = min(wx, d.W / 4 - 1) * 4 + c;
-  int oy = sy + d.shift, ox = sx + d.shift;
-  if (oy >= d.H) oy -= d.H;
-  if (ox >= d.W) ox -= d.W;
-  pix = oy * d.W + ox;
-  lab = d.shift > 0 ? w4_region(sy, d.H, d.shift) * 3 + w4_region(sx, d.W, d.shift) : 0;
+  valid = wx < d.nwx;
+  const Tok tk = token(d, 4, wy, min(wx, d.nwx - 1), t);   // windows beyond the row end: clamped addresses, never stored
+  pix = tk.pix;
+  lab = tk.lab;
 }
 
 template <int HD>
-__global__ __launch_bounds__(256) void winattn_mfma16_fwd_kernel(const W4Desc d) {
+__global__ __launch_bounds__(256) void winattn_mfma16_fwd_kernel(const WaDesc d) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   constexpr int ND = (HD + 15) / 16;
   using LDS = W4Lds<HD, 3>;
@@ -650,7 +559,7 @@ __global__ __launch_bounds__(256) void winattn_mfma16_fwd_kernel(const W4Desc d)
 }
 
 template <int HD>
-__global__ __launch_bounds__(128) void winattn_mfma16_bwd_kernel(const W4Desc d) {
+__global__ __launch_bounds__(128) void winattn_mfma16_bwd_kernel(const WaDesc d) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   constexpr int ND = (HD + 15) / 16;
   using LDS = W4Lds<HD, 4>;
@@ -774,80 +683,28 @@ __global__ __launch_bounds__(128) void winattn_mfma16_bwd_kernel(const W4Desc d)
   }
 }
 
-typedef void (*W4Fn)(const W4Desc);
-static bool w4_pick(int hd, W4Fn& f, W4Fn& b, size_t& lf, size_t& lb) {
+static bool w4_pick(int hd, int backward, WaPlan& p) {
   switch (hd) {
-#define C_(n)                                                 \
-  case n:                                                     \
-    f = winattn_mfma16_fwd_kernel<n>;                         \
-    b = winattn_mfma16_bwd_kernel<n>;                         \
-    lf = (size_t)4 * W4Lds<n, 3>::kFloats * sizeof(float);    \
-    lb = (size_t)2 * W4Lds<n, 4>::kFloats * sizeof(float);    \
+#define C_(n)                                                                                   \
+  case n:                                                                                       \
+    p.fn = backward ? winattn_mfma16_bwd_kernel<n> : winattn_mfma16_fwd_kernel<n>;              \
+    p.lds = (backward ? 2 * W4Lds<n, 4>::kFloats : 4 * W4Lds<n, 3>::kFloats) * sizeof(float);   \
     return true;
     C_(8) C_(16) C_(24) C_(32) C_(40)
 #undef C_
     default: return false;
   }
 }
-static bool w4_fill(W4Desc& d, int N, int C, int H, int W, int heads, int ws, int shift) {
-  if (ws != 4 || heads <= 0 || C % heads || H % 4 || W % 4 || shift < 0 || shift >= 4) return false;
-  d.N = N; d.C = C; d.H = H; d.W = W; d.heads = heads; d.shift = shift;
-  d.ngx = (W / 4 + 3) / 4; d.nwy = H / 4;
-  d.scale = 1.0f / sqrtf((float)(C / heads));
-  return true;
-}
 
-// does the 4x4 family take this geometry?  Same role as wm_plan
-static bool w4_plan(W4Desc& d, W4Fn& fn, size_t& lds, int N, int C, int H, int W, int heads, int ws, int shift,
-                    int backward) {
-  W4Fn f, b;
-  size_t lf, lb;
-  if (!w4_fill(d, N, C, H, W, heads, ws, shift) || !w4_pick(C / heads, f, b, lf, lb)) return false;
-  fn = backward ? b : f;
-  lds = backward ? lb : lf;
-  return lds <= 160 * 1024;
-}
-bool winattn_mfma16_takes(int N, int C, int H, int W, int heads, int ws, int shift, int backward) {
-  W4Desc d{};
-  W4Fn fn;
-  size_t lds;
-  return w4_plan(d, fn, lds, N, C, H, W, heads, ws, shift, backward);
-}
-
-// number of table-gradient slabs the 4x4 backward writes (one per wave task = group of four windows), or -1
-int winattn_mfma16_slabs(int N, int C, int H, int W, int heads, int ws, int shift) {
-  W4Desc d{};
-  W4Fn b;
-  size_t lb;
-  if (!w4_plan(d, b, lb, N, C, H, W, heads, ws, shift, 1)) return -1;
-  return N * d.nwy * d.ngx;
-}
-
-int winattn_mfma16_fwd(const float* qkv, const float* table, float* out, int N, int C, int H, int W, int heads, int ws,
-                       int shift, hipStream_t stream) {
-  W4Desc d{};
-  W4Fn f;
-  size_t lf;
-  if (!w4_plan(d, f, lf, N, C, H, W, heads, ws, shift, 0)) return -1;
-  d.qkv = qkv; d.table = table; d.out = out;
-  if (lf > 64 * 1024 && !ensure_max_lds(reinterpret_cast<const void*>(f))) return ICM_ERR_LAUNCH;
-  const int nwt = N * d.nwy * d.ngx * heads;
-  hipLaunchKernelGGL(f, dim3((nwt + 3) / 4), dim3(256), lf, stream, d);
-  ICM_CHECK_LAUNCH();
-  return ICM_OK;
-}
-int winattn_mfma16_bwd(const float* qkv, const float* table, const float* dout, float* dqkv, float* dtable_ws, int N,
-                       int C, int H, int W, int heads, int ws, int shift, hipStream_t stream) {
-  W4Desc d{};
-  W4Fn b;
-  size_t lb;
-  if (!w4_plan(d, b, lb, N, C, H, W, heads, ws, shift, 1)) return -1;
-  d.qkv = qkv; d.table = table; d.dout = dout; d.dqkv = dqkv; d.dtable_ws = dtable_ws;
-  if (lb > 64 * 1024 && !ensure_max_lds(reinterpret_cast<const void*>(b))) return ICM_ERR_LAUNCH;
-  const int nwt = N * d.nwy * d.ngx * heads;
-  hipLaunchKernelGGL(b, dim3((nwt + 1) / 2), dim3(128), lb, stream, d);
-  ICM_CHECK_LAUNCH();
-  return ICM_OK;
+// one wave per (group of four windows, head): four waves per workgroup forward, two backward; the backward writes one
+// table-gradient slab per group
+int winattn_mfma16_plan(const WaDesc& d, int backward, WaPlan& p) {
+  if (d.ws != 4 || !w4_pick(d.hd, backward, p)) return ICM_ERR_UNSUPPORTED;
+  const int waves = backward ? 2 : 4;
+  p.slabs = d.N * d.nwy * d.ngx;
+  p.grid = (p.slabs * d.heads + waves - 1) / waves;
+  p.block = 64 * waves;
+  return p.lds > kWaLdsLimit ? ICM_ERR_UNSUPPORTED : ICM_OK;
 }
 
 }  // namespace icm

@@ -110,3 +110,27 @@ def test_every_case_reaches_the_family_it_is_meant_for():
                       ((1, 10, 4, 4, 3, 4, 0), R.ERR_ARG), ((1, 8, 9, 9, 1, 9, 0), R.ERR_UNSUPPORTED),
                       ((1, 12, 4, 4, 1, 4, 0), R.ERR_UNSUPPORTED)):
         assert [lib.icm_debug_winattn_route(*geo, b) for b in (0, 1)] == [-code, -code], geo
+
+
+def test_recorded_routes_replay():
+    """tests/golden/winattn_routes.npz (tests/golden/make_winattn_routes.py): every recorded row gets the family, the
+    refusal code and the backward workspace size it got when the fixture was written"""
+    import os
+    import numpy as np
+    from icm_amd import _lib
+    lib = _lib.lib()
+    rec = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "winattn_routes.npz"))
+    args, route, wsf = rec["args"], rec["route"], rec["wsf"]
+    assert len(args) >= 3000 and len(args) == len(route) == len(wsf)
+    bad = []
+    try:
+        for row, want_r, want_w in zip(args.tolist(), route.tolist(), wsf.tolist()):
+            force, geo = row[0], row[1:]
+            lib.icm_debug_force_winattn_valu(force)
+            got_r = [lib.icm_debug_winattn_route(*geo, b) for b in (0, 1)]
+            got_w = lib.icm_winattn_bwd_workspace_floats(*geo[:6])
+            if got_r != want_r or got_w != want_w:
+                bad.append((row, got_r, want_r, got_w, want_w))
+    finally:
+        lib.icm_debug_force_winattn_valu(0)
+    assert not bad, (len(bad), bad[:5])
