@@ -1,0 +1,502 @@
+// Lane streams on the device: the kernels behind compress(coder="lanes") / decompress(coder="lanes").
+//
+// Format and state machine: icm_amd/bitstream.py ("lane stream"); executable definition: csrc/rans.cpp
+// (icm_rans_lanes_encode / icm_rans_lanes_decoder_*), which these kernels match byte for byte.  Parity unpinned: no
+// counterpart in the reference.
+//
+// One wave codes one body.  A lane owns one 32-bit rANS state; in step t of a run, lane l of wave g handles element
+// g c + 64 t + l.  The only cross-lane traffic is the word order inside a phase: the lanes that renormalise take
+// consecutive words in ascending lane order = a 64-bit ballot and a popcount of the lower lanes (v_mbcnt), no LDS.
+// The word cursor is wave-uniform and lives in a scalar register between steps.
+//
+// Bounds.  Every loop is counted by the run length and G (steps), by the constant 3 (escape phases) or by
+// ceil(log2(cdf_stride)) (table search); nothing in a stream can lengthen one.  Every word read is checked against
+// the body's word count first and sets ICM_LANES_ST_OVERRUN instead of reading; every CDF index is checked against
+// ncdf and its table size against the stride before a table entry is read; the search keeps 0 <= lo < hi <= size - 1.
+// The encoder checks every word position against its scratch region and sets an overflow flag instead of writing.
+#include "icm_common.h"
+
+#include <cstring>
+#include <new>
+#include <vector>
+
+namespace {
+
+constexpr uint32_t kL = 1u << 16;
+constexpr int kLanes = 64;
+constexpr int kBlock = 256;   // pack / init / finish launches; upper bound of a coding workgroup
+constexpr int kMaxG = 4096;
+constexpr int kEncBad = 1, kEncOverflow = 2;   // flags of the encoder's result record
+
+struct Tab {
+  const int32_t* cdfs;
+  const int32_t* sizes;
+  const int32_t* offsets;
+  int stride, ncdf, maxit;
+};
+
+struct EncResult {   // first 16 bytes of the encoder workspace
+  int64_t nbytes;
+  int32_t flags, pad;
+};
+
+struct WaveCtl {     // decoder: one per body
+  uint32_t off;      // byte offset of the body's first word (after its 64 states) inside the uploaded string
+  uint32_t nwords;
+  uint32_t cursor;
+  uint32_t status;
+};
+
+__device__ __forceinline__ int lane_id() { return (int)(threadIdx.x & (kLanes - 1)); }
+__device__ __forceinline__ int rank_below(unsigned long long mask) {
+  return (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
+}
+__device__ __forceinline__ int wave_or(int v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v |= __shfl_xor(v, o, 64);
+  return v;
+}
+
+// ------------------------------------------------------------------------------------------------------ encoder
+__global__ void lanes_enc_init_kernel(uint32_t* __restrict__ states, int32_t* __restrict__ wptr, EncResult* res, int G,
+                                      int cap) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < G * kLanes) states[i] = kL;
+  if (i < G) wptr[i] = cap;
+  if (i == 0) { res->nbytes = 0; res->flags = 0; res->pad = 0; }
+}
+
+// one run, walked last step to first; the words go downwards into this wave's scratch region [0, cap)
+__global__ __launch_bounds__(kBlock) void lanes_enc_run_kernel(const int32_t* __restrict__ symbols,
+                                                               const int32_t* __restrict__ indexes, long long n,
+                                                               long long c, Tab T, uint32_t* __restrict__ states,
+                                                               int32_t* __restrict__ wptr, uint16_t* __restrict__ scratch,
+                                                               int cap, EncResult* res, int G) {
+  const int g = __builtin_amdgcn_readfirstlane((int)(blockIdx.x * (blockDim.x / kLanes) + threadIdx.x / kLanes));
+  if (g >= G) return;
+  const int lane = lane_id();
+  const long long e0 = (long long)g * c;
+  const long long e1 = min(n, e0 + c);
+  if (e1 <= e0) return;
+  const int steps = (int)((e1 - e0 + kLanes - 1) / kLanes);
+  uint32_t x = states[g * kLanes + lane];
+  int wp = __builtin_amdgcn_readfirstlane(wptr[g]);
+  uint16_t* out = scratch + (long long)g * cap;
+  int flags = 0;
+  for (int t = steps - 1; t >= 0; --t) {
+    const long long e = e0 + (long long)t * kLanes + lane;
+    const bool active = e < e1;
+    uint32_t start = 0, freq = 0;
+    unsigned long long raw = 0;
+    bool esc = false, ok = false;
+    if (active) {
+      const int idx = indexes[e];
+      const int size = (idx >= 0 && idx < T.ncdf) ? T.sizes[idx] : 0;
+      if (size >= 2 && size <= T.stride) {
+        const int32_t* cdf = T.cdfs + (long long)idx * T.stride;
+        const int overflow = size - 2;
+        long long v = (long long)symbols[e] - T.offsets[idx];
+        if (v < 0) { raw = (unsigned long long)(-2 * v - 1); v = overflow; esc = true; }
+        else if (v >= overflow) { raw = (unsigned long long)(2 * (v - overflow)); v = overflow; esc = true; }
+        const int lo = cdf[v], hi = cdf[v + 1];
+        ok = hi > lo && lo >= 0 && hi <= 65536 && hi - lo <= 0xFFFF;
+        start = (uint32_t)lo;
+        freq = (uint32_t)(hi - lo);
+      }
+      if (!ok) { flags |= kEncBad; esc = false; }
+    }
+#pragma unroll
+    for (int ph = 3; ph >= 0; --ph) {
+      const bool put = ok && (ph == 0 || esc);
+      const uint32_t f = ph == 0 ? freq : 1u;
+      const uint32_t s = ph == 0 ? start : (uint32_t)((raw >> (16 * (ph - 1))) & 0xFFFF);
+      const bool emit = put && x >= (f << 16);        // f <= 0xFFFF: no overflow
+      const unsigned long long mask = __ballot(emit);
+      if (mask == 0 && !__any(put)) continue;
+      wp -= __popcll(mask);
+      if (emit) {
+        const int pos = wp + rank_below(mask);
+        if (pos >= 0) out[pos] = (uint16_t)(x & 0xFFFF);
+        else flags |= kEncOverflow;
+        x >>= 16;
+      }
+      if (put) x = ((x / f) << 16) + x % f + s;
+    }
+  }
+  states[g * kLanes + lane] = x;
+  if (lane == 0) wptr[g] = wp;
+  flags = wave_or(flags);
+  if (lane == 0 && flags) atomicOr(&res->flags, flags);
+}
+
+// body g -> its place in the string; block g adds up the lengths before it (G <= 4096), the last block writes the total
+__global__ __launch_bounds__(kBlock) void lanes_pack_kernel(const uint32_t* __restrict__ states,
+                                                            const int32_t* __restrict__ wptr,
+                                                            const uint16_t* __restrict__ scratch, int cap, int G,
+                                                            uint8_t* __restrict__ out, EncResult* res) {
+  __shared__ long long part[kBlock];
+  const int g = blockIdx.x, tid = threadIdx.x;
+  long long sum = 0;
+  for (int k = tid; k < g; k += kBlock) sum += 4 * kLanes + 2ll * (cap - max(wptr[k], 0));
+  part[tid] = sum;
+  __syncthreads();
+  for (int o = kBlock / 2; o > 0; o >>= 1) {
+    if (tid < o) part[tid] += part[tid + o];
+    __syncthreads();
+  }
+  const int wp = max(wptr[g], 0);
+  const int nwords = cap - wp;
+  const long long off = 8 + 4ll * G + part[0];
+  const uint32_t len = (uint32_t)(4 * kLanes + 2 * nwords);
+  uint16_t* o16 = reinterpret_cast<uint16_t*>(out);   // every offset below is even
+  if (tid == 0) {
+    if (g == 0) {
+      out[0] = 'I'; out[1] = 'C'; out[2] = 'M'; out[3] = 'L';
+      o16[2] = 1;
+      o16[3] = (uint16_t)G;
+    }
+    o16[4 + 2 * g] = (uint16_t)(len & 0xFFFF);
+    o16[5 + 2 * g] = (uint16_t)(len >> 16);
+    if (g == G - 1) res->nbytes = off + len;
+  }
+  uint16_t* body = o16 + off / 2;
+  if (tid < kLanes) {
+    const uint32_t x = states[g * kLanes + tid];
+    body[2 * tid] = (uint16_t)(x & 0xFFFF);
+    body[2 * tid + 1] = (uint16_t)(x >> 16);
+  }
+  const uint16_t* src = scratch + (long long)g * cap + wp;
+  for (int k = tid; k < nwords; k += kBlock) body[2 * kLanes + k] = src[k];
+}
+
+// ------------------------------------------------------------------------------------------------------ decoder
+// s with cdf[s] <= cum < cdf[s + 1], for a table with cdf[0] = 0 and cdf[size - 1] = 2^16 (any other table still ends
+// with 0 <= s <= size - 2 after at most 2 maxit probes).  CENTRE: gallop outward from the bin of symbol 0 first --
+// nearly every symbol of a Gaussian table lies a few bins from it, but a wave pays for its farthest lane, in both
+// directions of the divergent gallop: measured slower than the plain search, kept as a measurement switch.
+template <bool CENTRE>
+__device__ __forceinline__ int cdf_search(const int32_t* __restrict__ cdf, int size, int centre, int cum, int maxit) {
+  int lo = 0, hi = size - 1;
+  if (CENTRE) {
+    const int c = min(max(centre, 0), size - 2);
+    if (cdf[c] <= cum) {
+      lo = c;
+      int step = 1;
+      for (int it = 0; it < maxit; ++it) {
+        const int p = lo + step;
+        if (p >= hi) break;
+        if (cdf[p] <= cum) { lo = p; step <<= 1; }
+        else { hi = p; break; }
+      }
+    } else {
+      hi = c;
+      int step = 1;
+      for (int it = 0; it < maxit; ++it) {
+        const int p = hi - step;
+        if (p <= lo) break;
+        if (cdf[p] > cum) { hi = p; step <<= 1; }
+        else { lo = p; break; }
+      }
+    }
+  }
+  for (int it = 0; it < maxit && hi - lo > 1; ++it) {
+    const int mid = (lo + hi) >> 1;
+    if (cdf[mid] <= cum) lo = mid;
+    else hi = mid;
+  }
+  return lo;
+}
+
+template <bool CENTRE>
+__global__ __launch_bounds__(kBlock) void lanes_dec_run_kernel(const uint8_t* __restrict__ string, WaveCtl* __restrict__ ctl,
+                                                               uint32_t* __restrict__ states,
+                                                               const int32_t* __restrict__ indexes, long long n,
+                                                               long long c, Tab T, int32_t* __restrict__ out, int G) {
+  const int g = __builtin_amdgcn_readfirstlane((int)(blockIdx.x * (blockDim.x / kLanes) + threadIdx.x / kLanes));
+  if (g >= G) return;
+  const int lane = lane_id();
+  const long long e0 = (long long)g * c;
+  const long long e1 = min(n, e0 + c);
+  if (e1 <= e0) return;
+  const int steps = (int)((e1 - e0 + kLanes - 1) / kLanes);
+  const uint16_t* __restrict__ words = reinterpret_cast<const uint16_t*>(string + ctl[g].off);
+  const uint32_t nwords = __builtin_amdgcn_readfirstlane(ctl[g].nwords);
+  uint32_t cur = __builtin_amdgcn_readfirstlane(ctl[g].cursor);
+  uint32_t x = states[g * kLanes + lane];
+  int st = 0;
+  for (int t = 0; t < steps; ++t) {
+    const long long e = e0 + (long long)t * kLanes + lane;
+    const bool active = e < e1;
+    bool ok = false, esc = false;
+    int sym = 0, overflow = 0, offset = 0;
+    if (active) {
+      const int idx = indexes[e];
+      const int size = (idx >= 0 && idx < T.ncdf) ? T.sizes[idx] : 0;
+      if (size >= 2 && size <= T.stride) {
+        const int32_t* cdf = T.cdfs + (long long)idx * T.stride;
+        offset = T.offsets[idx];
+        overflow = size - 2;
+        const int cum = (int)(x & 0xFFFF);
+        const int s = cdf_search<CENTRE>(cdf, size, -offset, cum, T.maxit);
+        const int lo = cdf[s], hi = cdf[s + 1];
+        if (lo <= cum && cum < hi) {
+          ok = true;
+          x = (uint32_t)(hi - lo) * (x >> 16) + (uint32_t)(cum - lo);
+          esc = s == overflow;
+          sym = s + offset;
+        } else {
+          st |= ICM_LANES_ST_SYMBOL;
+        }
+      } else {
+        st |= ICM_LANES_ST_INDEX;
+      }
+    }
+    {   // phase 0 renormalisation
+      const bool need = ok && x < kL;
+      const unsigned long long mask = __ballot(need);
+      if (need) {
+        const uint32_t k = cur + (uint32_t)rank_below(mask);
+        uint32_t w = 0;
+        if (k < nwords) w = words[k];
+        else st |= ICM_LANES_ST_OVERRUN;
+        x = (x << 16) | w;
+      }
+      cur += (uint32_t)__popcll(mask);
+    }
+    const unsigned long long emask = __ballot(esc);
+    if (emask) {   // wave-uniform: phases 1..3, raw 16-bit groups of the lanes that escaped
+      unsigned long long raw = 0;
+      const int cnt = __popcll(emask);
+#pragma unroll
+      for (int ph = 0; ph < 3; ++ph) {
+        if (esc) {
+          raw |= (unsigned long long)(x & 0xFFFF) << (16 * ph);
+          const uint32_t k = cur + (uint32_t)rank_below(emask);
+          uint32_t w = 0;
+          if (k < nwords) w = words[k];
+          else st |= ICM_LANES_ST_OVERRUN;
+          x = (x & 0xFFFF0000u) | w;
+        }
+        cur += (uint32_t)cnt;
+      }
+      if (esc) {
+        const long long half = (long long)(raw >> 1);
+        const long long v = ((raw & 1) ? -half - 1 : half + overflow) + offset;
+        if (v < INT32_MIN || v > INT32_MAX) { st |= ICM_LANES_ST_ESCAPE; sym = 0; }
+        else sym = (int)v;
+      }
+    }
+    if (active) out[e] = sym;
+  }
+  states[g * kLanes + lane] = x;
+  st = wave_or(st);
+  if (lane == 0) {
+    ctl[g].cursor = cur;
+    if (st) ctl[g].status |= (uint32_t)st;
+  }
+}
+
+__global__ void lanes_dec_finish_kernel(const WaveCtl* __restrict__ ctl, const uint32_t* __restrict__ states,
+                                        uint32_t* __restrict__ status, int G) {
+  const int g = blockIdx.x * blockDim.x + threadIdx.x;
+  if (g >= G) return;
+  uint32_t st = ctl[g].status;
+  if (ctl[g].cursor != ctl[g].nwords) st |= ICM_LANES_ST_CURSOR;
+  for (int l = 0; l < kLanes; ++l)
+    if (states[g * kLanes + l] != kL) st |= ICM_LANES_ST_STATE;
+  status[g] = st;
+}
+
+// ------------------------------------------------------------------------------------------------------ host side
+inline int64_t align16(int64_t v) { return (v + 15) & ~(int64_t)15; }
+inline int64_t chunk(int64_t n, int G) { return ((n + G - 1) / G + kLanes - 1) / kLanes * kLanes; }
+
+struct EncPlan {
+  int G = 0;
+  int64_t cap = 0;        // u16 words of scratch per wave
+  int64_t o_states, o_wptr, o_scratch, o_out, bytes;
+};
+
+bool enc_plan(const int64_t* run_lengths, int nruns, int64_t spw, int worst, EncPlan& P) {
+  P.G = icm_rans_lanes_waves(run_lengths, nruns, spw);
+  if (P.G < 1) return false;
+  int64_t sum_c = 0;
+  for (int r = 0; r < nruns; ++r) sum_c += chunk(run_lengths[r], P.G);
+  P.cap = (worst ? 4 : 1) * sum_c;
+  if (P.cap >= (1ll << 29)) return false;           // word positions are 32-bit in the kernels: a wave's pointer starts
+                                                    // at cap and falls by at most 4 cap, so it stays above INT32_MIN
+  P.o_states = align16((int64_t)sizeof(EncResult));
+  P.o_wptr = P.o_states + align16(4ll * P.G * kLanes);
+  P.o_scratch = P.o_wptr + align16(4ll * P.G);
+  P.o_out = P.o_scratch + align16(2 * P.cap * P.G);
+  P.bytes = P.o_out + align16(8 + 4ll * P.G + (int64_t)P.G * (4 * kLanes + 2 * P.cap));
+  return true;
+}
+
+bool make_tab(const int32_t* cdfs, int stride, const int32_t* sizes, const int32_t* offsets, int ncdf, Tab& T) {
+  if (!cdfs || !sizes || !offsets || ncdf < 1 || stride < 2) return false;
+  T = Tab{cdfs, sizes, offsets, stride, ncdf, icm::ceil_log2(stride) + 1};
+  return true;
+}
+
+struct GpuDecoder {
+  std::vector<uint8_t> host;    // what create uploads; kept until destroy (the copy is asynchronous)
+  uint8_t* dev = nullptr;
+  int G = 0;
+  int64_t o_ctl, o_states, o_status, o_string;
+  hipStream_t stream = nullptr;   // the stream create uploaded on
+};
+
+int g_search_centre = 0;   // binary search: measured 2x faster than centre-first on wide tables
+
+// Waves (bodies) per coding workgroup.  The waves of a stream share nothing, and a stream has few of them (48 per slice
+// of a 2048x3072 image), each a serial chain of dependent loads: one wave per workgroup lets the dispatcher spread
+// them over as many CUs as there are bodies.  ICM_LANES_WPB (1, 2 or 4) is the measurement knob.
+int waves_per_block() {
+  static const int w = icm::env_int("ICM_LANES_WPB", 1);
+  return w == 2 || w == 4 ? w : 1;
+}
+
+}  // namespace
+
+#define ST ((hipStream_t)stream)
+
+extern "C" {
+
+void icm_debug_lanes_search(int centre) { g_search_centre = centre ? 1 : 0; }
+
+int64_t icm_rans_lanes_encode_gpu_workspace(const int64_t* run_lengths, int nruns, int64_t symbols_per_wave,
+                                            int worst_case) {
+  EncPlan P;
+  return enc_plan(run_lengths, nruns, symbols_per_wave, worst_case, P) ? P.bytes : -1;
+}
+
+int64_t icm_rans_lanes_encode_gpu(const int32_t* symbols, const int32_t* indexes, const int64_t* run_lengths, int nruns,
+                                  const int32_t* cdfs, int cdf_stride, const int32_t* cdf_sizes, const int32_t* offsets,
+                                  int ncdf, int64_t symbols_per_wave, int worst_case, void* ws, int64_t ws_bytes,
+                                  int64_t* string_offset, void* stream) {
+  EncPlan P;
+  Tab T;
+  if (!enc_plan(run_lengths, nruns, symbols_per_wave, worst_case, P) || !make_tab(cdfs, cdf_stride, cdf_sizes, offsets, ncdf, T))
+    return -1;
+  int64_t total = 0;
+  for (int r = 0; r < nruns; ++r) total += run_lengths[r];
+  if ((total > 0 && (!symbols || !indexes)) || !ws || !string_offset || ws_bytes < P.bytes ||
+      (reinterpret_cast<uintptr_t>(ws) & 15))
+    return -1;
+  uint8_t* base = static_cast<uint8_t*>(ws);
+  EncResult* res = reinterpret_cast<EncResult*>(base);
+  uint32_t* states = reinterpret_cast<uint32_t*>(base + P.o_states);
+  int32_t* wptr = reinterpret_cast<int32_t*>(base + P.o_wptr);
+  uint16_t* scratch = reinterpret_cast<uint16_t*>(base + P.o_scratch);
+  const int G = P.G, cap = (int)P.cap;
+  hipLaunchKernelGGL(lanes_enc_init_kernel, dim3((G * kLanes + kBlock - 1) / kBlock), dim3(kBlock), 0, ST, states, wptr,
+                     res, G, cap);
+  if (hipGetLastError() != hipSuccess) return -3;
+  const int wpb = waves_per_block();
+  const int blocks = (G + wpb - 1) / wpb;
+  int64_t off = total;
+  for (int r = nruns - 1; r >= 0; --r) {
+    const int64_t n = run_lengths[r];
+    off -= n;
+    if (n == 0) continue;
+    hipLaunchKernelGGL(lanes_enc_run_kernel, dim3(blocks), dim3(wpb * kLanes), 0, ST, symbols + off, indexes + off,
+                       (long long)n, (long long)chunk(n, G), T, states, wptr, scratch, cap, res, G);
+    if (hipGetLastError() != hipSuccess) return -3;
+  }
+  hipLaunchKernelGGL(lanes_pack_kernel, dim3(G), dim3(kBlock), 0, ST, states, wptr, scratch, cap, G, base + P.o_out, res);
+  if (hipGetLastError() != hipSuccess) return -3;
+  EncResult h;
+  if (hipMemcpyAsync(&h, res, sizeof(h), hipMemcpyDeviceToHost, ST) != hipSuccess) return -3;
+  if (hipStreamSynchronize(ST) != hipSuccess) return -3;
+  if (h.flags & kEncBad) return -1;
+  if (h.flags & kEncOverflow) return -2;
+  *string_offset = P.o_out;
+  return h.nbytes;
+}
+
+void* icm_rans_lanes_decoder_gpu_create(const uint8_t* stream_bytes, int64_t nbytes, void* stream) {
+  if (!stream_bytes || nbytes < 8 || nbytes >= (1ll << 31)) return nullptr;
+  void* chk = icm_rans_lanes_decoder_create(stream_bytes, nbytes);   // header and length table, on the host
+  if (!chk) return nullptr;
+  icm_rans_lanes_decoder_destroy(chk);
+  GpuDecoder* D = new (std::nothrow) GpuDecoder();
+  if (!D) return nullptr;
+  try {
+    const int G = stream_bytes[6] | (stream_bytes[7] << 8);
+    D->G = G;
+    D->stream = ST;
+    D->o_ctl = 0;
+    D->o_states = align16((int64_t)sizeof(WaveCtl) * G);
+    D->o_status = D->o_states + align16(4ll * G * kLanes);
+    D->o_string = D->o_status + align16(4ll * G);
+    D->host.assign((size_t)(D->o_string + align16(nbytes)), 0);
+    WaveCtl* ctl = reinterpret_cast<WaveCtl*>(D->host.data());
+    int64_t pos = 8 + 4ll * G;
+    for (int g = 0; g < G; ++g) {
+      uint32_t len;
+      std::memcpy(&len, stream_bytes + 8 + 4 * g, 4);
+      ctl[g] = WaveCtl{(uint32_t)(D->o_string + pos + 4 * kLanes), (len - 4 * kLanes) / 2, 0u, 0u};
+      std::memcpy(D->host.data() + D->o_states + 4ll * g * kLanes, stream_bytes + pos, 4 * kLanes);
+      pos += len;
+    }
+    std::memcpy(D->host.data() + D->o_string, stream_bytes, (size_t)nbytes);
+    if (hipMalloc(reinterpret_cast<void**>(&D->dev), D->host.size()) == hipSuccess &&
+        hipMemcpyAsync(D->dev, D->host.data(), D->host.size(), hipMemcpyHostToDevice, ST) == hipSuccess)
+      return D;
+  } catch (const std::bad_alloc&) {
+  }
+  icm_rans_lanes_decoder_gpu_destroy(D);
+  return nullptr;
+}
+
+int icm_rans_lanes_decoder_gpu_decode_run(void* decoder, const int32_t* indexes, int64_t n, const int32_t* cdfs,
+                                          int cdf_stride, const int32_t* cdf_sizes, const int32_t* offsets, int ncdf,
+                                          int32_t* out, void* stream) {
+  Tab T;
+  if (!decoder || n < 0 || (n > 0 && (!indexes || !out)) || !make_tab(cdfs, cdf_stride, cdf_sizes, offsets, ncdf, T))
+    return ICM_ERR_ARG;
+  GpuDecoder& D = *static_cast<GpuDecoder*>(decoder);
+  if (n == 0) return ICM_OK;
+  const int wpb = waves_per_block();
+  const int blocks = (D.G + wpb - 1) / wpb;
+  WaveCtl* ctl = reinterpret_cast<WaveCtl*>(D.dev + D.o_ctl);
+  uint32_t* states = reinterpret_cast<uint32_t*>(D.dev + D.o_states);
+  // the kernel addresses the string from the allocation's base: WaveCtl.off includes o_string
+  if (g_search_centre)
+    hipLaunchKernelGGL(lanes_dec_run_kernel<true>, dim3(blocks), dim3(wpb * kLanes), 0, ST, D.dev, ctl, states, indexes,
+                       (long long)n, (long long)chunk(n, D.G), T, out, D.G);
+  else
+    hipLaunchKernelGGL(lanes_dec_run_kernel<false>, dim3(blocks), dim3(wpb * kLanes), 0, ST, D.dev, ctl, states, indexes,
+                       (long long)n, (long long)chunk(n, D.G), T, out, D.G);
+  ICM_CHECK_LAUNCH();
+  return ICM_OK;
+}
+
+int icm_rans_lanes_decoder_gpu_finish(void* decoder, void* stream) {
+  if (!decoder) return -1;
+  GpuDecoder& D = *static_cast<GpuDecoder*>(decoder);
+  uint32_t* status = reinterpret_cast<uint32_t*>(D.dev + D.o_status);
+  hipLaunchKernelGGL(lanes_dec_finish_kernel, dim3((D.G + kBlock - 1) / kBlock), dim3(kBlock), 0, ST,
+                     reinterpret_cast<const WaveCtl*>(D.dev + D.o_ctl),
+                     reinterpret_cast<const uint32_t*>(D.dev + D.o_states), status, D.G);
+  if (hipGetLastError() != hipSuccess) return -1;
+  std::vector<uint32_t> h((size_t)D.G);
+  if (hipMemcpyAsync(h.data(), status, 4 * (size_t)D.G, hipMemcpyDeviceToHost, ST) != hipSuccess) return -1;
+  if (hipStreamSynchronize(ST) != hipSuccess) return -1;
+  int st = 0;
+  for (uint32_t v : h) st |= (int)v;
+  return st;
+}
+
+void icm_rans_lanes_decoder_gpu_destroy(void* decoder) {
+  GpuDecoder* D = static_cast<GpuDecoder*>(decoder);
+  if (!D) return;
+  if (D->dev) {
+    (void)hipStreamSynchronize(D->stream);   // the upload of create reads D->host; the launches read D->dev
+    (void)hipFree(D->dev);
+  }
+  delete D;
+}
+
+}  // extern "C"

@@ -81,6 +81,11 @@ SYMBOLS = [
     "icm_zigzag_order", "icm_zigzag_splits", "icm_zigzag_reverse",
     "icm_pmf_to_quantized_cdf", "icm_rans_encode_with_indexes", "icm_rans_decode_with_indexes",
     "icm_rans_decoder_create", "icm_rans_decoder_decode", "icm_rans_decoder_destroy",
+    "icm_rans_lanes_waves", "icm_rans_lanes_encode", "icm_rans_lanes_decoder_create",
+    "icm_rans_lanes_decoder_decode_run", "icm_rans_lanes_decoder_finish", "icm_rans_lanes_decoder_destroy",
+    "icm_rans_lanes_encode_gpu_workspace", "icm_rans_lanes_encode_gpu", "icm_rans_lanes_decoder_gpu_create",
+    "icm_rans_lanes_decoder_gpu_decode_run", "icm_rans_lanes_decoder_gpu_finish", "icm_rans_lanes_decoder_gpu_destroy",
+    "icm_debug_lanes_search",
     "icm_eb_table_bounds", "icm_eb_pmf_table", "icm_gc_table_centers", "icm_gc_pmf_table", "icm_gc_build_indexes",
     "icm_quantize", "icm_dequantize", "icm_clamp", "icm_pad2d",
     "icm_msssim_workspace_floats", "icm_msssim_fwd", "icm_msssim_bwd",
@@ -182,6 +187,29 @@ def lib():
         L.icm_rans_decoder_decode.argtypes = [vp, i32p, i64, i32p, i32, i32p, i32p, i32, i32p]
         L.icm_rans_decoder_destroy.argtypes = [vp]
         L.icm_rans_decoder_destroy.restype = None
+        # lane streams: host definition, then the device side (tables / symbols / indexes are device pointers there)
+        i64p = C.POINTER(C.c_int64)
+        L.icm_rans_lanes_waves.argtypes = [i64p, i32, i64]
+        L.icm_rans_lanes_encode.argtypes = [i32p, i32p, i64p, i32, i32p, i32, i32p, i32p, i32, i64, vp, i64]
+        L.icm_rans_lanes_encode.restype = i64
+        L.icm_rans_lanes_decoder_create.argtypes = [vp, i64]
+        L.icm_rans_lanes_decoder_create.restype = vp
+        L.icm_rans_lanes_decoder_decode_run.argtypes = [vp, i32p, i64, i32p, i32, i32p, i32p, i32, i32p]
+        L.icm_rans_lanes_decoder_finish.argtypes = [vp]
+        L.icm_rans_lanes_decoder_destroy.argtypes = [vp]
+        L.icm_rans_lanes_decoder_destroy.restype = None
+        L.icm_rans_lanes_encode_gpu_workspace.argtypes = [i64p, i32, i64, i32]
+        L.icm_rans_lanes_encode_gpu_workspace.restype = i64
+        L.icm_rans_lanes_encode_gpu.argtypes = [vp, vp, i64p, i32, vp, i32, vp, vp, i32, i64, i32, vp, i64, i64p, vp]
+        L.icm_rans_lanes_encode_gpu.restype = i64
+        L.icm_rans_lanes_decoder_gpu_create.argtypes = [vp, i64, vp]
+        L.icm_rans_lanes_decoder_gpu_create.restype = vp
+        L.icm_rans_lanes_decoder_gpu_decode_run.argtypes = [vp, vp, i64, vp, i32, vp, vp, i32, vp, vp]
+        L.icm_rans_lanes_decoder_gpu_finish.argtypes = [vp, vp]
+        L.icm_rans_lanes_decoder_gpu_destroy.argtypes = [vp]
+        L.icm_rans_lanes_decoder_gpu_destroy.restype = None
+        L.icm_debug_lanes_search.argtypes = [i32]
+        L.icm_debug_lanes_search.restype = None
         L.icm_eb_table_bounds.argtypes = [vp, i32, vp, vp, vp]
         L.icm_eb_pmf_table.argtypes = [C.POINTER(EbParams), vp, i32, i32, vp, vp, vp]
         L.icm_gc_table_centers.argtypes = [vp, i32, f32, vp, vp]

@@ -3,7 +3,11 @@
 The reference imports these three classes from a binary-only pybind11 extension (``compressai/ans.cpython-38-*.so``,
 used at entropy_models/entropy_models.py:32-36,200-208,268-276 and models/cnn.py:5,228,263-264,300-318); the
 interface below keeps their call signatures -- Python lists (or anything ``numpy.asarray`` accepts) in, ``bytes`` /
-``list[int]`` out -- and hands flat int32 arrays to ``icm_rans_*``.  Host-side, like the reference's coder."""
+``list[int]`` out -- and hands flat int32 arrays to ``icm_rans_*``.  Host-side, like the reference's coder.
+
+Below them: the lane-stream coder (``coder="lanes"``, format in ``icm_amd.bitstream``; parity unpinned: no counterpart
+in the reference) -- ``lanes_encode`` / ``LanesDecoder`` on the host, the executable definition of the format, and
+``lanes_encode_gpu`` / ``LanesDecoderGpu`` over the kernels of csrc/rans_lanes.hip, which take device tensors."""
 from __future__ import annotations
 
 import ctypes as C
@@ -143,3 +147,187 @@ def pmf_to_quantized_cdf(pmf: Sequence[float], precision: int = 16) -> List[int]
     if rc:
         raise ValueError("pmf_to_quantized_cdf: invalid pmf (negative / non-finite / empty / all zero)")
     return out.tolist()
+
+
+# ---------------------------------------------------------------------------------------------------- lane streams
+CODERS = ("host", "lanes")
+SYMBOLS_PER_WAVE = 16384      # default of every ``symbols_per_wave`` keyword (why this value)
+_i64p = C.POINTER(C.c_int64)
+_LANES_STATUS = ((1, "a body ran out of words"), (2, "a value no table bin holds"), (4, "an escape outside int32"),
+                 (8, "a CDF index outside the tables"), (16, "a lane did not end at 2^16"),
+                 (32, "words of a body were left unread"))
+
+
+def check_coder(coder) -> str:
+    if coder not in CODERS:
+        raise ValueError(f"unknown coder {coder!r}; choose from {list(CODERS)}")
+    return coder
+
+
+def _lanes_status(st: int) -> None:
+    if st:
+        why = [text for bit, text in _LANES_STATUS if st & bit] or [f"runtime failure ({st})"]
+        raise ValueError("lane stream decode: corrupt stream or wrong indexes / CDF tables: " + "; ".join(why))
+
+
+def _runs(run_lengths, total: int):
+    runs = np.ascontiguousarray(np.asarray(run_lengths, dtype=np.int64).reshape(-1))
+    if (runs < 0).any() or int(runs.sum()) != total:
+        raise ValueError("run_lengths must be non-negative and add up to the number of symbols")
+    return runs
+
+
+def lanes_waves(run_lengths, symbols_per_wave: int = SYMBOLS_PER_WAVE) -> int:
+    """G of the lane stream that codes runs of these lengths"""
+    runs = np.ascontiguousarray(np.asarray(run_lengths, dtype=np.int64).reshape(-1))
+    g = L.lib().icm_rans_lanes_waves(runs.ctypes.data_as(_i64p), int(runs.size), int(symbols_per_wave))
+    if g < 1:
+        raise ValueError("lane stream: run lengths must be non-negative and symbols_per_wave at least 1")
+    return g
+
+
+def lanes_encode(symbols, indexes, run_lengths, t: _Tables, symbols_per_wave: int = SYMBOLS_PER_WAVE) -> bytes:
+    """host encoder: the runs back to back in ``symbols`` / ``indexes`` -> one lane stream"""
+    sym, idx = _arr(symbols), _arr(indexes)
+    if sym.shape != idx.shape:
+        raise ValueError("symbols and indexes must have the same length")
+    runs = _runs(run_lengths, int(sym.size))
+    lanes_waves(runs, symbols_per_wave)
+    args = (sym.ctypes.data_as(_i32p), idx.ctypes.data_as(_i32p), runs.ctypes.data_as(_i64p), int(runs.size), *t.args(),
+            int(symbols_per_wave))
+    need = L.lib().icm_rans_lanes_encode(*args, None, 0)
+    if need < 0:
+        raise ValueError("lane stream encode: invalid symbols / indexes / CDF tables")
+    buf = (C.c_uint8 * need)()
+    if L.lib().icm_rans_lanes_encode(*args, buf, need) != need:
+        raise ValueError("lane stream encode failed")
+    return bytes(buf)
+
+
+class LanesDecoder:
+    """host decoder of one lane stream: ``decode_run`` per run in stream order, then ``finish``"""
+
+    def __init__(self, stream: bytes):
+        self._keep = (C.c_uint8 * max(1, len(stream))).from_buffer_copy(bytes(stream) or b"\0")
+        self._h = L.lib().icm_rans_lanes_decoder_create(self._keep, len(stream))
+        if not self._h:
+            raise ValueError("lane stream decode: not a lane stream (magic, version, G or a length table that "
+                             "disagrees with the string's length)")
+
+    def close(self):
+        if self._h:
+            L.lib().icm_rans_lanes_decoder_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def decode_run(self, indexes, t: _Tables) -> np.ndarray:
+        idx = _arr(indexes)
+        out = np.empty(idx.size, dtype=np.int32)
+        rc = L.lib().icm_rans_lanes_decoder_decode_run(self._h, idx.ctypes.data_as(_i32p), int(idx.size), *t.args(),
+                                                       out.ctypes.data_as(_i32p))
+        if rc:
+            _lanes_status(L.lib().icm_rans_lanes_decoder_finish(self._h) or -1)
+        return out
+
+    def finish(self) -> None:
+        st = L.lib().icm_rans_lanes_decoder_finish(self._h)
+        self.close()
+        _lanes_status(st)
+
+
+def lanes_decode(stream: bytes, indexes, run_lengths, t: _Tables) -> np.ndarray:
+    """host decode of a whole stream whose indexes are known up front (tests, z strings)"""
+    idx = _arr(indexes)
+    runs = _runs(run_lengths, int(idx.size))
+    dec = LanesDecoder(stream)
+    out, pos = [], 0
+    for n in runs.tolist():
+        out.append(dec.decode_run(idx[pos:pos + n], t))
+        pos += n
+    dec.finish()
+    return np.concatenate(out) if out else np.empty(0, np.int32)
+
+
+def _dev_tables(cdf, sizes, offsets):
+    import torch
+    for b in (cdf, sizes, offsets):
+        if not (b.is_cuda and b.dtype == torch.int32 and b.is_contiguous()):
+            raise ValueError("lane stream: the CDF tables must be contiguous int32 device tensors")
+    if cdf.dim() != 2 or sizes.numel() != cdf.size(0) or offsets.numel() != cdf.size(0):
+        raise ValueError("cdfs, cdfs_sizes and offsets must describe the same number of tables")
+    return (cdf.data_ptr(), int(cdf.size(1)), sizes.data_ptr(), offsets.data_ptr(), int(cdf.size(0)))
+
+
+def lanes_encode_gpu(symbols, indexes, run_lengths, cdf, sizes, offsets,
+                     symbols_per_wave: int = SYMBOLS_PER_WAVE) -> bytes:
+    """device encoder: flat int32 device tensors (the runs back to back) and the device-resident tables -> the same
+    bytes as ``lanes_encode``.  Only the finished string crosses to the host."""
+    import torch
+    if symbols.shape != indexes.shape or symbols.dim() != 1:
+        raise ValueError("symbols and indexes must be flat tensors of the same length")
+    for b in (symbols, indexes):
+        if not (b.is_cuda and b.dtype == torch.int32 and b.is_contiguous()):
+            raise ValueError("lane stream: symbols and indexes must be contiguous int32 device tensors")
+    runs = _runs(run_lengths, int(symbols.numel()))
+    lanes_waves(runs, symbols_per_wave)
+    tabs = _dev_tables(cdf, sizes, offsets)
+    lib, rp = L.lib(), runs.ctypes.data_as(_i64p)
+    off = C.c_int64(0)
+    for worst in (0, 1):          # optimistic: one word per symbol; escape-heavy input: the worst case, once
+        nws = lib.icm_rans_lanes_encode_gpu_workspace(rp, int(runs.size), int(symbols_per_wave), worst)
+        if nws < 0:
+            raise ValueError("lane stream encode: the runs are too long for one stream")
+        ws = torch.empty(nws, dtype=torch.uint8, device=symbols.device)
+        nb = lib.icm_rans_lanes_encode_gpu(symbols.data_ptr(), indexes.data_ptr(), rp, int(runs.size), *tabs,
+                                           int(symbols_per_wave), worst, ws.data_ptr(), nws, C.byref(off), L.stream())
+        if nb != -2:
+            break
+    if nb == -1:
+        raise ValueError("lane stream encode: invalid symbols / indexes / CDF tables")
+    if nb < 0:
+        raise L.IcmError(f"lane stream encode failed (code {nb})")
+    return ws[off.value:off.value + nb].cpu().numpy().tobytes()
+
+
+class LanesDecoderGpu:
+    """device decoder of one lane stream.  ``decode_run`` is one launch on the current stream and returns a device
+    tensor; nothing is known to be valid until ``finish`` has looked at the status words."""
+
+    def __init__(self, stream: bytes):
+        self._keep = (C.c_uint8 * max(1, len(stream))).from_buffer_copy(bytes(stream) or b"\0")
+        self._h = L.lib().icm_rans_lanes_decoder_gpu_create(self._keep, len(stream), L.stream())
+        if not self._h:
+            raise ValueError("lane stream decode: not a lane stream (magic, version, G or a length table that "
+                             "disagrees with the string's length)")
+
+    def close(self):
+        if self._h:
+            L.lib().icm_rans_lanes_decoder_gpu_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def decode_run(self, indexes, cdf, sizes, offsets, out=None):
+        import torch
+        if not (indexes.is_cuda and indexes.dtype == torch.int32 and indexes.is_contiguous()):
+            raise ValueError("lane stream: indexes must be a contiguous int32 device tensor")
+        if out is None:
+            out = torch.empty(indexes.shape, dtype=torch.int32, device=indexes.device)
+        L.check(L.lib().icm_rans_lanes_decoder_gpu_decode_run(self._h, indexes.data_ptr(), int(indexes.numel()),
+                                                              *_dev_tables(cdf, sizes, offsets), out.data_ptr(),
+                                                              L.stream()), "lanes decode_run")
+        return out
+
+    def finish(self) -> None:
+        st = L.lib().icm_rans_lanes_decoder_gpu_finish(self._h, L.stream())
+        self.close()
+        _lanes_status(st)

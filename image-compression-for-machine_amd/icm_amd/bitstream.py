@@ -8,7 +8,10 @@ Layout -- fixed-width little-endian integers, no padding between fields:
     offset  size  field
          0     4  magic, the bytes ``ICMB``
          4     2  format version (u16), ``VERSION`` = 1
-         6     2  architecture id (u16), index into ``ARCHS`` = ("cnn", "stf")
+         6     2  low byte: architecture id, index into ``ARCHS`` = ("cnn", "stf"); high byte: coder id, index into
+                  ``CODERS`` = ("host", "lanes"): what kind of stream every string is (see "lane stream" below).
+                  Files of the host coder have a zero high byte, as before the field was split, and a reader from
+                  before refuses a lanes file as an unknown architecture id
          8     4  original image height (u32, >= 1)
         12     4  original image width (u32, >= 1)
         16     8  pad amounts left, right, top, bottom (4 x u16): what the encoder added around the image
@@ -44,6 +47,36 @@ refuses the other's files for their magic.
        end-4     4  CRC-32 of every byte before it
 
 rows / cols are redundant with the four numbers before them, and a reader refuses a file in which they disagree.
+The coder id lives in the tile streams alone: the high byte of the ICMT architecture field stays zero.
+
+Lane stream -- the string format of coder id 1, made to be coded by one GPU wave per body (csrc/rans_lanes.hip; the
+executable definition is ``icm_rans_lanes_encode`` / ``icm_rans_lanes_decoder_*`` of csrc/rans.cpp).  Parity unpinned:
+no counterpart in the reference.  A stream codes R runs; run r holds n_r (symbol, CDF index) pairs -- the y string
+one run per slice in slice order, each flat in (n, c, h, w) order, a z string one run -- with the tables, offsets and
+sizes of the host coder (16-bit precision, the last bin of a table is the escape bin).
+
+    offset  size  field
+         0     4  magic, the bytes ``ICML``
+         4     2  version (u16) = 1
+         6     2  G = number of waves (u16, 1..4096)
+         8   4 G  byte length of each wave body (u32); each >= 256 and even
+       ...   ...  the G bodies, back to back; nothing after them
+    body:  64 x u32  the decoder's initial state of lanes 0..63 (little-endian)
+           then u16 words in the order the decoder reads them
+
+G = clamp(ceil(max_r n_r / symbols_per_wave), 1, 4096), chosen by the encoder; the decoder takes it from the stream.
+With c_r = ceil(n_r / G) rounded up to a multiple of 64, wave g owns elements [g c_r, min(n_r, (g + 1) c_r)) of run r
+(possibly none) and in step t its lane l handles element g c_r + 64 t + l, idle when that lies past the end.  States
+and the word cursor carry over from run to run: a lane is flushed once per stream.  Per lane a 32-bit rANS state with
+16-bit words and L = 2^16: the encoder's put of (start, freq) out of 2^16 emits ``x & 0xFFFF`` and shifts x right by
+16 if x >= freq << 16, then sets x = ((x / freq) << 16) + x % freq + start; the decoder takes cum = x & 0xFFFF, finds
+s with cdf[s] <= cum < cdf[s + 1], sets x = freq (x >> 16) + cum - start and, if x < L, x = (x << 16) | next word.
+A step has four phases: the table symbol of every active lane, then -- for the lanes whose symbol fell in the escape
+bin only -- bits 0-15, 16-31 and 32-47 of the escape value (the host coder's zig-zag: -2 v - 1 below the table,
+2 (v - overflow) above it), each a put with freq = 1 and start = the 16 bits.  Within a phase the lanes that read a
+word take consecutive words in ascending lane order.  The encoder is the mirror: runs, steps and phases backwards
+from x = L, words written downwards.  A valid body leaves every decoder lane at exactly L with the cursor at its end;
+an escape whose symbol does not fit int32 is an error.  The format costs about 4 + 260 G bytes per string.
 """
 from __future__ import annotations
 
@@ -54,6 +87,7 @@ from typing import Dict, List, Sequence, Tuple
 MAGIC = b"ICMB"
 VERSION = 1
 ARCHS = ("cnn", "stf")
+CODERS = ("host", "lanes")                  # high byte of the architecture field
 
 _FIXED = struct.Struct("<4sHHII4H2HIH")     # magic .. number of strings
 _U32 = struct.Struct("<I")
@@ -75,9 +109,12 @@ def _uint(name: str, v, hi: int, lo: int = 0) -> int:
     return v
 
 
-def pack(header: Dict, strings: Sequence[bytes]) -> bytes:
+def pack(header: Dict, strings: Sequence[bytes], coder: str = "host") -> bytes:
     """``header``: {"arch": name in ARCHS, "height", "width", "pads": (left, right, top, bottom),
-    "shape": (z height, z width), "fingerprint": u32}; ``strings``: the flattened ``compress()["strings"]``."""
+    "shape": (z height, z width), "fingerprint": u32}; ``strings``: the flattened ``compress()["strings"]``;
+    ``coder``: the name in CODERS that made them."""
+    if coder not in CODERS:
+        raise ValueError(f"bitstream: unknown coder {coder!r}; the format knows {list(CODERS)}")
     missing = [k for k in HEADER_KEYS if k not in header]
     if missing:
         raise ValueError(f"bitstream: header lacks {missing}")
@@ -89,7 +126,7 @@ def pack(header: Dict, strings: Sequence[bytes]) -> bytes:
     strings = [bytes(s) for s in strings]
     n = _uint("number of strings", len(strings), U16_MAX)
     out = bytearray(_FIXED.pack(
-        MAGIC, VERSION, ARCHS.index(header["arch"]),
+        MAGIC, VERSION, ARCHS.index(header["arch"]) | CODERS.index(coder) << 8,
         _uint("height", header["height"], U32_MAX, 1), _uint("width", header["width"], U32_MAX, 1),
         *(_uint("pad", p, U16_MAX) for p in pads), *(_uint("shape", s, U16_MAX) for s in shape),
         _uint("fingerprint", header["fingerprint"], U32_MAX), n))
@@ -101,9 +138,31 @@ def pack(header: Dict, strings: Sequence[bytes]) -> bytes:
     return bytes(out)
 
 
+def _arch_field(field: int) -> Tuple[int, int]:
+    """(architecture id, coder id) of the u16 field, both known to this reader"""
+    arch_id, coder_id = field & 0xFF, field >> 8
+    if coder_id >= len(CODERS):
+        raise ValueError(f"bitstream: unknown coder id {coder_id} (this reader knows 0..{len(CODERS) - 1})")
+    if arch_id >= len(ARCHS):
+        raise ValueError(f"bitstream: unknown architecture id {arch_id} (this reader knows 0..{len(ARCHS) - 1})")
+    return arch_id, coder_id
+
+
+def coder_of(data: bytes) -> str:
+    """name of the coder that made the strings of an ICMB stream (``unpack`` does not report it: its header dict is
+    unchanged).  Looks at the magic, the version and the field alone; ValueError for anything else."""
+    data = bytes(data[:FIXED_BYTES]) if isinstance(data, (bytes, bytearray, memoryview)) else b""
+    if len(data) < 8 or data[:4] != MAGIC:
+        raise ValueError("bitstream: bad magic (not an ICMB stream)")
+    version, field = struct.unpack_from("<HH", data, 4)
+    if version != VERSION:
+        raise ValueError(f"bitstream: unknown format version {version} (this reader knows {VERSION})")
+    return CODERS[_arch_field(field)[1]]
+
+
 def unpack(data: bytes) -> Tuple[Dict, List[bytes]]:
-    """inverse of ``pack``: (header, strings).  ValueError for a bad magic, an unknown version or architecture id, a
-    declared length that runs past the data, trailing bytes or a CRC mismatch."""
+    """inverse of ``pack``: (header, strings).  ValueError for a bad magic, an unknown version, architecture or coder
+    id, a declared length that runs past the data, trailing bytes or a CRC mismatch.  The coder: ``coder_of``."""
     if not isinstance(data, (bytes, bytearray, memoryview)):
         raise ValueError(f"bitstream: expected bytes, got {type(data).__name__}")
     data = bytes(data)
@@ -114,8 +173,7 @@ def unpack(data: bytes) -> Tuple[Dict, List[bytes]]:
     (_, version, arch_id, height, width, pl, pr, pt, pb, zh, zw, fp, n) = _FIXED.unpack_from(data, 0)
     if version != VERSION:
         raise ValueError(f"bitstream: unknown format version {version} (this reader knows {VERSION})")
-    if arch_id >= len(ARCHS):
-        raise ValueError(f"bitstream: unknown architecture id {arch_id} (this reader knows 0..{len(ARCHS) - 1})")
+    arch_id, _ = _arch_field(arch_id)
     if height < 1 or width < 1:
         raise ValueError(f"bitstream: empty image {height}x{width}")
     pos = FIXED_BYTES + 4 * n

@@ -1,6 +1,6 @@
 """``python -m icm_amd.codec`` -- image file to bit-stream file and back, in two processes that share a checkpoint.
 
-    python -m icm_amd.codec encode IMAGE -o FILE -a cnn -p CKPT [--tile N [--overlap M]]
+    python -m icm_amd.codec encode IMAGE -o FILE -a cnn -p CKPT [--tile N [--overlap M]] [--coder {host,lanes}]
     python -m icm_amd.codec decode FILE -o IMAGE.png -p CKPT [--reference IMAGE] [--region Y0,X0,H,W]
 
 Parity unpinned: no counterpart in the reference (upstream CompressAI's ``examples/codec.py`` is not in its tree).  The
@@ -18,7 +18,11 @@ Large images are coded as a grid of independently coded tiles (``--tile``): the 
 set with 32-bit offsets, which bounds one ``compress()`` call near 11 megapixels, and activation memory grows with the
 image.  Each tile is a complete single-image stream of its crop, all of them wrapped in an ``ICMT`` container; the
 decoder adds the decoded tiles into an f32 canvas, their overlap bands weighted by a linear ramp
-(``icm_image_tile_blend``), and quantises the canvas once.  ``--region`` decodes only the tiles a region touches."""
+(``icm_image_tile_blend``), and quantises the canvas once.  ``--region`` decodes only the tiles a region touches.
+
+``--coder lanes`` codes the strings as lane streams on the device (csrc/rans_lanes.hip; format in
+``icm_amd.bitstream``) instead of the host's scalar stream, the default.  The stream records its coder, so ``decode``
+takes no flag."""
 from __future__ import annotations
 
 import argparse
@@ -35,6 +39,7 @@ import torch
 from . import _lib as L
 from . import bitstream as B
 from ._lib import check
+from .ans import SYMBOLS_PER_WAVE
 
 PAD_MULTIPLE = 64      # six stride-2 stages (utils.pad_to_multiple)
 
@@ -150,20 +155,26 @@ def image_tile_blend(x: torch.Tensor, pads: Tuple[int, int, int, int], canvas: t
           "image_tile_blend")
 
 
-def _encode_one(model, arch: str, fp: int, u8: torch.Tensor) -> bytes:
+def _encode_one(model, arch: str, fp: int, u8: torch.Tensor, coder: str = "host",
+                symbols_per_wave: Optional[int] = None) -> bytes:
     H, W = u8.size(0), u8.size(1)
     pads = center_pads(H, W)
-    enc = model.compress(image_u8_to_f32(u8, pads))
+    kw = {} if coder == "host" else {"coder": coder, "symbols_per_wave": symbols_per_wave or SYMBOLS_PER_WAVE}
+    enc = model.compress(image_u8_to_f32(u8, pads), **kw)
     header = {"arch": arch, "height": H, "width": W, "pads": pads, "shape": tuple(int(s) for s in enc["shape"]),
               "fingerprint": fp}
-    return B.pack(header, [s for part in enc["strings"] for s in part])
+    return B.pack(header, [s for part in enc["strings"] for s in part], coder=coder)
 
 
 @torch.no_grad()
-def encode_image(model, img, tile: Optional[int] = None, overlap: int = 0) -> bytes:
+def encode_image(model, img, tile: Optional[int] = None, overlap: int = 0, coder: str = "host",
+                 symbols_per_wave: Optional[int] = None) -> bytes:
     """8-bit [H, W, 3] image (tensor on any device, or anything ``numpy.asarray`` accepts) -> one bit-stream.  With
     ``tile``, an image of more than one tile (``plan_tiles``) becomes an ICMT stream whose tile k is
-    ``encode_image(model, crop k)``, the tiles coded one after another; an image of one tile is written untiled."""
+    ``encode_image(model, crop k)``, the tiles coded one after another; an image of one tile is written untiled.
+    ``coder`` / ``symbols_per_wave``: as ``model.compress``; every ICMB stream records its coder."""
+    if coder not in B.CODERS:
+        raise ValueError(f"codec: unknown coder {coder!r}; choose from {list(B.CODERS)}")
     arch = _ready(model)
     device = next(model.parameters()).device
     u8 = _as_u8_image(img, device)
@@ -176,8 +187,9 @@ def encode_image(model, img, tile: Optional[int] = None, overlap: int = 0) -> by
         plan = plan_tiles(H, W, tile, overlap)[2]
     fp = B.fingerprint(model)
     if len(plan) == 1:
-        return _encode_one(model, arch, fp, u8)
-    streams = [_encode_one(model, arch, fp, u8[y0:y0 + h, x0:x0 + w].contiguous()) for y0, x0, h, w in plan]
+        return _encode_one(model, arch, fp, u8, coder, symbols_per_wave)
+    streams = [_encode_one(model, arch, fp, u8[y0:y0 + h, x0:x0 + w].contiguous(), coder, symbols_per_wave)
+               for y0, x0, h, w in plan]
     return B.pack_tiled({"arch": arch, "height": H, "width": W, "tile": tile, "overlap": overlap, "fingerprint": fp},
                         streams)
 
@@ -195,9 +207,10 @@ def _check_strings(arch: str, strings, what: str = "this one") -> None:
         raise ValueError(f"codec: {arch} streams hold two strings, {what} holds {len(strings)}")
 
 
-def _decompress_one(model, arch: str, header: Dict, strings) -> torch.Tensor:
+def _decompress_one(model, arch: str, header: Dict, strings, coder: str = "host") -> torch.Tensor:
     H, W, pads = header["height"], header["width"], header["pads"]
-    x_hat = model.decompress([[strings[0]], [strings[1]]], header["shape"])["x_hat"]
+    kw = {} if coder == "host" else {"coder": coder}
+    x_hat = model.decompress([[strings[0]], [strings[1]]], header["shape"], **kw)["x_hat"]
     left, right, top, bottom = pads
     if tuple(x_hat.shape) != (1, 3, top + H + bottom, left + W + right):
         raise ValueError(f"codec: latent shape {header['shape']} decodes to {tuple(x_hat.shape)}, not to a padded "
@@ -237,6 +250,7 @@ def decode_image(model, data: bytes, reference=None, region=None) -> Tuple[torch
         H, W = outer["height"], outer["width"]
         rows, cols, plan = plan_tiles(H, W, outer["tile"], outer["overlap"])
         inner = [B.unpack(s) for s in streams]          # every header checked before any payload is decoded
+        coders = [B.coder_of(s) for s in streams]
         for k, ((y0, x0, h, w), (hd, tile_strings)) in enumerate(zip(plan, inner)):
             _check_model(hd, arch, fp, f"tile {k}")
             _check_strings(arch, tile_strings, f"tile {k}")
@@ -244,6 +258,7 @@ def decode_image(model, data: bytes, reference=None, region=None) -> Tuple[torch
                 raise ValueError(f"codec: tile {k} holds a {hd['height']}x{hd['width']} image, the plan has {h}x{w}")
     else:
         header, strings = B.unpack(data)
+        coder = B.coder_of(data)
         _check_model(header, arch, fp)
         H, W = header["height"], header["width"]
         _check_strings(arch, strings)
@@ -265,13 +280,13 @@ def decode_image(model, data: bytes, reference=None, region=None) -> Tuple[torch
         ramp = torch.from_numpy(blend_ramp(m)).to(device) if m else None
         for k in sel:                                    # plan order, one stream: a fixed order of additions per pixel
             hd, strings = inner[k]
-            x_hat = _decompress_one(model, arch, hd, strings)
+            x_hat = _decompress_one(model, arch, hd, strings, coders[k])
             image_tile_blend(x_hat, hd["pads"], canvas, plan[k][0] - by, plan[k][1] - bx, ramp,
                              tile_edges(k // cols, k % cols, rows, cols))
         x_hat, top, left = canvas[None], ry - by, rx - bx
         info.update(tile=outer["tile"], overlap=m, tiles=rows * cols, tiles_decoded=len(sel))
     else:
-        x_hat = _decompress_one(model, arch, header, strings)
+        x_hat = _decompress_one(model, arch, header, strings, coder)
         top, left = header["pads"][2] + ry, header["pads"][0] + rx
     if region is not None:
         info["region"] = [ry, rx, rh, rw]
@@ -320,6 +335,8 @@ def setup_args() -> argparse.ArgumentParser:
                      help="code the image as tiles of N x N pixels (a multiple of 64); one tile: the untiled stream")
     enc.add_argument("--overlap", default=0, type=int, metavar="M",
                      help="pixels neighbouring tiles share, blended by the decoder (needs --tile; at most N / 2)")
+    enc.add_argument("--coder", default="host", choices=list(B.CODERS),
+                     help="entropy coder of the strings: the host's scalar stream, or lane streams coded on the GPU")
     for s in (enc, dec):
         s.add_argument("-o", "--output", required=True, help="file to write")
         s.add_argument("-p", "--path", dest="paths", required=True, type=str, help="checkpoint path")
@@ -375,7 +392,7 @@ def main(argv) -> int:
         torch.cuda.synchronize()
         t0 = time.perf_counter()
         if args.command == "encode":
-            data = encode_image(model, payload, args.tile, args.overlap)
+            data = encode_image(model, payload, args.tile, args.overlap, coder=args.coder)
             torch.cuda.synchronize()
             dt = time.perf_counter() - t0
             h, w = payload.shape[:2]

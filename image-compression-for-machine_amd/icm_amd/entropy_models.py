@@ -2,7 +2,9 @@
 (entropy_models.py:66-666).  Likelihoods run on the fused HIP kernels; ``update()`` builds the quantised CDF tables
 from device-computed pmfs (``icm_eb_pmf_table`` / ``icm_gc_pmf_table`` + host ``icm_pmf_to_quantized_cdf``);
 ``compress()`` / ``decompress()`` quantise on the device (``icm_quantize`` / ``icm_gc_build_indexes`` /
-``icm_dequantize``) and code the symbols with the host rANS coder (``icm_amd.ans``), as the reference does."""
+``icm_dequantize``) and code the symbols with the host rANS coder (``icm_amd.ans``), as the reference does, or, with
+``coder="lanes"``, with the lane-stream kernels (csrc/rans_lanes.hip), which read the symbols, the indexes and the
+tables where they already lie: in device memory."""
 from __future__ import annotations
 
 import ctypes as C
@@ -159,7 +161,14 @@ class EntropyModel(nn.Module):
         return self._tab
 
     # ---- coding (entropy_models.py:200-290)
-    def compress(self, inputs, indexes, means=None, flag=1):
+    def _device_tables(self):
+        """the three table buffers as the lane-stream kernels read them: contiguous int32 on the device"""
+        return tuple(b.detach().to(torch.int32).contiguous()
+                     for b in (self._quantized_cdf, self._cdf_length, self._offset))
+
+    def compress(self, inputs, indexes, means=None, flag=1, coder="host", symbols_per_wave=None):
+        from .ans import SYMBOLS_PER_WAVE, check_coder, lanes_encode_gpu
+        check_coder(coder)
         symbols = self.quantize(inputs, "symbols", means)
         if len(inputs.size()) < 2:
             raise ValueError("Invalid `inputs` size. Expected a tensor with at least 2 dimensions.")
@@ -168,6 +177,13 @@ class EntropyModel(nn.Module):
         self._check_cdf_size()
         self._check_cdf_length()
         self._check_offsets_size()
+        if coder == "lanes":       # one single-run lane stream per image, coded where the symbols lie
+            tabs = self._device_tables()
+            idx = indexes.to(symbols.device, torch.int32)
+            spw = SYMBOLS_PER_WAVE if symbols_per_wave is None else symbols_per_wave
+            return [lanes_encode_gpu(symbols[i].reshape(-1).contiguous(), idx[i].reshape(-1).contiguous(),
+                                     [symbols[i].numel()], *tabs, symbols_per_wave=spw)
+                    for i in range(symbols.shape[0])]
         from .ans import _encode
         t = self._tables()
         sym = symbols.detach().cpu().numpy().astype(np.int32)
@@ -175,7 +191,9 @@ class EntropyModel(nn.Module):
         return [_encode(np.ascontiguousarray(sym[i].reshape(-1)), np.ascontiguousarray(idx[i].reshape(-1)), t)
                 for i in range(sym.shape[0])]
 
-    def decompress(self, strings, indexes, means=None, flag=1):
+    def decompress(self, strings, indexes, means=None, flag=1, coder="host"):
+        from .ans import LanesDecoderGpu, check_coder
+        check_coder(coder)
         if not isinstance(strings, (tuple, list)):
             raise ValueError("Invalid `strings` parameter type.")
         if not len(strings) == indexes.size(0):
@@ -192,6 +210,16 @@ class EntropyModel(nn.Module):
                 for i in range(2, len(indexes.size())):
                     if means.size(i) != 1:
                         raise ValueError("Invalid means parameters")
+        if coder == "lanes":
+            tabs = self._device_tables()
+            dev = self._quantized_cdf.device
+            idx = indexes.to(dev, torch.int32).contiguous()
+            sym = torch.empty(idx.shape, dtype=torch.int32, device=dev)
+            for i, sbytes in enumerate(strings):
+                dec = LanesDecoderGpu(sbytes)
+                dec.decode_run(idx[i], *tabs, out=sym[i])
+                dec.finish()
+            return self.dequantize(sym, means)
         from .ans import RansDecoder
         t = self._tables()
         idx = indexes.detach().cpu().numpy().astype(np.int32)
@@ -315,19 +343,19 @@ class EntropyBottleneck(EntropyModel):
     def _extend_ndims(tensor, n):
         return tensor.reshape(-1, *([1] * n)) if n > 0 else tensor.reshape(-1)
 
-    def compress(self, x):
+    def compress(self, x, coder="host", symbols_per_wave=None):
         indexes = self._build_indexes(x.size())
         spatial_dims = len(x.size()) - 2
         medians = self._extend_ndims(self._get_medians().detach(), spatial_dims)
         medians = medians.expand(x.size(0), *([-1] * (spatial_dims + 1)))
-        return super().compress(x, indexes, medians, 0)
+        return super().compress(x, indexes, medians, 0, coder=coder, symbols_per_wave=symbols_per_wave)
 
-    def decompress(self, strings, size):
+    def decompress(self, strings, size, coder="host"):
         output_size = (len(strings), self._quantized_cdf.size(0), *size)
         indexes = self._build_indexes(output_size)
         medians = self._extend_ndims(self._get_medians().detach(), len(size))
         medians = medians.expand(len(strings), *([-1] * (len(size) + 1)))
-        return super().decompress(strings, indexes, medians, 0)
+        return super().decompress(strings, indexes, medians, 0, coder=coder)
 
 
 class _EbAux(torch.autograd.Function):

@@ -318,6 +318,62 @@ int icm_rans_decoder_decode(void* decoder, const int32_t* indexes, int64_t n, co
                             const int32_t* cdf_sizes, const int32_t* offsets, int ncdf, int32_t* out);
 void icm_rans_decoder_destroy(void* decoder);
 
+/* ---- lane streams: the second, opt-in stream format (`coder="lanes"`), made for the GPU -------------------------
+ * Parity unpinned: no counterpart in the reference.  Layout and state machine: icm_amd/bitstream.py ("lane stream").
+ * A stream codes nruns runs of (symbol, CDF index) pairs with the tables of the host coder above; G = clamp(ceil(max
+ * run length / symbols_per_wave), 1, 4096) wave bodies of 64 interleaved 32-bit rANS states each, flushed once per
+ * stream.  The host functions are the executable definition of the format; the *_gpu functions (csrc/rans_lanes.hip)
+ * produce and consume the same bytes from device memory, one wave per body. */
+#define ICM_LANES_ST_OVERRUN 1   /* a word was wanted past the end of a body */
+#define ICM_LANES_ST_SYMBOL 2    /* no table bin holds the decoded cumulative value */
+#define ICM_LANES_ST_ESCAPE 4    /* an escape decodes to a symbol outside int32 */
+#define ICM_LANES_ST_INDEX 8     /* a CDF index outside [0, ncdf), or a table size outside [2, cdf_stride] */
+#define ICM_LANES_ST_STATE 16    /* finish: a lane did not end at 2^16 */
+#define ICM_LANES_ST_CURSOR 32   /* finish: words of a body were left unread */
+/* G of a stream of these runs; -1 on bad arguments (negative length, symbols_per_wave < 1) */
+int icm_rans_lanes_waves(const int64_t* run_lengths, int nruns, int64_t symbols_per_wave);
+/* symbols / indexes: the runs back to back.  Returns the stream length in bytes, -1 on bad arguments / capacity;
+ * out = NULL only measures. */
+int64_t icm_rans_lanes_encode(const int32_t* symbols, const int32_t* indexes, const int64_t* run_lengths, int nruns,
+                              const int32_t* cdfs, int cdf_stride, const int32_t* cdf_sizes, const int32_t* offsets,
+                              int ncdf, int64_t symbols_per_wave, uint8_t* out, int64_t out_capacity);
+/* create: NULL unless the header and the length table describe exactly nbytes.  decode_run: the next run, in stream
+ * order; always writes n symbols (0 where a lane failed) and reads no byte outside the stream; ICM_ERR_ARG once any
+ * status bit is set.  finish: the ICM_LANES_ST_* bits of the whole stream, 0 = every body ended at its last word
+ * with every lane at 2^16. */
+void* icm_rans_lanes_decoder_create(const uint8_t* stream, int64_t nbytes);
+int icm_rans_lanes_decoder_decode_run(void* decoder, const int32_t* indexes, int64_t n, const int32_t* cdfs,
+                                      int cdf_stride, const int32_t* cdf_sizes, const int32_t* offsets, int ncdf,
+                                      int32_t* out);
+int icm_rans_lanes_decoder_finish(void* decoder);
+void icm_rans_lanes_decoder_destroy(void* decoder);
+
+/* Device side.  symbols / indexes / tables / ws are DEVICE memory, run_lengths is host memory.
+ * encode: ws = icm_rans_lanes_encode_gpu_workspace(...) bytes, 16-byte aligned.  worst_case = 0 gives every wave one
+ * word per symbol (enough for any input without escapes), 1 the four words per symbol no input exceeds.  Launches on
+ * `stream`, waits for it, and returns the stream length: the string then lies at ws + *string_offset.  -1: bad
+ * arguments, or an index / table the coder cannot use (the host coder's refusals); -2: worst_case = 0 was too small,
+ * call again with 1; -3: a launch or copy failed. */
+int64_t icm_rans_lanes_encode_gpu_workspace(const int64_t* run_lengths, int nruns, int64_t symbols_per_wave,
+                                            int worst_case);
+int64_t icm_rans_lanes_encode_gpu(const int32_t* symbols, const int32_t* indexes, const int64_t* run_lengths, int nruns,
+                                  const int32_t* cdfs, int cdf_stride, const int32_t* cdf_sizes, const int32_t* offsets,
+                                  int ncdf, int64_t symbols_per_wave, int worst_case, void* ws, int64_t ws_bytes,
+                                  int64_t* string_offset, void* stream);
+/* create: stream = HOST bytes; validates header and length table before anything touches the device, then uploads
+ * the string with the per-wave state, cursor and status (one allocation, one copy).  decode_run: one launch on
+ * `stream`, no host sync; indexes / out / tables are device memory.  finish: one small launch, one copy of G status
+ * words and a wait on `stream`; returns the ICM_LANES_ST_* bits, or -1 if the runtime failed. */
+void* icm_rans_lanes_decoder_gpu_create(const uint8_t* stream_bytes, int64_t nbytes, void* stream);
+int icm_rans_lanes_decoder_gpu_decode_run(void* decoder, const int32_t* indexes, int64_t n, const int32_t* cdfs,
+                                          int cdf_stride, const int32_t* cdf_sizes, const int32_t* offsets, int ncdf,
+                                          int32_t* out, void* stream);
+int icm_rans_lanes_decoder_gpu_finish(void* decoder, void* stream);
+void icm_rans_lanes_decoder_gpu_destroy(void* decoder);
+/* CDF search of the decode kernel: 1 probes outward from the table's centre bin, 0 = plain binary search; the
+ * default is the form DESIGN.md 5 measured faster */
+void icm_debug_lanes_search(int centre);
+
 /* device side of update() / compress() / decompress() (stream-ordered like every other kernel entry point) */
 /* EntropyBottleneck.update (entropy_models.py:354-393): minima / maxima [C] int32, then pmf [C][max_length] and
  * tail_mass [C] on the integer grid median - minima + k */

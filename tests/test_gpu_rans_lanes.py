@@ -1,0 +1,257 @@
+"""GPU: the lane-stream kernels (csrc/rans_lanes.hip) against the host implementation of the format, which
+tests/test_rans_lanes.py holds to the restatement -- same cases, byte for byte; then ``coder="lanes"`` through the
+models (icm_amd/models.py, entropy_models.py), the container and ``icm_amd.codec``.  Every comparison is exact.
+
+Weights: the formula state-dicts of oracle/weights.py, as the other codec tests build theirs."""
+import json
+import os
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+import torch
+from PIL import Image
+
+import _lanes_cases as K
+from oracle import weights as W
+
+pytestmark = pytest.mark.gpu
+DEV = "cuda:0"
+PKG = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "image-compression-for-machine_amd")
+
+
+def _t(a):
+    return torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
+
+
+@pytest.fixture(scope="module")
+def tabs():
+    from icm_amd.ans import _Tables
+    return _Tables(*K.tables_np())
+
+
+@pytest.fixture(scope="module")
+def dtabs():
+    return tuple(_t(a) for a in K.tables_np())
+
+
+def _gpu_decode(stream, idx, runs, dtabs):
+    """one decode_run per run on one decoder, state carried on the device; finish() raises for a bad stream"""
+    from icm_amd import ans
+    dec = ans.LanesDecoderGpu(stream)
+    d_idx, out, pos = _t(idx), [], 0
+    for n in runs:
+        out.append(dec.decode_run(d_idx[pos:pos + n], *dtabs))
+        pos += n
+    dec.finish()
+    return torch.cat(out).cpu().numpy()
+
+
+@pytest.mark.parametrize("name", list(K.cases()))
+def test_kernel_encode_is_byte_identical_to_the_host(name, tabs, dtabs):
+    from icm_amd import ans
+    sym, idx, runs, spw, _ = K.cases()[name]
+    assert ans.lanes_encode_gpu(_t(sym), _t(idx), runs, *dtabs, symbols_per_wave=spw) == \
+        ans.lanes_encode(sym, idx, runs, tabs, spw)
+
+
+@pytest.mark.parametrize("name", list(K.cases()))
+def test_kernel_decodes_host_streams_run_by_run(name, tabs, dtabs):
+    from icm_amd import ans
+    sym, idx, runs, spw, _ = K.cases()[name]
+    assert np.array_equal(_gpu_decode(ans.lanes_encode(sym, idx, runs, tabs, spw), idx, runs, dtabs), sym)
+
+
+@pytest.mark.parametrize("centre", [0, 1])
+def test_both_table_searches_decode_the_same(centre, tabs, dtabs):
+    from icm_amd import _lib as L
+    from icm_amd import ans
+    sym, idx, runs, spw, _ = K.cases()["n5000_g3"]
+    L.lib().icm_debug_lanes_search(centre)
+    try:
+        assert np.array_equal(_gpu_decode(ans.lanes_encode(sym, idx, runs, tabs, spw), idx, runs, dtabs), sym)
+    finally:
+        L.lib().icm_debug_lanes_search(0)      # the default
+
+
+def test_escape_heavy_input_takes_the_worst_case_retry(tabs, dtabs):
+    """every symbol an escape: four words each, more than the optimistic one word per symbol"""
+    from icm_amd import ans
+    n = 300
+    idx = (np.arange(n) % 4).astype(np.int32)
+    sym = np.where(np.arange(n) % 2, 10 ** 6 + np.arange(n), -10 ** 6 - np.arange(n)).astype(np.int32)
+    want = ans.lanes_encode(sym, idx, [n], tabs, 128)
+    assert len(want) > 8 + 4 * 3 + 3 * 256 + 2 * 3 * 128      # more words than three waves' optimistic scratch
+    assert ans.lanes_encode_gpu(_t(sym), _t(idx), [n], *dtabs, symbols_per_wave=128) == want
+    assert np.array_equal(_gpu_decode(want, idx, [n], dtabs), sym)
+
+
+def test_kernel_refusals(dtabs):
+    from icm_amd import ans
+    one = torch.zeros(4, dtype=torch.int32, device=DEV)
+    with pytest.raises(ValueError):
+        ans.lanes_encode_gpu(one, torch.full_like(one, 4), [4], *dtabs)          # CDF index past the tables
+    with pytest.raises(ValueError):
+        ans.lanes_encode_gpu(torch.full_like(one, K.OFFSETS[3]), torch.full_like(one, 3), [4], *dtabs)   # zero width
+    with pytest.raises(ValueError):
+        ans.lanes_encode_gpu(one, one, [3], *dtabs)
+    with pytest.raises(ValueError):
+        ans.lanes_encode_gpu(one.cpu(), one.cpu(), [4], *dtabs)
+
+
+def test_finish_reports_every_corrupt_stream_of_the_cpu_list(dtabs):
+    """the corrupt streams tests/test_rans_lanes.py runs through the host decoder: where the restatement fails, create or
+    finish raises; elsewhere the kernel decodes what the restatement decodes"""
+    bad = 0
+    for label, name, data, want in K.corruptions():
+        _, idx, runs, _, _ = K.cases()[name]
+        if want is None:
+            bad += 1
+            with pytest.raises(ValueError):
+                _gpu_decode(data, idx, runs, dtabs)
+        else:
+            assert _gpu_decode(data, idx, runs, dtabs).tolist() == want, label
+    assert bad >= 150
+
+
+def test_wrong_indexes_are_reported_by_finish(tabs, dtabs):
+    from icm_amd import ans
+    sym, idx, runs, spw, _ = K.cases()["n65_g1"]
+    wrong = idx.copy()
+    wrong[7], wrong[40] = 99, -1
+    with pytest.raises(ValueError, match="CDF index"):
+        _gpu_decode(ans.lanes_encode(sym, idx, runs, tabs, spw), wrong, runs, dtabs)
+
+
+# ------------------------------------------------------------------------------------------------------ model level
+def _build(arch, salt=0):
+    from icm_amd.zoo import models
+    m = models[arch]()
+    m.load_state_dict(W.make_wacnn_state_dict(salt=salt) if arch == "cnn" else W.make_stf_state_dict())
+    m = m.to(DEV).eval()
+    m.update(force=True)
+    return m
+
+
+@pytest.fixture(scope="module")
+def nets():
+    return {arch: _build(arch) for arch in ("cnn", "stf")}
+
+
+@pytest.fixture(scope="module")
+def second_nets():
+    """second instances of the same checkpoints: decoders that share nothing with the encoder but the weights"""
+    return {arch: _build(arch) for arch in ("cnn", "stf")}
+
+
+@pytest.fixture(scope="module")
+def stf6():
+    from icm_amd.zoo import models
+    return models["stf6"]().eval()
+
+
+def _image_f32(h, w, seed):
+    return torch.from_numpy(np.random.default_rng(seed).random((1, 3, h, w), dtype=np.float32)).to(DEV)
+
+
+@pytest.mark.parametrize("arch", ["cnn", "stf"])
+@pytest.mark.parametrize("hw,spw", [((64, 64), 16384), ((128, 192), 1024)])
+def test_model_round_trip_matches_the_host_coder(nets, second_nets, arch, hw, spw):
+    """(128, 192) at 1024 symbols per wave: slices of 3 072 symbols in G = 3 bodies"""
+    from icm_amd import ans
+    net = nets[arch]
+    x = _image_f32(*hw, seed=5)
+    dbg_h, dbg_l = {}, {}
+    host = net.compress(x, _debug=dbg_h)
+    lanes = net.compress(x, _debug=dbg_l, coder="lanes", symbols_per_wave=spw)
+    assert np.array_equal(dbg_h["symbols"], dbg_l["symbols"]) and np.array_equal(dbg_h["indexes"], dbg_l["indexes"])
+    assert tuple(lanes["shape"]) == tuple(host["shape"]) and [len(p) for p in lanes["strings"]] == [1, 1]
+    y_string = lanes["strings"][0][0]
+    runs = [dbg_l["symbols"].size // net.num_slices] * net.num_slices
+    assert y_string[:4] == b"ICML" and y_string == ans.lanes_encode(
+        dbg_l["symbols"], dbg_l["indexes"], runs, net.gaussian_conditional._tables(), spw)
+    assert int.from_bytes(y_string[6:8], "little") == ans.lanes_waves(runs, spw) == (1 if spw == 16384 else 3)
+    want = net.decompress(host["strings"], host["shape"])["x_hat"]
+    got = net.decompress(lanes["strings"], lanes["shape"], coder="lanes")["x_hat"]
+    assert torch.equal(got, want)
+    assert torch.equal(second_nets[arch].decompress(lanes["strings"], lanes["shape"], coder="lanes")["x_hat"], want)
+
+
+def test_model_refusals(nets, stf6):
+    net = nets["cnn"]
+    x = _image_f32(64, 64, seed=6)
+    with pytest.raises(ValueError, match="unknown coder"):
+        net.compress(x, coder="gpu")
+    enc = net.compress(x, coder="lanes")
+    with pytest.raises(ValueError, match="unknown coder"):
+        net.decompress(enc["strings"], enc["shape"], coder="gpu")
+    with pytest.raises(ValueError):          # a lane stream is no host stream and the other way round
+        net.decompress(net.compress(x)["strings"], enc["shape"], coder="lanes")
+    bad = bytearray(enc["strings"][0][0])
+    assert bad[6:8] == b"\x01\x00"
+    bad[8 + 4 + 2] ^= 1          # bit 16 of lane 0's initial state: every later state of the lane is off
+    with pytest.raises(ValueError, match="lane stream decode"):
+        net.decompress([[bytes(bad)], enc["strings"][1]], enc["shape"], coder="lanes")
+    with pytest.raises(NotImplementedError):
+        stf6.compress(x, coder="lanes")
+
+
+# ------------------------------------------------------------------------------------------------------ codec level
+def _synthetic(h, w, seed):
+    rng = np.random.default_rng(seed)
+    yy, xx = np.mgrid[0:h, 0:w]
+    base = np.stack([(yy * 3 + xx * 2 + 40 * c) % 256 for c in range(3)], -1)
+    return np.clip(base + rng.integers(-12, 13, size=(h, w, 3)), 0, 255).astype(np.uint8)
+
+
+def test_codec_lanes_round_trip_untiled_tiled_and_region(nets, stf6):
+    from icm_amd import bitstream as B
+    from icm_amd import codec
+    net = nets["cnn"]
+    a = _synthetic(128, 192, seed=31)
+    host = codec.encode_image(net, a)
+    lanes = codec.encode_image(net, a, coder="lanes")
+    assert B.coder_of(host) == "host" and B.coder_of(lanes) == "lanes" and B.unpack(lanes)[0] == B.unpack(host)[0]
+    want, info_h = codec.decode_image(net, host, reference=a)
+    got, info = codec.decode_image(net, lanes, reference=a)
+    assert torch.equal(got, want) and info["psnr"] == info_h["psnr"] and info["bytes"] == len(lanes)
+    # tiles of 64 overlapping by 16: 3 x 4 tiles, every one a lanes ICMB stream inside the unchanged ICMT container
+    t_host = codec.encode_image(net, a, tile=64, overlap=16)
+    t_lanes = codec.encode_image(net, a, tile=64, overlap=16, coder="lanes", symbols_per_wave=256)
+    outer, streams = B.unpack_tiled(t_lanes)
+    assert outer == B.unpack_tiled(t_host)[0] and len(streams) == 12
+    assert all(B.coder_of(s) == "lanes" for s in streams)
+    want = codec.decode_image(net, t_host)[0]
+    assert torch.equal(codec.decode_image(net, t_lanes)[0], want)
+    crop, info = codec.decode_image(net, t_lanes, region=(40, 50, 30, 70))
+    assert torch.equal(crop, want[40:70, 50:120]) and info["tiles_decoded"] == 6
+    with pytest.raises(ValueError, match="unknown coder"):
+        codec.encode_image(net, a, coder="gpu")
+    with pytest.raises(ValueError, match="no bit-stream codec"):
+        codec.encode_image(stf6, a, coder="lanes")
+
+
+def test_cli_encode_and_decode_with_lanes_in_one_child_process(nets, tmp_path):
+    from icm_amd import bitstream as B
+    from icm_amd import codec
+    a = _synthetic(100, 120, seed=32)
+    src, ckpt = str(tmp_path / "in.png"), str(tmp_path / "cnn.pt")
+    stream, out = str(tmp_path / "in.icmb"), str(tmp_path / "out.png")
+    Image.fromarray(a).save(src)
+    torch.save(W.make_wacnn_state_dict(), ckpt)
+    code = ("import sys; from icm_amd import codec; "
+            f"rc = codec.main(['encode', {src!r}, '-o', {stream!r}, '-p', {ckpt!r}, '--coder', 'lanes']); "
+            f"sys.exit(rc or codec.main(['decode', {stream!r}, '-o', {out!r}, '-p', {ckpt!r}, '--reference', {src!r}]))")
+    env = {**os.environ, "PYTHONPATH": os.pathsep.join([PKG] + [p for p in [os.environ.get("PYTHONPATH")] if p])}
+    r = subprocess.run([sys.executable, "-c", code], env=env, capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stderr[-2000:]
+    enc_rep, dec_rep = [json.loads(line) for line in r.stdout.strip().splitlines()[-2:]]
+    data = open(stream, "rb").read()
+    assert B.coder_of(data) == "lanes" and enc_rep["bytes"] == dec_rep["bytes"] == len(data)
+    assert data == codec.encode_image(nets["cnn"], a, coder="lanes")
+    want, info = codec.decode_image(nets["cnn"], codec.encode_image(nets["cnn"], a), reference=a)
+    assert np.array_equal(np.asarray(Image.open(out)), want.numpy()) and dec_rep["psnr"] == info["psnr"]
+    with pytest.raises(SystemExit) as e:      # an unknown coder name is an argument error of the CLI
+        codec.main(["encode", src, "-o", stream + "2", "-p", ckpt, "--coder", "gpu"])
+    assert e.value.code == 2 and not os.path.exists(stream + "2")

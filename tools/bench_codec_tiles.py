@@ -12,9 +12,14 @@
 The model is a randomly initialised ``cnn`` (seeded), so file sizes and PSNR say nothing about a trained codec; they
 are there for the tiled / untiled difference.  Prints one JSON line per part.
 
-    python tools/bench_codec_tiles.py [--iters 200] [--rounds 3] [--kernel-only]
+    python tools/bench_codec_tiles.py [--iters 200] [--rounds 3] [--kernel-only] [--coder {host,lanes}]
+                                      [--symbols-per-wave N] [--coder-kernels]
 
 --kernel-only runs the kernel part alone (the run to put under rocprofv3 --kernel-trace --stats).
+--coder picks the entropy coder of the two codec parts (every result line names it); --coder-kernels replaces them by
+    lanes_kernels   the lane-stream kernels alone on the symbols of the 2048x3072 image: HIP-event time and symbols/s
+             of the whole-string encode (its launches, the 16-byte result copy and the wait) and of one decode_run
+             (slice 0 of the y string), with both table searches of the decode kernel.
 """
 import argparse
 import json
@@ -77,11 +82,93 @@ def kernel_part(args, torch, codec, L):
                               "(50 MB) fit the 256 MiB last-level cache, so this is no pure HBM figure"}), flush=True)
 
 
+def lanes_kernel_part(args, torch, np, codec, L):
+    from icm_amd import ans
+    from icm_amd.zoo import models
+    torch.manual_seed(0)
+    model = models["cnn"]().to("cuda:0").eval()
+    model.update(force=True)
+    h, w = 2048, 3072
+    x = codec.image_u8_to_f32(torch.from_numpy(synthetic(np, h, w, seed=1)).to("cuda:0"), (0, 0, 0, 0))
+    dbg = {}
+    model.compress(x, _debug=dbg, coder="lanes", symbols_per_wave=args.symbols_per_wave)
+    gc = model.gaussian_conditional
+    tabs = gc._device_tables()
+    sym, idx = torch.from_numpy(dbg["symbols"]).to("cuda:0"), torch.from_numpy(dbg["indexes"]).to("cuda:0")
+    n = sym.numel() // model.num_slices
+    runs = [n] * model.num_slices
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+
+    def events(fn, iters):
+        ts = []
+        for _ in range(iters):
+            torch.cuda.synchronize()
+            e0.record()
+            fn()
+            e1.record()
+            torch.cuda.synchronize()
+            ts.append(e0.elapsed_time(e1))
+        return statistics.median(ts)
+
+    string = ans.lanes_encode_gpu(sym, idx, runs, *tabs, symbols_per_wave=args.symbols_per_wave)
+    host_s = wall(lambda: ans.lanes_encode(dbg["symbols"], dbg["indexes"], runs, gc._tables(), args.symbols_per_wave), torch)
+    assert host_s[1] == string
+    res = {"metric": "lanes_kernels", "height": h, "width": w, "symbols": int(sym.numel()), "slice_symbols": n,
+           "symbols_per_wave": args.symbols_per_wave, "waves": ans.lanes_waves(runs, args.symbols_per_wave),
+           "y_string_bytes": len(string), "host_lanes_encode_s": round(host_s[0], 4)}
+    ms = events(lambda: ans.lanes_encode_gpu(sym, idx, runs, *tabs, symbols_per_wave=args.symbols_per_wave), 10)
+    res.update(encode_ms=round(ms, 3), encode_Msym_per_s=round(sym.numel() / ms / 1e3, 1),
+               encode_note="workspace allocation, init + 10 run launches + pack, result copy and wait, string D2H")
+    out = torch.empty(n, dtype=torch.int32, device="cuda:0")
+    for centre in (1, 0):
+        L.lib().icm_debug_lanes_search(centre)
+        ts = []
+        for _ in range(7):
+            dec = ans.LanesDecoderGpu(string)
+            ts.append(events(lambda: dec.decode_run(idx[:n], *tabs, out=out), 1))
+            dec.close()
+            assert torch.equal(out, sym[:n])
+        ms = statistics.median(ts)
+        key = "centre" if centre else "binary"
+        res.update({f"decode_run_{key}_ms": round(ms, 3), f"decode_run_{key}_Msym_per_s": round(n / ms / 1e3, 1)})
+    print(json.dumps(res), flush=True)
+
+    # the random model puts nearly every symbol in the centre bin of the narrowest tables (the y string above holds no
+    # word at all), which exercises neither the search nor the renormalisation reads.  A slice of the same size drawn
+    # the way a trained model's latents are distributed: table index uniform over the scale table, symbol =
+    # round(N(0, scale[index])), so the wide tables (up to ~3 100 bins) and several bits per symbol take part.
+    g = torch.Generator(device="cuda:0").manual_seed(1)
+    sidx = torch.randint(0, gc.scale_table.numel(), (n,), generator=g, device="cuda:0", dtype=torch.int32)
+    scale = gc.scale_table.to("cuda:0", torch.float32)[sidx.long()]
+    ssym = torch.round(torch.randn(n, generator=g, device="cuda:0") * scale).to(torch.int32)
+    sstring = ans.lanes_encode_gpu(ssym, sidx, [n], *tabs, symbols_per_wave=args.symbols_per_wave)
+    res = {"metric": "lanes_kernels_synthetic", "slice_symbols": n, "symbols_per_wave": args.symbols_per_wave,
+           "waves": ans.lanes_waves([n], args.symbols_per_wave), "string_bytes": len(sstring),
+           "bits_per_symbol": round(8.0 * len(sstring) / n, 3)}
+    ms = events(lambda: ans.lanes_encode_gpu(ssym, sidx, [n], *tabs, symbols_per_wave=args.symbols_per_wave), 10)
+    res.update(encode_ms=round(ms, 3), encode_Msym_per_s=round(n / ms / 1e3, 1))
+    for centre in (1, 0):
+        L.lib().icm_debug_lanes_search(centre)
+        ts = []
+        for _ in range(7):
+            dec = ans.LanesDecoderGpu(sstring)
+            ts.append(events(lambda: dec.decode_run(sidx, *tabs, out=out), 1))
+            dec.finish()
+            assert torch.equal(out, ssym)
+        ms = statistics.median(ts)
+        key = "centre" if centre else "binary"
+        res.update({f"decode_run_{key}_ms": round(ms, 3), f"decode_run_{key}_Msym_per_s": round(n / ms / 1e3, 1)})
+    print(json.dumps(res), flush=True)
+
+
 def codec_parts(args, torch, np, codec):
     from icm_amd.zoo import models
     torch.manual_seed(0)
     model = models["cnn"]().to("cuda:0").eval()
     model.update(force=True)
+    if args.coder != "host":      # the host rows stay the calls they were
+        enc0 = codec.encode_image
+        codec.encode_image = lambda m, a, **kw: enc0(m, a, coder=args.coder, symbols_per_wave=args.symbols_per_wave, **kw)
 
     def timed(fn):
         ts, r = [], None
@@ -92,7 +179,7 @@ def codec_parts(args, torch, np, codec):
 
     h, w = 2048, 3072
     a = synthetic(np, h, w, seed=1)
-    res = {"metric": "codec_tiled_vs_untiled", "height": h, "width": w, "tile": TILE, "overlap": OVERLAP,
+    res = {"metric": "codec_tiled_vs_untiled", "coder": args.coder, "height": h, "width": w, "tile": TILE, "overlap": OVERLAP,
            "model": "cnn, randomly initialised (seed 0)", "rounds": args.rounds}
     for name, kw in (("untiled", {}), ("tiled", {"tile": TILE, "overlap": OVERLAP})):
         codec.encode_image(model, a, **kw)                                  # warm every shape up
@@ -107,7 +194,7 @@ def codec_parts(args, torch, np, codec):
 
     h, w = 3008, 4032
     a = synthetic(np, h, w, seed=2)
-    res = {"metric": "codec_tiled_over_limit", "height": h, "width": w, "tile": TILE, "overlap": OVERLAP,
+    res = {"metric": "codec_tiled_over_limit", "coder": args.coder, "height": h, "width": w, "tile": TILE, "overlap": OVERLAP,
            "model": "cnn, randomly initialised (seed 0)", "rounds": args.rounds}
     codec.encode_image(model, a, tile=TILE, overlap=OVERLAP)
     t_enc, data = timed(lambda: codec.encode_image(model, a, tile=TILE, overlap=OVERLAP))
@@ -126,6 +213,9 @@ def main():
     ap.add_argument("--iters", type=int, default=200)
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--kernel-only", action="store_true")
+    ap.add_argument("--coder", default="host", choices=["host", "lanes"])
+    ap.add_argument("--symbols-per-wave", type=int, default=16384)
+    ap.add_argument("--coder-kernels", action="store_true")
     args = ap.parse_args()
     import numpy as np
     import torch
@@ -133,6 +223,9 @@ def main():
         sys.exit("bench_codec_tiles: no GPU (there is no CPU fallback)")
     from icm_amd import _lib as L
     from icm_amd import codec
+    if args.coder_kernels:
+        lanes_kernel_part(args, torch, np, codec, L)
+        return
     kernel_part(args, torch, codec, L)
     if not args.kernel_only:
         codec_parts(args, torch, np, codec)
