@@ -9,7 +9,7 @@ objs=""
 pids=""
 for f in conv_igemm conv_1x1 conv_ks8 conv_wino conv_wgrad wgrad_wino pointwise entropy msssim imageio rans_lanes winattn winattn_mfma; do
   stale=0
-  for dep in csrc/$f.hip csrc/icm_common.h ../include/icm_hip.h $(for h in conv_common.h winattn_common.h; do grep -q $h csrc/$f.hip && echo csrc/$h; done); do
+  for dep in csrc/$f.hip csrc/icm_common.h ../include/icm_hip.h $(for h in conv_common.h winattn_common.h rans_lanes_common.h; do grep -q $h csrc/$f.hip && echo csrc/$h; done); do
     if [ ! -f build/$f.o ] || [ $dep -nt build/$f.o ]; then stale=1; fi
   done
   if [ $stale = 1 ]; then
@@ -19,7 +19,11 @@ for f in conv_igemm conv_1x1 conv_ks8 conv_wino conv_wgrad wgrad_wino pointwise 
   fi
   objs="$objs build/$f.o"
 done
-if [ ! -f build/rans.o ] || [ csrc/rans.cpp -nt build/rans.o ] || [ ../include/icm_hip.h -nt build/rans.o ]; then
+stale=0
+for dep in csrc/rans.cpp csrc/rans_lanes_common.h ../include/icm_hip.h; do
+  if [ ! -f build/rans.o ] || [ $dep -nt build/rans.o ]; then stale=1; fi
+done
+if [ $stale = 1 ]; then
   g++ -O2 -fPIC -std=c++17 -Wall -c csrc/rans.cpp -o build/rans.o || { echo "compile failed"; exit 1; }
 fi
 objs="$objs build/rans.o"

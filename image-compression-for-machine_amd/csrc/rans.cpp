@@ -22,6 +22,7 @@
 #include <vector>
 
 #include "../../include/icm_hip.h"
+#include "rans_lanes_common.h"
 
 namespace {
 
@@ -83,15 +84,7 @@ struct Dec {
   }
 };
 
-struct Tables {
-  const int32_t* cdfs;
-  int stride;
-  const int32_t* sizes;
-  const int32_t* offsets;
-  int n;
-  bool ok() const { return cdfs && sizes && offsets && n > 0 && stride >= 2; }
-  bool ok(int idx) const { return idx >= 0 && idx < n && sizes[idx] >= 2 && sizes[idx] <= stride; }
-};
+using icm::lanes::Tables;     // one table struct and validity rule for both streams (rans_lanes_common.h)
 
 struct Item {
   uint16_t start, width;
@@ -197,88 +190,28 @@ struct Decoder {
 };
 
 // ---- lane streams: 64 interleaved 32-bit rANS states per wave body (format: icm_amd/bitstream.py) ----------------
-// The executable definition the kernels of rans_lanes.hip are held to.  One body = 64 initial decoder states, then the
-// 16-bit words in the order the decoder reads them; a step of 64 elements runs four phases (table symbol, then three
-// raw 16-bit groups for the lanes that escaped), and inside a phase the lanes that renormalise take consecutive words
-// in ascending lane order.  Every loop below is counted by the run lengths and G, never by stream contents.
-constexpr uint32_t kLaneL = 1u << 16;
-constexpr int kLanes = 64;
-constexpr int kLanesMaxG = 4096;
-constexpr int64_t kLanesBodyMin = 4 * kLanes;
-
-inline int64_t lanes_chunk(int64_t n, int G) { return ((n + G - 1) / G + kLanes - 1) / kLanes * kLanes; }
-
-int lanes_waves(const int64_t* run_lengths, int nruns, int64_t symbols_per_wave) {
-  int64_t nmax = 0;
-  for (int r = 0; r < nruns; ++r) nmax = std::max(nmax, run_lengths[r]);
-  const int64_t g = (nmax + symbols_per_wave - 1) / symbols_per_wave;
-  return (int)std::min<int64_t>(std::max<int64_t>(g, 1), kLanesMaxG);
-}
-
-struct LaneItem {
-  uint16_t start, freq;    // freq == 0: no put (idle lane, or a lane that did not escape)
-};
-
-// the four (start, freq) puts of one element; false for an index or a table the coder cannot use
-bool lanes_plan(int32_t symbol, int32_t idx, const Tables& T, LaneItem it[4]) {
-  if (!T.ok(idx)) return false;
-  const int32_t* cdf = T.cdfs + (int64_t)idx * T.stride;
-  const int32_t overflow = T.sizes[idx] - 2;
-  int64_t v = (int64_t)symbol - T.offsets[idx];
-  uint64_t raw = 0;
-  bool esc = false;
-  if (v < 0) { raw = (uint64_t)(-2 * v - 1); v = overflow; esc = true; }
-  else if (v >= overflow) { raw = (uint64_t)(2 * (v - overflow)); v = overflow; esc = true; }
-  const int32_t lo = cdf[v], hi = cdf[v + 1];
-  if (hi <= lo || lo < 0 || hi > (1 << kPrecision) || hi - lo > 0xFFFF) return false;
-  it[0] = {(uint16_t)lo, (uint16_t)(hi - lo)};
-  for (int k = 0; k < 3; ++k) it[k + 1] = {(uint16_t)(esc ? (raw >> (16 * k)) & 0xFFFF : 0), (uint16_t)(esc ? 1 : 0)};
-  return true;
-}
+// The executable definition the kernels of rans_lanes.hip are held to: the arithmetic of a lane's step is
+// rans_lanes_common.h, which the kernels compile too; the loops below add the order.  One body = 64 initial decoder
+// states, then the 16-bit words in the order the decoder reads them; a step of 64 elements runs four phases (table
+// symbol, then three raw 16-bit groups for the lanes that escaped), and inside a phase the lanes that renormalise take
+// consecutive words in ascending lane order.  Every loop is counted by the run lengths and G, never by stream contents.
+using namespace icm::lanes;
 
 struct LaneDecoder {
   std::vector<uint8_t> data;
   int G = 0;
-  std::vector<int64_t> body_off, body_words;   // byte offset of each body, number of u16 words after its 64 states
+  std::vector<Body> body;
   std::vector<uint32_t> x;                     // [G][64]
   std::vector<int64_t> cur;                    // [G] word cursor
   int status = 0;                              // ICM_LANES_ST_* bits, sticky
   inline uint32_t word(int g, int64_t k) {
-    if (k >= body_words[g]) { status |= ICM_LANES_ST_OVERRUN; return 0; }
-    const uint8_t* p = data.data() + body_off[g] + kLanesBodyMin + 2 * k;
-    return (uint32_t)p[0] | ((uint32_t)p[1] << 8);
+    if (k >= body[g].words) { status |= ICM_LANES_ST_OVERRUN; return 0; }
+    return le16(data.data() + body[g].off + kBodyMin + 2 * k);
   }
 };
 
-int lanes_parse(LaneDecoder& D) {
-  const uint8_t* s = D.data.data();
-  const int64_t n = (int64_t)D.data.size();
-  if (n < 8 || std::memcmp(s, "ICML", 4) != 0) return ICM_ERR_ARG;
-  const uint32_t version = s[4] | (s[5] << 8), G = s[6] | (s[7] << 8);
-  if (version != 1 || G < 1 || G > (uint32_t)kLanesMaxG || 8 + 4 * (int64_t)G > n) return ICM_ERR_ARG;
-  D.G = (int)G;
-  int64_t pos = 8 + 4 * (int64_t)G;
-  for (uint32_t g = 0; g < G; ++g) {
-    const uint8_t* p = s + 8 + 4 * g;
-    const int64_t len = (int64_t)((uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | ((uint32_t)p[3] << 24));
-    if (len < kLanesBodyMin || (len & 1) || pos + len > n) return ICM_ERR_ARG;
-    D.body_off.push_back(pos);
-    D.body_words.push_back((len - kLanesBodyMin) / 2);
-    pos += len;
-  }
-  if (pos != n) return ICM_ERR_ARG;
-  D.x.resize((size_t)G * kLanes);
-  D.cur.assign(G, 0);
-  for (uint32_t g = 0; g < G; ++g)
-    for (int l = 0; l < kLanes; ++l) {
-      const uint8_t* p = s + D.body_off[g] + 4 * l;
-      D.x[g * kLanes + l] = (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | ((uint32_t)p[3] << 24);
-    }
-  return ICM_OK;
-}
-
 void lanes_decode_run(LaneDecoder& D, const int32_t* indexes, int64_t n, const Tables& T, int32_t* out) {
-  const int64_t c = lanes_chunk(n, D.G);
+  const int64_t c = chunk(n, D.G);
   for (int g = 0; g < D.G; ++g) {
     uint32_t* x = D.x.data() + (size_t)g * kLanes;
     const int64_t e0 = (int64_t)g * c, e1 = std::min(n, e0 + c);
@@ -292,16 +225,15 @@ void lanes_decode_run(LaneDecoder& D, const int32_t* indexes, int64_t n, const T
         esc[l] = false;
         raw[l] = 0;
         out[base + l] = 0;
-        const int idx = indexes[base + l];
-        if (!T.ok(idx)) { D.status |= ICM_LANES_ST_INDEX; overflow[l] = -1; continue; }
+        const int idx = indexes[base + l], size = ICM_LANES_SIZE(T, idx);
+        if (!ICM_LANES_FITS(T, size)) { D.status |= ICM_LANES_ST_INDEX; overflow[l] = -1; continue; }
         const int32_t* cdf = T.cdfs + (int64_t)idx * T.stride;
-        const int32_t size = T.sizes[idx];
         overflow[l] = size - 2;
-        const uint32_t cum = x[l] & 0xFFFF;
-        int32_t s = (int32_t)(std::upper_bound(cdf, cdf + size, (int32_t)cum) - cdf) - 1;
+        const int cum = (int)(x[l] & 0xFFFF);
+        const int32_t s = (int32_t)(std::upper_bound(cdf, cdf + size, (int32_t)cum) - cdf) - 1;
         if (s < 0 || s > overflow[l] || cdf[s + 1] <= cdf[s]) { D.status |= ICM_LANES_ST_SYMBOL; overflow[l] = -1; continue; }
-        x[l] = (uint32_t)(cdf[s + 1] - cdf[s]) * (x[l] >> 16) + cum - (uint32_t)cdf[s];
-        if (x[l] < kLaneL) x[l] = (x[l] << 16) | D.word(g, k++);
+        x[l] = advance(x[l], cum, cdf[s], cdf[s + 1]);
+        if (x[l] < kL) x[l] = (x[l] << 16) | D.word(g, k++);
         esc[l] = s == overflow[l];
         out[base + l] = s + T.offsets[idx];
       }
@@ -313,10 +245,9 @@ void lanes_decode_run(LaneDecoder& D, const int32_t* indexes, int64_t n, const T
           }
       for (int l = 0; l < act; ++l)
         if (esc[l]) {
-          const int64_t half = (int64_t)(raw[l] >> 1);
-          const int64_t v = ((raw[l] & 1) ? -half - 1 : half + overflow[l]) + T.offsets[indexes[base + l]];
-          if (v < INT32_MIN || v > INT32_MAX) { D.status |= ICM_LANES_ST_ESCAPE; out[base + l] = 0; }
-          else out[base + l] = (int32_t)v;
+          const int64_t v = unescape(raw[l], overflow[l], T.offsets[indexes[base + l]]);
+          if (is_int32(v)) out[base + l] = (int32_t)v;
+          else { D.status |= ICM_LANES_ST_ESCAPE; out[base + l] = 0; }
         }
       D.cur[g] = k;
     }
@@ -329,15 +260,19 @@ extern "C" {
 
 int icm_rans_lanes_waves(const int64_t* run_lengths, int nruns, int64_t symbols_per_wave) {
   if (nruns < 0 || (nruns > 0 && !run_lengths) || symbols_per_wave < 1) return -1;
-  for (int r = 0; r < nruns; ++r)
+  int64_t nmax = 0;
+  for (int r = 0; r < nruns; ++r) {
     if (run_lengths[r] < 0) return -1;
-  return lanes_waves(run_lengths, nruns, symbols_per_wave);
+    nmax = std::max(nmax, run_lengths[r]);
+  }
+  const int64_t g = (nmax + symbols_per_wave - 1) / symbols_per_wave;
+  return (int)std::min<int64_t>(std::max<int64_t>(g, 1), kMaxG);
 }
 
 int64_t icm_rans_lanes_encode(const int32_t* symbols, const int32_t* indexes, const int64_t* run_lengths, int nruns,
                               const int32_t* cdfs, int cdf_stride, const int32_t* cdf_sizes, const int32_t* offsets,
                               int ncdf, int64_t symbols_per_wave, uint8_t* out, int64_t out_capacity) {
-  const Tables T{cdfs, cdf_stride, cdf_sizes, offsets, ncdf};
+  const Tables T{cdfs, cdf_sizes, offsets, cdf_stride, ncdf};
   const int G = icm_rans_lanes_waves(run_lengths, nruns, symbols_per_wave);
   if (G < 1 || !T.ok()) return -1;
   int64_t total = 0;
@@ -347,33 +282,36 @@ int64_t icm_rans_lanes_encode(const int32_t* symbols, const int32_t* indexes, co
     std::vector<int64_t> run_off((size_t)nruns + 1, 0);
     for (int r = 0; r < nruns; ++r) run_off[r + 1] = run_off[r] + run_lengths[r];
     std::vector<std::vector<uint16_t>> words((size_t)G);   // per body, in emission order (the body holds them reversed)
-    std::vector<uint32_t> states((size_t)G * kLanes, kLaneL);
+    std::vector<uint32_t> states((size_t)G * kLanes, kL);
     for (int g = 0; g < G; ++g) {
       uint32_t* x = states.data() + (size_t)g * kLanes;
       std::vector<uint16_t>& w = words[g];
       for (int r = nruns - 1; r >= 0; --r) {
-        const int64_t n = run_lengths[r], c = lanes_chunk(n, G);
+        const int64_t n = run_lengths[r], c = chunk(n, G);
         const int64_t e0 = (int64_t)g * c, e1 = std::min(n, e0 + c);
         if (e1 <= e0) continue;
         const int64_t steps = (e1 - e0 + kLanes - 1) / kLanes;
         for (int64_t t = steps - 1; t >= 0; --t) {
           const int64_t base = e0 + t * kLanes;
           const int act = (int)std::min<int64_t>(kLanes, e1 - base);
-          LaneItem it[kLanes][4];
-          for (int l = 0; l < act; ++l)
-            if (!lanes_plan(symbols[run_off[r] + base + l], indexes[run_off[r] + base + l], T, it[l])) return -1;
+          Puts it[kLanes];
+          for (int l = 0; l < act; ++l) {
+            const int64_t e = run_off[r] + base + l;
+            const int idx = indexes[e], size = ICM_LANES_SIZE(T, idx);
+            if (!ICM_LANES_FITS(T, size) || !plan(T, idx, size, symbols[e], it[l])) return -1;
+          }
           for (int ph = 3; ph >= 0; --ph)
             for (int l = act - 1; l >= 0; --l) {     // descending lanes going down = ascending lanes in the body
-              const uint32_t freq = it[l][ph].freq;
-              if (!freq) continue;
-              if ((uint64_t)x[l] >= ((uint64_t)freq << 16)) { w.push_back((uint16_t)(x[l] & 0xFFFF)); x[l] >>= 16; }
-              x[l] = ((x[l] / freq) << 16) + x[l] % freq + it[l][ph].start;
+              if (!it[l].has(ph)) continue;
+              const uint32_t freq = it[l].freq(ph);
+              if (put_emits(x[l], freq)) { w.push_back((uint16_t)(x[l] & 0xFFFF)); x[l] >>= 16; }
+              x[l] = put(x[l], it[l].start(ph), freq);
             }
         }
       }
     }
     int64_t nbytes = 8 + 4 * (int64_t)G;
-    for (int g = 0; g < G; ++g) nbytes += kLanesBodyMin + 2 * (int64_t)words[g].size();
+    for (int g = 0; g < G; ++g) nbytes += kBodyMin + 2 * (int64_t)words[g].size();
     if (!out) return nbytes;
     if (out_capacity < nbytes) return -1;
     auto put16 = [](uint8_t* p, uint32_t v) { p[0] = (uint8_t)v; p[1] = (uint8_t)(v >> 8); };
@@ -384,7 +322,7 @@ int64_t icm_rans_lanes_encode(const int32_t* symbols, const int32_t* indexes, co
     uint8_t* p = out + 8 + 4 * (int64_t)G;
     for (int g = 0; g < G; ++g) {
       const std::vector<uint16_t>& w = words[g];
-      put32(out + 8 + 4 * g, (uint32_t)(kLanesBodyMin + 2 * w.size()));
+      put32(out + 8 + 4 * g, (uint32_t)(kBodyMin + 2 * w.size()));
       for (int l = 0; l < kLanes; ++l, p += 4) put32(p, states[(size_t)g * kLanes + l]);
       for (size_t k = w.size(); k-- > 0; p += 2) put16(p, w[k]);
     }
@@ -400,7 +338,14 @@ void* icm_rans_lanes_decoder_create(const uint8_t* stream, int64_t nbytes) {
   if (!D) return nullptr;
   try {
     D->data.assign(stream, stream + nbytes);
-    if (lanes_parse(*D) == ICM_OK) return D;
+    if (parse(D->data.data(), nbytes, D->body)) {
+      D->G = (int)D->body.size();
+      D->cur.assign((size_t)D->G, 0);
+      D->x.resize((size_t)D->G * kLanes);
+      for (int g = 0; g < D->G; ++g)
+        for (int l = 0; l < kLanes; ++l) D->x[(size_t)g * kLanes + l] = le32(D->data.data() + D->body[g].off + 4 * l);
+      return D;
+    }
   } catch (const std::bad_alloc&) {
   }
   delete D;
@@ -410,7 +355,7 @@ void* icm_rans_lanes_decoder_create(const uint8_t* stream, int64_t nbytes) {
 int icm_rans_lanes_decoder_decode_run(void* handle, const int32_t* indexes, int64_t n, const int32_t* cdfs,
                                       int cdf_stride, const int32_t* cdf_sizes, const int32_t* offsets, int ncdf,
                                       int32_t* out) {
-  const Tables T{cdfs, cdf_stride, cdf_sizes, offsets, ncdf};
+  const Tables T{cdfs, cdf_sizes, offsets, cdf_stride, ncdf};
   if (!handle || n < 0 || (n > 0 && (!indexes || !out)) || !T.ok()) return ICM_ERR_ARG;
   LaneDecoder& D = *static_cast<LaneDecoder*>(handle);
   lanes_decode_run(D, indexes, n, T, out);
@@ -421,9 +366,9 @@ int icm_rans_lanes_decoder_finish(void* handle) {
   if (!handle) return -1;
   LaneDecoder& D = *static_cast<LaneDecoder*>(handle);
   for (int g = 0; g < D.G; ++g) {
-    if (D.cur[g] != D.body_words[g]) D.status |= ICM_LANES_ST_CURSOR;
+    if (D.cur[g] != D.body[g].words) D.status |= ICM_LANES_ST_CURSOR;
     for (int l = 0; l < kLanes; ++l)
-      if (D.x[(size_t)g * kLanes + l] != kLaneL) D.status |= ICM_LANES_ST_STATE;
+      if (D.x[(size_t)g * kLanes + l] != kL) D.status |= ICM_LANES_ST_STATE;
   }
   return D.status;
 }
@@ -469,7 +414,7 @@ int icm_pmf_to_quantized_cdf(const float* pmf, int n, int precision, int32_t* cd
 int64_t icm_rans_encode_with_indexes(const int32_t* symbols, const int32_t* indexes, int64_t n, const int32_t* cdfs,
                                      int cdf_stride, const int32_t* cdf_sizes, const int32_t* offsets, int ncdf,
                                      uint8_t* out, int64_t out_capacity) {
-  const Tables T{cdfs, cdf_stride, cdf_sizes, offsets, ncdf};
+  const Tables T{cdfs, cdf_sizes, offsets, cdf_stride, ncdf};
   if (n < 0 || (n > 0 && (!symbols || !indexes)) || !T.ok()) return -1;
   std::vector<Item> items;
   try {
@@ -507,7 +452,7 @@ void* icm_rans_decoder_create(const uint8_t* stream, int64_t nbytes) {
 
 int icm_rans_decoder_decode(void* handle, const int32_t* indexes, int64_t n, const int32_t* cdfs, int cdf_stride,
                             const int32_t* cdf_sizes, const int32_t* offsets, int ncdf, int32_t* out) {
-  const Tables T{cdfs, cdf_stride, cdf_sizes, offsets, ncdf};
+  const Tables T{cdfs, cdf_sizes, offsets, cdf_stride, ncdf};
   if (!handle || n < 0 || (n > 0 && (!indexes || !out)) || !T.ok()) return ICM_ERR_ARG;
   return decode_run(static_cast<Decoder*>(handle)->d, indexes, n, T, out);
 }

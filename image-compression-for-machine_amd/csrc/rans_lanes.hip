@@ -1,8 +1,9 @@
 // Lane streams on the device: the kernels behind compress(coder="lanes") / decompress(coder="lanes").
 //
-// Format and state machine: icm_amd/bitstream.py ("lane stream"); executable definition: csrc/rans.cpp
-// (icm_rans_lanes_encode / icm_rans_lanes_decoder_*), which these kernels match byte for byte.  Parity unpinned: no
-// counterpart in the reference.
+// Format and state machine: icm_amd/bitstream.py ("lane stream"); executable definition: csrc/rans_lanes_common.h (the
+// arithmetic of a lane's step, compiled here and into the host coder alike) plus the host loops of csrc/rans.cpp
+// (icm_rans_lanes_encode / icm_rans_lanes_decoder_*), which these kernels match byte for byte.  What is this file's
+// own: the word order inside a phase and the CDF search.  Parity unpinned: no counterpart in the reference.
 //
 // One wave codes one body.  A lane owns one 32-bit rANS state; in step t of a run, lane l of wave g handles element
 // g c + 64 t + l.  The only cross-lane traffic is the word order inside a phase: the lanes that renormalise take
@@ -15,6 +16,7 @@
 // ncdf and its table size against the stride before a table entry is read; the search keeps 0 <= lo < hi <= size - 1.
 // The encoder checks every word position against its scratch region and sets an overflow flag instead of writing.
 #include "icm_common.h"
+#include "rans_lanes_common.h"
 
 #include <cstring>
 #include <new>
@@ -22,17 +24,13 @@
 
 namespace {
 
-constexpr uint32_t kL = 1u << 16;
-constexpr int kLanes = 64;
+using namespace icm::lanes;
+
 constexpr int kBlock = 256;   // pack / init / finish launches; upper bound of a coding workgroup
-constexpr int kMaxG = 4096;
 constexpr int kEncBad = 1, kEncOverflow = 2;   // flags of the encoder's result record
 
-struct Tab {
-  const int32_t* cdfs;
-  const int32_t* sizes;
-  const int32_t* offsets;
-  int stride, ncdf, maxit;
+struct Tab : Tables {
+  int maxit;                  // probes that bound the CDF search: ceil(log2(stride)) + 1
 };
 
 struct EncResult {   // first 16 bytes of the encoder workspace
@@ -86,33 +84,20 @@ __global__ __launch_bounds__(kBlock) void lanes_enc_run_kernel(const int32_t* __
   for (int t = steps - 1; t >= 0; --t) {
     const long long e = e0 + (long long)t * kLanes + lane;
     const bool active = e < e1;
-    uint32_t start = 0, freq = 0;
-    unsigned long long raw = 0;
-    bool esc = false, ok = false;
+    Puts p = {};
+    bool ok = false;
     if (active) {
-      const int idx = indexes[e];
-      const int size = (idx >= 0 && idx < T.ncdf) ? T.sizes[idx] : 0;
-      if (size >= 2 && size <= T.stride) {
-        const int32_t* cdf = T.cdfs + (long long)idx * T.stride;
-        const int overflow = size - 2;
-        long long v = (long long)symbols[e] - T.offsets[idx];
-        if (v < 0) { raw = (unsigned long long)(-2 * v - 1); v = overflow; esc = true; }
-        else if (v >= overflow) { raw = (unsigned long long)(2 * (v - overflow)); v = overflow; esc = true; }
-        const int lo = cdf[v], hi = cdf[v + 1];
-        ok = hi > lo && lo >= 0 && hi <= 65536 && hi - lo <= 0xFFFF;
-        start = (uint32_t)lo;
-        freq = (uint32_t)(hi - lo);
-      }
-      if (!ok) { flags |= kEncBad; esc = false; }
+      const int idx = indexes[e], size = ICM_LANES_SIZE(T, idx);
+      if (ICM_LANES_FITS(T, size)) ok = plan(T, idx, size, symbols[e], p);
+      if (!ok) { flags |= kEncBad; p.esc = false; }
     }
 #pragma unroll
     for (int ph = 3; ph >= 0; --ph) {
-      const bool put = ok && (ph == 0 || esc);
-      const uint32_t f = ph == 0 ? freq : 1u;
-      const uint32_t s = ph == 0 ? start : (uint32_t)((raw >> (16 * (ph - 1))) & 0xFFFF);
-      const bool emit = put && x >= (f << 16);        // f <= 0xFFFF: no overflow
+      const bool puts = ok && p.has(ph);
+      const uint32_t f = p.freq(ph), s = p.start(ph);
+      const bool emit = puts && put_emits(x, f);
       const unsigned long long mask = __ballot(emit);
-      if (mask == 0 && !__any(put)) continue;
+      if (mask == 0 && !__any(puts)) continue;
       wp -= __popcll(mask);
       if (emit) {
         const int pos = wp + rank_below(mask);
@@ -120,7 +105,7 @@ __global__ __launch_bounds__(kBlock) void lanes_enc_run_kernel(const int32_t* __
         else flags |= kEncOverflow;
         x >>= 16;
       }
-      if (put) x = ((x / f) << 16) + x % f + s;
+      if (puts) x = put(x, s, f);
     }
   }
   states[g * kLanes + lane] = x;
@@ -230,18 +215,17 @@ __global__ __launch_bounds__(kBlock) void lanes_dec_run_kernel(const uint8_t* __
     bool ok = false, esc = false;
     int sym = 0, overflow = 0, offset = 0;
     if (active) {
-      const int idx = indexes[e];
-      const int size = (idx >= 0 && idx < T.ncdf) ? T.sizes[idx] : 0;
-      if (size >= 2 && size <= T.stride) {
+      const int idx = indexes[e], size = ICM_LANES_SIZE(T, idx);
+      if (ICM_LANES_FITS(T, size)) {
         const int32_t* cdf = T.cdfs + (long long)idx * T.stride;
         offset = T.offsets[idx];
         overflow = size - 2;
         const int cum = (int)(x & 0xFFFF);
         const int s = cdf_search<CENTRE>(cdf, size, -offset, cum, T.maxit);
         const int lo = cdf[s], hi = cdf[s + 1];
-        if (lo <= cum && cum < hi) {
+        if (in_bin(cum, lo, hi)) {
           ok = true;
-          x = (uint32_t)(hi - lo) * (x >> 16) + (uint32_t)(cum - lo);
+          x = advance(x, cum, lo, hi);
           esc = s == overflow;
           sym = s + offset;
         } else {
@@ -280,9 +264,8 @@ __global__ __launch_bounds__(kBlock) void lanes_dec_run_kernel(const uint8_t* __
         cur += (uint32_t)cnt;
       }
       if (esc) {
-        const long long half = (long long)(raw >> 1);
-        const long long v = ((raw & 1) ? -half - 1 : half + overflow) + offset;
-        if (v < INT32_MIN || v > INT32_MAX) { st |= ICM_LANES_ST_ESCAPE; sym = 0; }
+        const long long v = unescape(raw, overflow, offset);
+        if (!is_int32(v)) { st |= ICM_LANES_ST_ESCAPE; sym = 0; }
         else sym = (int)v;
       }
     }
@@ -309,7 +292,6 @@ __global__ void lanes_dec_finish_kernel(const WaveCtl* __restrict__ ctl, const u
 
 // ------------------------------------------------------------------------------------------------------ host side
 inline int64_t align16(int64_t v) { return (v + 15) & ~(int64_t)15; }
-inline int64_t chunk(int64_t n, int G) { return ((n + G - 1) / G + kLanes - 1) / kLanes * kLanes; }
 
 struct EncPlan {
   int G = 0;
@@ -334,8 +316,9 @@ bool enc_plan(const int64_t* run_lengths, int nruns, int64_t spw, int worst, Enc
 }
 
 bool make_tab(const int32_t* cdfs, int stride, const int32_t* sizes, const int32_t* offsets, int ncdf, Tab& T) {
-  if (!cdfs || !sizes || !offsets || ncdf < 1 || stride < 2) return false;
-  T = Tab{cdfs, sizes, offsets, stride, ncdf, icm::ceil_log2(stride) + 1};
+  T = Tab{{cdfs, sizes, offsets, stride, ncdf}, 0};
+  if (!T.ok()) return false;
+  T.maxit = icm::ceil_log2(stride) + 1;
   return true;
 }
 
@@ -417,13 +400,12 @@ int64_t icm_rans_lanes_encode_gpu(const int32_t* symbols, const int32_t* indexes
 
 void* icm_rans_lanes_decoder_gpu_create(const uint8_t* stream_bytes, int64_t nbytes, void* stream) {
   if (!stream_bytes || nbytes < 8 || nbytes >= (1ll << 31)) return nullptr;
-  void* chk = icm_rans_lanes_decoder_create(stream_bytes, nbytes);   // header and length table, on the host
-  if (!chk) return nullptr;
-  icm_rans_lanes_decoder_destroy(chk);
-  GpuDecoder* D = new (std::nothrow) GpuDecoder();
-  if (!D) return nullptr;
+  GpuDecoder* D = nullptr;
   try {
-    const int G = stream_bytes[6] | (stream_bytes[7] << 8);
+    std::vector<Body> body;
+    if (!parse(stream_bytes, nbytes, body)) return nullptr;   // header and length table, on the host
+    D = new GpuDecoder();
+    const int G = (int)body.size();
     D->G = G;
     D->stream = ST;
     D->o_ctl = 0;
@@ -432,13 +414,9 @@ void* icm_rans_lanes_decoder_gpu_create(const uint8_t* stream_bytes, int64_t nby
     D->o_string = D->o_status + align16(4ll * G);
     D->host.assign((size_t)(D->o_string + align16(nbytes)), 0);
     WaveCtl* ctl = reinterpret_cast<WaveCtl*>(D->host.data());
-    int64_t pos = 8 + 4ll * G;
     for (int g = 0; g < G; ++g) {
-      uint32_t len;
-      std::memcpy(&len, stream_bytes + 8 + 4 * g, 4);
-      ctl[g] = WaveCtl{(uint32_t)(D->o_string + pos + 4 * kLanes), (len - 4 * kLanes) / 2, 0u, 0u};
-      std::memcpy(D->host.data() + D->o_states + 4ll * g * kLanes, stream_bytes + pos, 4 * kLanes);
-      pos += len;
+      ctl[g] = WaveCtl{(uint32_t)(D->o_string + body[g].off + kBodyMin), (uint32_t)body[g].words, 0u, 0u};
+      std::memcpy(D->host.data() + D->o_states + 4ll * g * kLanes, stream_bytes + body[g].off, kBodyMin);
     }
     std::memcpy(D->host.data() + D->o_string, stream_bytes, (size_t)nbytes);
     if (hipMalloc(reinterpret_cast<void**>(&D->dev), D->host.size()) == hipSuccess &&
@@ -463,12 +441,9 @@ int icm_rans_lanes_decoder_gpu_decode_run(void* decoder, const int32_t* indexes,
   WaveCtl* ctl = reinterpret_cast<WaveCtl*>(D.dev + D.o_ctl);
   uint32_t* states = reinterpret_cast<uint32_t*>(D.dev + D.o_states);
   // the kernel addresses the string from the allocation's base: WaveCtl.off includes o_string
-  if (g_search_centre)
-    hipLaunchKernelGGL(lanes_dec_run_kernel<true>, dim3(blocks), dim3(wpb * kLanes), 0, ST, D.dev, ctl, states, indexes,
-                       (long long)n, (long long)chunk(n, D.G), T, out, D.G);
-  else
-    hipLaunchKernelGGL(lanes_dec_run_kernel<false>, dim3(blocks), dim3(wpb * kLanes), 0, ST, D.dev, ctl, states, indexes,
-                       (long long)n, (long long)chunk(n, D.G), T, out, D.G);
+  hipLaunchKernelGGL(g_search_centre ? lanes_dec_run_kernel<true> : lanes_dec_run_kernel<false>, dim3(blocks),
+                     dim3(wpb * kLanes), 0, ST, D.dev, ctl, states, indexes, (long long)n, (long long)chunk(n, D.G), T,
+                     out, D.G);
   ICM_CHECK_LAUNCH();
   return ICM_OK;
 }

@@ -6,16 +6,20 @@ interface below keeps their call signatures -- Python lists (or anything ``numpy
 ``list[int]`` out -- and hands flat int32 arrays to ``icm_rans_*``.  Host-side, like the reference's coder.
 
 Below them: the lane-stream coder (``coder="lanes"``, format in ``icm_amd.bitstream``; parity unpinned: no counterpart
-in the reference) -- ``lanes_encode`` / ``LanesDecoder`` on the host, the executable definition of the format, and
-``lanes_encode_gpu`` / ``LanesDecoderGpu`` over the kernels of csrc/rans_lanes.hip, which take device tensors."""
+in the reference) -- ``lanes_encode`` / ``LanesDecoder`` on the host, the executable definition of the format (the
+host loops of csrc/rans.cpp over the lane arithmetic of csrc/rans_lanes_common.h), and ``lanes_encode_gpu`` /
+``LanesDecoderGpu`` over the kernels of csrc/rans_lanes.hip, which compile the same arithmetic and take device tensors.
+Last: ``coder_for``, the one object behind every ``coder=`` keyword, so that no caller asks which coder it holds."""
 from __future__ import annotations
 
 import ctypes as C
+from types import SimpleNamespace
 from typing import List, Sequence
 
 import numpy as np
 
 from . import _lib as L
+from .bitstream import CODERS, check_coder      # noqa: F401  defined with the container format, part of this surface
 
 _i32p = C.POINTER(C.c_int32)
 
@@ -150,18 +154,11 @@ def pmf_to_quantized_cdf(pmf: Sequence[float], precision: int = 16) -> List[int]
 
 
 # ---------------------------------------------------------------------------------------------------- lane streams
-CODERS = ("host", "lanes")
-SYMBOLS_PER_WAVE = 16384      # default of every ``symbols_per_wave`` keyword (why this value)
+SYMBOLS_PER_WAVE = 16384      # what ``symbols_per_wave=None`` means: ``coder_for`` (why this value)
 _i64p = C.POINTER(C.c_int64)
 _LANES_STATUS = ((1, "a body ran out of words"), (2, "a value no table bin holds"), (4, "an escape outside int32"),
                  (8, "a CDF index outside the tables"), (16, "a lane did not end at 2^16"),
                  (32, "words of a body were left unread"))
-
-
-def check_coder(coder) -> str:
-    if coder not in CODERS:
-        raise ValueError(f"unknown coder {coder!r}; choose from {list(CODERS)}")
-    return coder
 
 
 def _lanes_status(st: int) -> None:
@@ -204,19 +201,20 @@ def lanes_encode(symbols, indexes, run_lengths, t: _Tables, symbols_per_wave: in
     return bytes(buf)
 
 
-class LanesDecoder:
-    """host decoder of one lane stream: ``decode_run`` per run in stream order, then ``finish``"""
+class _LanesHandle:
+    """what the host and the device decoder of a lane stream share: the C handle (made and freed by the functions
+    that ``_create`` and ``_destroy`` name) on a copy of the string"""
 
-    def __init__(self, stream: bytes):
+    def __init__(self, stream: bytes, *stream_arg):
         self._keep = (C.c_uint8 * max(1, len(stream))).from_buffer_copy(bytes(stream) or b"\0")
-        self._h = L.lib().icm_rans_lanes_decoder_create(self._keep, len(stream))
+        self._h = getattr(L.lib(), self._create)(self._keep, len(stream), *stream_arg)
         if not self._h:
             raise ValueError("lane stream decode: not a lane stream (magic, version, G or a length table that "
                              "disagrees with the string's length)")
 
     def close(self):
         if self._h:
-            L.lib().icm_rans_lanes_decoder_destroy(self._h)
+            getattr(L.lib(), self._destroy)(self._h)
             self._h = None
 
     def __del__(self):
@@ -224,6 +222,11 @@ class LanesDecoder:
             self.close()
         except Exception:
             pass
+
+
+class LanesDecoder(_LanesHandle):
+    """host decoder of one lane stream: ``decode_run`` per run in stream order, then ``finish``"""
+    _create, _destroy = "icm_rans_lanes_decoder_create", "icm_rans_lanes_decoder_destroy"
 
     def decode_run(self, indexes, t: _Tables) -> np.ndarray:
         idx = _arr(indexes)
@@ -294,27 +297,14 @@ def lanes_encode_gpu(symbols, indexes, run_lengths, cdf, sizes, offsets,
     return ws[off.value:off.value + nb].cpu().numpy().tobytes()
 
 
-class LanesDecoderGpu:
+class LanesDecoderGpu(_LanesHandle):
     """device decoder of one lane stream.  ``decode_run`` is one launch on the current stream and returns a device
     tensor; nothing is known to be valid until ``finish`` has looked at the status words."""
 
+    _create, _destroy = "icm_rans_lanes_decoder_gpu_create", "icm_rans_lanes_decoder_gpu_destroy"
+
     def __init__(self, stream: bytes):
-        self._keep = (C.c_uint8 * max(1, len(stream))).from_buffer_copy(bytes(stream) or b"\0")
-        self._h = L.lib().icm_rans_lanes_decoder_gpu_create(self._keep, len(stream), L.stream())
-        if not self._h:
-            raise ValueError("lane stream decode: not a lane stream (magic, version, G or a length table that "
-                             "disagrees with the string's length)")
-
-    def close(self):
-        if self._h:
-            L.lib().icm_rans_lanes_decoder_gpu_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        super().__init__(stream, L.stream())
 
     def decode_run(self, indexes, cdf, sizes, offsets, out=None):
         import torch
@@ -331,3 +321,56 @@ class LanesDecoderGpu:
         st = L.lib().icm_rans_lanes_decoder_gpu_finish(self._h, L.stream())
         self.close()
         _lanes_status(st)
+
+
+# ------------------------------------------------------------------------------------------- one coder behind both
+class HostCoder:
+    """the reference's scalar stream, coded on the host from ``em._tables()`` (``em``: the EntropyModel whose tables
+    apply).  ``encode``: flat int32 symbols and indexes cross to the host once each; the runs are concatenated.
+    ``decoder(string, em)``: ``decode_run(indexes, out=None)`` -> int32 symbols shaped like ``indexes`` on its device (a
+    copy down and one up per call), ``finish()`` (the scalar stream has no end mark to check) and ``close()``."""
+    name = "host"
+
+    def encode(self, symbols, indexes, run_lengths, em) -> bytes:
+        _runs(run_lengths, int(symbols.numel()))
+        return _encode(_arr(symbols.detach().cpu().numpy()), _arr(indexes.detach().cpu().numpy()), em._tables())
+
+    def decoder(self, string: bytes, em):
+        import torch
+        dec, t = RansDecoder(), em._tables()
+        dec.set_stream(string)
+
+        def decode_run(indexes, out=None):
+            sym = torch.from_numpy(dec.decode_stream_np(_arr(indexes.detach().cpu().numpy()), t).reshape(indexes.shape))
+            return sym.to(indexes.device) if out is None else out.copy_(sym)
+        return SimpleNamespace(decode_run=decode_run, finish=lambda: None, close=dec._close)
+
+
+class LanesCoder(HostCoder):
+    """lane streams, coded by the kernels from ``em._device_tables()`` where the symbols lie: the same surface; host
+    indexes are brought to the device, ``decode_run`` is one launch without a wait and answers on the device, and
+    nothing is known to be valid until ``finish`` has read the status words."""
+    name = "lanes"
+
+    def __init__(self, symbols_per_wave):
+        self.symbols_per_wave = symbols_per_wave
+
+    def encode(self, symbols, indexes, run_lengths, em) -> bytes:
+        import torch
+        return lanes_encode_gpu(symbols.contiguous(), indexes.to(symbols.device, torch.int32).contiguous(), run_lengths,
+                                *em._device_tables(), symbols_per_wave=self.symbols_per_wave)
+
+    def decoder(self, string: bytes, em):
+        import torch
+        dec, t = LanesDecoderGpu(string), em._device_tables()
+        return SimpleNamespace(finish=dec.finish, close=dec.close, decode_run=lambda indexes, out=None: dec.decode_run(
+            indexes.to(t[0].device, torch.int32).contiguous(), *t, out=out))
+
+
+def coder_for(coder, symbols_per_wave=None):
+    """the coder object of a ``coder=`` keyword (one that already is an object passes through): the one place that
+    checks the name and gives ``symbols_per_wave=None`` its meaning, SYMBOLS_PER_WAVE; 0 is refused by the encoder"""
+    if isinstance(coder, str):
+        spw = SYMBOLS_PER_WAVE if symbols_per_wave is None else symbols_per_wave
+        coder = HostCoder() if check_coder(coder) == "host" else LanesCoder(spw)
+    return coder

@@ -50,8 +50,9 @@ rows / cols are redundant with the four numbers before them, and a reader refuse
 The coder id lives in the tile streams alone: the high byte of the ICMT architecture field stays zero.
 
 Lane stream -- the string format of coder id 1, made to be coded by one GPU wave per body (csrc/rans_lanes.hip; the
-executable definition is ``icm_rans_lanes_encode`` / ``icm_rans_lanes_decoder_*`` of csrc/rans.cpp).  Parity unpinned:
-no counterpart in the reference.  A stream codes R runs; run r holds n_r (symbol, CDF index) pairs -- the y string
+executable definition is csrc/rans_lanes_common.h, the arithmetic of a lane's step that host and kernels both compile,
+under the loops of ``icm_rans_lanes_encode`` / ``icm_rans_lanes_decoder_*`` of csrc/rans.cpp).  Parity unpinned: no
+counterpart in the reference.  A stream codes R runs; run r holds n_r (symbol, CDF index) pairs -- the y string
 one run per slice in slice order, each flat in (n, c, h, w) order, a z string one run -- with the tables, offsets and
 sizes of the host coder (16-bit precision, the last bin of a table is the escape bin).
 
@@ -109,12 +110,19 @@ def _uint(name: str, v, hi: int, lo: int = 0) -> int:
     return v
 
 
+def check_coder(coder, who: str = "") -> str:
+    """``coder`` if CODERS names it, ValueError otherwise: the one check of a coder's name (``icm_amd.ans`` imports
+    CODERS and this check from here, the module that defines what the names mean in a stream)"""
+    if coder not in CODERS:
+        raise ValueError(f"{who}unknown coder {coder!r}; choose from {list(CODERS)}")
+    return coder
+
+
 def pack(header: Dict, strings: Sequence[bytes], coder: str = "host") -> bytes:
     """``header``: {"arch": name in ARCHS, "height", "width", "pads": (left, right, top, bottom),
     "shape": (z height, z width), "fingerprint": u32}; ``strings``: the flattened ``compress()["strings"]``;
     ``coder``: the name in CODERS that made them."""
-    if coder not in CODERS:
-        raise ValueError(f"bitstream: unknown coder {coder!r}; the format knows {list(CODERS)}")
+    check_coder(coder, "bitstream: ")
     missing = [k for k in HEADER_KEYS if k not in header]
     if missing:
         raise ValueError(f"bitstream: header lacks {missing}")

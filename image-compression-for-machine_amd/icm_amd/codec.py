@@ -39,7 +39,6 @@ import torch
 from . import _lib as L
 from . import bitstream as B
 from ._lib import check
-from .ans import SYMBOLS_PER_WAVE
 
 PAD_MULTIPLE = 64      # six stride-2 stages (utils.pad_to_multiple)
 
@@ -159,8 +158,7 @@ def _encode_one(model, arch: str, fp: int, u8: torch.Tensor, coder: str = "host"
                 symbols_per_wave: Optional[int] = None) -> bytes:
     H, W = u8.size(0), u8.size(1)
     pads = center_pads(H, W)
-    kw = {} if coder == "host" else {"coder": coder, "symbols_per_wave": symbols_per_wave or SYMBOLS_PER_WAVE}
-    enc = model.compress(image_u8_to_f32(u8, pads), **kw)
+    enc = model.compress(image_u8_to_f32(u8, pads), coder=coder, symbols_per_wave=symbols_per_wave)
     header = {"arch": arch, "height": H, "width": W, "pads": pads, "shape": tuple(int(s) for s in enc["shape"]),
               "fingerprint": fp}
     return B.pack(header, [s for part in enc["strings"] for s in part], coder=coder)
@@ -173,8 +171,7 @@ def encode_image(model, img, tile: Optional[int] = None, overlap: int = 0, coder
     ``tile``, an image of more than one tile (``plan_tiles``) becomes an ICMT stream whose tile k is
     ``encode_image(model, crop k)``, the tiles coded one after another; an image of one tile is written untiled.
     ``coder`` / ``symbols_per_wave``: as ``model.compress``; every ICMB stream records its coder."""
-    if coder not in B.CODERS:
-        raise ValueError(f"codec: unknown coder {coder!r}; choose from {list(B.CODERS)}")
+    B.check_coder(coder, "codec: ")
     arch = _ready(model)
     device = next(model.parameters()).device
     u8 = _as_u8_image(img, device)
@@ -209,8 +206,7 @@ def _check_strings(arch: str, strings, what: str = "this one") -> None:
 
 def _decompress_one(model, arch: str, header: Dict, strings, coder: str = "host") -> torch.Tensor:
     H, W, pads = header["height"], header["width"], header["pads"]
-    kw = {} if coder == "host" else {"coder": coder}
-    x_hat = model.decompress([[strings[0]], [strings[1]]], header["shape"], **kw)["x_hat"]
+    x_hat = model.decompress([[strings[0]], [strings[1]]], header["shape"], coder=coder)["x_hat"]
     left, right, top, bottom = pads
     if tuple(x_hat.shape) != (1, 3, top + H + bottom, left + W + right):
         raise ValueError(f"codec: latent shape {header['shape']} decodes to {tuple(x_hat.shape)}, not to a padded "

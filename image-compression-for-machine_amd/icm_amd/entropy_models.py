@@ -2,9 +2,9 @@
 (entropy_models.py:66-666).  Likelihoods run on the fused HIP kernels; ``update()`` builds the quantised CDF tables
 from device-computed pmfs (``icm_eb_pmf_table`` / ``icm_gc_pmf_table`` + host ``icm_pmf_to_quantized_cdf``);
 ``compress()`` / ``decompress()`` quantise on the device (``icm_quantize`` / ``icm_gc_build_indexes`` /
-``icm_dequantize``) and code the symbols with the host rANS coder (``icm_amd.ans``), as the reference does, or, with
-``coder="lanes"``, with the lane-stream kernels (csrc/rans_lanes.hip), which read the symbols, the indexes and the
-tables where they already lie: in device memory."""
+``icm_dequantize``) and hand the symbols to the coder object that ``icm_amd.ans.coder_for`` gives for ``coder=``: the
+host rANS coder, as the reference does, or the lane-stream kernels (csrc/rans_lanes.hip), which read symbols, indexes
+and tables where they lie, in device memory.  A model offers its tables as ``_tables()`` and ``_device_tables()``."""
 from __future__ import annotations
 
 import ctypes as C
@@ -129,23 +129,13 @@ class EntropyModel(nn.Module):
             cdf[i, :len(row)] = torch.tensor(row, dtype=torch.int32)
         return cdf.to(pmf.device)
 
-    def _check_cdf_size(self):
-        if self._quantized_cdf.numel() == 0:
-            raise ValueError("Uninitialized CDFs. Run update() first")
-        if len(self._quantized_cdf.size()) != 2:
-            raise ValueError(f"Invalid CDF size {self._quantized_cdf.size()}")
-
-    def _check_offsets_size(self):
-        if self._offset.numel() == 0:
-            raise ValueError("Uninitialized offsets. Run update() first")
-        if len(self._offset.size()) != 1:
-            raise ValueError(f"Invalid offsets size {self._offset.size()}")
-
-    def _check_cdf_length(self):
-        if self._cdf_length.numel() == 0:
-            raise ValueError("Uninitialized CDF lengths. Run update() first")
-        if len(self._cdf_length.size()) != 1:
-            raise ValueError(f"Invalid offsets size {self._cdf_length.size()}")
+    def _check_tables(self):   # entropy_models.py:180-199: _check_cdf_size, _check_cdf_length, _check_offsets_size
+        for what, t, ndim, name in (("CDFs", self._quantized_cdf, 2, "CDF"), ("CDF lengths", self._cdf_length, 1, "offsets"),
+                                    ("offsets", self._offset, 1, "offsets")):
+            if t.numel() == 0:
+                raise ValueError(f"Uninitialized {what}. Run update() first")
+            if t.dim() != ndim:
+                raise ValueError(f"Invalid {name} size {t.size()}")
 
     def _tables(self):
         """host copies of the coder tables, cached until the buffers change"""
@@ -167,42 +157,27 @@ class EntropyModel(nn.Module):
                      for b in (self._quantized_cdf, self._cdf_length, self._offset))
 
     def compress(self, inputs, indexes, means=None, flag=1, coder="host", symbols_per_wave=None):
-        from .ans import SYMBOLS_PER_WAVE, check_coder, lanes_encode_gpu
-        check_coder(coder)
+        from .ans import coder_for
+        coder = coder_for(coder, symbols_per_wave)
         symbols = self.quantize(inputs, "symbols", means)
         if len(inputs.size()) < 2:
             raise ValueError("Invalid `inputs` size. Expected a tensor with at least 2 dimensions.")
         if inputs.size() != indexes.size():
             raise ValueError("`inputs` and `indexes` should have the same size.")
-        self._check_cdf_size()
-        self._check_cdf_length()
-        self._check_offsets_size()
-        if coder == "lanes":       # one single-run lane stream per image, coded where the symbols lie
-            tabs = self._device_tables()
-            idx = indexes.to(symbols.device, torch.int32)
-            spw = SYMBOLS_PER_WAVE if symbols_per_wave is None else symbols_per_wave
-            return [lanes_encode_gpu(symbols[i].reshape(-1).contiguous(), idx[i].reshape(-1).contiguous(),
-                                     [symbols[i].numel()], *tabs, symbols_per_wave=spw)
-                    for i in range(symbols.shape[0])]
-        from .ans import _encode
-        t = self._tables()
-        sym = symbols.detach().cpu().numpy().astype(np.int32)
-        idx = indexes.detach().cpu().numpy().astype(np.int32)
-        return [_encode(np.ascontiguousarray(sym[i].reshape(-1)), np.ascontiguousarray(idx[i].reshape(-1)), t)
-                for i in range(sym.shape[0])]
+        self._check_tables()
+        return [coder.encode(symbols[i].reshape(-1), indexes[i].reshape(-1), [symbols[i].numel()], self)
+                for i in range(symbols.shape[0])]
 
     def decompress(self, strings, indexes, means=None, flag=1, coder="host"):
-        from .ans import LanesDecoderGpu, check_coder
-        check_coder(coder)
+        from .ans import coder_for
+        coder = coder_for(coder)
         if not isinstance(strings, (tuple, list)):
             raise ValueError("Invalid `strings` parameter type.")
         if not len(strings) == indexes.size(0):
             raise ValueError("Invalid strings or indexes parameters")
         if len(indexes.size()) < 2:
             raise ValueError("Invalid `indexes` size. Expected a tensor with at least 2 dimensions.")
-        self._check_cdf_size()
-        self._check_cdf_length()
-        self._check_offsets_size()
+        self._check_tables()
         if means is not None:
             if means.size()[:2] != indexes.size()[:2]:
                 raise ValueError("Invalid means or indexes parameters")
@@ -210,25 +185,14 @@ class EntropyModel(nn.Module):
                 for i in range(2, len(indexes.size())):
                     if means.size(i) != 1:
                         raise ValueError("Invalid means parameters")
-        if coder == "lanes":
-            tabs = self._device_tables()
-            dev = self._quantized_cdf.device
-            idx = indexes.to(dev, torch.int32).contiguous()
-            sym = torch.empty(idx.shape, dtype=torch.int32, device=dev)
-            for i, sbytes in enumerate(strings):
-                dec = LanesDecoderGpu(sbytes)
-                dec.decode_run(idx[i], *tabs, out=sym[i])
-                dec.finish()
-            return self.dequantize(sym, means)
-        from .ans import RansDecoder
-        t = self._tables()
-        idx = indexes.detach().cpu().numpy().astype(np.int32)
-        out = np.empty(idx.shape, dtype=np.int32)
-        dec = RansDecoder()
+        sym = torch.empty(indexes.shape, dtype=torch.int32, device=self._quantized_cdf.device)
         for i, sbytes in enumerate(strings):
-            dec.set_stream(sbytes)
-            out[i] = dec.decode_stream_np(np.ascontiguousarray(idx[i].reshape(-1)), t).reshape(idx[i].shape)
-        sym = torch.from_numpy(out).to(self._quantized_cdf.device)
+            dec = coder.decoder(sbytes, self)
+            try:
+                dec.decode_run(indexes[i], out=sym[i])
+                dec.finish()
+            finally:
+                dec.close()
         return self.dequantize(sym, means)
 
     def _invalidate_tables(self):

@@ -15,7 +15,7 @@ import torch.nn as nn
 from . import _lib as L
 from . import engine as E
 from ._lib import ACT_GELU
-from .ans import SYMBOLS_PER_WAVE, check_coder
+from .ans import coder_for
 from .engine import VT
 from .entropy_models import EntropyBottleneck, GaussianConditional
 from .layers import (GDN, Conv2d, Win_noShift_Attention, WindowAttention, conv, conv3x3, deconv, subpel_conv3x3,
@@ -75,41 +75,31 @@ class CompressionModel(nn.Module):
         names, params = _named(self)
         return dict(zip(names, [p.detach() for p in params]))
 
-    def _compress_latent(self, tape, P, y, debug=None, coder="host", symbols_per_wave=None):
-        """cnn.py:214-266 from ``y`` on: {"strings": [[y_string], z_strings], "shape": z spatial size}.
-        coder="lanes": the y string is one lane stream with a run per slice, coded by the kernel from the recorded
-        device tensors; the z strings are single-run lane streams (``icm_amd.ans``)."""
-        from .ans import _encode, lanes_encode_gpu
-        codec = {"gc": self.gaussian_conditional, "symbols": {}, "indexes": {}}
+    def _compress_latent(self, tape, P, y, coder, debug=None):
+        """cnn.py:214-266 from ``y`` on: {"strings": [[y_string], z_strings], "shape": z spatial size}.  ``coder``
+        (``icm_amd.ans.coder_for``) codes the recorded device tensors of all slices as one y string, a run per slice,
+        and the z strings as single-run strings."""
+        gc = self.gaussian_conditional
+        codec = {"gc": gc, "symbols": {}, "indexes": {}}
         keep = {}
         hyper_slices(tape, P, y, None, None, self.num_slices, self.max_support_slices, keep=keep, codec=codec)
         z = keep["z"]
-        z_strings = self.entropy_bottleneck.compress(z, coder=coder, symbols_per_wave=symbols_per_wave)
+        z_strings = self.entropy_bottleneck.compress(z, coder=coder)
         sym = torch.cat([codec["symbols"][i].reshape(-1) for i in range(self.num_slices)])
         idx = torch.cat([codec["indexes"][i].reshape(-1) for i in range(self.num_slices)])
-        self.gaussian_conditional._check_cdf_size()
-        self.gaussian_conditional._check_cdf_length()
-        self.gaussian_conditional._check_offsets_size()
-        if coder == "lanes":
-            y_string = lanes_encode_gpu(sym, idx, [codec["symbols"][i].numel() for i in range(self.num_slices)],
-                                        *self.gaussian_conditional._device_tables(),
-                                        symbols_per_wave=symbols_per_wave or SYMBOLS_PER_WAVE)
-            if debug is not None:
-                sym, idx = sym.cpu().numpy(), idx.cpu().numpy()
-        else:
-            sym, idx = sym.cpu().numpy(), idx.cpu().numpy()
-            y_string = _encode(sym, idx, self.gaussian_conditional._tables())
+        gc._check_tables()
+        y_string = coder.encode(sym, idx, [codec["symbols"][i].numel() for i in range(self.num_slices)], gc)
         if debug is not None:      # tests: the coded symbols / CDF indexes (slice-major, cnn.py:254-255)
-            debug.update(symbols=sym, indexes=idx)
+            debug.update(symbols=sym.cpu().numpy(), indexes=idx.cpu().numpy())
         return {"strings": [[y_string], z_strings], "shape": z.size()[-2:]}
 
-    def _decompress_latent(self, tape, P, strings, shape, M, coder="host"):
+    def _decompress_latent(self, tape, P, strings, shape, M, coder):
         """cnn.py:289-328: y_hat from the two streams"""
         if not isinstance(strings, (list, tuple)) or len(strings) != 2:
             raise ValueError("strings must be [y_strings, z_strings]")
         z_hat = self.entropy_bottleneck.decompress(strings[1], shape, coder=coder)
         return decode_slices(tape, P, z_hat, strings[0][0], self.gaussian_conditional, self.num_slices,
-                             self.max_support_slices, M, coder=coder)
+                             self.max_support_slices, M, coder)
 
     def load_state_dict(self, state_dict, strict: bool = False):
         # models/base.py:62-70: resize the CDF buffers to whatever the checkpoint holds, then strict=False
@@ -343,54 +333,31 @@ def _record_symbols(codec, i, y_slice, mu, sc):
     codec["indexes"][i] = codec["gc"].build_indexes(sc)
 
 
-def decode_slices(tape: E.Tape, P, z_hat, y_string: bytes, gc, num_slices: int, max_support: int, M: int,
-                  coder: str = "host"):
+def decode_slices(tape: E.Tape, P, z_hat, y_string: bytes, gc, num_slices: int, max_support: int, M: int, coder):
     """Decoder side of the slice loop (cnn.py:296-326): hyper_slices in decode mode -- per slice the chains give
-    mu / scale -> CDF indexes -> the rANS decoder yields the symbols -> y_hat_pre = symbols + mu; the LRP correction
-    and the support bookkeeping are the forward's own.  Returns y_hat [N,M,h,w].
-    coder="lanes": the decoder's state stays on the device; per slice one ``decode_run`` launch between
-    ``build_indexes`` and ``icm_dequantize``, no host copy and no wait; ``finish`` reads the status after the loop."""
-    from .ans import LanesDecoderGpu, RansDecoder
-    gc._check_cdf_size()
-    gc._check_cdf_length()
-    gc._check_offsets_size()
+    mu / scale -> CDF indexes -> ``decode_run`` of the coder's decoder yields the symbols -> y_hat_pre = symbols + mu;
+    the LRP correction and the support bookkeeping are the forward's own.  Returns y_hat [N,M,h,w].  ``coder``: of
+    ``icm_amd.ans.coder_for``; what a ``decode_run`` costs (host: a copy down and one up; lanes: one launch, no wait,
+    the status read by ``finish`` after the loop) is the coder's business."""
+    gc._check_tables()
+    dec = coder.decoder(y_string, gc)
     state = {"next": 0}
-    if coder == "lanes":
-        dtabs = gc._device_tables()
-        ldec = LanesDecoderGpu(y_string)
-
-        def one_lanes(i, mu, sc, yh_pre):
-            if i != state["next"]:
-                raise RuntimeError("slices must be decoded in stream order")
-            state["next"] += 1
-            N, Cc, h, w = mu.shape
-            sym = ldec.decode_run(gc.build_indexes(sc), *dtabs)
-            L.check(L.lib().icm_dequantize(sym.data_ptr(), L.ptr(mu), L.bs(mu), h * w, 1, L.ptr(yh_pre), L.bs(yh_pre), N,
-                                           Cc, h * w, tape.st), "dequantize")
-
-        try:
-            Y_hat, _, _ = hyper_slices(tape, P, None, None, None, num_slices, max_support,
-                                       decode={"z_hat": z_hat, "M": M, "slice": one_lanes})
-            ldec.finish()
-        finally:
-            ldec.close()
-        return Y_hat
-    tabs = gc._tables()
-    dec = RansDecoder()
-    dec.set_stream(y_string)
 
     def one(i, mu, sc, yh_pre):
         if i != state["next"]:
             raise RuntimeError("slices must be decoded in stream order")
         state["next"] += 1
         N, Cc, h, w = mu.shape
-        idx = gc.build_indexes(sc).cpu().numpy().reshape(-1)
-        sym = torch.from_numpy(dec.decode_stream_np(idx, tabs).reshape(N, Cc, h, w)).to(mu.device)
+        sym = dec.decode_run(gc.build_indexes(sc))
         L.check(L.lib().icm_dequantize(sym.data_ptr(), L.ptr(mu), L.bs(mu), h * w, 1, L.ptr(yh_pre), L.bs(yh_pre), N, Cc,
                                        h * w, tape.st), "dequantize")
 
-    Y_hat, _, _ = hyper_slices(tape, P, None, None, None, num_slices, max_support,
-                               decode={"z_hat": z_hat, "M": M, "slice": one})
+    try:
+        Y_hat, _, _ = hyper_slices(tape, P, None, None, None, num_slices, max_support,
+                                   decode={"z_hat": z_hat, "M": M, "slice": one})
+        dec.finish()
+    finally:
+        dec.close()
     return Y_hat
 
 
@@ -752,20 +719,20 @@ class WACNN(CompressionModel):
         return self._update_tables(scale_table, force)
 
     @torch.no_grad()
-    def compress(self, x, _debug=None, coder="host", symbols_per_wave=SYMBOLS_PER_WAVE):
+    def compress(self, x, _debug=None, coder="host", symbols_per_wave=None):
         """cnn.py:210-266 -> {"strings": [[y_string], z_strings], "shape": z.shape[-2:]}; ``coder``: "host" (the
         reference's scalar stream) or "lanes" (lane streams coded on the device, ``symbols_per_wave`` symbols of a
-        slice per wave body); the decoder must be told the same coder"""
-        check_coder(coder)
+        slice per wave body, None: ``icm_amd.ans.SYMBOLS_PER_WAVE``); the decoder must be told the same coder"""
+        coder = coder_for(coder, symbols_per_wave)
         _check_codec_input(x)
         P = self._params()
         tape = E.Tape(need_grad=False, packed_cache=self._pack_cache())
-        return self._compress_latent(tape, P, wacnn_g_a(tape, P, x.contiguous()), _debug, coder, symbols_per_wave)
+        return self._compress_latent(tape, P, wacnn_g_a(tape, P, x.contiguous()), coder, _debug)
 
     @torch.no_grad()
     def decompress(self, strings, shape, coder="host"):
         """cnn.py:289-332 -> {"x_hat"} clamped to [0, 1]"""
-        check_coder(coder)
+        coder = coder_for(coder)
         P = self._params()
         tape = E.Tape(need_grad=False, packed_cache=self._pack_cache())
         x_hat = wacnn_g_s(tape, P, self._decompress_latent(tape, P, strings, shape, 320, coder))
@@ -1011,18 +978,18 @@ class SymmetricalTransFormer(CompressionModel):
         return self._update_tables(scale_table, force)
 
     @torch.no_grad()
-    def compress(self, x, _debug=None, coder="host", symbols_per_wave=SYMBOLS_PER_WAVE):
+    def compress(self, x, _debug=None, coder="host", symbols_per_wave=None):
         """stf.py compress(): analysis transform, then the shared latent coder (``coder``: see WACNN.compress)"""
-        check_coder(coder)
+        coder = coder_for(coder, symbols_per_wave)
         _check_codec_input(x)
         P = self._params()
         tape = E.Tape(need_grad=False, packed_cache=self._pack_cache())
-        return self._compress_latent(tape, P, stf_analysis(tape, P, x.contiguous(), None, self.window_size), _debug,
-                                     coder, symbols_per_wave)
+        return self._compress_latent(tape, P, stf_analysis(tape, P, x.contiguous(), None, self.window_size), coder,
+                                     _debug)
 
     @torch.no_grad()
     def decompress(self, strings, shape, coder="host"):
-        check_coder(coder)
+        coder = coder_for(coder)
         P = self._params()
         tape = E.Tape(need_grad=False, packed_cache=self._pack_cache())
         y_hat = self._decompress_latent(tape, P, strings, shape, 384, coder)
@@ -1121,7 +1088,7 @@ class SymmetricalTransFormer3(SymmetricalTransFormer):
     def update(self, scale_table=None, force=False):
         return self._update_tables(scale_table, force)
 
-    def compress(self, x, _debug=None, coder="host", symbols_per_wave=SYMBOLS_PER_WAVE):
+    def compress(self, x, _debug=None, coder="host", symbols_per_wave=None):
         raise NotImplementedError("stf6: the zigzag entropy coder loop (stf6.py:898-1057) is not mirrored")
 
     def decompress(self, strings, shape, coder="host"):

@@ -1,6 +1,7 @@
 """GPU: the lane-stream kernels (csrc/rans_lanes.hip) against the host implementation of the format, which
-tests/test_rans_lanes.py holds to the restatement -- same cases, byte for byte; then ``coder="lanes"`` through the
-models (icm_amd/models.py, entropy_models.py), the container and ``icm_amd.codec``.  Every comparison is exact.
+tests/test_rans_lanes.py holds to the restatement -- same cases, byte for byte; the two coder objects of
+``icm_amd.ans.coder_for`` on device tensors; then ``coder="lanes"`` through the models (icm_amd/models.py,
+entropy_models.py), the container and ``icm_amd.codec``.  Every comparison is exact.
 
 Weights: the formula state-dicts of oracle/weights.py, as the other codec tests build theirs."""
 import json
@@ -122,6 +123,44 @@ def test_wrong_indexes_are_reported_by_finish(tabs, dtabs):
     wrong[7], wrong[40] = 99, -1
     with pytest.raises(ValueError, match="CDF index"):
         _gpu_decode(ans.lanes_encode(sym, idx, runs, tabs, spw), wrong, runs, dtabs)
+
+
+# ------------------------------------------------------------------------------------------------------ coder objects
+@pytest.fixture(scope="module")
+def em(dtabs):
+    """an EntropyModel whose tables are those of the cases, on the device"""
+    from icm_amd.entropy_models import EntropyModel
+    m = EntropyModel()
+    m._quantized_cdf, m._cdf_length, m._offset = dtabs
+    return m
+
+
+@pytest.mark.parametrize("coder", ["host", "lanes"])
+@pytest.mark.parametrize("name", ["r10_unequal", "n5000_g3"])
+def test_coder_objects_encode_and_decode_run_by_run(name, coder, tabs, em):
+    """coder_for(...) on device tensors: the bytes of the function it wraps, and the symbols back exactly.  Ten runs
+    in G = 3 bodies, and 5000 symbols with escapes on both sides of every table.  (Not the case made of the ends of
+    int32: the scalar stream's decoder refuses INT32_MAX under a negative offset, tests/test_rans_lanes.py.)"""
+    from icm_amd import ans
+    sym, idx, runs, spw, G = K.cases()[name]
+    v = sym.astype(np.int64) - np.array(K.OFFSETS)[idx]
+    assert G == 3 and (v < 0).any() and (v >= np.array(K.SIZES)[idx] - 2).any()
+    assert len(runs) > 1 or name != "r10_unequal"
+    want = {"host": lambda: ans._encode(sym, idx, tabs), "lanes": lambda: ans.lanes_encode(sym, idx, runs, tabs, spw)}
+    c = ans.coder_for(coder, spw)
+    d_sym, d_idx = _t(sym), _t(idx)
+    string = c.encode(d_sym, d_idx, runs, em)
+    assert string == want[coder]()
+    dec, out, pos = c.decoder(string, em), [], 0
+    try:
+        for n in runs:
+            out.append(dec.decode_run(d_idx[pos:pos + n]))
+            pos += n
+        dec.finish()
+    finally:
+        dec.close()
+    got = torch.cat(out)
+    assert got.dtype == torch.int32 and got.device == d_idx.device and torch.equal(got, d_sym)
 
 
 # ------------------------------------------------------------------------------------------------------ model level

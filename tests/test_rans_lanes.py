@@ -1,7 +1,8 @@
 """CPU: the host implementation of the lane-stream format (csrc/rans.cpp ``icm_rans_lanes_*`` through
 ``icm_amd.ans``) against the exact-integer restatement of the format (tests/_lanes_ref.py), byte for byte and round
 trip, on the cases of tests/_lanes_cases.py; corrupt streams, which the host decoder must refuse exactly where the
-restatement does; and the coder id of the ICMB container (icm_amd/bitstream.py)."""
+restatement does; the coder objects of ``icm_amd.ans.coder_for`` (the host one on CPU tensors); and the coder id of
+the ICMB container (icm_amd/bitstream.py)."""
 import struct
 import zlib
 
@@ -122,6 +123,62 @@ def test_wrong_indexes_are_reported_not_read(tabs):
     wrong[7] = 99
     with pytest.raises(ValueError, match="CDF index"):
         ans.lanes_decode(stream, wrong, runs, tabs)
+
+
+# ------------------------------------------------------------------------------------------------------ coder objects
+@pytest.fixture(scope="module")
+def em():
+    """an EntropyModel on the CPU whose tables are those of the cases"""
+    import torch
+    from icm_amd.entropy_models import EntropyModel
+    m = EntropyModel()
+    m._quantized_cdf, m._cdf_length, m._offset = (torch.from_numpy(a) for a in K.tables_np())
+    return m
+
+
+@pytest.mark.parametrize("name", list(K.cases()))
+def test_host_coder_object_is_the_rans_classes(name, em):
+    """coder_for("host") on CPU tensors: the bytes of RansEncoder, and run by run what RansDecoder gives -- the
+    symbols, or its refusal: the scalar stream's decoder checks an escape against int32 before it adds the table's
+    offset, so it refuses INT32_MAX under a negative offset, which only the case made of the ends of int32 holds"""
+    import torch
+    from icm_amd import ans
+    sym, idx, runs, _, _ = K.cases()[name]
+    lists = [a.tolist() for a in K.tables_np()]
+    coder = ans.coder_for("host")
+    string = coder.encode(torch.from_numpy(sym), torch.from_numpy(idx), runs, em)
+    assert string == ans.RansEncoder().encode_with_indexes(sym.tolist(), idx.tolist(), *lists)
+    ref = ans.RansDecoder()
+    ref.set_stream(string)
+    dec, pos, refused = coder.decoder(string, em), 0, False
+    for n in runs:
+        try:
+            want = ref.decode_stream(idx[pos:pos + n].tolist(), *lists)
+        except ValueError:
+            refused = True
+            with pytest.raises(ValueError, match="rANS decode"):
+                dec.decode_run(torch.from_numpy(idx[pos:pos + n]))
+            break
+        got = dec.decode_run(torch.from_numpy(idx[pos:pos + n]))
+        assert got.dtype == torch.int32 and got.device.type == "cpu" and tuple(got.shape) == (n,)
+        assert got.tolist() == want == sym[pos:pos + n].tolist()
+        pos += n
+    assert refused == (name == "escapes_int32_ends")
+    dec.finish()
+    dec.close()
+    with pytest.raises(ValueError, match="run_lengths"):
+        coder.encode(torch.from_numpy(sym), torch.from_numpy(idx), runs + [1], em)
+
+
+def test_coder_for_checks_the_name_and_resolves_the_default():
+    from icm_amd import ans
+    from icm_amd import bitstream as B
+    with pytest.raises(ValueError, match=r"unknown coder 'nope'; choose from \['host', 'lanes'\]"):
+        ans.coder_for("nope")
+    assert ans.coder_for("lanes", None).symbols_per_wave == ans.SYMBOLS_PER_WAVE == 16384
+    assert ans.coder_for("lanes", 100).symbols_per_wave == 100
+    assert ans.CODERS is B.CODERS and ans.check_coder is B.check_coder
+    assert [ans.coder_for(n).name for n in ans.CODERS] == list(ans.CODERS)
 
 
 # ------------------------------------------------------------------------------------------------------ container
