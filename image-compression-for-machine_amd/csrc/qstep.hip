@@ -1,0 +1,150 @@
+// Quantiser step on the latent y (the codec's quality knob), gfx950.  Parity unpinned: no counterpart in the reference.
+//
+// With a step D = 2^(k/8) the codec codes round((y - mu) / D) under the predicted Gaussian of scale sigma / D and
+// rebuilds y_hat = s D + mu.  The host passes two floats, `step` = D and `inv` = 1 / D, both derived from k in one
+// place (icm_amd/bitstream.py: step_of); the arithmetic below is all f32, every operation rounded once:
+//
+//     t = y - mu;  u = t * inv;  s = rint(u) clamped to +-2^30;  symbol = (int)s
+//     y_hat = ((float)symbol * step) + mu            a multiply, then an add: never an FMA
+//     se = max(scale, scale_bound) * inv
+//     index = (ns - 1) - #{ j < ns - 1 : se <= table[j] }       the count of gc_build_indexes_kernel (entropy.hip)
+//
+// The decoder has the integer symbol, mu and scale, and must arrive at the encoder's y_hat and index bit for bit:
+// `yh_of` and `index_of` are the only statements of those two expressions, and the encoder's fused kernel and the
+// decoder's two kernels all call them.  (y_hat is formed from the symbol after its trip through int, in the encoder
+// too, so a -0 of rint is the +0 the decoder sees.)  With step = inv = 1 the symbols are icm_quantize's, the indexes
+// icm_gc_build_indexes' and y_hat the fused forward's.
+//
+// Memory-bound elementwise work on [N][C][HW] operands that are channel slices of wider buffers (an element batch
+// stride per float operand; the int32 outputs are dense): one element per lane and pass, consecutive lanes on
+// consecutive addresses, a grid-stride loop.  The table index j is wave-uniform, so the 64-entry table is read
+// through the scalar cache; no LDS.  A slice of the largest image one compress() call takes has under a million
+// elements: the grid is capped at one 256-thread workgroup per CU, which covers it in a few passes (measured: 19 us
+// for the fused kernel on the 786 432 elements of a 2048x3072 image's slice, against 45 us for the three launches it
+// replaces).
+#include <algorithm>
+#include <cmath>
+#include "icm_common.h"
+
+namespace icm {
+
+// One rounding each, never fused (the reasoning is at the same pair in imageio.hip: under contract(off) the operators
+// stay a v_mul / v_add pair, where __fmul_rn / __fadd_rn get folded into an FMA).
+__device__ __forceinline__ float mul_rn(float a, float b) {
+#pragma clang fp contract(off)
+  return a * b;
+}
+__device__ __forceinline__ float add_rn(float a, float b) {
+#pragma clang fp contract(off)
+  return a + b;
+}
+
+constexpr float SYMBOL_MAX = 1073741824.0f;   // 2^30: the cast to int is defined for every finite input
+
+__device__ __forceinline__ int symbol_of(float y, float mu, float inv) {
+  const float s = rintf(mul_rn(y - mu, inv));   // half to even
+  return (int)fminf(fmaxf(s, -SYMBOL_MAX), SYMBOL_MAX);
+}
+__device__ __forceinline__ float yh_of(int symbol, float mu, float step) {
+  return add_rn(mul_rn((float)symbol, step), mu);
+}
+__device__ __forceinline__ int index_of(float scale, float bound, float inv, const float* __restrict__ table, int ns) {
+  const float se = mul_rn(fmaxf(scale, bound), inv);
+  int v = ns - 1;
+#pragma unroll 8   // j is wave-uniform: eight entries per scalar load and wait
+  for (int j = 0; j < ns - 1; ++j) v -= (se <= table[j]) ? 1 : 0;
+  return v;
+}
+
+// shape and batch strides (elements) of the operands; a stride of an operand a kernel does not take is unused
+struct QGeom {
+  long long y_bs, mu_bs, sc_bs, yh_bs;
+  int N, C, HW;
+};
+
+// encoder: symbols, indexes and y_hat (into its strided slot) of one slice in one launch
+__global__ __launch_bounds__(256) void gc_code_q_kernel(const float* __restrict__ y, const float* __restrict__ mu,
+                                                         const float* __restrict__ sc, const float* __restrict__ table,
+                                                         int ns, float bound, float step, float inv,
+                                                         int* __restrict__ sym, int* __restrict__ idx,
+                                                         float* __restrict__ yh, const QGeom g) {
+  const long long per = (long long)g.C * g.HW, total = per * g.N;
+  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total;
+       i += (long long)gridDim.x * blockDim.x) {
+    const long long n = i / per, r = i - n * per;
+    const float m = mu[n * g.mu_bs + r];
+    const int s = symbol_of(y[n * g.y_bs + r], m, inv);
+    sym[i] = s;
+    idx[i] = index_of(sc[n * g.sc_bs + r], bound, inv, table, ns);
+    yh[n * g.yh_bs + r] = yh_of(s, m, step);
+  }
+}
+// decoder, before the entropy decoder's run: scale -> indexes
+__global__ __launch_bounds__(256) void gc_indexes_q_kernel(const float* __restrict__ sc, const float* __restrict__ table,
+                                                            int ns, float bound, float inv, int* __restrict__ idx,
+                                                            const QGeom g) {
+  const long long per = (long long)g.C * g.HW, total = per * g.N;
+  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total;
+       i += (long long)gridDim.x * blockDim.x) {
+    const long long n = i / per, r = i - n * per;
+    idx[i] = index_of(sc[n * g.sc_bs + r], bound, inv, table, ns);
+  }
+}
+// decoder, after it: symbols, mu -> y_hat
+__global__ __launch_bounds__(256) void dequantize_q_kernel(const int* __restrict__ sym, const float* __restrict__ mu,
+                                                            float step, float* __restrict__ yh, const QGeom g) {
+  const long long per = (long long)g.C * g.HW, total = per * g.N;
+  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total;
+       i += (long long)gridDim.x * blockDim.x) {
+    const long long n = i / per, r = i - n * per;
+    yh[n * g.yh_bs + r] = yh_of(sym[i], mu[n * g.mu_bs + r], step);
+  }
+}
+
+}  // namespace icm
+
+using namespace icm;
+
+static inline bool step_ok(float v) { return std::isfinite(v) && v > 0.0f; }
+static inline bool dims_ok(int N, int C, int HW) { return N >= 1 && C >= 1 && HW >= 1; }
+static inline int q_blocks(long long total) {
+  return (int)std::max<long long>(1, std::min<long long>((total + 255) / 256, 256));
+}
+
+extern "C" {
+
+int icm_gc_code_q(const float* y, int64_t y_bs, const float* mu, int64_t mu_bs, const float* scale, int64_t sc_bs,
+                  const float* scale_table, int ns, float scale_bound, float step, float inv, int32_t* symbols,
+                  int32_t* indexes, float* yh, int64_t yh_bs, int N, int C, int HW, void* stream) {
+  if (!y || !mu || !scale || !scale_table || !symbols || !indexes || !yh) return ICM_ERR_ARG;
+  if (!step_ok(step) || !step_ok(inv) || ns < 1 || !dims_ok(N, C, HW)) return ICM_ERR_ARG;
+  const QGeom g{y_bs, mu_bs, sc_bs, yh_bs, N, C, HW};
+  hipLaunchKernelGGL(gc_code_q_kernel, dim3(q_blocks((long long)N * C * HW)), dim3(256), 0, (hipStream_t)stream, y, mu,
+                     scale, scale_table, ns, scale_bound, step, inv, symbols, indexes, yh, g);
+  ICM_CHECK_LAUNCH();
+  return ICM_OK;
+}
+
+int icm_gc_indexes_q(const float* scale, int64_t sc_bs, const float* scale_table, int ns, float scale_bound, float inv,
+                     int32_t* indexes, int N, int C, int HW, void* stream) {
+  if (!scale || !scale_table || !indexes) return ICM_ERR_ARG;
+  if (!step_ok(inv) || ns < 1 || !dims_ok(N, C, HW)) return ICM_ERR_ARG;
+  const QGeom g{0, 0, sc_bs, 0, N, C, HW};
+  hipLaunchKernelGGL(gc_indexes_q_kernel, dim3(q_blocks((long long)N * C * HW)), dim3(256), 0, (hipStream_t)stream,
+                     scale, scale_table, ns, scale_bound, inv, indexes, g);
+  ICM_CHECK_LAUNCH();
+  return ICM_OK;
+}
+
+int icm_dequantize_q(const int32_t* symbols, const float* mu, int64_t mu_bs, float step, float* yh, int64_t yh_bs, int N,
+                     int C, int HW, void* stream) {
+  if (!symbols || !mu || !yh) return ICM_ERR_ARG;
+  if (!step_ok(step) || !dims_ok(N, C, HW)) return ICM_ERR_ARG;
+  const QGeom g{0, mu_bs, 0, yh_bs, N, C, HW};
+  hipLaunchKernelGGL(dequantize_q_kernel, dim3(q_blocks((long long)N * C * HW)), dim3(256), 0, (hipStream_t)stream,
+                     symbols, mu, step, yh, g);
+  ICM_CHECK_LAUNCH();
+  return ICM_OK;
+}
+
+}  // extern "C"

@@ -27,6 +27,14 @@ A stream of two strings therefore carries ``HEADER_BYTES_2`` = 46 bytes besides 
 what ``bpp`` is computed from.  ``unpack`` raises ``ValueError`` -- and nothing else -- for anything that is not
 exactly one such stream; each message names the condition that failed.
 
+Quantiser step -- a stream coded with a step on the latent y (``step_of``: step index k in ``QSTEP_MIN`` .. ``QSTEP_MAX``
+= -16 .. 32, step = 2^(k/8); k = 0 is no step) carries a third string of exactly one byte after the y and z strings:
+k as a signed byte (``qstep_string`` / ``qstep_from_strings``).  It is written only when k != 0 -- a stream without a
+step is byte for byte what it was before the step existed -- and a stored 0, a k outside the range or a third string
+of another length is refused, so one content has one encoding.  Only k is stored; both sides derive the two floats
+the kernels use from it.  The fixed header, the version and the coder ids are unchanged: a reader from before the step
+refuses a stepped stream for its string count ("holds 3", exit code 4 of the CLI) instead of decoding garbage.
+
 A tiled image is a second container with its own magic: a grid of independently coded tiles (``tile_grid`` below gives
 the grid), each of them one complete ``ICMB`` stream.  ``ICMB`` and ``unpack`` are unchanged by it, and each reader
 refuses the other's files for their magic.
@@ -47,7 +55,8 @@ refuses the other's files for their magic.
        end-4     4  CRC-32 of every byte before it
 
 rows / cols are redundant with the four numbers before them, and a reader refuses a file in which they disagree.
-The coder id lives in the tile streams alone: the high byte of the ICMT architecture field stays zero.
+The coder id lives in the tile streams alone: the high byte of the ICMT architecture field stays zero.  So does the
+quantiser step: every tile stream of a stepped image carries its own byte (the encoder writes the same k in all).
 
 Lane stream -- the string format of coder id 1, made to be coded by one GPU wave per body (csrc/rans_lanes.hip; the
 executable definition is csrc/rans_lanes_common.h, the arithmetic of a lane's step that host and kernels both compile,
@@ -204,6 +213,52 @@ def unpack(data: bytes) -> Tuple[Dict, List[bytes]]:
     header = {"arch": ARCHS[arch_id], "height": height, "width": width, "pads": (pl, pr, pt, pb), "shape": (zh, zw),
               "fingerprint": fp}
     return header, strings
+
+
+# ------------------------------------------------------------------------------------------------- quantiser step
+QSTEP_MIN, QSTEP_MAX = -16, 32              # step index k: step = 2^(k/8), 0.25 .. 16; 0 = no step
+
+
+def check_qstep(k, who: str = "") -> int:
+    """``k`` as an int if it is an integer in [QSTEP_MIN, QSTEP_MAX], ValueError otherwise"""
+    if isinstance(k, bool) or not isinstance(k, int) and not hasattr(k, "__index__"):
+        raise ValueError(f"{who}qstep must be an integer, got {k!r}")
+    k = int(k)
+    if not QSTEP_MIN <= k <= QSTEP_MAX:
+        raise ValueError(f"{who}qstep = {k} outside [{QSTEP_MIN}, {QSTEP_MAX}]")
+    return k
+
+
+def step_of(k) -> Tuple[float, float]:
+    """(step, inv) of step index k, each the value of an f32: step = f32(2^(k/8)), inv = f32(1 / step).  The one place
+    the two floats the kernels take are derived; encoder and decoder both call it, and only k is stored."""
+    k = check_qstep(k, "bitstream: ")
+    step = struct.unpack("<f", struct.pack("<f", 2.0 ** (k / 8)))[0]
+    return step, struct.unpack("<f", struct.pack("<f", 1.0 / step))[0]
+
+
+def qstep_string(k) -> bytes:
+    """the third string of a stepped stream: k as one signed byte.  k = 0 has no string (ValueError)."""
+    k = check_qstep(k, "bitstream: ")
+    if k == 0:
+        raise ValueError("bitstream: qstep 0 is written as no string at all")
+    return struct.pack("<b", k)
+
+
+def qstep_from_strings(strings: Sequence[bytes]) -> int:
+    """step index of the flattened strings of a cnn / stf stream: 0 for two strings, the signed byte for three.
+    ValueError for any other count, a third string that is not one byte, a k outside the range, or a stored 0."""
+    if len(strings) == 2:
+        return 0
+    if len(strings) != 3:
+        raise ValueError(f"bitstream: a stream holds two strings, or three with a quantiser step; this one holds "
+                         f"{len(strings)}")
+    if len(strings[2]) != 1:
+        raise ValueError(f"bitstream: the quantiser-step string must be one byte, this one has {len(strings[2])}")
+    k = check_qstep(struct.unpack("<b", bytes(strings[2]))[0], "bitstream: stored ")
+    if k == 0:
+        raise ValueError("bitstream: a stored qstep of 0 (a stream without a step has two strings)")
+    return k
 
 
 def fingerprint(model) -> int:

@@ -1,6 +1,7 @@
 """``python -m icm_amd.codec`` -- image file to bit-stream file and back, in two processes that share a checkpoint.
 
     python -m icm_amd.codec encode IMAGE -o FILE -a cnn -p CKPT [--tile N [--overlap M]] [--coder {host,lanes}]
+                                   [--qstep K | --target-bytes N | --target-bpp F]
     python -m icm_amd.codec decode FILE -o IMAGE.png -p CKPT [--reference IMAGE] [--region Y0,X0,H,W]
 
 Parity unpinned: no counterpart in the reference (upstream CompressAI's ``examples/codec.py`` is not in its tree).  The
@@ -22,7 +23,13 @@ decoder adds the decoded tiles into an f32 canvas, their overlap bands weighted 
 
 ``--coder lanes`` codes the strings as lane streams on the device (csrc/rans_lanes.hip; format in
 ``icm_amd.bitstream``) instead of the host's scalar stream, the default.  The stream records its coder, so ``decode``
-takes no flag."""
+takes no flag.
+
+``--qstep K`` is the quality knob of one checkpoint: a scalar quantiser step 2^(K/8) on the latent y, K in -16 .. 32
+(csrc/qstep.hip; ``icm_amd.bitstream`` for how K travels).  K = 0, the default, is the codec without a step, and its
+files are byte for byte what they were.  ``--target-bytes`` / ``--target-bpp`` search K for a budget with real encodes
+as probes (``search_qstep``: at most 8, the analysis transform run once); a budget the coarsest step misses exits 4
+and writes nothing.  ``decode`` reads K from the stream.  Parity unpinned: no counterpart in the reference."""
 from __future__ import annotations
 
 import argparse
@@ -154,24 +161,65 @@ def image_tile_blend(x: torch.Tensor, pads: Tuple[int, int, int, int], canvas: t
           "image_tile_blend")
 
 
-def _encode_one(model, arch: str, fp: int, u8: torch.Tensor, coder: str = "host",
-                symbols_per_wave: Optional[int] = None) -> bytes:
-    H, W = u8.size(0), u8.size(1)
-    pads = center_pads(H, W)
-    enc = model.compress(image_u8_to_f32(u8, pads), coder=coder, symbols_per_wave=symbols_per_wave)
+def _pack_one(arch: str, fp: int, H: int, W: int, pads, enc: Dict, coder: str) -> bytes:
+    """the ICMB stream of one ``compress()`` result; a quantiser step travels as a third, one-byte string"""
     header = {"arch": arch, "height": H, "width": W, "pads": pads, "shape": tuple(int(s) for s in enc["shape"]),
               "fingerprint": fp}
-    return B.pack(header, [s for part in enc["strings"] for s in part], coder=coder)
+    strings = [s for part in enc["strings"] for s in part]
+    if enc["qstep"]:
+        strings.append(B.qstep_string(enc["qstep"]))
+    return B.pack(header, strings, coder=coder)
+
+
+def _encode_one(model, arch: str, fp: int, u8: torch.Tensor, coder: str = "host",
+                symbols_per_wave: Optional[int] = None, qstep: int = 0) -> bytes:
+    H, W = u8.size(0), u8.size(1)
+    pads = center_pads(H, W)
+    enc = model.compress(image_u8_to_f32(u8, pads), coder=coder, symbols_per_wave=symbols_per_wave, qstep=qstep)
+    return _pack_one(arch, fp, H, W, pads, enc, coder)
+
+
+def search_qstep(fits, lo: int = B.QSTEP_MIN, hi: int = B.QSTEP_MAX) -> Tuple[int, int]:
+    """Smallest step index the bisection finds whose encode fits a budget -> (k, number of probes).  ``fits(k)`` makes
+    the encode at k and says whether it fits; the size need not be monotone in k, and the guarantee asks for nothing
+    of it: fits(k) was seen true, and k == lo or fits(k - 1) was seen false.  ``hi`` is probed first (ValueError if
+    even the coarsest step does not fit), then ``lo`` (returned if it fits), then the integers between are bisected
+    under the invariant "lo does not fit, hi fits": 2 + ceil(log2(hi - lo)) probes at the most, 8 over -16 .. 32.
+    Pure host code."""
+    if hi < lo:
+        raise ValueError(f"search_qstep: empty range [{lo}, {hi}]")
+    probes = 1
+    if not fits(hi):
+        raise ValueError(f"search_qstep: the budget is out of reach: the encode at the coarsest step, qstep = {hi}, "
+                         f"does not fit")
+    if hi == lo:
+        return hi, probes
+    probes += 1
+    if fits(lo):
+        return lo, probes
+    while hi - lo > 1:
+        mid = (lo + hi) // 2
+        probes += 1
+        if fits(mid):
+            hi = mid
+        else:
+            lo = mid
+    return hi, probes
 
 
 @torch.no_grad()
-def encode_image(model, img, tile: Optional[int] = None, overlap: int = 0, coder: str = "host",
-                 symbols_per_wave: Optional[int] = None) -> bytes:
-    """8-bit [H, W, 3] image (tensor on any device, or anything ``numpy.asarray`` accepts) -> one bit-stream.  With
-    ``tile``, an image of more than one tile (``plan_tiles``) becomes an ICMT stream whose tile k is
-    ``encode_image(model, crop k)``, the tiles coded one after another; an image of one tile is written untiled.
-    ``coder`` / ``symbols_per_wave``: as ``model.compress``; every ICMB stream records its coder."""
+def encode_image_info(model, img, tile: Optional[int] = None, overlap: int = 0, coder: str = "host",
+                      symbols_per_wave: Optional[int] = None, qstep: int = 0,
+                      max_bytes: Optional[int] = None) -> Tuple[bytes, Dict]:
+    """``encode_image`` with its outcome: (stream, {"qstep": k, "step": 2^(k/8), "probes": encodes made})"""
     B.check_coder(coder, "codec: ")
+    qstep = B.check_qstep(qstep, "codec: ")
+    if max_bytes is not None:
+        if qstep != 0:
+            raise ValueError("codec: give a quantiser step or a byte budget, not both")
+        if isinstance(max_bytes, bool) or not hasattr(max_bytes, "__index__") or int(max_bytes) < 1:
+            raise ValueError(f"codec: max_bytes must be a positive integer, got {max_bytes!r}")
+        max_bytes = int(max_bytes)
     arch = _ready(model)
     device = next(model.parameters()).device
     u8 = _as_u8_image(img, device)
@@ -183,12 +231,54 @@ def encode_image(model, img, tile: Optional[int] = None, overlap: int = 0, coder
     else:
         plan = plan_tiles(H, W, tile, overlap)[2]
     fp = B.fingerprint(model)
-    if len(plan) == 1:
-        return _encode_one(model, arch, fp, u8, coder, symbols_per_wave)
-    streams = [_encode_one(model, arch, fp, u8[y0:y0 + h, x0:x0 + w].contiguous(), coder, symbols_per_wave)
-               for y0, x0, h, w in plan]
-    return B.pack_tiled({"arch": arch, "height": H, "width": W, "tile": tile, "overlap": overlap, "fingerprint": fp},
-                        streams)
+    outer = {"arch": arch, "height": H, "width": W, "tile": tile, "overlap": overlap, "fingerprint": fp}
+    crops = [u8] if len(plan) == 1 else [u8[y0:y0 + h, x0:x0 + w].contiguous() for y0, x0, h, w in plan]
+
+    def wrap(streams):
+        return streams[0] if len(plan) == 1 else B.pack_tiled(outer, streams)
+
+    if max_bytes is None:
+        data = wrap([_encode_one(model, arch, fp, c, coder, symbols_per_wave, qstep) for c in crops])
+        return data, {"qstep": qstep, "step": B.step_of(qstep)[0], "probes": 1}
+    # encode to size: the analysis transform once per tile, then only the latent coder per probe; a probe is the very
+    # container that would be written (headers, CRCs and the lanes coder's flushes included), and the answer is the
+    # stream of its probe, not a second encode
+    tiles = []
+    for c in crops:
+        pads = center_pads(c.size(0), c.size(1))
+        tiles.append((c.size(0), c.size(1), pads, model.analysis(image_u8_to_f32(c, pads))))
+    sizes, kept = {}, {}
+
+    def fits(k):
+        data = wrap([_pack_one(arch, fp, h, w, pads, model.compress_latent(y, coder=coder,
+                                                                           symbols_per_wave=symbols_per_wave, qstep=k),
+                               coder) for h, w, pads, y in tiles])
+        sizes[k] = len(data)
+        if len(data) <= max_bytes:
+            kept.clear()
+            kept[k] = data
+            return True
+        return False
+
+    try:
+        k, probes = search_qstep(fits)
+    except ValueError:
+        raise ValueError(f"codec: {max_bytes} bytes are out of reach: the coarsest step (qstep {B.QSTEP_MAX}) still "
+                         f"takes {min(sizes.values())} bytes")
+    return kept[k], {"qstep": k, "step": B.step_of(k)[0], "probes": probes}
+
+
+def encode_image(model, img, tile: Optional[int] = None, overlap: int = 0, coder: str = "host",
+                 symbols_per_wave: Optional[int] = None, qstep: int = 0, max_bytes: Optional[int] = None) -> bytes:
+    """8-bit [H, W, 3] image (tensor on any device, or anything ``numpy.asarray`` accepts) -> one bit-stream.  With
+    ``tile``, an image of more than one tile (``plan_tiles``) becomes an ICMT stream whose tile k is
+    ``encode_image(model, crop k)``, the tiles coded one after another; an image of one tile is written untiled.
+    ``coder`` / ``symbols_per_wave``: as ``model.compress``; every ICMB stream records its coder.
+    ``qstep``: step index of a quantiser step on the latent (``model.compress``; 0, the default: none, and the stream
+    is what it was before the step existed).  ``max_bytes`` (instead of ``qstep``): the finest step ``search_qstep``
+    finds at which the whole stream, of all tiles with one step, has at most that many bytes; ValueError if the
+    coarsest step does not get there.  ``encode_image_info`` also returns the step and the number of encodes."""
+    return encode_image_info(model, img, tile, overlap, coder, symbols_per_wave, qstep, max_bytes)[0]
 
 
 def _check_model(header: Dict, arch: str, fp: int, what: str = "the stream") -> None:
@@ -199,14 +289,21 @@ def _check_model(header: Dict, arch: str, fp: int, what: str = "the stream") -> 
                          f"{header['fingerprint']:#010x}, this checkpoint has {fp:#010x}")
 
 
-def _check_strings(arch: str, strings, what: str = "this one") -> None:
-    if len(strings) != 2:
-        raise ValueError(f"codec: {arch} streams hold two strings, {what} holds {len(strings)}")
+def _check_strings(arch: str, strings, what: str = "this one") -> int:
+    """the stream's quantiser step index: two strings, or three with a valid step byte (``B.qstep_from_strings``)"""
+    if len(strings) not in (2, 3):
+        raise ValueError(f"codec: {arch} streams hold two strings, or three with a quantiser step; {what} holds "
+                         f"{len(strings)}")
+    try:
+        return B.qstep_from_strings(strings)
+    except ValueError as e:
+        raise ValueError(f"codec: {what}: {e}")
 
 
 def _decompress_one(model, arch: str, header: Dict, strings, coder: str = "host") -> torch.Tensor:
     H, W, pads = header["height"], header["width"], header["pads"]
-    x_hat = model.decompress([[strings[0]], [strings[1]]], header["shape"], coder=coder)["x_hat"]
+    x_hat = model.decompress([[strings[0]], [strings[1]]], header["shape"], coder=coder,
+                             qstep=B.qstep_from_strings(strings))["x_hat"]
     left, right, top, bottom = pads
     if tuple(x_hat.shape) != (1, 3, top + H + bottom, left + W + right):
         raise ValueError(f"codec: latent shape {header['shape']} decodes to {tuple(x_hat.shape)}, not to a padded "
@@ -235,7 +332,8 @@ def decode_image(model, data: bytes, reference=None, region=None) -> Tuple[torch
     length / (H W), header included, and, given ``reference`` (the original 8-bit image), "psnr" of the two 8-bit
     images.  ``region`` = (y0, x0, h, w): only that window is returned ([h, w, 3]; "sse" / "psnr" are over it, against
     the same window of ``reference``); of a tiled stream only the tiles that touch it are decoded
-    (``info["tiles_decoded"]``), and the result is bit for bit the same crop of the full decode."""
+    (``info["tiles_decoded"]``), and the result is bit for bit the same crop of the full decode.  "qstep": the step
+    index the stream was coded with (0: none), or the list per tile should they differ."""
     arch = _ready(model)
     fp = B.fingerprint(model)
     device = next(model.parameters()).device
@@ -247,9 +345,10 @@ def decode_image(model, data: bytes, reference=None, region=None) -> Tuple[torch
         rows, cols, plan = plan_tiles(H, W, outer["tile"], outer["overlap"])
         inner = [B.unpack(s) for s in streams]          # every header checked before any payload is decoded
         coders = [B.coder_of(s) for s in streams]
+        qsteps = []
         for k, ((y0, x0, h, w), (hd, tile_strings)) in enumerate(zip(plan, inner)):
             _check_model(hd, arch, fp, f"tile {k}")
-            _check_strings(arch, tile_strings, f"tile {k}")
+            qsteps.append(_check_strings(arch, tile_strings, f"tile {k}"))
             if (hd["height"], hd["width"]) != (h, w):
                 raise ValueError(f"codec: tile {k} holds a {hd['height']}x{hd['width']} image, the plan has {h}x{w}")
     else:
@@ -257,14 +356,15 @@ def decode_image(model, data: bytes, reference=None, region=None) -> Tuple[torch
         coder = B.coder_of(data)
         _check_model(header, arch, fp)
         H, W = header["height"], header["width"]
-        _check_strings(arch, strings)
+        qsteps = [_check_strings(arch, strings)]
     ry, rx, rh, rw = _check_region(region, H, W)
     ref = None if reference is None else _as_u8_image(reference, device, "reference")
     if ref is not None and tuple(ref.shape) != (H, W, 3):
         raise ValueError(f"codec: the reference is {ref.size(0)}x{ref.size(1)}, the stream holds a {H}x{W} image")
     if ref is not None and region is not None:
         ref = ref[ry:ry + rh, rx:rx + rw].contiguous()
-    info = {"arch": arch, "height": H, "width": W, "bytes": len(data), "bpp": 8.0 * len(data) / (H * W)}
+    info = {"arch": arch, "height": H, "width": W, "bytes": len(data), "bpp": 8.0 * len(data) / (H * W),
+            "qstep": qsteps[0] if len(set(qsteps)) == 1 else qsteps}
     if tiled:
         sel = [k for k, (y0, x0, h, w) in enumerate(plan)
                if y0 < ry + rh and ry < y0 + h and x0 < rx + rw and rx < x0 + w]
@@ -333,6 +433,13 @@ def setup_args() -> argparse.ArgumentParser:
                      help="pixels neighbouring tiles share, blended by the decoder (needs --tile; at most N / 2)")
     enc.add_argument("--coder", default="host", choices=list(B.CODERS),
                      help="entropy coder of the strings: the host's scalar stream, or lane streams coded on the GPU")
+    enc.add_argument("--qstep", default=None, type=int, metavar="K",
+                     help=f"quantiser step 2^(K/8) on the latent, K in {B.QSTEP_MIN}..{B.QSTEP_MAX} (0: none; larger: "
+                          f"smaller file)")
+    enc.add_argument("--target-bytes", default=None, type=int, metavar="N",
+                     help="the finest quantiser step at which the file has at most N bytes")
+    enc.add_argument("--target-bpp", default=None, type=float, metavar="F",
+                     help="the same for floor(F x height x width / 8) bytes")
     for s in (enc, dec):
         s.add_argument("-o", "--output", required=True, help="file to write")
         s.add_argument("-p", "--path", dest="paths", required=True, type=str, help="checkpoint path")
@@ -363,6 +470,19 @@ def main(argv) -> int:
         except ValueError as e:
             print(f"Error: {e}", file=sys.stderr)
             return 2
+    if args.command == "encode":
+        try:
+            if sum(v is not None for v in (args.qstep, args.target_bytes, args.target_bpp)) > 1:
+                raise ValueError("give at most one of --qstep, --target-bytes and --target-bpp")
+            if args.qstep is not None:
+                B.check_qstep(args.qstep, "--")
+            if args.target_bytes is not None and args.target_bytes < 1:
+                raise ValueError(f"--target-bytes must be at least 1, got {args.target_bytes}")
+            if args.target_bpp is not None and not (args.target_bpp > 0 and math.isfinite(args.target_bpp)):
+                raise ValueError(f"--target-bpp must be a positive number, got {args.target_bpp}")
+        except ValueError as e:
+            print(f"Error: {e}", file=sys.stderr)
+            return 2
     try:
         if args.command == "encode":
             payload = read_image_u8(args.input)
@@ -388,14 +508,16 @@ def main(argv) -> int:
         torch.cuda.synchronize()
         t0 = time.perf_counter()
         if args.command == "encode":
-            data = encode_image(model, payload, args.tile, args.overlap, coder=args.coder)
+            h, w = payload.shape[:2]
+            budget = args.target_bytes if args.target_bpp is None else int(math.floor(args.target_bpp * h * w / 8))
+            data, found = encode_image_info(model, payload, args.tile, args.overlap, coder=args.coder,
+                                            qstep=args.qstep or 0, max_bytes=budget)
             torch.cuda.synchronize()
             dt = time.perf_counter() - t0
-            h, w = payload.shape[:2]
             with open(args.output, "wb") as f:
                 f.write(data)
             report = {"command": "encode", "arch": arch, "height": h, "width": w, "bytes": len(data),
-                      "bpp": 8.0 * len(data) / (h * w), "encode_time": dt}
+                      "bpp": 8.0 * len(data) / (h * w), "encode_time": dt, **found}
         else:
             img, info = decode_image(model, payload, reference, args.region)
             torch.cuda.synchronize()

@@ -22,6 +22,7 @@ import torch
 from . import _lib as L
 from ._lib import (ACT_GELU, ACT_NONE, ACT_SQUARE, EPI_AXPY2, EPI_GDN, EPI_IGDN, EPI_LRP, EPI_MUL_DGELU, EPI_NONE,
                    EPI_RES, EPI_RES_GELU, EPI_RES_MUL_DGELU, bs, check, ptr)
+from .bitstream import step_of
 
 PEDESTAL = 2.0 ** -36
 _SKIP_WGRAD = _os.environ.get("ICM_DEBUG_SKIP_WGRAD", "0") == "1"
@@ -1237,6 +1238,35 @@ def gc_likelihood_ste(tape, y, mu, scale, noise, lik_out, yh_out, yh2_out=None, 
                                                     lik_bound, acc, tape.st), "gc_bwd")
         tape.bw.append(bwd)
 
+
+# ---- quantiser step on y (csrc/qstep.hip; inference only: the codec's compress / decompress).  ``qstep`` is the step
+# index k; the two floats the kernels take come from bitstream.step_of on both sides.  ``st``: the stream to launch on.
+def gc_code_q(st, y, mu, scale, table, scale_bound, qstep, yh_out):
+    """encoder, one launch per slice: (symbols, CDF indexes), both dense int32 of y's shape; y_hat_pre -> yh_out"""
+    step, inv = step_of(qstep)
+    N, Cc, H, W = y.shape
+    sym = torch.empty((N, Cc, H, W), dtype=torch.int32, device=y.device)
+    idx = torch.empty((N, Cc, H, W), dtype=torch.int32, device=y.device)
+    check(L.lib().icm_gc_code_q(ptr(y), bs(y), ptr(mu), bs(mu), ptr(scale), bs(scale), ptr(table), int(table.numel()),
+                                scale_bound, step, inv, sym.data_ptr(), idx.data_ptr(), ptr(yh_out), bs(yh_out), N, Cc,
+                                H * W, st), "gc_code_q")
+    return sym, idx
+
+
+def gc_indexes_q(st, scale, table, scale_bound, qstep):
+    """decoder, before the entropy decoder's run: the CDF indexes the encoder's gc_code_q coded with"""
+    N, Cc, H, W = scale.shape
+    idx = torch.empty((N, Cc, H, W), dtype=torch.int32, device=scale.device)
+    check(L.lib().icm_gc_indexes_q(ptr(scale), bs(scale), ptr(table), int(table.numel()), scale_bound, step_of(qstep)[1],
+                                   idx.data_ptr(), N, Cc, H * W, st), "gc_indexes_q")
+    return idx
+
+
+def dequantize_q(st, sym, mu, qstep, yh_out):
+    """decoder, after it: y_hat_pre = symbols * step + mu -> yh_out, the encoder's bit for bit"""
+    N, Cc, H, W = mu.shape
+    check(L.lib().icm_dequantize_q(sym.data_ptr(), ptr(mu), bs(mu), step_of(qstep)[0], ptr(yh_out), bs(yh_out), N, Cc,
+                                   H * W, st), "dequantize_q")
 
 
 # ------------------------------------------------------------------------------------------------ stf6 plumbing

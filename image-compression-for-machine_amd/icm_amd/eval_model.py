@@ -20,6 +20,7 @@ from typing import Dict, List
 import torch
 
 from . import utils as U
+from .bitstream import check_qstep
 from .datasets import IMG_EXTENSIONS, ToTensor, to_pil_image
 from .zoo import models
 
@@ -56,8 +57,11 @@ def load_checkpoint(arch: str, checkpoint_path: str) -> torch.nn.Module:
 
 @torch.no_grad()
 def eval_model(model, filepaths: List[str], entropy_estimation: bool = False, recon_path: str = "",
-               metric_names=None) -> Dict[str, float]:
-    """eval_model/__main__.py:472-487 (per-image metrics averaged over the folder)"""
+               metric_names=None, qstep: int = 0) -> Dict[str, float]:
+    """eval_model/__main__.py:472-487 (per-image metrics averaged over the folder); ``qstep``: the codec's quantiser
+    step index (``utils.inference``; the estimate path has no step)"""
+    if qstep and entropy_estimation:
+        raise ValueError("the entropy estimation has no quantiser step")
     device = next(model.parameters()).device
     metrics: Dict[str, float] = defaultdict(float)
     for f in filepaths:
@@ -67,7 +71,7 @@ def eval_model(model, filepaths: List[str], entropy_estimation: bool = False, re
             raise ValueError(f"{f}: {x.shape[-1]}x{x.shape[-2]} is too small for MS-SSIM (both sides must exceed 160 "
                              "pixels: five levels of an 11-tap window)")
         rv = fn(model, x, recon=(lambda xh, name=os.path.basename(f): reconstruct(xh, name, recon_path)) if recon_path else None,
-                **({} if metric_names is None else {"metrics": metric_names}))
+                **({} if metric_names is None else {"metrics": metric_names}), **({"qstep": qstep} if qstep else {}))
         for k, v in rv.items():
             metrics[k] += v
     return {k: v / len(filepaths) for k, v in metrics.items()}
@@ -99,6 +103,8 @@ def setup_args() -> argparse.ArgumentParser:
                    help="checkpoint path (default: the architecture's initial weights)")
     p.add_argument("--metric", dest="metric", action="append", default=None, metavar="{psnr,ms-ssim}",
                    help="quality metric(s) of the report; repeat the flag or separate by commas (default: psnr)")
+    p.add_argument("--qstep", type=int, default=0, metavar="K",
+                   help="quantiser step 2^(K/8) on the latent of the real codec, K in -16..32 (default 0: none)")
     p.add_argument("--limit", type=int, default=0, help="evaluate only the first N images (0 = all)")
     return p
 
@@ -112,6 +118,13 @@ def main(argv) -> int:
         return 2
     if args.half:
         print("Error: --half is not supported (f32 path).", file=sys.stderr)
+        return 2
+    try:
+        check_qstep(args.qstep, "--")
+        if args.qstep and args.entropy_estimation:
+            raise ValueError("--qstep needs the real codec: the entropy estimation has no quantiser step")
+    except ValueError as e:
+        print(f"Error: {e}", file=sys.stderr)
         return 2
     filepaths = collect_images(args.dataset)
     if args.limit > 0:
@@ -129,7 +142,7 @@ def main(argv) -> int:
         sys.stderr.write(f"Evaluating {args.paths or '<initial weights>'} on {len(filepaths)} images\n")
     try:
         metrics = eval_model(model, filepaths, args.entropy_estimation, args.recon_path,
-                             metric_names=metric_names if args.metric else None)
+                             metric_names=metric_names if args.metric else None, qstep=args.qstep)
     except ValueError as e:
         print(f"Error: {e}", file=sys.stderr)
         return 4

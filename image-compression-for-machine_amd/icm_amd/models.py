@@ -16,6 +16,7 @@ from . import _lib as L
 from . import engine as E
 from ._lib import ACT_GELU
 from .ans import coder_for
+from .bitstream import check_qstep
 from .engine import VT
 from .entropy_models import EntropyBottleneck, GaussianConditional
 from .layers import (GDN, Conv2d, Win_noShift_Attention, WindowAttention, conv, conv3x3, deconv, subpel_conv3x3,
@@ -75,31 +76,44 @@ class CompressionModel(nn.Module):
         names, params = _named(self)
         return dict(zip(names, [p.detach() for p in params]))
 
-    def _compress_latent(self, tape, P, y, coder, debug=None):
-        """cnn.py:214-266 from ``y`` on: {"strings": [[y_string], z_strings], "shape": z spatial size}.  ``coder``
-        (``icm_amd.ans.coder_for``) codes the recorded device tensors of all slices as one y string, a run per slice,
-        and the z strings as single-run strings."""
+    def _compress_latent(self, tape, P, y, coder, debug=None, qstep=0):
+        """cnn.py:214-266 from ``y`` on: {"strings": [[y_string], z_strings], "shape": z spatial size, "qstep"}.
+        ``coder`` (``icm_amd.ans.coder_for``) codes the recorded device tensors of all slices as one y string, a run
+        per slice, and the z strings as single-run strings.  ``qstep``: step index of the quantiser step on y (0: none;
+        z and its EntropyBottleneck know no step)."""
         gc = self.gaussian_conditional
         codec = {"gc": gc, "symbols": {}, "indexes": {}}
         keep = {}
-        hyper_slices(tape, P, y, None, None, self.num_slices, self.max_support_slices, keep=keep, codec=codec)
+        hyper_slices(tape, P, y, None, None, self.num_slices, self.max_support_slices, keep=keep, codec=codec,
+                     qstep=qstep)
         z = keep["z"]
         z_strings = self.entropy_bottleneck.compress(z, coder=coder)
         sym = torch.cat([codec["symbols"][i].reshape(-1) for i in range(self.num_slices)])
         idx = torch.cat([codec["indexes"][i].reshape(-1) for i in range(self.num_slices)])
         gc._check_tables()
         y_string = coder.encode(sym, idx, [codec["symbols"][i].numel() for i in range(self.num_slices)], gc)
-        if debug is not None:      # tests: the coded symbols / CDF indexes (slice-major, cnn.py:254-255)
-            debug.update(symbols=sym.cpu().numpy(), indexes=idx.cpu().numpy())
-        return {"strings": [[y_string], z_strings], "shape": z.size()[-2:]}
+        if debug is not None:      # tests: the coded symbols / CDF indexes (slice-major, cnn.py:254-255), the final y_hat
+            debug.update(symbols=sym.cpu().numpy(), indexes=idx.cpu().numpy(), y_hat=keep["y_hat"])
+        return {"strings": [[y_string], z_strings], "shape": z.size()[-2:], "qstep": qstep}
 
-    def _decompress_latent(self, tape, P, strings, shape, M, coder):
+    @torch.no_grad()
+    def compress_latent(self, y, _debug=None, coder="host", symbols_per_wave=None, qstep=0):
+        """``compress`` from the latent on: ``y`` is what ``analysis(x)`` returned.  A rate search runs the analysis
+        transform once per image and this once per probe."""
+        qstep = check_qstep(qstep, "compress: ")
+        coder = coder_for(coder, symbols_per_wave)
+        if not isinstance(y, torch.Tensor) or y.dim() != 4 or y.dtype != torch.float32:
+            raise ValueError("compress_latent: expected the f32 [B,M,h,w] latent of analysis()")
+        tape = E.Tape(need_grad=False, packed_cache=self._pack_cache())
+        return self._compress_latent(tape, self._params(), y.contiguous(), coder, _debug, qstep)
+
+    def _decompress_latent(self, tape, P, strings, shape, M, coder, qstep=0):
         """cnn.py:289-328: y_hat from the two streams"""
         if not isinstance(strings, (list, tuple)) or len(strings) != 2:
             raise ValueError("strings must be [y_strings, z_strings]")
         z_hat = self.entropy_bottleneck.decompress(strings[1], shape, coder=coder)
         return decode_slices(tape, P, z_hat, strings[0][0], self.gaussian_conditional, self.num_slices,
-                             self.max_support_slices, M, coder)
+                             self.max_support_slices, M, coder, qstep)
 
     def load_state_dict(self, state_dict, strict: bool = False):
         # models/base.py:62-70: resize the CDF buffers to whatever the checkpoint holds, then strict=False
@@ -178,7 +192,7 @@ SLICE_SPLIT = _os.environ.get("ICM_SLICE_SPLIT", "1") != "0"
 
 def hyper_slices(tape: E.Tape, P: Dict[str, torch.Tensor], y: torch.Tensor, noise_z, noise_y, num_slices: int,
                  max_support: int, keep: Optional[dict] = None, bucket_marks: Optional[dict] = None,
-                 batch_tail: bool = True, codec: Optional[dict] = None, decode: Optional[dict] = None):
+                 batch_tail: bool = True, codec: Optional[dict] = None, decode: Optional[dict] = None, qstep: int = 0):
     """Hyperprior + channel-conditional slice loop shared by the cnn and stf models
     (cnn.py:144-183 == stf.py:596-637) -> (y_hat, y_likelihoods, z_likelihoods).  torch.cat / chunk become
     channel-slice views of persistent support buffers.
@@ -186,12 +200,17 @@ def hyper_slices(tape: E.Tape, P: Dict[str, torch.Tensor], y: torch.Tensor, nois
     round(y - mu) and CDF indexes of every slice are recorded (device tensors, keyed by slice).
     decode (decompress(), cnn.py:289-326): {"z_hat", "M", "slice": callable(i, mu, sc, yh_pre)} -- y is None; the
     SAME launch sequence runs (identical kernels on identical inputs give the bit-identical mu / scale the encoder saw,
-    which the CDF indexes depend on), but each slice's y_hat_pre comes from the entropy decoder instead of from y."""
+    which the CDF indexes depend on), but each slice's y_hat_pre comes from the entropy decoder instead of from y.
+    qstep (codec / decode only): step index of the quantiser step on y.  Non-zero, the encoder's work per slice is ONE
+    launch (``_record_symbols``: symbols, indexes and y_hat_pre; no likelihoods, which compress() never reads), and
+    the decoder's callback, which ``decode_slices`` builds for the same step, mirrors it."""
+    if qstep and codec is None and decode is None:
+        raise ValueError("the quantiser step exists in the codec only (compress / decompress)")
     if SLICE_SPLIT and batch_tail:
         from .slices import hyper_slices_split
         return hyper_slices_split(tape, P, y, noise_z, noise_y, num_slices, max_support, keep, bucket_marks, codec,
                                   decode, lambda t, P_, y_: _chain(t, P_, "h_a", VT(y_), strides=(1, 1, 2, 1, 2)),
-                                  _h_s_pair, _record_symbols)
+                                  _h_s_pair, _record_symbols, qstep)
     if decode is not None:
         z_hat = decode["z_hat"].contiguous()
         dev, N, M = z_hat.device, z_hat.shape[0], decode["M"]
@@ -236,7 +255,8 @@ def hyper_slices(tape: E.Tape, P: Dict[str, torch.Tensor], y: torch.Tensor, nois
         raise ValueError("hyper-synthesis output does not match the latent size (input must be a multiple of 64)")
     _h_s_pair(tape, P, "h_scale_s", "h_mean_s", z_hat, SS[:, :M], MS[:, :M])
     Y_hat = E.new((N, M, h, w), dev)
-    Y_lik = E.new((N, M, h, w), dev) if decode is None else None
+    fused = codec is not None and qstep != 0       # the step-aware encoder: one launch per slice, no likelihoods
+    Y_lik = E.new((N, M, h, w), dev) if decode is None and not fused else None
     if need:
         dYh = E.zeros(Y_hat.shape, dev)
         tape.bind_grad(Y_hat, dYh, True)
@@ -265,11 +285,13 @@ def hyper_slices(tape: E.Tape, P: Dict[str, torch.Tensor], y: torch.Tensor, nois
         _copy_op(tape, ms, LS[:, :M + sc_ * k])
         if decode is not None:
             decode["slice"](i, mu, sc, yh_pre)
+        elif fused:
+            _record_symbols(codec, i, y[:, ch], mu, sc, yh_pre, qstep)
         else:
             E.gc_likelihood_ste(tape, y[:, ch], mu, sc, None if noise_y is None else noise_y[:, ch], Y_lik[:, ch],
                                 yh_pre)
-        if codec is not None:
-            _record_symbols(codec, i, y[:, ch], mu, sc)
+            if codec is not None:
+                _record_symbols(codec, i, y[:, ch], mu, sc)
         _chain(tape, P, f"lrp_transforms.{i}", VT(LS), out=Y_hat[:, ch], lrp_aux=yh_pre)
         if i < max_support:
             sl = slice(M + sc_ * i, M + sc_ * (i + 1))
@@ -301,11 +323,13 @@ def hyper_slices(tape: E.Tape, P: Dict[str, torch.Tensor], y: torch.Tensor, nois
             _copy_op(tape, ms, LS[:, :M + sc_ * k])
             if decode is not None:
                 decode["slice"](i, mu_t[j], sc_t[j], yh_pre)
+            elif fused:
+                _record_symbols(codec, i, y[:, ch], mu_t[j], sc_t[j], yh_pre, qstep)
             else:
                 E.gc_likelihood_ste(tape, y[:, ch], mu_t[j], sc_t[j], None if noise_y is None else noise_y[:, ch],
                                     Y_lik[:, ch], yh_pre)
-            if codec is not None:
-                _record_symbols(codec, i, y[:, ch], mu_t[j], sc_t[j])
+                if codec is not None:
+                    _record_symbols(codec, i, y[:, ch], mu_t[j], sc_t[j])
             LSs.append(LS)
             pres.append(yh_pre)
         # lrp chains of all tail slices, LRP tail fused into the last grouped launch
@@ -323,8 +347,19 @@ def hyper_slices(tape: E.Tape, P: Dict[str, torch.Tensor], y: torch.Tensor, nois
     return Y_hat, Y_lik, z_lik
 
 
-def _record_symbols(codec, i, y_slice, mu, sc):
-    """symbols = quantize(y_slice, "symbols", mu) and indexes = build_indexes(scale) of slice i (cnn.py:246-252)"""
+def _scale_table(gc, dev):
+    return gc.scale_table.detach().to(dev, torch.float32).contiguous()
+
+
+def _record_symbols(codec, i, y_slice, mu, sc, yh_pre=None, qstep=0):
+    """symbols = quantize(y_slice, "symbols", mu) and indexes = build_indexes(scale) of slice i (cnn.py:246-252).
+    With a quantiser step: symbols round((y - mu) / step), indexes of scale / step and y_hat_pre = symbols * step + mu
+    -> yh_pre, all from ONE launch (the caller then makes no likelihood launch)."""
+    if qstep:
+        gc, dev = codec["gc"], y_slice.device
+        codec["symbols"][i], codec["indexes"][i] = E.gc_code_q(L.stream(), y_slice, mu, sc, _scale_table(gc, dev),
+                                                               gc._scale_bound, qstep, yh_pre)
+        return
     N, Cc, h, w = y_slice.shape
     sym = torch.empty((N, Cc, h, w), dtype=torch.int32, device=y_slice.device)
     L.check(L.lib().icm_quantize(L.ptr(y_slice), L.bs(y_slice), L.ptr(mu), L.bs(mu), h * w, 1, sym.data_ptr(), 0, N, Cc,
@@ -333,28 +368,35 @@ def _record_symbols(codec, i, y_slice, mu, sc):
     codec["indexes"][i] = codec["gc"].build_indexes(sc)
 
 
-def decode_slices(tape: E.Tape, P, z_hat, y_string: bytes, gc, num_slices: int, max_support: int, M: int, coder):
+def decode_slices(tape: E.Tape, P, z_hat, y_string: bytes, gc, num_slices: int, max_support: int, M: int, coder,
+                  qstep: int = 0):
     """Decoder side of the slice loop (cnn.py:296-326): hyper_slices in decode mode -- per slice the chains give
     mu / scale -> CDF indexes -> ``decode_run`` of the coder's decoder yields the symbols -> y_hat_pre = symbols + mu;
     the LRP correction and the support bookkeeping are the forward's own.  Returns y_hat [N,M,h,w].  ``coder``: of
     ``icm_amd.ans.coder_for``; what a ``decode_run`` costs (host: a copy down and one up; lanes: one launch, no wait,
-    the status read by ``finish`` after the loop) is the coder's business."""
+    the status read by ``finish`` after the loop) is the coder's business.  With a quantiser step ``qstep`` the two
+    launches around ``decode_run`` are the step-aware ones, which share their arithmetic with the encoder's kernel."""
     gc._check_tables()
     dec = coder.decoder(y_string, gc)
     state = {"next": 0}
+    table = _scale_table(gc, z_hat.device) if qstep else None
 
     def one(i, mu, sc, yh_pre):
         if i != state["next"]:
             raise RuntimeError("slices must be decoded in stream order")
         state["next"] += 1
         N, Cc, h, w = mu.shape
+        if qstep:
+            sym = dec.decode_run(E.gc_indexes_q(tape.st, sc, table, gc._scale_bound, qstep))
+            E.dequantize_q(tape.st, sym, mu, qstep, yh_pre)
+            return
         sym = dec.decode_run(gc.build_indexes(sc))
         L.check(L.lib().icm_dequantize(sym.data_ptr(), L.ptr(mu), L.bs(mu), h * w, 1, L.ptr(yh_pre), L.bs(yh_pre), N, Cc,
                                        h * w, tape.st), "dequantize")
 
     try:
         Y_hat, _, _ = hyper_slices(tape, P, None, None, None, num_slices, max_support,
-                                   decode={"z_hat": z_hat, "M": M, "slice": one})
+                                   decode={"z_hat": z_hat, "M": M, "slice": one}, qstep=qstep)
         dec.finish()
     finally:
         dec.close()
@@ -719,23 +761,34 @@ class WACNN(CompressionModel):
         return self._update_tables(scale_table, force)
 
     @torch.no_grad()
-    def compress(self, x, _debug=None, coder="host", symbols_per_wave=None):
-        """cnn.py:210-266 -> {"strings": [[y_string], z_strings], "shape": z.shape[-2:]}; ``coder``: "host" (the
-        reference's scalar stream) or "lanes" (lane streams coded on the device, ``symbols_per_wave`` symbols of a
-        slice per wave body, None: ``icm_amd.ans.SYMBOLS_PER_WAVE``); the decoder must be told the same coder"""
+    def analysis(self, x):
+        """the analysis transform g_a alone -> y, what ``compress_latent`` takes"""
+        _check_codec_input(x)
+        tape = E.Tape(need_grad=False, packed_cache=self._pack_cache())
+        return wacnn_g_a(tape, self._params(), x.contiguous())
+
+    @torch.no_grad()
+    def compress(self, x, _debug=None, coder="host", symbols_per_wave=None, qstep=0):
+        """cnn.py:210-266 -> {"strings": [[y_string], z_strings], "shape": z.shape[-2:], "qstep"}; ``coder``: "host"
+        (the reference's scalar stream) or "lanes" (lane streams coded on the device, ``symbols_per_wave`` symbols of
+        a slice per wave body, None: ``icm_amd.ans.SYMBOLS_PER_WAVE``); ``qstep``: step index k of a quantiser step
+        2^(k/8) on y (``icm_amd.bitstream.step_of``; 0: none, a larger k a smaller stream; parity unpinned: no
+        counterpart in the reference); the decoder must be told the same coder and the same step"""
+        qstep = check_qstep(qstep, "compress: ")
         coder = coder_for(coder, symbols_per_wave)
         _check_codec_input(x)
         P = self._params()
         tape = E.Tape(need_grad=False, packed_cache=self._pack_cache())
-        return self._compress_latent(tape, P, wacnn_g_a(tape, P, x.contiguous()), coder, _debug)
+        return self._compress_latent(tape, P, wacnn_g_a(tape, P, x.contiguous()), coder, _debug, qstep)
 
     @torch.no_grad()
-    def decompress(self, strings, shape, coder="host"):
+    def decompress(self, strings, shape, coder="host", qstep=0):
         """cnn.py:289-332 -> {"x_hat"} clamped to [0, 1]"""
+        qstep = check_qstep(qstep, "decompress: ")
         coder = coder_for(coder)
         P = self._params()
         tape = E.Tape(need_grad=False, packed_cache=self._pack_cache())
-        x_hat = wacnn_g_s(tape, P, self._decompress_latent(tape, P, strings, shape, 320, coder))
+        x_hat = wacnn_g_s(tape, P, self._decompress_latent(tape, P, strings, shape, 320, coder, qstep))
         L.check(L.lib().icm_clamp(L.ptr(x_hat), x_hat.numel(), 0.0, 1.0, tape.st), "clamp")
         return {"x_hat": x_hat}
 
@@ -978,21 +1031,31 @@ class SymmetricalTransFormer(CompressionModel):
         return self._update_tables(scale_table, force)
 
     @torch.no_grad()
-    def compress(self, x, _debug=None, coder="host", symbols_per_wave=None):
-        """stf.py compress(): analysis transform, then the shared latent coder (``coder``: see WACNN.compress)"""
+    def analysis(self, x):
+        """the analysis transform alone -> y, what ``compress_latent`` takes"""
+        _check_codec_input(x)
+        tape = E.Tape(need_grad=False, packed_cache=self._pack_cache())
+        return stf_analysis(tape, self._params(), x.contiguous(), None, self.window_size)
+
+    @torch.no_grad()
+    def compress(self, x, _debug=None, coder="host", symbols_per_wave=None, qstep=0):
+        """stf.py compress(): analysis transform, then the shared latent coder (``coder``, ``qstep``: see
+        WACNN.compress)"""
+        qstep = check_qstep(qstep, "compress: ")
         coder = coder_for(coder, symbols_per_wave)
         _check_codec_input(x)
         P = self._params()
         tape = E.Tape(need_grad=False, packed_cache=self._pack_cache())
         return self._compress_latent(tape, P, stf_analysis(tape, P, x.contiguous(), None, self.window_size), coder,
-                                     _debug)
+                                     _debug, qstep)
 
     @torch.no_grad()
-    def decompress(self, strings, shape, coder="host"):
+    def decompress(self, strings, shape, coder="host", qstep=0):
+        qstep = check_qstep(qstep, "decompress: ")
         coder = coder_for(coder)
         P = self._params()
         tape = E.Tape(need_grad=False, packed_cache=self._pack_cache())
-        y_hat = self._decompress_latent(tape, P, strings, shape, 384, coder)
+        y_hat = self._decompress_latent(tape, P, strings, shape, 384, coder, qstep)
         x_hat = stf_synthesis(tape, P, y_hat, None, self.window_size)
         L.check(L.lib().icm_clamp(L.ptr(x_hat), x_hat.numel(), 0.0, 1.0, tape.st), "clamp")
         return {"x_hat": x_hat}
@@ -1088,8 +1151,11 @@ class SymmetricalTransFormer3(SymmetricalTransFormer):
     def update(self, scale_table=None, force=False):
         return self._update_tables(scale_table, force)
 
-    def compress(self, x, _debug=None, coder="host", symbols_per_wave=None):
+    def compress(self, x, _debug=None, coder="host", symbols_per_wave=None, qstep=0):
         raise NotImplementedError("stf6: the zigzag entropy coder loop (stf6.py:898-1057) is not mirrored")
 
-    def decompress(self, strings, shape, coder="host"):
+    def compress_latent(self, y, _debug=None, coder="host", symbols_per_wave=None, qstep=0):
+        raise NotImplementedError("stf6: the zigzag entropy coder loop (stf6.py:898-1057) is not mirrored")
+
+    def decompress(self, strings, shape, coder="host", qstep=0):
         raise NotImplementedError("stf6: the zigzag entropy coder loop (stf6.py:898-1057) is not mirrored")

@@ -85,18 +85,20 @@ def _quality(x: torch.Tensor, x_hat: torch.Tensor, metrics: Optional[Sequence[st
 
 
 @torch.no_grad()
-def inference(model, x: torch.Tensor, recon=None, metrics: Optional[Sequence[str]] = None) -> Dict[str, float]:
+def inference(model, x: torch.Tensor, recon=None, metrics: Optional[Sequence[str]] = None,
+              qstep: int = 0) -> Dict[str, float]:
     """eval_model/__main__.py:96-139: actual bit-stream size and reconstruction quality of one image x [3,H,W] or
     [1,3,H,W] in [0,1]; ``recon(x_hat)`` (optional) receives the cropped reconstruction (the reference saves it, :130);
-    ``metrics`` (optional) lists the quality entries to report (EVAL_METRICS; default: "psnr" alone)"""
+    ``metrics`` (optional) lists the quality entries to report (EVAL_METRICS; default: "psnr" alone); ``qstep``: step
+    index of the codec's quantiser step on the latent (``model.compress``; 0: none, the reference's codec)"""
     if x.dim() == 3:
         x = x.unsqueeze(0)
     xp, pads = pad_to_multiple(x, 64)
     t0 = time.time()
-    enc = model.compress(xp)
+    enc = model.compress(xp, qstep=qstep)
     torch.cuda.synchronize() if x.is_cuda else None
     t1 = time.time()
-    dec = model.decompress(enc["strings"], enc["shape"])
+    dec = model.decompress(enc["strings"], enc["shape"], qstep=qstep)
     torch.cuda.synchronize() if x.is_cuda else None
     t2 = time.time()
     x_hat = crop(dec["x_hat"], pads)

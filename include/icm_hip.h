@@ -394,6 +394,26 @@ int icm_quantize(const float* x, int64_t x_bs, const float* means, int64_t m_bs,
 int icm_dequantize(const int32_t* symbols, const float* means, int64_t m_bs, int64_t m_cs, int64_t m_ps, float* out,
                    int64_t out_bs, int N, int C, int HW, void* stream);
 
+/* ---- quantiser step on y: the codec's quality knob (csrc/qstep.hip).  Parity unpinned: no counterpart in the
+ * reference.  `step` = 2^(k/8) and `inv` = 1 / step as f32, both from icm_amd/bitstream.py:step_of.  All f32, every
+ * operation rounded once, no FMA:
+ *   symbol = (int)clamp(rint((y - mu) * inv), -2^30, 2^30);  y_hat = ((float)symbol * step) + mu;
+ *   index = (ns - 1) - #{ j < ns - 1 : max(scale, scale_bound) * inv <= scale_table[j] }
+ * Operands are [N][C][HW] with an element batch stride per float operand (channel slices of wider buffers); symbols
+ * and indexes are dense int32.  code_q is the encoder's one launch per slice; indexes_q and dequantize_q are the
+ * decoder's steps before and after the entropy decoder's run, and compute index and y_hat through the device
+ * functions code_q uses.  With step = inv = 1: icm_quantize's symbols, icm_gc_build_indexes' indexes and the y_hat of
+ * icm_gc_likelihood_ste_fwd.  NaN inputs are outside the contract, as for icm_quantize.
+ * ICM_ERR_ARG before any launch, outputs untouched: a null pointer, step or inv not finite or <= 0, ns < 1, N, C or
+ * HW < 1. */
+int icm_gc_code_q(const float* y, int64_t y_bs, const float* mu, int64_t mu_bs, const float* scale, int64_t sc_bs,
+                  const float* scale_table, int ns, float scale_bound, float step, float inv, int32_t* symbols,
+                  int32_t* indexes, float* yh, int64_t yh_bs, int N, int C, int HW, void* stream);
+int icm_gc_indexes_q(const float* scale, int64_t sc_bs, const float* scale_table, int ns, float scale_bound, float inv,
+                     int32_t* indexes, int N, int C, int HW, void* stream);
+int icm_dequantize_q(const int32_t* symbols, const float* mu, int64_t mu_bs, float step, float* yh, int64_t yh_bs, int N,
+                     int C, int HW, void* stream);
+
 /* ---- R-D loss (train.py:53-61, train_czigzag.py:63,71) --------------------------------------
  * out[0]=bpp, out[1]=mse, out[2]=loss, out[3]=sum log(lik_y), out[4]=sum log(lik_z) (5 floats, overwritten);
  * ws: ICM_REDUCE_WS_FLOATS floats of scratch (per-workgroup partial sums, added in workgroup order). */

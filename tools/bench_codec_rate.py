@@ -1,0 +1,176 @@
+#!/usr/bin/env python
+"""The codec's quantiser step and its rate search on one 2048x3072 synthetic image, randomly initialised ``cnn``.
+
+    step_vs_plain   encode wall time at qstep 0 (the path without a step: likelihood + quantise + index launches per
+                    slice) and at qstep 8 (one fused launch per slice), alternated within one run, median of --rounds.
+    slice_kernels   the per-slice encoder work alone on one slice of this image ([1, 32, 128 x 192] out of the wide
+                    buffers): today's three launches (and the copy ``build_indexes`` makes of a strided scale) against
+                    the one fused launch, microseconds per slice from HIP events over --iters repetitions.
+    rate_points     file bytes and PSNR of the decoded 8-bit image at qstep -16, -8, 0, 8, 16, 24, 32.
+    target_bpp      encode wall time and probe count of an encode to size at two budgets, the size of the qstep -8
+                    file and the middle between it and the qstep 0 file (where this model's sizes still move; a budget
+                    the coarsest step misses is reported as such), with the wall time of the analysis transform alone
+                    and of one probe (``compress_latent`` + container) next to them.
+
+Every part runs for both coders, warmed, with the host clock around a device synchronise.  The model is randomly
+initialised (seeded): bytes and PSNR exercise the mechanism and say nothing about a trained codec's rate-distortion.
+Prints one JSON line per part and coder.
+
+    python tools/bench_codec_rate.py [--rounds 5] [--iters 100] [--coder {host,lanes,both}]
+"""
+import argparse
+import json
+import os
+import statistics
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+for p in (ROOT, os.path.join(ROOT, "image-compression-for-machine_amd")):
+    if p not in sys.path:
+        sys.path.insert(0, p)
+
+H, W = 2048, 3072
+RATE_POINTS = (-16, -8, 0, 8, 16, 24, 32)
+
+
+def synthetic(np, h, w, seed):
+    """gradients, a coarse texture and a little noise: 8-bit [h, w, 3] (the image of tools/bench_codec_tiles.py)"""
+    rng = np.random.default_rng(seed)
+    yy, xx = np.mgrid[0:h, 0:w].astype(np.float32)
+    img = np.stack([127 + 90 * np.sin(yy / (37.0 + 9 * c)) * np.cos(xx / (53.0 - 7 * c)) + 0.02 * (xx - yy)
+                    for c in range(3)], -1)
+    return np.clip(img + rng.integers(-6, 7, size=(h, w, 3)), 0, 255).astype(np.uint8)
+
+
+def wall(fn, torch):
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    r = fn()
+    torch.cuda.synchronize()
+    return time.perf_counter() - t0, r
+
+
+def slice_kernels(args, torch):
+    from icm_amd import _lib as L
+    from icm_amd import engine as E
+    from icm_amd.zoo import models
+    model = models["cnn"]().to("cuda:0").eval()
+    model.update(force=True)
+    gc = model.gaussian_conditional
+    g = torch.Generator(device="cuda:0").manual_seed(0)
+    N, M, c, h, w = 1, 320, 32, H // 16, W // 16
+    Y, MU, YP, LIK = (torch.randn((N, M, h, w), generator=g, device="cuda:0") for _ in range(4))
+    SC = torch.rand((N, M, h, w), generator=g, device="cuda:0") * 2
+    s1 = slice(64, 96)
+    tape = E.Tape(need_grad=False)
+    table = gc.scale_table.detach().to("cuda:0", torch.float32).contiguous()
+
+    def plain():
+        E.gc_likelihood_ste(tape, Y[:, s1], MU[:, s1], SC[:, s1], None, LIK[:, s1], YP[:, s1])
+        sym = torch.empty((N, c, h, w), dtype=torch.int32, device="cuda:0")
+        L.check(L.lib().icm_quantize(L.ptr(Y[:, s1]), L.bs(Y[:, s1]), L.ptr(MU[:, s1]), L.bs(MU[:, s1]), h * w, 1,
+                                     sym.data_ptr(), 0, N, c, h * w, L.stream()), "quantize")
+        return sym, gc.build_indexes(SC[:, s1])
+
+    def fused():
+        return E.gc_code_q(L.stream(), Y[:, s1], MU[:, s1], SC[:, s1], table, gc._scale_bound, 8, YP[:, s1])
+
+    res = {"metric": "slice_kernels", "slice": [N, c, h, w], "iters": args.iters}
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    for name, fn in (("plain_three_launches_us", plain), ("fused_one_launch_us", fused), ("plain_again_us", plain),
+                     ("fused_again_us", fused)):
+        for _ in range(10):
+            fn()
+        torch.cuda.synchronize()
+        e0.record()
+        for _ in range(args.iters):
+            fn()
+        e1.record()
+        torch.cuda.synchronize()
+        res[name] = round(e0.elapsed_time(e1) / args.iters * 1e3, 2)
+    print(json.dumps(res), flush=True)
+
+
+def run(args, coder, torch, np, codec, B):
+    from icm_amd.zoo import models
+    torch.manual_seed(0)
+    model = models["cnn"]().to("cuda:0").eval()
+    model.update(force=True)
+    a = synthetic(np, H, W, seed=1)
+    base = {"coder": coder, "height": H, "width": W, "model": "cnn, randomly initialised (seed 0)", "rounds": args.rounds}
+
+    def encode(**kw):
+        return codec.encode_image_info(model, a, coder=coder, **kw)
+
+    # ---- (a) the fused launch against today's three, alternated
+    for k in (0, 8):
+        encode(qstep=k)
+    ts = {0: [], 8: []}
+    for _ in range(args.rounds):
+        for k in (0, 8):
+            ts[k].append(wall(lambda: encode(qstep=k), torch)[0])
+    plain = len(encode(qstep=0)[0])
+    print(json.dumps({"metric": "step_vs_plain", **base, "qstep0_encode_s": round(statistics.median(ts[0]), 4),
+                      "qstep8_encode_s": round(statistics.median(ts[8]), 4),
+                      "qstep0_all_s": [round(t, 4) for t in ts[0]], "qstep8_all_s": [round(t, 4) for t in ts[8]]}),
+          flush=True)
+
+    # ---- (c) the rate points of one checkpoint
+    pts = []
+    for k in RATE_POINTS:
+        data, _ = encode(qstep=k)
+        _, info = codec.decode_image(model, data, reference=a)
+        assert info["qstep"] == k
+        pts.append({"qstep": k, "step": B.step_of(k)[0], "bytes": len(data), "bpp": round(info["bpp"], 5),
+                    "psnr": round(info["psnr"], 4)})
+    print(json.dumps({"metric": "rate_points", **base, "points": pts}), flush=True)
+    sizes = {p_["qstep"]: p_["bytes"] for p_ in pts}
+
+    # ---- (b) encode to size
+    pads = codec.center_pads(H, W)
+    u8 = torch.from_numpy(a).to("cuda:0")
+    x = codec.image_u8_to_f32(u8, pads)
+    y = model.analysis(x)
+    t_ana = statistics.median(wall(lambda: model.analysis(x), torch)[0] for _ in range(args.rounds))
+    arch, fp = codec.arch_of(model), B.fingerprint(model)
+    t_probe = statistics.median(
+        wall(lambda: codec._pack_one(arch, fp, H, W, pads, model.compress_latent(y, coder=coder, qstep=8), coder), torch)[0]
+        for _ in range(args.rounds))
+    res = {"metric": "target_bpp", **base, "qstep0_bytes": plain, "analysis_s": round(t_ana, 4),
+           "one_probe_s": round(t_probe, 4), "budgets": []}
+    for budget in (sizes[-8], (sizes[-8] + sizes[0]) // 2):
+        bpp = 8.0 * (budget + 0.5) / (H * W)
+        if sizes[B.QSTEP_MAX] > budget:
+            res["budgets"].append({"target_bpp": round(bpp, 5), "budget_bytes": budget, "result": "out of reach: the "
+                                   f"file at qstep {B.QSTEP_MAX} has {sizes[B.QSTEP_MAX]} bytes"})
+            continue
+        encode(max_bytes=budget)
+        t = []
+        for _ in range(args.rounds):
+            dt, (data, found) = wall(lambda: encode(max_bytes=budget), torch)
+            t.append(dt)
+        res["budgets"].append({"target_bpp": round(bpp, 5), "budget_bytes": budget, "bytes": len(data), **found,
+                               "encode_s": round(statistics.median(t), 4)})
+    print(json.dumps(res), flush=True)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--rounds", type=int, default=5)
+    ap.add_argument("--iters", type=int, default=100)
+    ap.add_argument("--coder", default="both", choices=["host", "lanes", "both"])
+    args = ap.parse_args()
+    import numpy as np
+    import torch
+    if not torch.cuda.is_available():
+        sys.exit("bench_codec_rate: no GPU (there is no CPU fallback)")
+    from icm_amd import bitstream as B
+    from icm_amd import codec
+    slice_kernels(args, torch)
+    for coder in (("host", "lanes") if args.coder == "both" else (args.coder,)):
+        run(args, coder, torch, np, codec, B)
+
+
+if __name__ == "__main__":
+    main()
