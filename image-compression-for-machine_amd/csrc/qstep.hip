@@ -101,6 +101,70 @@ __global__ __launch_bounds__(256) void dequantize_q_kernel(const int* __restrict
   }
 }
 
+// ---- quality map: a step per latent position.  `qmap` holds HW step indexes k (int8, dense, shared by every n and c),
+// `steps` 256 (step, inv) pairs indexed by the map byte read as unsigned (icm_amd/bitstream.py: step_table; bytes that
+// are no valid k hold (1, 1), so no byte indexes outside it and nothing here clamps or branches on validity).  The
+// arithmetic is symbol_of / yh_of / index_of above, called with the pair of the element's position.
+// Layout: a 3-D grid, x over HW, y over c, z over n, each a grid-stride loop, so a position index is never divided
+// out of a flat one.  A lane reads its map byte and its pair once per position (consecutive lanes on consecutive map
+// bytes: 64 bytes per wave) and keeps them in registers over the channels and images it walks; the operand accesses
+// stay consecutive lanes on consecutive addresses.  `se` differs per lane now, table[j] is still wave-uniform and
+// still comes through the scalar cache.  The pairs are read with plain global loads (one 8-byte load per lane and
+// position; the table is 2 KB, read-only and stays in cache); the plain form is the one kept and an LDS-staged
+// table was not needed: on the 786 432-element slice the fused map kernel measured 19.9 - 20.0 us against the scalar
+// kernel's 19.5 - 19.9 us in the same run.
+__global__ __launch_bounds__(256) void gc_code_qmap_kernel(const float* __restrict__ y, const float* __restrict__ mu,
+                                                            const float* __restrict__ sc,
+                                                            const float* __restrict__ table, int ns, float bound,
+                                                            const unsigned char* __restrict__ qmap,
+                                                            const float2* __restrict__ steps, int* __restrict__ sym,
+                                                            int* __restrict__ idx, float* __restrict__ yh,
+                                                            const QGeom g) {
+  for (long long p = blockIdx.x * 256 + threadIdx.x; p < g.HW; p += gridDim.x * 256) {
+    const float2 si = steps[qmap[p]];   // x: step, y: inv
+    for (int n = blockIdx.z; n < g.N; n += gridDim.z) {
+      for (int c = blockIdx.y; c < g.C; c += gridDim.y) {
+        const long long r = (long long)c * g.HW + p;
+        const long long i = (long long)n * g.C * g.HW + r;
+        const float m = mu[n * g.mu_bs + r];
+        const int s = symbol_of(y[n * g.y_bs + r], m, si.y);
+        sym[i] = s;
+        idx[i] = index_of(sc[n * g.sc_bs + r], bound, si.y, table, ns);
+        yh[n * g.yh_bs + r] = yh_of(s, m, si.x);
+      }
+    }
+  }
+}
+__global__ __launch_bounds__(256) void gc_indexes_qmap_kernel(const float* __restrict__ sc,
+                                                               const float* __restrict__ table, int ns, float bound,
+                                                               const unsigned char* __restrict__ qmap,
+                                                               const float2* __restrict__ steps,
+                                                               int* __restrict__ idx, const QGeom g) {
+  for (long long p = blockIdx.x * 256 + threadIdx.x; p < g.HW; p += gridDim.x * 256) {
+    const float inv = steps[qmap[p]].y;
+    for (int n = blockIdx.z; n < g.N; n += gridDim.z) {
+      for (int c = blockIdx.y; c < g.C; c += gridDim.y) {
+        const long long r = (long long)c * g.HW + p;
+        idx[(long long)n * g.C * g.HW + r] = index_of(sc[n * g.sc_bs + r], bound, inv, table, ns);
+      }
+    }
+  }
+}
+__global__ __launch_bounds__(256) void dequantize_qmap_kernel(const int* __restrict__ sym, const float* __restrict__ mu,
+                                                               const unsigned char* __restrict__ qmap,
+                                                               const float2* __restrict__ steps,
+                                                               float* __restrict__ yh, const QGeom g) {
+  for (long long p = blockIdx.x * 256 + threadIdx.x; p < g.HW; p += gridDim.x * 256) {
+    const float step = steps[qmap[p]].x;
+    for (int n = blockIdx.z; n < g.N; n += gridDim.z) {
+      for (int c = blockIdx.y; c < g.C; c += gridDim.y) {
+        const long long r = (long long)c * g.HW + p;
+        yh[n * g.yh_bs + r] = yh_of(sym[(long long)n * g.C * g.HW + r], mu[n * g.mu_bs + r], step);
+      }
+    }
+  }
+}
+
 }  // namespace icm
 
 using namespace icm;
@@ -109,6 +173,15 @@ static inline bool step_ok(float v) { return std::isfinite(v) && v > 0.0f; }
 static inline bool dims_ok(int N, int C, int HW) { return N >= 1 && C >= 1 && HW >= 1; }
 static inline int q_blocks(long long total) {
   return (int)std::max<long long>(1, std::min<long long>((total + 255) / 256, 256));
+}
+// grid of the map kernels: x covers HW in 256-lane blocks, then c and n share what is left of QMAP_BLOCKS workgroups
+// (four per CU: each walks a few channels with its positions' pairs in registers)
+constexpr int QMAP_BLOCKS = 1024;
+static inline dim3 qmap_grid(int N, int C, int HW) {
+  const int gx = std::min((HW - 1) / 256 + 1, QMAP_BLOCKS);
+  const int gy = std::min(C, std::max(1, QMAP_BLOCKS / gx));
+  const int gz = std::min(N, std::max(1, QMAP_BLOCKS / (gx * gy)));
+  return dim3(gx, gy, gz);
 }
 
 extern "C" {
@@ -143,6 +216,42 @@ int icm_dequantize_q(const int32_t* symbols, const float* mu, int64_t mu_bs, flo
   const QGeom g{0, mu_bs, 0, yh_bs, N, C, HW};
   hipLaunchKernelGGL(dequantize_q_kernel, dim3(q_blocks((long long)N * C * HW)), dim3(256), 0, (hipStream_t)stream,
                      symbols, mu, step, yh, g);
+  ICM_CHECK_LAUNCH();
+  return ICM_OK;
+}
+
+int icm_gc_code_qmap(const float* y, int64_t y_bs, const float* mu, int64_t mu_bs, const float* scale, int64_t sc_bs,
+                     const float* scale_table, int ns, float scale_bound, const int8_t* qmap, const float* step_table,
+                     int32_t* symbols, int32_t* indexes, float* yh, int64_t yh_bs, int N, int C, int HW, void* stream) {
+  if (!y || !mu || !scale || !scale_table || !qmap || !step_table || !symbols || !indexes || !yh) return ICM_ERR_ARG;
+  if (ns < 1 || !dims_ok(N, C, HW)) return ICM_ERR_ARG;
+  const QGeom g{y_bs, mu_bs, sc_bs, yh_bs, N, C, HW};
+  hipLaunchKernelGGL(gc_code_qmap_kernel, qmap_grid(N, C, HW), dim3(256), 0, (hipStream_t)stream, y, mu, scale,
+                     scale_table, ns, scale_bound, (const unsigned char*)qmap, (const float2*)step_table, symbols,
+                     indexes, yh, g);
+  ICM_CHECK_LAUNCH();
+  return ICM_OK;
+}
+
+int icm_gc_indexes_qmap(const float* scale, int64_t sc_bs, const float* scale_table, int ns, float scale_bound,
+                        const int8_t* qmap, const float* step_table, int32_t* indexes, int N, int C, int HW,
+                        void* stream) {
+  if (!scale || !scale_table || !qmap || !step_table || !indexes) return ICM_ERR_ARG;
+  if (ns < 1 || !dims_ok(N, C, HW)) return ICM_ERR_ARG;
+  const QGeom g{0, 0, sc_bs, 0, N, C, HW};
+  hipLaunchKernelGGL(gc_indexes_qmap_kernel, qmap_grid(N, C, HW), dim3(256), 0, (hipStream_t)stream, scale, scale_table,
+                     ns, scale_bound, (const unsigned char*)qmap, (const float2*)step_table, indexes, g);
+  ICM_CHECK_LAUNCH();
+  return ICM_OK;
+}
+
+int icm_dequantize_qmap(const int32_t* symbols, const float* mu, int64_t mu_bs, const int8_t* qmap,
+                        const float* step_table, float* yh, int64_t yh_bs, int N, int C, int HW, void* stream) {
+  if (!symbols || !mu || !qmap || !step_table || !yh) return ICM_ERR_ARG;
+  if (!dims_ok(N, C, HW)) return ICM_ERR_ARG;
+  const QGeom g{0, mu_bs, 0, yh_bs, N, C, HW};
+  hipLaunchKernelGGL(dequantize_qmap_kernel, qmap_grid(N, C, HW), dim3(256), 0, (hipStream_t)stream, symbols, mu,
+                     (const unsigned char*)qmap, (const float2*)step_table, yh, g);
   ICM_CHECK_LAUNCH();
   return ICM_OK;
 }

@@ -89,6 +89,7 @@ SYMBOLS = [
     "icm_eb_table_bounds", "icm_eb_pmf_table", "icm_gc_table_centers", "icm_gc_pmf_table", "icm_gc_build_indexes",
     "icm_quantize", "icm_dequantize", "icm_clamp", "icm_pad2d",
     "icm_gc_code_q", "icm_gc_indexes_q", "icm_dequantize_q",
+    "icm_gc_code_qmap", "icm_gc_indexes_qmap", "icm_dequantize_qmap",
     "icm_msssim_workspace_floats", "icm_msssim_fwd", "icm_msssim_bwd",
     "icm_image_workspace_bytes", "icm_image_u8_to_f32", "icm_image_f32_to_u8",
     "icm_image_batch_u8_to_f32", "icm_image_tile_blend",
@@ -221,6 +222,9 @@ def lib():
         L.icm_gc_code_q.argtypes = [vp, i64, vp, i64, vp, i64, vp, i32, f32, f32, f32, vp, vp, vp, i64, i32, i32, i32, vp]
         L.icm_gc_indexes_q.argtypes = [vp, i64, vp, i32, f32, f32, vp, i32, i32, i32, vp]
         L.icm_dequantize_q.argtypes = [vp, vp, i64, f32, vp, i64, i32, i32, i32, vp]
+        L.icm_gc_code_qmap.argtypes = [vp, i64, vp, i64, vp, i64, vp, i32, f32, vp, vp, vp, vp, vp, i64, i32, i32, i32, vp]
+        L.icm_gc_indexes_qmap.argtypes = [vp, i64, vp, i32, f32, vp, vp, vp, i32, i32, i32, vp]
+        L.icm_dequantize_qmap.argtypes = [vp, vp, i64, vp, vp, vp, i64, i32, i32, i32, vp]
         L.icm_clamp.argtypes = [vp, i64, f32, f32, vp]
         L.icm_pad2d.argtypes = [vp, i32, i32, i32, i32, vp, i32, i32, i32, i32, f32, vp]
         L.icm_image_workspace_bytes.argtypes = [i32, i32]

@@ -35,6 +35,22 @@ of another length is refused, so one content has one encoding.  Only k is stored
 the kernels use from it.  The fixed header, the version and the coder ids are unchanged: a reader from before the step
 refuses a stepped stream for its string count ("holds 3", exit code 4 of the CLI) instead of decoding garbage.
 
+Quality map -- a stream whose step varies over the latent (region-of-interest coding) carries as its third string a
+map string instead of the step byte: one step index per latent position (a 16 x 16-pixel cell of the padded image),
+shared by all channels, run-length coded in row-major order (``qmap_string`` / ``qmap_from_string``):
+
+    u16 h, u16 w                       the latent's spatial size; must equal 4 x the header's z shape
+    then runs (u16 count >= 1, i8 k)   row-major, covering h w positions exactly
+
+The string is canonical: runs are maximal (neighbouring runs differ in k, except that a run of 65535 may be followed by
+one of the same k), every k lies in ``QSTEP_MIN`` .. ``QSTEP_MAX``, and at least two distinct k occur -- a map whose
+entries are all k is written as the scalar stream of k (no third string for k = 0), so one content keeps one encoding.
+The shortest map string has ``QMAP_STRING_MIN`` = 10 bytes, and a reader tells the two kinds of third string apart by
+their length (``quality_from_strings``).  A wrong size against the header, a count of 0, runs short of or past h w,
+trailing bytes, a non-maximal run, a k outside the range or a single distinct k is refused.  ``qstep_from_strings`` is
+what it was: a reader from before the map refuses a mapped stream there ("must be one byte", exit code 4 of the CLI).
+The kernels take a map byte as an index into a table of 256 (step, inv) pairs, ``step_table``, built from ``step_of``.
+
 A tiled image is a second container with its own magic: a grid of independently coded tiles (``tile_grid`` below gives
 the grid), each of them one complete ``ICMB`` stream.  ``ICMB`` and ``unpack`` are unchanged by it, and each reader
 refuses the other's files for their magic.
@@ -56,7 +72,8 @@ refuses the other's files for their magic.
 
 rows / cols are redundant with the four numbers before them, and a reader refuses a file in which they disagree.
 The coder id lives in the tile streams alone: the high byte of the ICMT architecture field stays zero.  So does the
-quantiser step: every tile stream of a stepped image carries its own byte (the encoder writes the same k in all).
+quantiser step: every tile stream of a stepped image carries its own byte (the encoder writes the same k in all), and
+every tile of a region-of-interest encode its own map string, or the step byte where its map came out uniform.
 
 Lane stream -- the string format of coder id 1, made to be coded by one GPU wave per body (csrc/rans_lanes.hip; the
 executable definition is csrc/rans_lanes_common.h, the arithmetic of a lane's step that host and kernels both compile,
@@ -92,7 +109,9 @@ from __future__ import annotations
 
 import struct
 import zlib
-from typing import Dict, List, Sequence, Tuple
+from typing import Dict, List, Optional, Sequence, Tuple
+
+import numpy as np
 
 MAGIC = b"ICMB"
 VERSION = 1
@@ -259,6 +278,115 @@ def qstep_from_strings(strings: Sequence[bytes]) -> int:
     if k == 0:
         raise ValueError("bitstream: a stored qstep of 0 (a stream without a step has two strings)")
     return k
+
+
+# ------------------------------------------------------------------------------------------------- quality map
+_MAP_HEAD = struct.Struct("<HH")            # h, w
+_MAP_RUN = struct.Struct("<Hb")             # count, k
+QMAP_STRING_MIN = _MAP_HEAD.size + 2 * _MAP_RUN.size        # two runs: the shortest string of a non-uniform map
+assert QMAP_STRING_MIN == 10
+
+
+def check_qmap(qmap, shape, qstep=0, who: str = "") -> np.ndarray:
+    """``qmap`` as a C-contiguous int8 host array if it is a 2-D integer array or tensor of exactly ``shape`` (the
+    latent's spatial size) with every entry in [QSTEP_MIN, QSTEP_MAX] and ``qstep`` is 0; ValueError otherwise.  The
+    one check of a quality map: the kernels index their step table with its bytes and check nothing."""
+    if check_qstep(qstep, who) != 0:
+        raise ValueError(f"{who}give a quality map or a quantiser step, not both (qstep = {qstep})")
+    if hasattr(qmap, "detach") and hasattr(qmap, "cpu"):       # a tensor, on any device
+        qmap = qmap.detach().cpu().numpy()
+    a = np.asarray(qmap)
+    if a.dtype.kind not in "iu":
+        raise ValueError(f"{who}qmap must hold integers, got dtype {a.dtype}")
+    if a.ndim != 2 or tuple(a.shape) != tuple(int(s) for s in shape):
+        raise ValueError(f"{who}qmap must have the latent's spatial size {tuple(int(s) for s in shape)}, got "
+                         f"{tuple(a.shape)}")
+    if a.size == 0:
+        raise ValueError(f"{who}qmap is empty")
+    lo, hi = int(a.min()), int(a.max())
+    if lo < QSTEP_MIN or hi > QSTEP_MAX:
+        raise ValueError(f"{who}qmap holds {lo if lo < QSTEP_MIN else hi}, outside [{QSTEP_MIN}, {QSTEP_MAX}]")
+    return np.ascontiguousarray(a, dtype=np.int8)
+
+
+def uniform_qmap(qmap: np.ndarray) -> Optional[int]:
+    """k if every entry of a checked map is k (such a map *is* the scalar step k), None otherwise"""
+    k = int(qmap.flat[0])
+    return k if bool((qmap == k).all()) else None
+
+
+def step_table() -> np.ndarray:
+    """the kernels' table: float32 [256, 2], row b = ``step_of(k)`` for the map byte b read as unsigned (k = b below
+    128, b - 256 from there), (1, 1) for the bytes that are no valid k.  No byte indexes outside it."""
+    t = np.ones((256, 2), dtype=np.float32)
+    for k in range(QSTEP_MIN, QSTEP_MAX + 1):
+        t[k & 0xFF] = step_of(k)
+    return t
+
+
+def qmap_string(qmap) -> bytes:
+    """the third string of a mapped stream.  A uniform map has none (ValueError): it is written as its scalar step."""
+    a = np.asarray(qmap)
+    a = check_qmap(a, a.shape, 0, "bitstream: ")
+    h, w = _uint("map height", a.shape[0], U16_MAX, 1), _uint("map width", a.shape[1], U16_MAX, 1)
+    if uniform_qmap(a) is not None:
+        raise ValueError(f"bitstream: a uniform quality map (every entry {int(a.flat[0])}) is written as the quantiser "
+                         f"step, not as a map string")
+    flat = a.reshape(-1)
+    starts = np.flatnonzero(np.concatenate(([True], flat[1:] != flat[:-1])))
+    ends = np.append(starts[1:], flat.size)
+    out = bytearray(_MAP_HEAD.pack(h, w))
+    for s, e in zip(starts.tolist(), ends.tolist()):
+        n, k = e - s, int(flat[s])
+        while n > 0:                                # a maximal run longer than a count holds: full counts first
+            c = min(n, U16_MAX)
+            out += _MAP_RUN.pack(c, k)
+            n -= c
+    return bytes(out)
+
+
+def qmap_from_string(data: bytes, shape) -> np.ndarray:
+    """inverse of ``qmap_string`` -> int8 [h, w]; ``shape``: the header's z shape, which the map must be 4 x of.
+    ValueError, naming the condition, for anything that is not the one canonical string of such a map."""
+    data = bytes(data)
+    zh, zw = (int(s) for s in shape)
+    if len(data) < QMAP_STRING_MIN:
+        raise ValueError(f"bitstream: a quality-map string has at least {QMAP_STRING_MIN} bytes, this one has {len(data)}")
+    h, w = _MAP_HEAD.unpack_from(data, 0)
+    if (h, w) != (4 * zh, 4 * zw):
+        raise ValueError(f"bitstream: the quality map is {h}x{w}, the header's latent is {4 * zh}x{4 * zw}")
+    if (len(data) - _MAP_HEAD.size) % _MAP_RUN.size:
+        raise ValueError(f"bitstream: {(len(data) - _MAP_HEAD.size) % _MAP_RUN.size} trailing bytes after the last "
+                         f"whole run of the quality map")
+    total, flat, pos, prev = h * w, np.empty(h * w, dtype=np.int8), 0, None
+    for off in range(_MAP_HEAD.size, len(data), _MAP_RUN.size):
+        if pos == total:
+            raise ValueError(f"bitstream: {len(data) - off} trailing bytes after the quality map's {total} positions")
+        count, k = _MAP_RUN.unpack_from(data, off)
+        if count == 0:
+            raise ValueError("bitstream: a run of the quality map has a count of 0")
+        check_qstep(k, "bitstream: quality map: stored ")
+        if prev is not None and prev[1] == k and prev[0] != U16_MAX:
+            raise ValueError(f"bitstream: the quality map's runs are not maximal: a run of {prev[0]} is followed by "
+                             f"another of the same k = {k}")
+        if pos + count > total:
+            raise ValueError(f"bitstream: the quality map's runs go past its {total} positions")
+        flat[pos:pos + count] = k
+        pos, prev = pos + count, (count, k)
+    if pos != total:
+        raise ValueError(f"bitstream: the quality map's runs cover {pos} of its {total} positions")
+    if bool((flat == flat[0]).all()):
+        raise ValueError(f"bitstream: the quality map holds a single k = {int(flat[0])} (a uniform map is written as "
+                         f"the quantiser step)")
+    return flat.reshape(h, w)
+
+
+def quality_from_strings(strings: Sequence[bytes], shape) -> Tuple[Optional[int], Optional[np.ndarray]]:
+    """(k, None) of a stream with a scalar step or none (``qstep_from_strings``), (None, map) of a mapped one; the two
+    kinds of third string are told apart by length.  ``shape``: the header's z shape."""
+    if len(strings) == 3 and len(strings[2]) >= QMAP_STRING_MIN:
+        return None, qmap_from_string(strings[2], shape)
+    return qstep_from_strings(strings), None
 
 
 def fingerprint(model) -> int:

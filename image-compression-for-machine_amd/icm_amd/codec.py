@@ -1,7 +1,7 @@
 """``python -m icm_amd.codec`` -- image file to bit-stream file and back, in two processes that share a checkpoint.
 
     python -m icm_amd.codec encode IMAGE -o FILE -a cnn -p CKPT [--tile N [--overlap M]] [--coder {host,lanes}]
-                                   [--qstep K | --target-bytes N | --target-bpp F]
+                                   [--qstep K | --target-bytes N | --target-bpp F] [--roi Y0,X0,H,W:D ...]
     python -m icm_amd.codec decode FILE -o IMAGE.png -p CKPT [--reference IMAGE] [--region Y0,X0,H,W]
 
 Parity unpinned: no counterpart in the reference (upstream CompressAI's ``examples/codec.py`` is not in its tree).  The
@@ -29,7 +29,14 @@ takes no flag.
 (csrc/qstep.hip; ``icm_amd.bitstream`` for how K travels).  K = 0, the default, is the codec without a step, and its
 files are byte for byte what they were.  ``--target-bytes`` / ``--target-bpp`` search K for a budget with real encodes
 as probes (``search_qstep``: at most 8, the analysis transform run once); a budget the coarsest step misses exits 4
-and writes nothing.  ``decode`` reads K from the stream.  Parity unpinned: no counterpart in the reference."""
+and writes nothing.  ``decode`` reads K from the stream.  Parity unpinned: no counterpart in the reference.
+
+``--roi Y0,X0,H,W:D`` (repeatable) spends the bits where a downstream task looks: the 16 x 16-pixel cells of the latent
+that hold a pixel of the rectangle are coded with the step index K + D instead of K (D negative: finer), clamped to the
+range; later rectangles win.  K is ``--qstep``, the step a budget search finds (it runs over K as without rectangles,
+the map rebuilt per probe), or 0.  The per-position map travels in the stream (``icm_amd.bitstream``, "Quality map"),
+per tile in a tiled one, and ``decode`` needs no flag; rectangles that change no cell leave the file what it is without
+them.  Parity unpinned: no counterpart in the reference, whose own answer is a task loss at training time."""
 from __future__ import annotations
 
 import argparse
@@ -38,7 +45,7 @@ import math
 import os
 import sys
 import time
-from typing import Dict, Optional, Tuple
+from typing import Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
@@ -162,21 +169,78 @@ def image_tile_blend(x: torch.Tensor, pads: Tuple[int, int, int, int], canvas: t
 
 
 def _pack_one(arch: str, fp: int, H: int, W: int, pads, enc: Dict, coder: str) -> bytes:
-    """the ICMB stream of one ``compress()`` result; a quantiser step travels as a third, one-byte string"""
+    """the ICMB stream of one ``compress()`` result; a quantiser step travels as a third, one-byte string, a quality
+    map as a third string of its runs"""
     header = {"arch": arch, "height": H, "width": W, "pads": pads, "shape": tuple(int(s) for s in enc["shape"]),
               "fingerprint": fp}
     strings = [s for part in enc["strings"] for s in part]
-    if enc["qstep"]:
+    if enc.get("qmap") is not None:
+        strings.append(B.qmap_string(enc["qmap"]))
+    elif enc["qstep"]:
         strings.append(B.qstep_string(enc["qstep"]))
     return B.pack(header, strings, coder=coder)
 
 
 def _encode_one(model, arch: str, fp: int, u8: torch.Tensor, coder: str = "host",
-                symbols_per_wave: Optional[int] = None, qstep: int = 0) -> bytes:
+                symbols_per_wave: Optional[int] = None, qstep: int = 0, qmap=None) -> bytes:
     H, W = u8.size(0), u8.size(1)
     pads = center_pads(H, W)
-    enc = model.compress(image_u8_to_f32(u8, pads), coder=coder, symbols_per_wave=symbols_per_wave, qstep=qstep)
+    enc = model.compress(image_u8_to_f32(u8, pads), coder=coder, symbols_per_wave=symbols_per_wave, qstep=qstep,
+                         qmap=qmap)
     return _pack_one(arch, fp, H, W, pads, enc, coder)
+
+
+# ------------------------------------------------------------------------------------------- regions of interest
+CELL = 16              # pixels per latent position and axis: four stride-2 stages of the analysis transform
+
+
+def check_rois(rois, H: int, W: int) -> List[Tuple[int, int, int, int, int]]:
+    """``rois`` as a list of (y0, x0, h, w, d) of ints: rectangles of image pixels inside the H x W image, each with
+    an integer offset d to the background step index.  ValueError otherwise.  Host-only."""
+    out = []
+    try:
+        rois = list(rois)
+    except TypeError:
+        raise ValueError(f"codec: roi must be a list of (y0, x0, h, w, d), got {rois!r}")
+    for r in rois:
+        try:
+            if len(r) != 5 or any(isinstance(v, bool) or not hasattr(v, "__index__") for v in r):
+                raise TypeError
+            y0, x0, h, w, d = (int(v) for v in r)
+        except TypeError:
+            raise ValueError(f"codec: a region of interest is five integers (y0, x0, h, w, d), got {r!r}")
+        if y0 < 0 or x0 < 0 or h < 1 or w < 1 or y0 + h > H or x0 + w > W:
+            raise ValueError(f"codec: region of interest {(y0, x0, h, w)} is not inside the {H}x{W} image")
+        out.append((y0, x0, h, w, d))
+    return out
+
+
+def roi_map(H: int, W: int, pads, base: int, rois) -> np.ndarray:
+    """The quality map of an H x W image padded by ``pads`` = (left, right, top, bottom): int8 [(top + H + bottom) / 16,
+    (left + W + right) / 16].  Every cell starts at the step index ``base``; the rectangles (``check_rois``) are
+    painted in list order, each onto every cell that holds at least one of its pixels, with clamp(base + d, QSTEP_MIN,
+    QSTEP_MAX); later rectangles win, and a cell that lies wholly in the padding keeps ``base``.  Host-only."""
+    base = B.check_qstep(base, "codec: ")
+    left, right, top, bottom = (int(p) for p in pads)
+    PH, PW = top + H + bottom, left + W + right
+    if PH % CELL or PW % CELL:
+        raise ValueError(f"codec: the padded image {PH}x{PW} is not a whole number of {CELL}-pixel cells")
+    m = np.full((PH // CELL, PW // CELL), base, dtype=np.int8)
+    for y0, x0, h, w, d in check_rois(rois, H, W):
+        k = min(max(base + d, B.QSTEP_MIN), B.QSTEP_MAX)
+        m[(top + y0) // CELL:(top + y0 + h - 1) // CELL + 1, (left + x0) // CELL:(left + x0 + w - 1) // CELL + 1] = k
+    return m
+
+
+def clip_rois(rois, y0: int, x0: int, h: int, w: int) -> List[Tuple[int, int, int, int, int]]:
+    """the rectangles' parts inside the tile (y0, x0, h, w), in the tile's coordinates and in list order"""
+    out = []
+    for ry, rx, rh, rw, d in rois:
+        a, b = max(ry, y0), min(ry + rh, y0 + h)
+        c, e = max(rx, x0), min(rx + rw, x0 + w)
+        if a < b and c < e:
+            out.append((a - y0, c - x0, b - a, e - c, d))
+    return out
 
 
 def search_qstep(fits, lo: int = B.QSTEP_MIN, hi: int = B.QSTEP_MAX) -> Tuple[int, int]:
@@ -210,8 +274,10 @@ def search_qstep(fits, lo: int = B.QSTEP_MIN, hi: int = B.QSTEP_MAX) -> Tuple[in
 @torch.no_grad()
 def encode_image_info(model, img, tile: Optional[int] = None, overlap: int = 0, coder: str = "host",
                       symbols_per_wave: Optional[int] = None, qstep: int = 0,
-                      max_bytes: Optional[int] = None) -> Tuple[bytes, Dict]:
-    """``encode_image`` with its outcome: (stream, {"qstep": k, "step": 2^(k/8), "probes": encodes made})"""
+                      max_bytes: Optional[int] = None, roi: Optional[Sequence] = None) -> Tuple[bytes, Dict]:
+    """``encode_image`` with its outcome: (stream, {"qstep": k, "step": 2^(k/8), "probes": encodes made}); k is the
+    background step.  With ``roi`` also "roi_cells", the number of latent cells (summed over the tiles) whose step
+    index differs from k, and "qmap_range": [smallest, largest step index in the maps]."""
     B.check_coder(coder, "codec: ")
     qstep = B.check_qstep(qstep, "codec: ")
     if max_bytes is not None:
@@ -233,13 +299,27 @@ def encode_image_info(model, img, tile: Optional[int] = None, overlap: int = 0, 
     fp = B.fingerprint(model)
     outer = {"arch": arch, "height": H, "width": W, "tile": tile, "overlap": overlap, "fingerprint": fp}
     crops = [u8] if len(plan) == 1 else [u8[y0:y0 + h, x0:x0 + w].contiguous() for y0, x0, h, w in plan]
+    # regions of interest: per tile the rectangles clipped to it, in its coordinates; the map of a tile is built from
+    # them with the tile's own pads, per probe, and a map that comes out uniform is coded as its scalar step
+    rois = None if roi is None else check_rois(roi, H, W)
+    tile_rois = None if roi is None else [clip_rois(rois, *t) for t in plan]
+
+    def maps(k):
+        """the tiles' quality maps at the background step k (None: no rectangles were given), and what they hold"""
+        if tile_rois is None:
+            return [None] * len(plan), {}
+        ms = [roi_map(h, w, center_pads(h, w), k, r) for (_, _, h, w), r in zip(plan, tile_rois)]
+        return ms, {"roi_cells": int(sum(int((m != k).sum()) for m in ms)),
+                    "qmap_range": [int(min(m.min() for m in ms)), int(max(m.max() for m in ms))]}
 
     def wrap(streams):
         return streams[0] if len(plan) == 1 else B.pack_tiled(outer, streams)
 
     if max_bytes is None:
-        data = wrap([_encode_one(model, arch, fp, c, coder, symbols_per_wave, qstep) for c in crops])
-        return data, {"qstep": qstep, "step": B.step_of(qstep)[0], "probes": 1}
+        ms, extra = maps(qstep)
+        data = wrap([_encode_one(model, arch, fp, c, coder, symbols_per_wave, 0 if m is not None else qstep, m)
+                     for c, m in zip(crops, ms)])
+        return data, {"qstep": qstep, "step": B.step_of(qstep)[0], "probes": 1, **extra}
     # encode to size: the analysis transform once per tile, then only the latent coder per probe; a probe is the very
     # container that would be written (headers, CRCs and the lanes coder's flushes included), and the answer is the
     # stream of its probe, not a second encode
@@ -250,13 +330,15 @@ def encode_image_info(model, img, tile: Optional[int] = None, overlap: int = 0, 
     sizes, kept = {}, {}
 
     def fits(k):
-        data = wrap([_pack_one(arch, fp, h, w, pads, model.compress_latent(y, coder=coder,
-                                                                           symbols_per_wave=symbols_per_wave, qstep=k),
-                               coder) for h, w, pads, y in tiles])
+        ms, extra = maps(k)
+        data = wrap([_pack_one(arch, fp, h, w, pads,
+                               model.compress_latent(y, coder=coder, symbols_per_wave=symbols_per_wave,
+                                                     qstep=0 if m is not None else k, qmap=m), coder)
+                     for (h, w, pads, y), m in zip(tiles, ms)])
         sizes[k] = len(data)
         if len(data) <= max_bytes:
             kept.clear()
-            kept[k] = data
+            kept[k] = (data, extra)
             return True
         return False
 
@@ -265,11 +347,12 @@ def encode_image_info(model, img, tile: Optional[int] = None, overlap: int = 0, 
     except ValueError:
         raise ValueError(f"codec: {max_bytes} bytes are out of reach: the coarsest step (qstep {B.QSTEP_MAX}) still "
                          f"takes {min(sizes.values())} bytes")
-    return kept[k], {"qstep": k, "step": B.step_of(k)[0], "probes": probes}
+    return kept[k][0], {"qstep": k, "step": B.step_of(k)[0], "probes": probes, **kept[k][1]}
 
 
 def encode_image(model, img, tile: Optional[int] = None, overlap: int = 0, coder: str = "host",
-                 symbols_per_wave: Optional[int] = None, qstep: int = 0, max_bytes: Optional[int] = None) -> bytes:
+                 symbols_per_wave: Optional[int] = None, qstep: int = 0, max_bytes: Optional[int] = None,
+                 roi: Optional[Sequence] = None) -> bytes:
     """8-bit [H, W, 3] image (tensor on any device, or anything ``numpy.asarray`` accepts) -> one bit-stream.  With
     ``tile``, an image of more than one tile (``plan_tiles``) becomes an ICMT stream whose tile k is
     ``encode_image(model, crop k)``, the tiles coded one after another; an image of one tile is written untiled.
@@ -277,8 +360,12 @@ def encode_image(model, img, tile: Optional[int] = None, overlap: int = 0, coder
     ``qstep``: step index of a quantiser step on the latent (``model.compress``; 0, the default: none, and the stream
     is what it was before the step existed).  ``max_bytes`` (instead of ``qstep``): the finest step ``search_qstep``
     finds at which the whole stream, of all tiles with one step, has at most that many bytes; ValueError if the
-    coarsest step does not get there.  ``encode_image_info`` also returns the step and the number of encodes."""
-    return encode_image_info(model, img, tile, overlap, coder, symbols_per_wave, qstep, max_bytes)[0]
+    coarsest step does not get there.  ``encode_image_info`` also returns the step and the number of encodes.
+    ``roi``: regions of interest [(y0, x0, h, w, d), ...], rectangles of image pixels inside the image, each with an
+    integer offset d to the background step index (negative: finer): the latent cells they touch are coded with
+    clamp(k + d) (``roi_map``), k being ``qstep`` or the step the search finds; the map travels in the stream, per
+    tile in a tiled one.  No rectangle, or none that changes a cell, gives byte for byte the stream without ``roi``."""
+    return encode_image_info(model, img, tile, overlap, coder, symbols_per_wave, qstep, max_bytes, roi)[0]
 
 
 def _check_model(header: Dict, arch: str, fp: int, what: str = "the stream") -> None:
@@ -300,10 +387,21 @@ def _check_strings(arch: str, strings, what: str = "this one") -> int:
         raise ValueError(f"codec: {what}: {e}")
 
 
+def _check_quality(arch: str, header: Dict, strings, what: str = "this one"):
+    """(step index, None) of a stream with a scalar step or none, (None, quality map) of a mapped one"""
+    if len(strings) == 3 and len(strings[2]) >= B.QMAP_STRING_MIN:
+        try:
+            return B.quality_from_strings(strings, header["shape"])
+        except ValueError as e:
+            raise ValueError(f"codec: {what}: {e}")
+    return _check_strings(arch, strings, what), None
+
+
 def _decompress_one(model, arch: str, header: Dict, strings, coder: str = "host") -> torch.Tensor:
     H, W, pads = header["height"], header["width"], header["pads"]
-    x_hat = model.decompress([[strings[0]], [strings[1]]], header["shape"], coder=coder,
-                             qstep=B.qstep_from_strings(strings))["x_hat"]
+    k, qmap = B.quality_from_strings(strings, header["shape"])
+    x_hat = model.decompress([[strings[0]], [strings[1]]], header["shape"], coder=coder, qstep=k or 0,
+                             qmap=qmap)["x_hat"]
     left, right, top, bottom = pads
     if tuple(x_hat.shape) != (1, 3, top + H + bottom, left + W + right):
         raise ValueError(f"codec: latent shape {header['shape']} decodes to {tuple(x_hat.shape)}, not to a padded "
@@ -333,7 +431,9 @@ def decode_image(model, data: bytes, reference=None, region=None) -> Tuple[torch
     images.  ``region`` = (y0, x0, h, w): only that window is returned ([h, w, 3]; "sse" / "psnr" are over it, against
     the same window of ``reference``); of a tiled stream only the tiles that touch it are decoded
     (``info["tiles_decoded"]``), and the result is bit for bit the same crop of the full decode.  "qstep": the step
-    index the stream was coded with (0: none), or the list per tile should they differ."""
+    index the stream was coded with (0: none), or the list per tile should they differ; None for a stream (in the
+    list: a tile) coded with a quality map, which "qmap" then holds: the int8 map, or of a tiled stream the list per
+    tile with None for the tiles of a scalar step.  Streams without a map have no "qmap"."""
     arch = _ready(model)
     fp = B.fingerprint(model)
     device = next(model.parameters()).device
@@ -345,10 +445,10 @@ def decode_image(model, data: bytes, reference=None, region=None) -> Tuple[torch
         rows, cols, plan = plan_tiles(H, W, outer["tile"], outer["overlap"])
         inner = [B.unpack(s) for s in streams]          # every header checked before any payload is decoded
         coders = [B.coder_of(s) for s in streams]
-        qsteps = []
+        quality = []
         for k, ((y0, x0, h, w), (hd, tile_strings)) in enumerate(zip(plan, inner)):
             _check_model(hd, arch, fp, f"tile {k}")
-            qsteps.append(_check_strings(arch, tile_strings, f"tile {k}"))
+            quality.append(_check_quality(arch, hd, tile_strings, f"tile {k}"))
             if (hd["height"], hd["width"]) != (h, w):
                 raise ValueError(f"codec: tile {k} holds a {hd['height']}x{hd['width']} image, the plan has {h}x{w}")
     else:
@@ -356,15 +456,18 @@ def decode_image(model, data: bytes, reference=None, region=None) -> Tuple[torch
         coder = B.coder_of(data)
         _check_model(header, arch, fp)
         H, W = header["height"], header["width"]
-        qsteps = [_check_strings(arch, strings)]
+        quality = [_check_quality(arch, header, strings)]
     ry, rx, rh, rw = _check_region(region, H, W)
     ref = None if reference is None else _as_u8_image(reference, device, "reference")
     if ref is not None and tuple(ref.shape) != (H, W, 3):
         raise ValueError(f"codec: the reference is {ref.size(0)}x{ref.size(1)}, the stream holds a {H}x{W} image")
     if ref is not None and region is not None:
         ref = ref[ry:ry + rh, rx:rx + rw].contiguous()
+    qsteps, qmaps = [q[0] for q in quality], [q[1] for q in quality]
     info = {"arch": arch, "height": H, "width": W, "bytes": len(data), "bpp": 8.0 * len(data) / (H * W),
             "qstep": qsteps[0] if len(set(qsteps)) == 1 else qsteps}
+    if any(m is not None for m in qmaps):
+        info["qmap"] = qmaps if tiled else qmaps[0]
     if tiled:
         sel = [k for k, (y0, x0, h, w) in enumerate(plan)
                if y0 < ry + rh and ry < y0 + h and x0 < rx + rw and rx < x0 + w]
@@ -414,6 +517,22 @@ def _region(text: str) -> Tuple[int, int, int, int]:
     return v
 
 
+def _roi(text: str) -> Tuple[int, int, int, int, int]:
+    try:
+        rect, d = text.split(":")
+        v = tuple(int(t) for t in rect.split(",")) + (int(d),)
+    except ValueError:
+        v = ()
+    if len(v) != 5:
+        raise argparse.ArgumentTypeError(f"expected Y0,X0,H,W:D, got {text!r}")
+    return v
+
+
+def _qmap_range(qmap) -> List[int]:
+    ms = [m for m in (qmap if isinstance(qmap, list) else [qmap]) if m is not None]
+    return [int(min(m.min() for m in ms)), int(max(m.max() for m in ms))]
+
+
 def setup_args() -> argparse.ArgumentParser:
     p = argparse.ArgumentParser(prog="icm_amd.codec")
     sub = p.add_subparsers(dest="command", required=True)
@@ -440,6 +559,9 @@ def setup_args() -> argparse.ArgumentParser:
                      help="the finest quantiser step at which the file has at most N bytes")
     enc.add_argument("--target-bpp", default=None, type=float, metavar="F",
                      help="the same for floor(F x height x width / 8) bytes")
+    enc.add_argument("--roi", default=None, type=_roi, action="append", metavar="Y0,X0,H,W:D",
+                     help="region of interest, repeatable: the latent cells this rectangle of image pixels touches are "
+                          "coded with the step index K + D (D < 0: finer), K the background step; later ones win")
     for s in (enc, dec):
         s.add_argument("-o", "--output", required=True, help="file to write")
         s.add_argument("-p", "--path", dest="paths", required=True, type=str, help="checkpoint path")
@@ -486,6 +608,12 @@ def main(argv) -> int:
     try:
         if args.command == "encode":
             payload = read_image_u8(args.input)
+            if args.roi is not None:
+                try:
+                    check_rois(args.roi, *payload.shape[:2])
+                except ValueError as e:
+                    print(f"Error: --roi: {e}", file=sys.stderr)
+                    return 2
         else:
             if not os.path.isfile(args.input):
                 raise ValueError(f"{args.input}: no such file")
@@ -511,7 +639,7 @@ def main(argv) -> int:
             h, w = payload.shape[:2]
             budget = args.target_bytes if args.target_bpp is None else int(math.floor(args.target_bpp * h * w / 8))
             data, found = encode_image_info(model, payload, args.tile, args.overlap, coder=args.coder,
-                                            qstep=args.qstep or 0, max_bytes=budget)
+                                            qstep=args.qstep or 0, max_bytes=budget, roi=args.roi)
             torch.cuda.synchronize()
             dt = time.perf_counter() - t0
             with open(args.output, "wb") as f:
@@ -524,7 +652,10 @@ def main(argv) -> int:
             dt = time.perf_counter() - t0
             from PIL import Image
             Image.fromarray(img.numpy()).save(args.output)
-            report = {"command": "decode", **{k: v for k, v in info.items() if k != "sse"}, "decode_time": dt}
+            report = {"command": "decode", **{k: v for k, v in info.items() if k not in ("sse", "qmap")},
+                      "decode_time": dt}
+            if "qmap" in info:
+                report["qmap_range"] = _qmap_range(info["qmap"])
     except (ValueError, FileNotFoundError) as e:
         print(f"Error: {e}", file=sys.stderr)
         return 4

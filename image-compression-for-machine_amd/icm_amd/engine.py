@@ -22,7 +22,7 @@ import torch
 from . import _lib as L
 from ._lib import (ACT_GELU, ACT_NONE, ACT_SQUARE, EPI_AXPY2, EPI_GDN, EPI_IGDN, EPI_LRP, EPI_MUL_DGELU, EPI_NONE,
                    EPI_RES, EPI_RES_GELU, EPI_RES_MUL_DGELU, bs, check, ptr)
-from .bitstream import step_of
+from .bitstream import step_of, step_table
 
 PEDESTAL = 2.0 ** -36
 _SKIP_WGRAD = _os.environ.get("ICM_DEBUG_SKIP_WGRAD", "0") == "1"
@@ -1267,6 +1267,54 @@ def dequantize_q(st, sym, mu, qstep, yh_out):
     N, Cc, H, W = mu.shape
     check(L.lib().icm_dequantize_q(sym.data_ptr(), ptr(mu), bs(mu), step_of(qstep)[0], ptr(yh_out), bs(yh_out), N, Cc,
                                    H * W, st), "dequantize_q")
+
+
+# ---- the same three with a quality map: ``qmap`` is a device int8 [H, W] tensor of step indexes the caller has checked
+# (bitstream.check_qmap), one per latent position, shared by the batch and the channels
+_step_tables = {}
+
+
+def qmap_step_table(device) -> torch.Tensor:
+    """bitstream.step_table on ``device``: uploaded once per device and kept"""
+    key = (device.type, device.index if device.index is not None else torch.cuda.current_device())
+    if key not in _step_tables:
+        _step_tables[key] = torch.from_numpy(step_table()).to(device).contiguous()
+    return _step_tables[key]
+
+
+def _qmap_ptr(qmap, H, W):
+    if qmap.dtype != torch.int8 or tuple(qmap.shape) != (H, W) or not qmap.is_contiguous():
+        raise ValueError(f"quality map: expected a contiguous int8 {(H, W)} tensor, got {qmap.dtype} {tuple(qmap.shape)}")
+    return qmap.data_ptr()
+
+
+def gc_code_qmap(st, y, mu, scale, table, scale_bound, qmap, yh_out):
+    """``gc_code_q`` with the step of each position taken from ``qmap``"""
+    N, Cc, H, W = y.shape
+    sym = torch.empty((N, Cc, H, W), dtype=torch.int32, device=y.device)
+    idx = torch.empty((N, Cc, H, W), dtype=torch.int32, device=y.device)
+    check(L.lib().icm_gc_code_qmap(ptr(y), bs(y), ptr(mu), bs(mu), ptr(scale), bs(scale), ptr(table), int(table.numel()),
+                                   scale_bound, _qmap_ptr(qmap, H, W), ptr(qmap_step_table(y.device)), sym.data_ptr(),
+                                   idx.data_ptr(), ptr(yh_out), bs(yh_out), N, Cc, H * W, st), "gc_code_qmap")
+    return sym, idx
+
+
+def gc_indexes_qmap(st, scale, table, scale_bound, qmap):
+    """``gc_indexes_q`` with a quality map: the CDF indexes the encoder's gc_code_qmap coded with"""
+    N, Cc, H, W = scale.shape
+    idx = torch.empty((N, Cc, H, W), dtype=torch.int32, device=scale.device)
+    check(L.lib().icm_gc_indexes_qmap(ptr(scale), bs(scale), ptr(table), int(table.numel()), scale_bound,
+                                      _qmap_ptr(qmap, H, W), ptr(qmap_step_table(scale.device)), idx.data_ptr(), N, Cc,
+                                      H * W, st), "gc_indexes_qmap")
+    return idx
+
+
+def dequantize_qmap(st, sym, mu, qmap, yh_out):
+    """``dequantize_q`` with a quality map: y_hat_pre -> yh_out, the encoder's bit for bit"""
+    N, Cc, H, W = mu.shape
+    check(L.lib().icm_dequantize_qmap(sym.data_ptr(), ptr(mu), bs(mu), _qmap_ptr(qmap, H, W),
+                                      ptr(qmap_step_table(mu.device)), ptr(yh_out), bs(yh_out), N, Cc, H * W, st),
+          "dequantize_qmap")
 
 
 # ------------------------------------------------------------------------------------------------ stf6 plumbing

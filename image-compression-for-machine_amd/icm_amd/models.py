@@ -16,7 +16,7 @@ from . import _lib as L
 from . import engine as E
 from ._lib import ACT_GELU
 from .ans import coder_for
-from .bitstream import check_qstep
+from .bitstream import check_qmap, check_qstep, uniform_qmap
 from .engine import VT
 from .entropy_models import EntropyBottleneck, GaussianConditional
 from .layers import (GDN, Conv2d, Win_noShift_Attention, WindowAttention, conv, conv3x3, deconv, subpel_conv3x3,
@@ -76,16 +76,17 @@ class CompressionModel(nn.Module):
         names, params = _named(self)
         return dict(zip(names, [p.detach() for p in params]))
 
-    def _compress_latent(self, tape, P, y, coder, debug=None, qstep=0):
+    def _compress_latent(self, tape, P, y, coder, debug=None, qstep=0, qmap=None):
         """cnn.py:214-266 from ``y`` on: {"strings": [[y_string], z_strings], "shape": z spatial size, "qstep"}.
         ``coder`` (``icm_amd.ans.coder_for``) codes the recorded device tensors of all slices as one y string, a run
         per slice, and the z strings as single-run strings.  ``qstep``: step index of the quantiser step on y (0: none;
-        z and its EntropyBottleneck know no step)."""
+        z and its EntropyBottleneck know no step).  ``qmap``: a non-uniform quality map as ``_quality`` returns it (a
+        checked int8 host array; ``qstep`` is then 0), returned under "qmap" with "qstep": None."""
         gc = self.gaussian_conditional
         codec = {"gc": gc, "symbols": {}, "indexes": {}}
         keep = {}
         hyper_slices(tape, P, y, None, None, self.num_slices, self.max_support_slices, keep=keep, codec=codec,
-                     qstep=qstep)
+                     qstep=qstep, qmap=None if qmap is None else torch.from_numpy(qmap).to(y.device))
         z = keep["z"]
         z_strings = self.entropy_bottleneck.compress(z, coder=coder)
         sym = torch.cat([codec["symbols"][i].reshape(-1) for i in range(self.num_slices)])
@@ -94,26 +95,30 @@ class CompressionModel(nn.Module):
         y_string = coder.encode(sym, idx, [codec["symbols"][i].numel() for i in range(self.num_slices)], gc)
         if debug is not None:      # tests: the coded symbols / CDF indexes (slice-major, cnn.py:254-255), the final y_hat
             debug.update(symbols=sym.cpu().numpy(), indexes=idx.cpu().numpy(), y_hat=keep["y_hat"])
+        if qmap is not None:
+            return {"strings": [[y_string], z_strings], "shape": z.size()[-2:], "qstep": None, "qmap": qmap}
         return {"strings": [[y_string], z_strings], "shape": z.size()[-2:], "qstep": qstep}
 
     @torch.no_grad()
-    def compress_latent(self, y, _debug=None, coder="host", symbols_per_wave=None, qstep=0):
+    def compress_latent(self, y, _debug=None, coder="host", symbols_per_wave=None, qstep=0, qmap=None):
         """``compress`` from the latent on: ``y`` is what ``analysis(x)`` returned.  A rate search runs the analysis
         transform once per image and this once per probe."""
         qstep = check_qstep(qstep, "compress: ")
         coder = coder_for(coder, symbols_per_wave)
         if not isinstance(y, torch.Tensor) or y.dim() != 4 or y.dtype != torch.float32:
             raise ValueError("compress_latent: expected the f32 [B,M,h,w] latent of analysis()")
+        qstep, qmap = _quality(qstep, qmap, y.shape[2:], "compress: ")
         tape = E.Tape(need_grad=False, packed_cache=self._pack_cache())
-        return self._compress_latent(tape, self._params(), y.contiguous(), coder, _debug, qstep)
+        return self._compress_latent(tape, self._params(), y.contiguous(), coder, _debug, qstep, qmap)
 
-    def _decompress_latent(self, tape, P, strings, shape, M, coder, qstep=0):
+    def _decompress_latent(self, tape, P, strings, shape, M, coder, qstep=0, qmap=None):
         """cnn.py:289-328: y_hat from the two streams"""
         if not isinstance(strings, (list, tuple)) or len(strings) != 2:
             raise ValueError("strings must be [y_strings, z_strings]")
         z_hat = self.entropy_bottleneck.decompress(strings[1], shape, coder=coder)
         return decode_slices(tape, P, z_hat, strings[0][0], self.gaussian_conditional, self.num_slices,
-                             self.max_support_slices, M, coder, qstep)
+                             self.max_support_slices, M, coder, qstep,
+                             None if qmap is None else torch.from_numpy(qmap).to(z_hat.device))
 
     def load_state_dict(self, state_dict, strict: bool = False):
         # models/base.py:62-70: resize the CDF buffers to whatever the checkpoint holds, then strict=False
@@ -192,7 +197,8 @@ SLICE_SPLIT = _os.environ.get("ICM_SLICE_SPLIT", "1") != "0"
 
 def hyper_slices(tape: E.Tape, P: Dict[str, torch.Tensor], y: torch.Tensor, noise_z, noise_y, num_slices: int,
                  max_support: int, keep: Optional[dict] = None, bucket_marks: Optional[dict] = None,
-                 batch_tail: bool = True, codec: Optional[dict] = None, decode: Optional[dict] = None, qstep: int = 0):
+                 batch_tail: bool = True, codec: Optional[dict] = None, decode: Optional[dict] = None, qstep: int = 0,
+                 qmap: Optional[torch.Tensor] = None):
     """Hyperprior + channel-conditional slice loop shared by the cnn and stf models
     (cnn.py:144-183 == stf.py:596-637) -> (y_hat, y_likelihoods, z_likelihoods).  torch.cat / chunk become
     channel-slice views of persistent support buffers.
@@ -203,14 +209,16 @@ def hyper_slices(tape: E.Tape, P: Dict[str, torch.Tensor], y: torch.Tensor, nois
     which the CDF indexes depend on), but each slice's y_hat_pre comes from the entropy decoder instead of from y.
     qstep (codec / decode only): step index of the quantiser step on y.  Non-zero, the encoder's work per slice is ONE
     launch (``_record_symbols``: symbols, indexes and y_hat_pre; no likelihoods, which compress() never reads), and
-    the decoder's callback, which ``decode_slices`` builds for the same step, mirrors it."""
-    if qstep and codec is None and decode is None:
+    the decoder's callback, which ``decode_slices`` builds for the same step, mirrors it.
+    qmap (codec / decode only, instead of qstep): a quality map, a device int8 [h, w] tensor of step indexes, one per
+    latent position; the same launches as with a step, the map-reading kernels in their place."""
+    if (qstep or qmap is not None) and codec is None and decode is None:
         raise ValueError("the quantiser step exists in the codec only (compress / decompress)")
     if SLICE_SPLIT and batch_tail:
         from .slices import hyper_slices_split
         return hyper_slices_split(tape, P, y, noise_z, noise_y, num_slices, max_support, keep, bucket_marks, codec,
                                   decode, lambda t, P_, y_: _chain(t, P_, "h_a", VT(y_), strides=(1, 1, 2, 1, 2)),
-                                  _h_s_pair, _record_symbols, qstep)
+                                  _h_s_pair, _record_symbols, qstep, qmap)
     if decode is not None:
         z_hat = decode["z_hat"].contiguous()
         dev, N, M = z_hat.device, z_hat.shape[0], decode["M"]
@@ -255,7 +263,8 @@ def hyper_slices(tape: E.Tape, P: Dict[str, torch.Tensor], y: torch.Tensor, nois
         raise ValueError("hyper-synthesis output does not match the latent size (input must be a multiple of 64)")
     _h_s_pair(tape, P, "h_scale_s", "h_mean_s", z_hat, SS[:, :M], MS[:, :M])
     Y_hat = E.new((N, M, h, w), dev)
-    fused = codec is not None and qstep != 0       # the step-aware encoder: one launch per slice, no likelihoods
+    # the step-aware encoder: one launch per slice, no likelihoods
+    fused = codec is not None and (qstep != 0 or qmap is not None)
     Y_lik = E.new((N, M, h, w), dev) if decode is None and not fused else None
     if need:
         dYh = E.zeros(Y_hat.shape, dev)
@@ -286,7 +295,7 @@ def hyper_slices(tape: E.Tape, P: Dict[str, torch.Tensor], y: torch.Tensor, nois
         if decode is not None:
             decode["slice"](i, mu, sc, yh_pre)
         elif fused:
-            _record_symbols(codec, i, y[:, ch], mu, sc, yh_pre, qstep)
+            _record_symbols(codec, i, y[:, ch], mu, sc, yh_pre, qstep, qmap)
         else:
             E.gc_likelihood_ste(tape, y[:, ch], mu, sc, None if noise_y is None else noise_y[:, ch], Y_lik[:, ch],
                                 yh_pre)
@@ -324,7 +333,7 @@ def hyper_slices(tape: E.Tape, P: Dict[str, torch.Tensor], y: torch.Tensor, nois
             if decode is not None:
                 decode["slice"](i, mu_t[j], sc_t[j], yh_pre)
             elif fused:
-                _record_symbols(codec, i, y[:, ch], mu_t[j], sc_t[j], yh_pre, qstep)
+                _record_symbols(codec, i, y[:, ch], mu_t[j], sc_t[j], yh_pre, qstep, qmap)
             else:
                 E.gc_likelihood_ste(tape, y[:, ch], mu_t[j], sc_t[j], None if noise_y is None else noise_y[:, ch],
                                     Y_lik[:, ch], yh_pre)
@@ -351,10 +360,27 @@ def _scale_table(gc, dev):
     return gc.scale_table.detach().to(dev, torch.float32).contiguous()
 
 
-def _record_symbols(codec, i, y_slice, mu, sc, yh_pre=None, qstep=0):
+def _quality(qstep, qmap, hw, who):
+    """(qstep, qmap) as the latent coder takes them, from the public pair: ``qmap`` checked against the latent's
+    spatial size ``hw`` (``bitstream.check_qmap``: ValueError before any GPU work, also for a map given together with
+    a step).  A uniform map *is* its scalar step: (k, None).  A non-uniform one: (0, int8 host array)."""
+    if qmap is None:
+        return qstep, None
+    qmap = check_qmap(qmap, hw, qstep, who)
+    k = uniform_qmap(qmap)
+    return (k, None) if k is not None else (0, qmap)
+
+
+def _record_symbols(codec, i, y_slice, mu, sc, yh_pre=None, qstep=0, qmap=None):
     """symbols = quantize(y_slice, "symbols", mu) and indexes = build_indexes(scale) of slice i (cnn.py:246-252).
     With a quantiser step: symbols round((y - mu) / step), indexes of scale / step and y_hat_pre = symbols * step + mu
-    -> yh_pre, all from ONE launch (the caller then makes no likelihood launch)."""
+    -> yh_pre, all from ONE launch (the caller then makes no likelihood launch); with a quality map the same launch
+    with the step of each position."""
+    if qmap is not None:
+        gc, dev = codec["gc"], y_slice.device
+        codec["symbols"][i], codec["indexes"][i] = E.gc_code_qmap(L.stream(), y_slice, mu, sc, _scale_table(gc, dev),
+                                                                  gc._scale_bound, qmap, yh_pre)
+        return
     if qstep:
         gc, dev = codec["gc"], y_slice.device
         codec["symbols"][i], codec["indexes"][i] = E.gc_code_q(L.stream(), y_slice, mu, sc, _scale_table(gc, dev),
@@ -369,23 +395,28 @@ def _record_symbols(codec, i, y_slice, mu, sc, yh_pre=None, qstep=0):
 
 
 def decode_slices(tape: E.Tape, P, z_hat, y_string: bytes, gc, num_slices: int, max_support: int, M: int, coder,
-                  qstep: int = 0):
+                  qstep: int = 0, qmap: Optional[torch.Tensor] = None):
     """Decoder side of the slice loop (cnn.py:296-326): hyper_slices in decode mode -- per slice the chains give
     mu / scale -> CDF indexes -> ``decode_run`` of the coder's decoder yields the symbols -> y_hat_pre = symbols + mu;
     the LRP correction and the support bookkeeping are the forward's own.  Returns y_hat [N,M,h,w].  ``coder``: of
     ``icm_amd.ans.coder_for``; what a ``decode_run`` costs (host: a copy down and one up; lanes: one launch, no wait,
     the status read by ``finish`` after the loop) is the coder's business.  With a quantiser step ``qstep`` the two
-    launches around ``decode_run`` are the step-aware ones, which share their arithmetic with the encoder's kernel."""
+    launches around ``decode_run`` are the step-aware ones, which share their arithmetic with the encoder's kernel;
+    with a quality map ``qmap`` (a device int8 [h, w] tensor) the map-reading ones."""
     gc._check_tables()
     dec = coder.decoder(y_string, gc)
     state = {"next": 0}
-    table = _scale_table(gc, z_hat.device) if qstep else None
+    table = _scale_table(gc, z_hat.device) if qstep or qmap is not None else None
 
     def one(i, mu, sc, yh_pre):
         if i != state["next"]:
             raise RuntimeError("slices must be decoded in stream order")
         state["next"] += 1
         N, Cc, h, w = mu.shape
+        if qmap is not None:
+            sym = dec.decode_run(E.gc_indexes_qmap(tape.st, sc, table, gc._scale_bound, qmap))
+            E.dequantize_qmap(tape.st, sym, mu, qmap, yh_pre)
+            return
         if qstep:
             sym = dec.decode_run(E.gc_indexes_q(tape.st, sc, table, gc._scale_bound, qstep))
             E.dequantize_q(tape.st, sym, mu, qstep, yh_pre)
@@ -396,7 +427,7 @@ def decode_slices(tape: E.Tape, P, z_hat, y_string: bytes, gc, num_slices: int, 
 
     try:
         Y_hat, _, _ = hyper_slices(tape, P, None, None, None, num_slices, max_support,
-                                   decode={"z_hat": z_hat, "M": M, "slice": one}, qstep=qstep)
+                                   decode={"z_hat": z_hat, "M": M, "slice": one}, qstep=qstep, qmap=qmap)
         dec.finish()
     finally:
         dec.close()
@@ -664,6 +695,15 @@ def _crop_eval_output(x_hat, pads):
     return crop(x_hat, pads)
 
 
+def _latent_hw(shape):
+    """spatial size of the latent y for the ``shape`` entry (z's) of a compress() result"""
+    try:
+        zh, zw = (int(s) for s in shape)
+    except (TypeError, ValueError):
+        raise ValueError(f"decompress: shape must be the two spatial sizes of z, got {shape!r}")
+    return 4 * zh, 4 * zw
+
+
 def _check_codec_input(x):
     if x.dim() != 4 or x.shape[1] != 3:
         raise ValueError("expected [B,3,H,W]")
@@ -768,27 +808,33 @@ class WACNN(CompressionModel):
         return wacnn_g_a(tape, self._params(), x.contiguous())
 
     @torch.no_grad()
-    def compress(self, x, _debug=None, coder="host", symbols_per_wave=None, qstep=0):
+    def compress(self, x, _debug=None, coder="host", symbols_per_wave=None, qstep=0, qmap=None):
         """cnn.py:210-266 -> {"strings": [[y_string], z_strings], "shape": z.shape[-2:], "qstep"}; ``coder``: "host"
         (the reference's scalar stream) or "lanes" (lane streams coded on the device, ``symbols_per_wave`` symbols of
         a slice per wave body, None: ``icm_amd.ans.SYMBOLS_PER_WAVE``); ``qstep``: step index k of a quantiser step
         2^(k/8) on y (``icm_amd.bitstream.step_of``; 0: none, a larger k a smaller stream; parity unpinned: no
-        counterpart in the reference); the decoder must be told the same coder and the same step"""
+        counterpart in the reference); the decoder must be told the same coder and the same step.
+        ``qmap`` (instead of ``qstep``): a quality map, a 2-D integer array or tensor of the latent's spatial size
+        (H / 16, W / 16) holding a step index per position, shared by the batch and all channels.  A map whose
+        entries are all k is ``qstep=k``, and that is what is returned; any other comes back, as an int8 host array,
+        under "qmap" with "qstep": None, and the decoder must be given it."""
         qstep = check_qstep(qstep, "compress: ")
         coder = coder_for(coder, symbols_per_wave)
         _check_codec_input(x)
+        qstep, qmap = _quality(qstep, qmap, (x.shape[2] // 16, x.shape[3] // 16), "compress: ")
         P = self._params()
         tape = E.Tape(need_grad=False, packed_cache=self._pack_cache())
-        return self._compress_latent(tape, P, wacnn_g_a(tape, P, x.contiguous()), coder, _debug, qstep)
+        return self._compress_latent(tape, P, wacnn_g_a(tape, P, x.contiguous()), coder, _debug, qstep, qmap)
 
     @torch.no_grad()
-    def decompress(self, strings, shape, coder="host", qstep=0):
+    def decompress(self, strings, shape, coder="host", qstep=0, qmap=None):
         """cnn.py:289-332 -> {"x_hat"} clamped to [0, 1]"""
         qstep = check_qstep(qstep, "decompress: ")
         coder = coder_for(coder)
+        qstep, qmap = _quality(qstep, qmap, None if qmap is None else _latent_hw(shape), "decompress: ")
         P = self._params()
         tape = E.Tape(need_grad=False, packed_cache=self._pack_cache())
-        x_hat = wacnn_g_s(tape, P, self._decompress_latent(tape, P, strings, shape, 320, coder, qstep))
+        x_hat = wacnn_g_s(tape, P, self._decompress_latent(tape, P, strings, shape, 320, coder, qstep, qmap))
         L.check(L.lib().icm_clamp(L.ptr(x_hat), x_hat.numel(), 0.0, 1.0, tape.st), "clamp")
         return {"x_hat": x_hat}
 
@@ -1038,24 +1084,26 @@ class SymmetricalTransFormer(CompressionModel):
         return stf_analysis(tape, self._params(), x.contiguous(), None, self.window_size)
 
     @torch.no_grad()
-    def compress(self, x, _debug=None, coder="host", symbols_per_wave=None, qstep=0):
-        """stf.py compress(): analysis transform, then the shared latent coder (``coder``, ``qstep``: see
+    def compress(self, x, _debug=None, coder="host", symbols_per_wave=None, qstep=0, qmap=None):
+        """stf.py compress(): analysis transform, then the shared latent coder (``coder``, ``qstep``, ``qmap``: see
         WACNN.compress)"""
         qstep = check_qstep(qstep, "compress: ")
         coder = coder_for(coder, symbols_per_wave)
         _check_codec_input(x)
+        qstep, qmap = _quality(qstep, qmap, (x.shape[2] // 16, x.shape[3] // 16), "compress: ")
         P = self._params()
         tape = E.Tape(need_grad=False, packed_cache=self._pack_cache())
         return self._compress_latent(tape, P, stf_analysis(tape, P, x.contiguous(), None, self.window_size), coder,
-                                     _debug, qstep)
+                                     _debug, qstep, qmap)
 
     @torch.no_grad()
-    def decompress(self, strings, shape, coder="host", qstep=0):
+    def decompress(self, strings, shape, coder="host", qstep=0, qmap=None):
         qstep = check_qstep(qstep, "decompress: ")
         coder = coder_for(coder)
+        qstep, qmap = _quality(qstep, qmap, None if qmap is None else _latent_hw(shape), "decompress: ")
         P = self._params()
         tape = E.Tape(need_grad=False, packed_cache=self._pack_cache())
-        y_hat = self._decompress_latent(tape, P, strings, shape, 384, coder, qstep)
+        y_hat = self._decompress_latent(tape, P, strings, shape, 384, coder, qstep, qmap)
         x_hat = stf_synthesis(tape, P, y_hat, None, self.window_size)
         L.check(L.lib().icm_clamp(L.ptr(x_hat), x_hat.numel(), 0.0, 1.0, tape.st), "clamp")
         return {"x_hat": x_hat}
@@ -1151,11 +1199,11 @@ class SymmetricalTransFormer3(SymmetricalTransFormer):
     def update(self, scale_table=None, force=False):
         return self._update_tables(scale_table, force)
 
-    def compress(self, x, _debug=None, coder="host", symbols_per_wave=None, qstep=0):
+    def compress(self, x, _debug=None, coder="host", symbols_per_wave=None, qstep=0, qmap=None):
         raise NotImplementedError("stf6: the zigzag entropy coder loop (stf6.py:898-1057) is not mirrored")
 
-    def compress_latent(self, y, _debug=None, coder="host", symbols_per_wave=None, qstep=0):
+    def compress_latent(self, y, _debug=None, coder="host", symbols_per_wave=None, qstep=0, qmap=None):
         raise NotImplementedError("stf6: the zigzag entropy coder loop (stf6.py:898-1057) is not mirrored")
 
-    def decompress(self, strings, shape, coder="host", qstep=0):
+    def decompress(self, strings, shape, coder="host", qstep=0, qmap=None):
         raise NotImplementedError("stf6: the zigzag entropy coder loop (stf6.py:898-1057) is not mirrored")

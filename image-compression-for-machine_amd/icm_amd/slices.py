@@ -87,9 +87,9 @@ def _block_grad(tape, w):
 
 def hyper_slices_split(tape: E.Tape, P: Dict[str, torch.Tensor], y, noise_z, noise_y, num_slices: int, max_support: int,
                        keep: Optional[dict], bucket_marks: Optional[dict], codec: Optional[dict], decode: Optional[dict],
-                       h_a, h_s_pair, record_symbols, qstep: int = 0):
+                       h_a, h_s_pair, record_symbols, qstep: int = 0, qmap=None):
     """see module docstring; h_a / h_s_pair / record_symbols are models.py's helpers (shared with the unsplit path);
-    qstep: the codec's quantiser step on y, as in models.hyper_slices"""
+    qstep / qmap: the codec's quantiser step on y or its quality map, as in models.hyper_slices"""
     if decode is not None:
         z_hat = decode["z_hat"].contiguous()
         dev, N, M = z_hat.device, z_hat.shape[0], decode["M"]
@@ -152,7 +152,8 @@ def hyper_slices_split(tape: E.Tape, P: Dict[str, torch.Tensor], y, noise_z, noi
     Y_hat = E.new((N, M, h, w), dev)
     YP = E.new((N, M, h, w), dev)                   # y_hat before the LRP correction, per slice (cnn.py:171-173)
     MU, SC = E.new((N, M, h, w), dev), E.new((N, M, h, w), dev)
-    fused = codec is not None and qstep != 0        # the step-aware encoder: one launch per slice, no likelihoods
+    # the step-aware encoder: one launch per slice, no likelihoods
+    fused = codec is not None and (qstep != 0 or qmap is not None)
     Y_lik = E.new((N, M, h, w), dev) if decode is None and not fused else None
     if need:
         dYh = E.zeros(Y_hat.shape, dev)
@@ -292,7 +293,7 @@ def hyper_slices_split(tape: E.Tape, P: Dict[str, torch.Tensor], y, noise_z, noi
             if decode is not None:
                 decode["slice"](i, MU[:, s1], SC[:, s1], YP[:, s1])
             elif fused:
-                record_symbols(codec, i, y[:, s1], MU[:, s1], SC[:, s1], YP[:, s1], qstep)
+                record_symbols(codec, i, y[:, s1], MU[:, s1], SC[:, s1], YP[:, s1], qstep, qmap)
             else:
                 E.gc_likelihood_ste(tape, y[:, s1], MU[:, s1], SC[:, s1], None if noise_y is None else noise_y[:, s1],
                                     Y_lik[:, s1], YP[:, s1])

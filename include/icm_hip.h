@@ -413,6 +413,21 @@ int icm_gc_indexes_q(const float* scale, int64_t sc_bs, const float* scale_table
                      int32_t* indexes, int N, int C, int HW, void* stream);
 int icm_dequantize_q(const int32_t* symbols, const float* mu, int64_t mu_bs, float step, float* yh, int64_t yh_bs, int N,
                      int C, int HW, void* stream);
+/* The same three with a quality map: a step per latent position, shared by every n and c.  `qmap`: HW step indexes k
+ * (int8, dense); `step_table`: 256 (step, inv) pairs of f32, 8-byte aligned, indexed by the map byte read as uint8_t
+ * (icm_amd/bitstream.py:step_table; bytes that are no valid k hold (1, 1)).  The element at position p of any (n, c)
+ * is coded with the pair of qmap[p], through the device functions the scalar kernels use: a map whose every entry is
+ * k gives the outputs of the scalar entry points at step_of(k).  The kernels neither clamp nor check the map; the
+ * callers refuse an invalid one.  ICM_ERR_ARG before any launch, outputs untouched: a null pointer (qmap and
+ * step_table included), ns < 1, N, C or HW < 1. */
+int icm_gc_code_qmap(const float* y, int64_t y_bs, const float* mu, int64_t mu_bs, const float* scale, int64_t sc_bs,
+                     const float* scale_table, int ns, float scale_bound, const int8_t* qmap, const float* step_table,
+                     int32_t* symbols, int32_t* indexes, float* yh, int64_t yh_bs, int N, int C, int HW, void* stream);
+int icm_gc_indexes_qmap(const float* scale, int64_t sc_bs, const float* scale_table, int ns, float scale_bound,
+                        const int8_t* qmap, const float* step_table, int32_t* indexes, int N, int C, int HW,
+                        void* stream);
+int icm_dequantize_qmap(const int32_t* symbols, const float* mu, int64_t mu_bs, const int8_t* qmap,
+                        const float* step_table, float* yh, int64_t yh_bs, int N, int C, int HW, void* stream);
 
 /* ---- R-D loss (train.py:53-61, train_czigzag.py:63,71) --------------------------------------
  * out[0]=bpp, out[1]=mse, out[2]=loss, out[3]=sum log(lik_y), out[4]=sum log(lik_z) (5 floats, overwritten);

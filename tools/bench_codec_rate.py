@@ -11,12 +11,19 @@
                     file and the middle between it and the qstep 0 file (where this model's sizes still move; a budget
                     the coarsest step misses is reported as such), with the wall time of the analysis transform alone
                     and of one probe (``compress_latent`` + container) next to them.
+    roi_encode      encode wall time at qstep 8 against the same encode with one centred region of interest (a quarter
+                    of the image at offset -16: a quality map, the map-reading kernel per slice), alternated, with both
+                    file sizes.
+
+``slice_kernels`` also times the map-reading fused kernel (``icm_gc_code_qmap``) against the scalar one
+(``icm_gc_code_q``) on the same operands in the same run, with the map of that centred region and with a map that
+changes its step at every position.
 
 Every part runs for both coders, warmed, with the host clock around a device synchronise.  The model is randomly
 initialised (seeded): bytes and PSNR exercise the mechanism and say nothing about a trained codec's rate-distortion.
 Prints one JSON line per part and coder.
 
-    python tools/bench_codec_rate.py [--rounds 5] [--iters 100] [--coder {host,lanes,both}]
+    python tools/bench_codec_rate.py [--rounds 5] [--iters 100] [--coder {host,lanes,both}] [--parts a,b,...]
 """
 import argparse
 import json
@@ -32,6 +39,8 @@ for p in (ROOT, os.path.join(ROOT, "image-compression-for-machine_amd")):
 
 H, W = 2048, 3072
 RATE_POINTS = (-16, -8, 0, 8, 16, 24, 32)
+PARTS = ("slice_kernels", "step_vs_plain", "rate_points", "target_bpp", "roi_encode")
+ROI = (H // 4, W // 4, H // 2, W // 2, -16)        # the centred quarter of the image, two octaves finer
 
 
 def synthetic(np, h, w, seed):
@@ -51,8 +60,9 @@ def wall(fn, torch):
     return time.perf_counter() - t0, r
 
 
-def slice_kernels(args, torch):
+def slice_kernels(args, torch, np):
     from icm_amd import _lib as L
+    from icm_amd import codec
     from icm_amd import engine as E
     from icm_amd.zoo import models
     model = models["cnn"]().to("cuda:0").eval()
@@ -76,10 +86,19 @@ def slice_kernels(args, torch):
     def fused():
         return E.gc_code_q(L.stream(), Y[:, s1], MU[:, s1], SC[:, s1], table, gc._scale_bound, 8, YP[:, s1])
 
+    roi = torch.from_numpy(codec.roi_map(H, W, codec.center_pads(H, W), 8, [ROI])).to("cuda:0")
+    busy = torch.from_numpy(np.array([-16, -3, 0, 5, 8, 32], dtype=np.int8)[(5 * np.arange(h * w)) % 6].reshape(h, w))
+    busy = busy.to("cuda:0")
+
+    def mapped(qmap):
+        return lambda: E.gc_code_qmap(L.stream(), Y[:, s1], MU[:, s1], SC[:, s1], table, gc._scale_bound, qmap, YP[:, s1])
+
     res = {"metric": "slice_kernels", "slice": [N, c, h, w], "iters": args.iters}
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     for name, fn in (("plain_three_launches_us", plain), ("fused_one_launch_us", fused), ("plain_again_us", plain),
-                     ("fused_again_us", fused)):
+                     ("fused_again_us", fused), ("map_roi_us", mapped(roi)), ("fused_third_us", fused),
+                     ("map_busy_us", mapped(busy)), ("fused_fourth_us", fused), ("map_roi_again_us", mapped(roi)),
+                     ("map_busy_again_us", mapped(busy))):
         for _ in range(10):
             fn()
         torch.cuda.synchronize()
@@ -102,6 +121,27 @@ def run(args, coder, torch, np, codec, B):
 
     def encode(**kw):
         return codec.encode_image_info(model, a, coder=coder, **kw)
+
+    # ---- (d) one centred region of interest against the scalar step, alternated
+    if "roi_encode" in args.parts:
+        kws = {"scalar": dict(qstep=8), "roi": dict(qstep=8, roi=[ROI])}
+        for kw in kws.values():
+            encode(**kw)
+        ts = {name: [] for name in kws}
+        for _ in range(args.rounds):
+            for name, kw in kws.items():
+                ts[name].append(wall(lambda: encode(**kw), torch)[0])
+        out = {name: encode(**kw) for name, kw in kws.items()}
+        print(json.dumps({"metric": "roi_encode", **base, "roi": list(ROI),
+                          "qstep8_encode_s": round(statistics.median(ts["scalar"]), 4),
+                          "qstep8_roi_encode_s": round(statistics.median(ts["roi"]), 4),
+                          "qstep8_all_s": [round(t, 4) for t in ts["scalar"]],
+                          "qstep8_roi_all_s": [round(t, 4) for t in ts["roi"]],
+                          "qstep8_bytes": len(out["scalar"][0]), "qstep8_roi_bytes": len(out["roi"][0]),
+                          "roi_cells": out["roi"][1]["roi_cells"], "qmap_range": out["roi"][1]["qmap_range"]}),
+              flush=True)
+    if not {"step_vs_plain", "rate_points", "target_bpp"} & set(args.parts):
+        return
 
     # ---- (a) the fused launch against today's three, alternated
     for k in (0, 8):
@@ -160,14 +200,23 @@ def main():
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--iters", type=int, default=100)
     ap.add_argument("--coder", default="both", choices=["host", "lanes", "both"])
+    ap.add_argument("--parts", default=",".join(PARTS),
+                    help=f"comma-separated parts to run, of {', '.join(PARTS)} (step_vs_plain, rate_points and "
+                         f"target_bpp build on one another and run together)")
     args = ap.parse_args()
+    args.parts = [p for p in args.parts.split(",") if p]
+    if set(args.parts) - set(PARTS):
+        ap.error(f"unknown part in --parts; choose from {', '.join(PARTS)}")
     import numpy as np
     import torch
     if not torch.cuda.is_available():
         sys.exit("bench_codec_rate: no GPU (there is no CPU fallback)")
     from icm_amd import bitstream as B
     from icm_amd import codec
-    slice_kernels(args, torch)
+    if "slice_kernels" in args.parts:
+        slice_kernels(args, torch, np)
+    if not set(args.parts) - {"slice_kernels"}:
+        return
     for coder in (("host", "lanes") if args.coder == "both" else (args.coder,)):
         run(args, coder, torch, np, codec, B)
 
