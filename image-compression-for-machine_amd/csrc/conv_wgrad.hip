@@ -1183,6 +1183,8 @@ static int wgrad_wino_grouped(const icm_wgrad_args* arr, int n, hipStream_t stre
   if (rc) return rc;
   if ((long long)a->N * ((a->W + 1) / 2) * ((a->H + 1) / 2) >= 65536) return ICM_ERR_UNSUPPORTED;   // tile index fits the fast division
   if (!members_agree(arr, n) || !workspaces_fit(arr, n, workspace_floats(nsplit, 16, a->Ca, a->Cb))) return ICM_ERR_ARG;
+  for (int i = 0; i < n; ++i)   // fill_reduce refuses this too, but only after the first launch has written the workspace
+    if (arr[i].dw_ld > 0 && arr[i].dw_ld < a->Cb) return ICM_ERR_ARG;
   const long long slab_all = slab_floats(nsplit, 16, a->Ca, a->Cb);
   float* wsp[WG_MAXG];
   float* dbp[WG_MAXG];
