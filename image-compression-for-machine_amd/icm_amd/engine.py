@@ -1239,38 +1239,7 @@ def gc_likelihood_ste(tape, y, mu, scale, noise, lik_out, yh_out, yh2_out=None, 
         tape.bw.append(bwd)
 
 
-# ---- quantiser step on y (csrc/qstep.hip; inference only: the codec's compress / decompress).  ``qstep`` is the step
-# index k; the two floats the kernels take come from bitstream.step_of on both sides.  ``st``: the stream to launch on.
-def gc_code_q(st, y, mu, scale, table, scale_bound, qstep, yh_out):
-    """encoder, one launch per slice: (symbols, CDF indexes), both dense int32 of y's shape; y_hat_pre -> yh_out"""
-    step, inv = step_of(qstep)
-    N, Cc, H, W = y.shape
-    sym = torch.empty((N, Cc, H, W), dtype=torch.int32, device=y.device)
-    idx = torch.empty((N, Cc, H, W), dtype=torch.int32, device=y.device)
-    check(L.lib().icm_gc_code_q(ptr(y), bs(y), ptr(mu), bs(mu), ptr(scale), bs(scale), ptr(table), int(table.numel()),
-                                scale_bound, step, inv, sym.data_ptr(), idx.data_ptr(), ptr(yh_out), bs(yh_out), N, Cc,
-                                H * W, st), "gc_code_q")
-    return sym, idx
-
-
-def gc_indexes_q(st, scale, table, scale_bound, qstep):
-    """decoder, before the entropy decoder's run: the CDF indexes the encoder's gc_code_q coded with"""
-    N, Cc, H, W = scale.shape
-    idx = torch.empty((N, Cc, H, W), dtype=torch.int32, device=scale.device)
-    check(L.lib().icm_gc_indexes_q(ptr(scale), bs(scale), ptr(table), int(table.numel()), scale_bound, step_of(qstep)[1],
-                                   idx.data_ptr(), N, Cc, H * W, st), "gc_indexes_q")
-    return idx
-
-
-def dequantize_q(st, sym, mu, qstep, yh_out):
-    """decoder, after it: y_hat_pre = symbols * step + mu -> yh_out, the encoder's bit for bit"""
-    N, Cc, H, W = mu.shape
-    check(L.lib().icm_dequantize_q(sym.data_ptr(), ptr(mu), bs(mu), step_of(qstep)[0], ptr(yh_out), bs(yh_out), N, Cc,
-                                   H * W, st), "dequantize_q")
-
-
-# ---- the same three with a quality map: ``qmap`` is a device int8 [H, W] tensor of step indexes the caller has checked
-# (bitstream.check_qmap), one per latent position, shared by the batch and the channels
+# ---- the codec's quantiser on y (inference only: compress / decompress)
 _step_tables = {}
 
 
@@ -1288,33 +1257,87 @@ def _qmap_ptr(qmap, H, W):
     return qmap.data_ptr()
 
 
-def gc_code_qmap(st, y, mu, scale, table, scale_bound, qmap, yh_out):
-    """``gc_code_q`` with the step of each position taken from ``qmap``"""
-    N, Cc, H, W = y.shape
-    sym = torch.empty((N, Cc, H, W), dtype=torch.int32, device=y.device)
-    idx = torch.empty((N, Cc, H, W), dtype=torch.int32, device=y.device)
-    check(L.lib().icm_gc_code_qmap(ptr(y), bs(y), ptr(mu), bs(mu), ptr(scale), bs(scale), ptr(table), int(table.numel()),
-                                   scale_bound, _qmap_ptr(qmap, H, W), ptr(qmap_step_table(y.device)), sym.data_ptr(),
-                                   idx.data_ptr(), ptr(yh_out), bs(yh_out), N, Cc, H * W, st), "gc_code_qmap")
-    return sym, idx
+def _int32_like(t):
+    return torch.empty(t.shape, dtype=torch.int32, device=t.device)
 
 
-def gc_indexes_qmap(st, scale, table, scale_bound, qmap):
-    """``gc_indexes_q`` with a quality map: the CDF indexes the encoder's gc_code_qmap coded with"""
-    N, Cc, H, W = scale.shape
-    idx = torch.empty((N, Cc, H, W), dtype=torch.int32, device=scale.device)
-    check(L.lib().icm_gc_indexes_qmap(ptr(scale), bs(scale), ptr(table), int(table.numel()), scale_bound,
-                                      _qmap_ptr(qmap, H, W), ptr(qmap_step_table(scale.device)), idx.data_ptr(), N, Cc,
-                                      H * W, st), "gc_indexes_qmap")
-    return idx
+class Quantiser:
+    """What one compress / decompress call quantises the slices of y with, built once per call from the
+    GaussianConditional ``gc`` and the quality the caller chose.  Three kinds, picked here and nowhere else:
 
+      none  symbols round(y - mu), CDF indexes of the scale (cnn.py:246-252, 296-326)
+      step  ``qstep`` != 0, the step index k of the step 2^(k/8) (csrc/qstep.hip; the two floats the kernels take come from
+            bitstream.step_of on both sides): symbols round((y - mu) / step), indexes of scale / step
+      map   ``qmap``, a device int8 [H, W] tensor of step indexes the caller has checked (bitstream.check_qmap), one per
+            latent position, shared by the batch and the channels: the same with the step of each position
 
-def dequantize_qmap(st, sym, mu, qmap, yh_out):
-    """``dequantize_q`` with a quality map: y_hat_pre -> yh_out, the encoder's bit for bit"""
-    N, Cc, H, W = mu.shape
-    check(L.lib().icm_dequantize_qmap(sym.data_ptr(), ptr(mu), bs(mu), _qmap_ptr(qmap, H, W),
-                                      ptr(qmap_step_table(mu.device)), ptr(yh_out), bs(yh_out), N, Cc, H * W, st),
-          "dequantize_qmap")
+    ``code`` is the encoder's side, ``indexes`` and ``dequantize`` the decoder's, before and after the entropy decoder's
+    run; ``st`` is the stream to launch on.  Symbols and indexes are dense int32 tensors of the slice's shape.
+    ``fused``: ``code`` is ONE launch that also writes y_hat_pre = symbols * step + mu, the decoder's bit for bit, so the
+    encoder makes no likelihood launch (compress() never reads the likelihoods)."""
+
+    def __init__(self, gc, qstep: int = 0, qmap: Optional[torch.Tensor] = None):
+        self.gc, self._table = gc, None
+        # _kind: suffix of the three entry points; _steps: what each of them (code, indexes, dequantize) takes as its step
+        if qmap is not None:
+            self._kind = "_qmap"
+            self._steps = lambda H, W, dev: ((_qmap_ptr(qmap, H, W), ptr(qmap_step_table(dev))),) * 3
+        elif qstep:
+            step, inv = step_of(qstep)
+            self._kind, self._steps = "_q", lambda H, W, dev: ((step, inv), (inv,), (step,))
+        else:
+            self._kind = None
+            self.code, self.indexes, self.dequantize = self._code_plain, self._indexes_plain, self._dequantize_plain
+        self.fused = self._kind is not None
+
+    def _entry(self, name):
+        return getattr(L.lib(), name + self._kind)
+
+    def _scale_table(self, dev):
+        if self._table is None:
+            self._table = self.gc.scale_table.detach().to(dev, torch.float32).contiguous()
+        return self._table
+
+    # ---- step and map
+    def code(self, st, y, mu, sc, yh_out):
+        """(symbols, indexes) of a slice; fused kinds write y_hat_pre -> yh_out, the plain one leaves it alone"""
+        N, Cc, H, W = y.shape
+        sym, idx, table = _int32_like(y), _int32_like(y), self._scale_table(y.device)
+        check(self._entry("icm_gc_code")(ptr(y), bs(y), ptr(mu), bs(mu), ptr(sc), bs(sc), ptr(table), int(table.numel()),
+                                         self.gc._scale_bound, *self._steps(H, W, y.device)[0], sym.data_ptr(),
+                                         idx.data_ptr(), ptr(yh_out), bs(yh_out), N, Cc, H * W, st), "gc_code" + self._kind)
+        return sym, idx
+
+    def indexes(self, st, sc):
+        """the CDF indexes the encoder's ``code`` coded the slice with"""
+        N, Cc, H, W = sc.shape
+        idx, table = _int32_like(sc), self._scale_table(sc.device)
+        check(self._entry("icm_gc_indexes")(ptr(sc), bs(sc), ptr(table), int(table.numel()), self.gc._scale_bound,
+                                            *self._steps(H, W, sc.device)[1], idx.data_ptr(), N, Cc, H * W, st),
+              "gc_indexes" + self._kind)
+        return idx
+
+    def dequantize(self, st, sym, mu, yh_out):
+        """y_hat_pre = symbols * step + mu -> yh_out"""
+        N, Cc, H, W = mu.shape
+        check(self._entry("icm_dequantize")(sym.data_ptr(), ptr(mu), bs(mu), *self._steps(H, W, mu.device)[2],
+                                            ptr(yh_out), bs(yh_out), N, Cc, H * W, st), "dequantize" + self._kind)
+
+    # ---- none
+    def _code_plain(self, st, y, mu, sc, yh_out):
+        N, Cc, H, W = y.shape
+        sym = _int32_like(y)
+        check(L.lib().icm_quantize(ptr(y), bs(y), ptr(mu), bs(mu), H * W, 1, sym.data_ptr(), 0, N, Cc, H * W, st),
+              "quantize")
+        return sym, self.gc.build_indexes(sc)
+
+    def _indexes_plain(self, st, sc):
+        return self.gc.build_indexes(sc)
+
+    def _dequantize_plain(self, st, sym, mu, yh_out):
+        N, Cc, H, W = mu.shape
+        check(L.lib().icm_dequantize(sym.data_ptr(), ptr(mu), bs(mu), H * W, 1, ptr(yh_out), bs(yh_out), N, Cc, H * W, st),
+              "dequantize")
 
 
 # ------------------------------------------------------------------------------------------------ stf6 plumbing

@@ -14,14 +14,14 @@ import torch.nn as nn
 
 from . import _lib as L
 from . import engine as E
-from ._lib import ACT_GELU
 from .ans import coder_for
 from .bitstream import check_qmap, check_qstep, uniform_qmap
 from .engine import VT
 from .entropy_models import EntropyBottleneck, GaussianConditional
 from .layers import (GDN, Conv2d, Win_noShift_Attention, WindowAttention, conv, conv3x3, deconv, subpel_conv3x3,
                      _named)
-from .slices import chain_layers
+from .slices import (Decoder, Encoder, _chain, _chain_pair, _copy_op, gaussian_step, hyper_slices_split,
+                     hyper_slices_unsplit, hyperprior)
 
 SCALES_MIN, SCALES_MAX, SCALES_LEVELS = 0.11, 256, 64
 
@@ -83,16 +83,15 @@ class CompressionModel(nn.Module):
         z and its EntropyBottleneck know no step).  ``qmap``: a non-uniform quality map as ``_quality`` returns it (a
         checked int8 host array; ``qstep`` is then 0), returned under "qmap" with "qstep": None."""
         gc = self.gaussian_conditional
-        codec = {"gc": gc, "symbols": {}, "indexes": {}}
+        codec = Encoder(E.Quantiser(gc, qstep, _qmap_on(qmap, y.device)))
         keep = {}
-        hyper_slices(tape, P, y, None, None, self.num_slices, self.max_support_slices, keep=keep, codec=codec,
-                     qstep=qstep, qmap=None if qmap is None else torch.from_numpy(qmap).to(y.device))
+        hyper_slices(tape, P, y, None, None, self.num_slices, self.max_support_slices, keep=keep, coding=codec)
         z = keep["z"]
         z_strings = self.entropy_bottleneck.compress(z, coder=coder)
-        sym = torch.cat([codec["symbols"][i].reshape(-1) for i in range(self.num_slices)])
-        idx = torch.cat([codec["indexes"][i].reshape(-1) for i in range(self.num_slices)])
+        sym = torch.cat([codec.symbols[i].reshape(-1) for i in range(self.num_slices)])
+        idx = torch.cat([codec.indexes[i].reshape(-1) for i in range(self.num_slices)])
         gc._check_tables()
-        y_string = coder.encode(sym, idx, [codec["symbols"][i].numel() for i in range(self.num_slices)], gc)
+        y_string = coder.encode(sym, idx, [codec.symbols[i].numel() for i in range(self.num_slices)], gc)
         if debug is not None:      # tests: the coded symbols / CDF indexes (slice-major, cnn.py:254-255), the final y_hat
             debug.update(symbols=sym.cpu().numpy(), indexes=idx.cpu().numpy(), y_hat=keep["y_hat"])
         if qmap is not None:
@@ -111,14 +110,53 @@ class CompressionModel(nn.Module):
         tape = E.Tape(need_grad=False, packed_cache=self._pack_cache())
         return self._compress_latent(tape, self._params(), y.contiguous(), coder, _debug, qstep, qmap)
 
-    def _decompress_latent(self, tape, P, strings, shape, M, coder, qstep=0, qmap=None):
+    def _decompress_latent(self, tape, P, strings, shape, coder, qstep=0, qmap=None):
         """cnn.py:289-328: y_hat from the two streams"""
         if not isinstance(strings, (list, tuple)) or len(strings) != 2:
             raise ValueError("strings must be [y_strings, z_strings]")
         z_hat = self.entropy_bottleneck.decompress(strings[1], shape, coder=coder)
         return decode_slices(tape, P, z_hat, strings[0][0], self.gaussian_conditional, self.num_slices,
-                             self.max_support_slices, M, coder, qstep,
-                             None if qmap is None else torch.from_numpy(qmap).to(z_hat.device))
+                             self.max_support_slices, self.M, coder, qstep, _qmap_on(qmap, z_hat.device))
+
+    # ---- the codec of a model whose subclass gives the latent width ``M`` and the two transforms as hooks on one tape:
+    # ``_g_a(tape, P, x) -> y`` and ``_g_s(tape, P, y_hat) -> x_hat``
+    @torch.no_grad()
+    def analysis(self, x):
+        """the analysis transform g_a alone -> y, what ``compress_latent`` takes"""
+        _check_codec_input(x)
+        tape = E.Tape(need_grad=False, packed_cache=self._pack_cache())
+        return self._g_a(tape, self._params(), x.contiguous())
+
+    @torch.no_grad()
+    def compress(self, x, _debug=None, coder="host", symbols_per_wave=None, qstep=0, qmap=None):
+        """cnn.py:210-266 -> {"strings": [[y_string], z_strings], "shape": z.shape[-2:], "qstep"}; ``coder``: "host"
+        (the reference's scalar stream) or "lanes" (lane streams coded on the device, ``symbols_per_wave`` symbols of
+        a slice per wave body, None: ``icm_amd.ans.SYMBOLS_PER_WAVE``); ``qstep``: step index k of a quantiser step
+        2^(k/8) on y (``icm_amd.bitstream.step_of``; 0: none, a larger k a smaller stream; parity unpinned: no
+        counterpart in the reference); the decoder must be told the same coder and the same step.
+        ``qmap`` (instead of ``qstep``): a quality map, a 2-D integer array or tensor of the latent's spatial size
+        (H / 16, W / 16) holding a step index per position, shared by the batch and all channels.  A map whose
+        entries are all k is ``qstep=k``, and that is what is returned; any other comes back, as an int8 host array,
+        under "qmap" with "qstep": None, and the decoder must be given it."""
+        qstep = check_qstep(qstep, "compress: ")
+        coder = coder_for(coder, symbols_per_wave)
+        _check_codec_input(x)
+        qstep, qmap = _quality(qstep, qmap, (x.shape[2] // 16, x.shape[3] // 16), "compress: ")
+        P = self._params()
+        tape = E.Tape(need_grad=False, packed_cache=self._pack_cache())
+        return self._compress_latent(tape, P, self._g_a(tape, P, x.contiguous()), coder, _debug, qstep, qmap)
+
+    @torch.no_grad()
+    def decompress(self, strings, shape, coder="host", qstep=0, qmap=None):
+        """cnn.py:289-332 -> {"x_hat"} clamped to [0, 1]"""
+        qstep = check_qstep(qstep, "decompress: ")
+        coder = coder_for(coder)
+        qstep, qmap = _quality(qstep, qmap, None if qmap is None else _latent_hw(shape), "decompress: ")
+        P = self._params()
+        tape = E.Tape(need_grad=False, packed_cache=self._pack_cache())
+        x_hat = self._g_s(tape, P, self._decompress_latent(tape, P, strings, shape, coder, qstep, qmap))
+        L.check(L.lib().icm_clamp(L.ptr(x_hat), x_hat.numel(), 0.0, 1.0, tape.st), "clamp")
+        return {"x_hat": x_hat}
 
     def load_state_dict(self, state_dict, strict: bool = False):
         # models/base.py:62-70: resize the CDF buffers to whatever the checkpoint holds, then strict=False
@@ -136,57 +174,9 @@ class CompressionModel(nn.Module):
         return super().load_state_dict(sd, strict=False)
 
 
-def _chain(tape, P, p, xv: VT, strides=(1, 1, 1, 1, 1), out=None, lrp_aux=None):
-    """five conv3x3 with virtual GELUs between (cnn.py:54-64, 89-127)."""
-    for j, i in enumerate((0, 2, 4, 6, 8)):
-        last = j == 4
-        t = E.conv2d(tape, xv, P[f"{p}.{i}.weight"], P[f"{p}.{i}.bias"], stride=strides[j], pad=1,
-                     out=out if last else None, lrp_aux=lrp_aux if last else None, act_out=not last)
-        xv = VT(t, ACT_GELU)
-    return t
-
-
-def _chain_pair(tape, P, p1, p2, xv1: VT, xv2: VT):
-    """cc_mean_transforms[i] and cc_scale_transforms[i] are independent and shape-identical: run each of
-    their five convolutions as one grouped launch (forward and dgrad)."""
-    return chain_layers(tape, P, [p1, p2], [xv1, xv2], (0, 2, 4, 6, 8))
-
-
-def _h_s(tape, P, p, z_hat, out):
-    """h_mean_s / h_scale_s (cnn.py:66-88): PixelShuffle fused into the subpel convs' stores."""
-    u = E.conv2d(tape, VT(z_hat), P[p + ".0.weight"], P[p + ".0.bias"], pad=1, act_out=True)
-    u = E.conv2d(tape, VT(u, ACT_GELU), P[p + ".2.0.weight"], P[p + ".2.0.bias"], pad=1, pixel_shuffle=2, act_out=True)
-    u = E.conv2d(tape, VT(u, ACT_GELU), P[p + ".4.weight"], P[p + ".4.bias"], pad=1, act_out=True)
-    u = E.conv2d(tape, VT(u, ACT_GELU), P[p + ".6.0.weight"], P[p + ".6.0.bias"], pad=1, pixel_shuffle=2, act_out=True)
-    return E.conv2d(tape, VT(u, ACT_GELU), P[p + ".8.weight"], P[p + ".8.bias"], pad=1, out=out)
-
-
-def _h_s_pair(tape, P, p1, p2, z_hat, out1, out2):
-    """h_scale_s and h_mean_s (cnn.py:66-88) are independent and shape-identical: each of their five convolutions
-    (two with the PixelShuffle store) runs as one grouped launch"""
-    xv = [VT(z_hat), VT(z_hat)]
-    for name, ps, last in ((".0", 0, False), (".2.0", 2, False), (".4", 0, False), (".6.0", 2, False), (".8", 0, True)):
-        ts = E.conv2d_group(tape, xv, [P[p1 + name + ".weight"], P[p2 + name + ".weight"]],
-                            [P[p1 + name + ".bias"], P[p2 + name + ".bias"]], pad=1, pixel_shuffle=ps,
-                            outs=[out1, out2] if last else None, act_out=not last)
-        xv = [VT(ts[0], ACT_GELU), VT(ts[1], ACT_GELU)]
-    return ts
-
-
-def _copy_op(tape, src, dst):
-    """dst = src (cat/chunk plumbing) with gradient routed back"""
-    E.copy_into(tape, src, dst)
-    if tape.need_grad:
-        def bwd():
-            g = tape.grad_of(dst)
-            if g is not None:
-                E.accumulate(tape, src, g)
-        tape.bw.append(bwd)
-
-
 # ICM_SLICE_SPLIT=1 (default): the first layer of every slice chain is split by input-channel block (slices.py): the
 # latent block of all 3 * num_slices chains runs as two wide convolutions outside the serial slice loop.  0 = the
-# per-chain form below (support buffers, cat -> chain).  Both are kept and both are parity-tested at the bench geometry.
+# per-chain form (slices.hyper_slices_unsplit: support buffers, cat -> chain).  Both are kept and both are parity-tested at the bench geometry.
 # Same-box A/B on MI355X (round 3, B=16): with the direct kernels only the split form LOSES (329.7 vs 335.7 img/s: its
 # wide launches have few output tiles, and the support / own-slice blocks add ~30 small launches per direction); with
 # the eight-wave Winograd kernel, whose wide co blocks are exactly what the 4 256-channel latent launch wants (460 us,
@@ -196,168 +186,14 @@ SLICE_SPLIT = _os.environ.get("ICM_SLICE_SPLIT", "1") != "0"
 
 
 def hyper_slices(tape: E.Tape, P: Dict[str, torch.Tensor], y: torch.Tensor, noise_z, noise_y, num_slices: int,
-                 max_support: int, keep: Optional[dict] = None, bucket_marks: Optional[dict] = None,
-                 batch_tail: bool = True, codec: Optional[dict] = None, decode: Optional[dict] = None, qstep: int = 0,
-                 qmap: Optional[torch.Tensor] = None):
+                 max_support: int, keep: Optional[dict] = None, bucket_marks: Optional[dict] = None, coding=None):
     """Hyperprior + channel-conditional slice loop shared by the cnn and stf models
-    (cnn.py:144-183 == stf.py:596-637) -> (y_hat, y_likelihoods, z_likelihoods).  torch.cat / chunk become
-    channel-slice views of persistent support buffers.
-    codec (compress(), cnn.py:246-252): {"gc": GaussianConditional, "symbols": {}, "indexes": {}} -- the int32 symbols
-    round(y - mu) and CDF indexes of every slice are recorded (device tensors, keyed by slice).
-    decode (decompress(), cnn.py:289-326): {"z_hat", "M", "slice": callable(i, mu, sc, yh_pre)} -- y is None; the
-    SAME launch sequence runs (identical kernels on identical inputs give the bit-identical mu / scale the encoder saw,
-    which the CDF indexes depend on), but each slice's y_hat_pre comes from the entropy decoder instead of from y.
-    qstep (codec / decode only): step index of the quantiser step on y.  Non-zero, the encoder's work per slice is ONE
-    launch (``_record_symbols``: symbols, indexes and y_hat_pre; no likelihoods, which compress() never reads), and
-    the decoder's callback, which ``decode_slices`` builds for the same step, mirrors it.
-    qmap (codec / decode only, instead of qstep): a quality map, a device int8 [h, w] tensor of step indexes, one per
-    latent position; the same launches as with a step, the map-reading kernels in their place."""
-    if (qstep or qmap is not None) and codec is None and decode is None:
-        raise ValueError("the quantiser step exists in the codec only (compress / decompress)")
-    if SLICE_SPLIT and batch_tail:
-        from .slices import hyper_slices_split
-        return hyper_slices_split(tape, P, y, noise_z, noise_y, num_slices, max_support, keep, bucket_marks, codec,
-                                  decode, lambda t, P_, y_: _chain(t, P_, "h_a", VT(y_), strides=(1, 1, 2, 1, 2)),
-                                  _h_s_pair, _record_symbols, qstep, qmap)
-    if decode is not None:
-        z_hat = decode["z_hat"].contiguous()
-        dev, N, M = z_hat.device, z_hat.shape[0], decode["M"]
-        h, w = z_hat.shape[2] * 4, z_hat.shape[3] * 4
-        if tape.need_grad:
-            raise ValueError("decode mode is inference only")
-    else:
-        dev = y.device
-        N = y.shape[0]
-        M, h, w = y.shape[1], y.shape[2], y.shape[3]
-    need = tape.need_grad
-    if M % num_slices != 0:
-        raise ValueError("latent channels must divide into num_slices")
-    sc_ = M // num_slices
-    if need:  # y is consumed whole (h_a) and by slices (GaussianConditional): one aliased gradient buffer
-        dY = E.zeros(y.shape, dev)
-        tape.bind_grad(y, dY, True)
-        for i in range(num_slices):
-            tape.bind_grad(y[:, i * sc_:(i + 1) * sc_], dY[:, i * sc_:(i + 1) * sc_], True)
-    if bucket_marks is not None:
-        bucket_marks[2] = len(tape.bw)   # backward reaching here => hyper-path gradients are complete
-    # ---- h_a + entropy bottleneck (cnn.py:144-152)
-    z = z_lik = None
-    if decode is None:
-        z = _chain(tape, P, "h_a", VT(y), strides=(1, 1, 2, 1, 2))
-        _, z_lik = E.eb_likelihood(tape, z, P, "entropy_bottleneck", noise_z)
-        z_hat = E.ste_round_medians(tape, z, P["entropy_bottleneck.quantiles"])
-    # ---- hyper synthesis straight into the support buffers (cnn.py:154-155,163,167)
-    nsup = sc_ * max_support
-    MS = E.new((N, M + nsup, h, w), dev)
-    SS = E.new((N, M + nsup, h, w), dev)
-    if need:
-        dMS, dSS = E.zeros(MS.shape, dev), E.zeros(SS.shape, dev)
-        for k in range(max_support + 1):
-            tape.bind_grad(MS[:, :M + sc_ * k], dMS[:, :M + sc_ * k], True)
-            tape.bind_grad(SS[:, :M + sc_ * k], dSS[:, :M + sc_ * k], True)
-        for j in range(max_support):
-            sl = slice(M + sc_ * j, M + sc_ * (j + 1))
-            tape.bind_grad(MS[:, sl], dMS[:, sl], True)
-            tape.bind_grad(SS[:, sl], dSS[:, sl], True)
-    if (h % 4) or (w % 4):
-        raise ValueError("hyper-synthesis output does not match the latent size (input must be a multiple of 64)")
-    _h_s_pair(tape, P, "h_scale_s", "h_mean_s", z_hat, SS[:, :M], MS[:, :M])
-    Y_hat = E.new((N, M, h, w), dev)
-    # the step-aware encoder: one launch per slice, no likelihoods
-    fused = codec is not None and (qstep != 0 or qmap is not None)
-    Y_lik = E.new((N, M, h, w), dev) if decode is None and not fused else None
-    if need:
-        dYh = E.zeros(Y_hat.shape, dev)
-        tape.bind_grad(Y_hat, dYh, True)
-        for i in range(num_slices):
-            tape.bind_grad(Y_hat[:, i * sc_:(i + 1) * sc_], dYh[:, i * sc_:(i + 1) * sc_], True)
-    mus, scs = [], []
-    if bucket_marks is not None:
-        bucket_marks[1] = len(tape.bw)   # => slice-chain gradients complete
-    # ---- channel-conditional slice loop (cnn.py:161-180).  The support of slice i is y_hat_slices[:max_support]
-    # (cnn.py:161): slices 0..max_support-1 form a serial chain, but every slice >= max_support sees the SAME fixed
-    # support (latent + the first max_support slices) and is independent of its neighbours -> their chains run as
-    # grouped launches (2 * n_tail mean/scale chains, then n_tail lrp chains).
-    n_serial = min(num_slices, max_support) if batch_tail else num_slices
-    for i in range(n_serial):
-        k = min(i, max_support)
-        ch = slice(i * sc_, (i + 1) * sc_)
-        ms, ss = MS[:, :M + sc_ * k], SS[:, :M + sc_ * k]
-        mu, sc = _chain_pair(tape, P, f"cc_mean_transforms.{i}", f"cc_scale_transforms.{i}", VT(ms), VT(ss))
-        LS = E.new((N, M + sc_ * (k + 1), h, w), dev)
-        yh_pre = LS[:, M + sc_ * k:]
-        if need:
-            dLS = E.zeros(LS.shape, dev)
-            tape.bind_grad(LS, dLS, True)
-            tape.bind_grad(LS[:, :M + sc_ * k], dLS[:, :M + sc_ * k], True)
-            tape.bind_grad(yh_pre, dLS[:, M + sc_ * k:], True)
-        _copy_op(tape, ms, LS[:, :M + sc_ * k])
-        if decode is not None:
-            decode["slice"](i, mu, sc, yh_pre)
-        elif fused:
-            _record_symbols(codec, i, y[:, ch], mu, sc, yh_pre, qstep, qmap)
-        else:
-            E.gc_likelihood_ste(tape, y[:, ch], mu, sc, None if noise_y is None else noise_y[:, ch], Y_lik[:, ch],
-                                yh_pre)
-            if codec is not None:
-                _record_symbols(codec, i, y[:, ch], mu, sc)
-        _chain(tape, P, f"lrp_transforms.{i}", VT(LS), out=Y_hat[:, ch], lrp_aux=yh_pre)
-        if i < max_support:
-            sl = slice(M + sc_ * i, M + sc_ * (i + 1))
-            _copy_op(tape, Y_hat[:, ch], MS[:, sl])
-            _copy_op(tape, Y_hat[:, ch], SS[:, sl])
-        if keep is not None:
-            mus.append(mu)
-            scs.append(sc)
-    tail = list(range(n_serial, num_slices))
-    for t0 in range(0, len(tail), E.MAX_GROUP // 2):
-        idx = tail[t0:t0 + E.MAX_GROUP // 2]
-        nt = len(idx)
-        k = max_support
-        ms, ss = MS[:, :M + sc_ * k], SS[:, :M + sc_ * k]
-        # mean / scale chains of all tail slices: one grouped launch per layer
-        names = [f"cc_mean_transforms.{i}" for i in idx] + [f"cc_scale_transforms.{i}" for i in idx]
-        ts = chain_layers(tape, P, names, [VT(ms)] * nt + [VT(ss)] * nt, (0, 2, 4, 6, 8))
-        mu_t, sc_t = ts[:nt], ts[nt:]
-        LSs, pres = [], []
-        for j, i in enumerate(idx):
-            ch = slice(i * sc_, (i + 1) * sc_)
-            LS = E.new((N, M + sc_ * (k + 1), h, w), dev)
-            yh_pre = LS[:, M + sc_ * k:]
-            if need:
-                dLS = E.zeros(LS.shape, dev)
-                tape.bind_grad(LS, dLS, True)
-                tape.bind_grad(LS[:, :M + sc_ * k], dLS[:, :M + sc_ * k], True)
-                tape.bind_grad(yh_pre, dLS[:, M + sc_ * k:], True)
-            _copy_op(tape, ms, LS[:, :M + sc_ * k])
-            if decode is not None:
-                decode["slice"](i, mu_t[j], sc_t[j], yh_pre)
-            elif fused:
-                _record_symbols(codec, i, y[:, ch], mu_t[j], sc_t[j], yh_pre, qstep, qmap)
-            else:
-                E.gc_likelihood_ste(tape, y[:, ch], mu_t[j], sc_t[j], None if noise_y is None else noise_y[:, ch],
-                                    Y_lik[:, ch], yh_pre)
-                if codec is not None:
-                    _record_symbols(codec, i, y[:, ch], mu_t[j], sc_t[j])
-            LSs.append(LS)
-            pres.append(yh_pre)
-        # lrp chains of all tail slices, LRP tail fused into the last grouped launch
-        lnames = [f"lrp_transforms.{i}" for i in idx]
-        chain_layers(tape, P, lnames, [VT(LS) for LS in LSs], (0, 2, 4, 6, 8),
-                     outs=[Y_hat[:, i * sc_:(i + 1) * sc_] for i in idx], lrp_auxs=pres)
-        if keep is not None:
-            mus.extend(mu_t)
-            scs.extend(sc_t)
-    if bucket_marks is not None:
-        bucket_marks[0] = len(tape.bw)   # => synthesis-transform gradients complete
-    if keep is not None:
-        keep.update(y=y, z=z, z_hat=z_hat, y_hat=Y_hat, mu=torch.cat(mus, 1), scale=torch.cat(scs, 1),
-                    lat_means=MS[:, :M], lat_scales=SS[:, :M])
-    return Y_hat, Y_lik, z_lik
-
-
-def _scale_table(gc, dev):
-    return gc.scale_table.detach().to(dev, torch.float32).contiguous()
+    (cnn.py:144-183 == stf.py:596-637) -> (y_hat, y_likelihoods, z_likelihoods), in the form SLICE_SPLIT names (read at
+    call time).  coding: None (forward, training), or what compress() / decompress() code the slices with -- a
+    ``slices.Encoder`` (y_likelihoods is None if its quantiser is fused) or a ``slices.Decoder`` (y is None, inference
+    only, both likelihoods are None).  keep: a dict that receives the intermediates (``slices.epilogue``)."""
+    form = hyper_slices_split if SLICE_SPLIT else hyper_slices_unsplit
+    return form(tape, P, y, noise_z, noise_y, num_slices, max_support, keep, bucket_marks, coding)
 
 
 def _quality(qstep, qmap, hw, who):
@@ -371,66 +207,27 @@ def _quality(qstep, qmap, hw, who):
     return (k, None) if k is not None else (0, qmap)
 
 
-def _record_symbols(codec, i, y_slice, mu, sc, yh_pre=None, qstep=0, qmap=None):
-    """symbols = quantize(y_slice, "symbols", mu) and indexes = build_indexes(scale) of slice i (cnn.py:246-252).
-    With a quantiser step: symbols round((y - mu) / step), indexes of scale / step and y_hat_pre = symbols * step + mu
-    -> yh_pre, all from ONE launch (the caller then makes no likelihood launch); with a quality map the same launch
-    with the step of each position."""
-    if qmap is not None:
-        gc, dev = codec["gc"], y_slice.device
-        codec["symbols"][i], codec["indexes"][i] = E.gc_code_qmap(L.stream(), y_slice, mu, sc, _scale_table(gc, dev),
-                                                                  gc._scale_bound, qmap, yh_pre)
-        return
-    if qstep:
-        gc, dev = codec["gc"], y_slice.device
-        codec["symbols"][i], codec["indexes"][i] = E.gc_code_q(L.stream(), y_slice, mu, sc, _scale_table(gc, dev),
-                                                               gc._scale_bound, qstep, yh_pre)
-        return
-    N, Cc, h, w = y_slice.shape
-    sym = torch.empty((N, Cc, h, w), dtype=torch.int32, device=y_slice.device)
-    L.check(L.lib().icm_quantize(L.ptr(y_slice), L.bs(y_slice), L.ptr(mu), L.bs(mu), h * w, 1, sym.data_ptr(), 0, N, Cc,
-                                 h * w, L.stream()), "quantize")
-    codec["symbols"][i] = sym
-    codec["indexes"][i] = codec["gc"].build_indexes(sc)
+def _qmap_on(qmap, dev):
+    """the host quality map of ``_quality`` as the device tensor the quantiser takes"""
+    return None if qmap is None else torch.from_numpy(qmap).to(dev)
 
 
 def decode_slices(tape: E.Tape, P, z_hat, y_string: bytes, gc, num_slices: int, max_support: int, M: int, coder,
                   qstep: int = 0, qmap: Optional[torch.Tensor] = None):
-    """Decoder side of the slice loop (cnn.py:296-326): hyper_slices in decode mode -- per slice the chains give
-    mu / scale -> CDF indexes -> ``decode_run`` of the coder's decoder yields the symbols -> y_hat_pre = symbols + mu;
+    """Decoder side of the slice loop (cnn.py:296-326): hyper_slices with a ``slices.Decoder`` -- per slice the chains
+    give mu / scale -> CDF indexes -> ``decode_run`` of the coder's decoder yields the symbols -> y_hat_pre = symbols + mu;
     the LRP correction and the support bookkeeping are the forward's own.  Returns y_hat [N,M,h,w].  ``coder``: of
     ``icm_amd.ans.coder_for``; what a ``decode_run`` costs (host: a copy down and one up; lanes: one launch, no wait,
-    the status read by ``finish`` after the loop) is the coder's business.  With a quantiser step ``qstep`` the two
-    launches around ``decode_run`` are the step-aware ones, which share their arithmetic with the encoder's kernel;
-    with a quality map ``qmap`` (a device int8 [h, w] tensor) the map-reading ones."""
+    the status read by ``finish`` after the loop) is the coder's business.  With a quantiser step ``qstep`` or a quality
+    map ``qmap`` (a device int8 [h, w] tensor) the two launches around ``decode_run`` are the quantiser's
+    (``engine.Quantiser``), which share their arithmetic with the encoder's kernel."""
     gc._check_tables()
-    dec = coder.decoder(y_string, gc)
-    state = {"next": 0}
-    table = _scale_table(gc, z_hat.device) if qstep or qmap is not None else None
-
-    def one(i, mu, sc, yh_pre):
-        if i != state["next"]:
-            raise RuntimeError("slices must be decoded in stream order")
-        state["next"] += 1
-        N, Cc, h, w = mu.shape
-        if qmap is not None:
-            sym = dec.decode_run(E.gc_indexes_qmap(tape.st, sc, table, gc._scale_bound, qmap))
-            E.dequantize_qmap(tape.st, sym, mu, qmap, yh_pre)
-            return
-        if qstep:
-            sym = dec.decode_run(E.gc_indexes_q(tape.st, sc, table, gc._scale_bound, qstep))
-            E.dequantize_q(tape.st, sym, mu, qstep, yh_pre)
-            return
-        sym = dec.decode_run(gc.build_indexes(sc))
-        L.check(L.lib().icm_dequantize(sym.data_ptr(), L.ptr(mu), L.bs(mu), h * w, 1, L.ptr(yh_pre), L.bs(yh_pre), N, Cc,
-                                       h * w, tape.st), "dequantize")
-
+    coding = Decoder(E.Quantiser(gc, qstep, qmap), coder.decoder(y_string, gc), z_hat, M)
     try:
-        Y_hat, _, _ = hyper_slices(tape, P, None, None, None, num_slices, max_support,
-                                   decode={"z_hat": z_hat, "M": M, "slice": one}, qstep=qstep, qmap=qmap)
-        dec.finish()
+        Y_hat, _, _ = hyper_slices(tape, P, None, None, None, num_slices, max_support, coding=coding)
+        coding.finish()
     finally:
-        dec.close()
+        coding.close()
     return Y_hat
 
 
@@ -595,11 +392,7 @@ def hyper_slices_zigzag(tape: E.Tape, P: Dict[str, torch.Tensor], y: torch.Tenso
         raise ValueError("stf6: the latent must split into 2 x 2 blocks that are multiples of the window (input % 128 == 0)")
     if bucket_marks is not None:
         bucket_marks[2] = len(tape.bw)
-    z = _chain(tape, P, "h_a", VT(y), strides=(1, 1, 2, 1, 2))
-    _, z_lik = E.eb_likelihood(tape, z, P, "entropy_bottleneck", noise_z)
-    z_hat = E.ste_round_medians(tape, z, P["entropy_bottleneck.quantiles"])
-    lat_scales, lat_means = E.new((N, M, h, w), dev), E.new((N, M, h, w), dev)
-    _h_s_pair(tape, P, "h_scale_s", "h_mean_s", z_hat, lat_scales, lat_means)
+    z, z_hat, z_lik, lat_scales, lat_means = hyperprior(tape, P, y, noise_z, None, (N, M, h, w), dev)
     y_zz = E.zigzag_splits(tape, y, num_slices, nH, nW)
     sc_zz = E.zigzag_splits(tape, lat_scales, num_slices, nH, nW)
     mu_zz = E.zigzag_splits(tape, lat_means, num_slices, nH, nW)
@@ -645,7 +438,7 @@ def hyper_slices_zigzag(tape: E.Tape, P: Dict[str, torch.Tensor], y: torch.Tenso
         for l in range(4):
             t = _basic_layer(tape, P, f"mu_Swin.{i}.{l}", t, rdepths[l], STF6_MU_HEADS, window, None, drops)
         mu = E.add(tape, mu, t)
-        E.gc_likelihood_ste(tape, y_zz[:, i], mu, sc, None if noise_y is None else noise_y[:, i], Y_lik[:, i], yh_pre)
+        gaussian_step(tape, None, i, (slice(None), i), y_zz, noise_y, Y_lik, mu, sc, yh_pre)
         _copy_op(tape, MSi, LSi[:, :cs * (1 + k)])
         _chain(tape, P, f"lrp_transforms2.{i}", VT(LSi), out=YH[:, i], lrp_aux=yh_pre)
         if keep is not None:
@@ -724,6 +517,7 @@ def _train_noise(injected, x, cz, cy):
 
 class WACNN(CompressionModel):
     """CNN based model (models/cnn.py:23-189): same modules, names and defaults as the reference."""
+    M = 320
 
     def __init__(self, N=192, M=320, **kwargs):
         super().__init__(**kwargs)
@@ -800,43 +594,11 @@ class WACNN(CompressionModel):
         """cnn.py:133-138"""
         return self._update_tables(scale_table, force)
 
-    @torch.no_grad()
-    def analysis(self, x):
-        """the analysis transform g_a alone -> y, what ``compress_latent`` takes"""
-        _check_codec_input(x)
-        tape = E.Tape(need_grad=False, packed_cache=self._pack_cache())
-        return wacnn_g_a(tape, self._params(), x.contiguous())
+    def _g_a(self, tape, P, x):
+        return wacnn_g_a(tape, P, x)
 
-    @torch.no_grad()
-    def compress(self, x, _debug=None, coder="host", symbols_per_wave=None, qstep=0, qmap=None):
-        """cnn.py:210-266 -> {"strings": [[y_string], z_strings], "shape": z.shape[-2:], "qstep"}; ``coder``: "host"
-        (the reference's scalar stream) or "lanes" (lane streams coded on the device, ``symbols_per_wave`` symbols of
-        a slice per wave body, None: ``icm_amd.ans.SYMBOLS_PER_WAVE``); ``qstep``: step index k of a quantiser step
-        2^(k/8) on y (``icm_amd.bitstream.step_of``; 0: none, a larger k a smaller stream; parity unpinned: no
-        counterpart in the reference); the decoder must be told the same coder and the same step.
-        ``qmap`` (instead of ``qstep``): a quality map, a 2-D integer array or tensor of the latent's spatial size
-        (H / 16, W / 16) holding a step index per position, shared by the batch and all channels.  A map whose
-        entries are all k is ``qstep=k``, and that is what is returned; any other comes back, as an int8 host array,
-        under "qmap" with "qstep": None, and the decoder must be given it."""
-        qstep = check_qstep(qstep, "compress: ")
-        coder = coder_for(coder, symbols_per_wave)
-        _check_codec_input(x)
-        qstep, qmap = _quality(qstep, qmap, (x.shape[2] // 16, x.shape[3] // 16), "compress: ")
-        P = self._params()
-        tape = E.Tape(need_grad=False, packed_cache=self._pack_cache())
-        return self._compress_latent(tape, P, wacnn_g_a(tape, P, x.contiguous()), coder, _debug, qstep, qmap)
-
-    @torch.no_grad()
-    def decompress(self, strings, shape, coder="host", qstep=0, qmap=None):
-        """cnn.py:289-332 -> {"x_hat"} clamped to [0, 1]"""
-        qstep = check_qstep(qstep, "decompress: ")
-        coder = coder_for(coder)
-        qstep, qmap = _quality(qstep, qmap, None if qmap is None else _latent_hw(shape), "decompress: ")
-        P = self._params()
-        tape = E.Tape(need_grad=False, packed_cache=self._pack_cache())
-        x_hat = wacnn_g_s(tape, P, self._decompress_latent(tape, P, strings, shape, 320, coder, qstep, qmap))
-        L.check(L.lib().icm_clamp(L.ptr(x_hat), x_hat.numel(), 0.0, 1.0, tape.st), "clamp")
-        return {"x_hat": x_hat}
+    def _g_s(self, tape, P, y_hat):
+        return wacnn_g_s(tape, P, y_hat)
 
 
 # ------------------------------------------------------------------------------------------------ stf modules
@@ -951,6 +713,7 @@ def _draw_drop(rate: float, B: int, device, generator=None):
 class SymmetricalTransFormer(CompressionModel):
     """Swin-transformer codec (models/stf.py:318-645): same modules, names, defaults and state-dict as the
     reference; ``forward`` runs as one tape of HIP kernels (``stf_forward``)."""
+    M = 384
 
     def __init__(self, pretrain_img_size=256, patch_size=2, in_chans=3, embed_dim=48, depths=[2, 2, 6, 2],
                  num_heads=[3, 6, 12, 24], window_size=4, num_slices=12, mlp_ratio=4., qkv_bias=True, qk_scale=None,
@@ -1076,37 +839,11 @@ class SymmetricalTransFormer(CompressionModel):
         """stf.py: same table refresh as the cnn model (cnn.py:133-138)"""
         return self._update_tables(scale_table, force)
 
-    @torch.no_grad()
-    def analysis(self, x):
-        """the analysis transform alone -> y, what ``compress_latent`` takes"""
-        _check_codec_input(x)
-        tape = E.Tape(need_grad=False, packed_cache=self._pack_cache())
-        return stf_analysis(tape, self._params(), x.contiguous(), None, self.window_size)
+    def _g_a(self, tape, P, x):
+        return stf_analysis(tape, P, x, None, self.window_size)
 
-    @torch.no_grad()
-    def compress(self, x, _debug=None, coder="host", symbols_per_wave=None, qstep=0, qmap=None):
-        """stf.py compress(): analysis transform, then the shared latent coder (``coder``, ``qstep``, ``qmap``: see
-        WACNN.compress)"""
-        qstep = check_qstep(qstep, "compress: ")
-        coder = coder_for(coder, symbols_per_wave)
-        _check_codec_input(x)
-        qstep, qmap = _quality(qstep, qmap, (x.shape[2] // 16, x.shape[3] // 16), "compress: ")
-        P = self._params()
-        tape = E.Tape(need_grad=False, packed_cache=self._pack_cache())
-        return self._compress_latent(tape, P, stf_analysis(tape, P, x.contiguous(), None, self.window_size), coder,
-                                     _debug, qstep, qmap)
-
-    @torch.no_grad()
-    def decompress(self, strings, shape, coder="host", qstep=0, qmap=None):
-        qstep = check_qstep(qstep, "decompress: ")
-        coder = coder_for(coder)
-        qstep, qmap = _quality(qstep, qmap, None if qmap is None else _latent_hw(shape), "decompress: ")
-        P = self._params()
-        tape = E.Tape(need_grad=False, packed_cache=self._pack_cache())
-        y_hat = self._decompress_latent(tape, P, strings, shape, 384, coder, qstep, qmap)
-        x_hat = stf_synthesis(tape, P, y_hat, None, self.window_size)
-        L.check(L.lib().icm_clamp(L.ptr(x_hat), x_hat.numel(), 0.0, 1.0, tape.st), "clamp")
-        return {"x_hat": x_hat}
+    def _g_s(self, tape, P, y_hat):
+        return stf_synthesis(tape, P, y_hat, None, self.window_size)
 
 
 class SymmetricalTransFormer3(SymmetricalTransFormer):

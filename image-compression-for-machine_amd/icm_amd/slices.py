@@ -1,5 +1,14 @@
-"""Channel-conditional slice loop of the cnn / stf models (compressai/models/cnn.py:154-183 == stf.py:607-637) with the
-FIRST layer of every chain split by input-channel block.
+"""Hyperprior + channel-conditional slice loop of the cnn / stf models (compressai/models/cnn.py:144-183 ==
+stf.py:596-637), in its two forms, and what they share with each other and with the zigzag loop of stf6 (models.py):
+
+  chain helpers   ``chain_layers``, ``_chain``, ``_chain_pair``, ``_h_s_pair``, ``_copy_op``
+  coding          what compress() / decompress() hand a loop as ``coding``: an ``Encoder`` that records the symbols and
+                  CDF indexes of every slice, or a ``Decoder`` that takes each slice's y_hat_pre from the entropy decoder;
+                  ``gaussian_step`` is the ONE per-slice Gaussian-conditional step of every loop
+  prologue / epilogue   ``hyperprior`` (h_a -> entropy bottleneck -> h_s pair), ``prologue`` (shapes, gradient aliasing,
+                  the buffers both forms write) and ``epilogue`` (what ``keep`` holds)
+  hyper_slices_unsplit   the per-chain form: support buffers, cat -> chain
+  hyper_slices_split     the FIRST layer of every chain split by input-channel block, described below
 
 The reference builds, per slice i, ``mean_support = cat([latent_means] + y_hat_slices[:max_support])`` and runs
 cc_mean / cc_scale on it (and lrp on ``cat([mean_support, y_hat_slice])``).  A convolution is linear in its input
@@ -25,6 +34,7 @@ their gradients, laid out family-major: channel ((f*S + i)*D0 + d) for family f 
 from __future__ import annotations
 
 import ctypes as C
+from types import SimpleNamespace
 from typing import Dict, Optional
 
 import torch
@@ -54,6 +64,231 @@ def chain_layers(tape, P, names, xvs, layers=(2, 4, 6, 8), outs=None, lrp_auxs=N
     return ts
 
 
+def _chain(tape, P, p, xv: VT, strides=(1, 1, 1, 1, 1), out=None, lrp_aux=None):
+    """five conv3x3 with virtual GELUs between (cnn.py:54-64, 89-127)."""
+    for j, i in enumerate((0, 2, 4, 6, 8)):
+        last = j == 4
+        t = E.conv2d(tape, xv, P[f"{p}.{i}.weight"], P[f"{p}.{i}.bias"], stride=strides[j], pad=1,
+                     out=out if last else None, lrp_aux=lrp_aux if last else None, act_out=not last)
+        xv = VT(t, ACT_GELU)
+    return t
+
+
+def _chain_pair(tape, P, p1, p2, xv1: VT, xv2: VT):
+    """cc_mean_transforms[i] and cc_scale_transforms[i] are independent and shape-identical: run each of
+    their five convolutions as one grouped launch (forward and dgrad)."""
+    return chain_layers(tape, P, [p1, p2], [xv1, xv2], (0, 2, 4, 6, 8))
+
+
+def _h_s_pair(tape, P, p1, p2, z_hat, out1, out2):
+    """h_scale_s and h_mean_s (cnn.py:66-88) are independent and shape-identical: each of their five convolutions
+    (two with the PixelShuffle store) runs as one grouped launch"""
+    xv = [VT(z_hat), VT(z_hat)]
+    for name, ps, last in ((".0", 0, False), (".2.0", 2, False), (".4", 0, False), (".6.0", 2, False), (".8", 0, True)):
+        ts = E.conv2d_group(tape, xv, [P[p1 + name + ".weight"], P[p2 + name + ".weight"]],
+                            [P[p1 + name + ".bias"], P[p2 + name + ".bias"]], pad=1, pixel_shuffle=ps,
+                            outs=[out1, out2] if last else None, act_out=not last)
+        xv = [VT(ts[0], ACT_GELU), VT(ts[1], ACT_GELU)]
+    return ts
+
+
+def _copy_op(tape, src, dst):
+    """dst = src (cat/chunk plumbing) with gradient routed back"""
+    E.copy_into(tape, src, dst)
+    if tape.need_grad:
+        def bwd():
+            g = tape.grad_of(dst)
+            if g is not None:
+                E.accumulate(tape, src, g)
+        tape.bw.append(bwd)
+
+
+# ------------------------------------------------------------------------------------------------ coding
+class Encoder:
+    """``coding`` of compress() (cnn.py:246-252): the int32 symbols and CDF indexes of every slice, as the quantiser
+    codes them, are recorded as device tensors keyed by slice.  With a fused quantiser that is the encoder's ONE launch per
+    slice (it writes y_hat_pre too); otherwise it follows the likelihood launch, which wrote y_hat_pre."""
+    decoding = False
+
+    def __init__(self, quantiser: E.Quantiser):
+        self.q, self.symbols, self.indexes = quantiser, {}, {}
+        self.likelihoods = not quantiser.fused
+
+    def slice(self, tape, i, y, mu, sc, yh_pre):
+        self.symbols[i], self.indexes[i] = self.q.code(L.stream(), y, mu, sc, yh_pre)
+
+
+class Decoder:
+    """``coding`` of decompress() (cnn.py:289-326): y is None and the loop starts from ``z_hat`` ([N, *, h/4, w/4], M
+    latent channels).  The SAME launch sequence runs (identical kernels on identical inputs give the bit-identical mu /
+    scale the encoder saw, which the CDF indexes depend on), but each slice's y_hat_pre comes from the entropy decoder:
+    scale -> CDF indexes -> ``decode_run`` of ``dec`` (a coder's decoder, ``icm_amd.ans``) -> symbols -> y_hat_pre."""
+    decoding, likelihoods = True, False
+
+    def __init__(self, quantiser: E.Quantiser, dec, z_hat, M: int):
+        self.q, self.dec, self.z_hat, self.M, self._next = quantiser, dec, z_hat, M, 0
+
+    def slice(self, tape, i, y, mu, sc, yh_pre):
+        if i != self._next:
+            raise RuntimeError("slices must be decoded in stream order")
+        self._next += 1
+        sym = self.dec.decode_run(self.q.indexes(tape.st, sc))
+        self.q.dequantize(tape.st, sym, mu, yh_pre)
+
+    def finish(self):
+        self.dec.finish()
+
+    def close(self):
+        self.dec.close()
+
+
+def gaussian_step(tape, coding, i, sel, y, noise_y, Y_lik, mu, sc, yh_pre):
+    """GaussianConditional + ste_round of slice i (cnn.py:170-173), the one such step of every loop: likelihoods ->
+    Y_lik[sel] and y_hat_pre -> yh_pre from y[sel] (``sel`` indexes the slice in y, the noise and Y_lik), then whatever
+    ``coding`` does with the slice.  A fused encoder and the decoder make no likelihood launch: they write yh_pre."""
+    if coding is None or coding.likelihoods:
+        E.gc_likelihood_ste(tape, y[sel], mu, sc, None if noise_y is None else noise_y[sel], Y_lik[sel], yh_pre)
+    if coding is not None:
+        coding.slice(tape, i, None if y is None else y[sel], mu, sc, yh_pre)
+
+
+# ------------------------------------------------------------------------------------------------ prologue / epilogue
+def hyperprior(tape, P, y, noise_z, z_hat, shape, dev, support: int = 0):
+    """h_a + entropy bottleneck (cnn.py:144-152), then the hyper synthesis pair (cnn.py:154-155) into the first M channels
+    of two fresh [N, M + support, h, w] buffers -> (z, z_hat, z_likelihoods, scales buffer, means buffer).  ``z_hat``
+    given (the decoder's): nothing runs before the pair, z and z_likelihoods are None."""
+    N, M, h, w = shape
+    z = z_lik = None
+    if z_hat is None:
+        z = _chain(tape, P, "h_a", VT(y), strides=(1, 1, 2, 1, 2))
+        _, z_lik = E.eb_likelihood(tape, z, P, "entropy_bottleneck", noise_z)
+        z_hat = E.ste_round_medians(tape, z, P["entropy_bottleneck.quantiles"])
+    if (h % 4) or (w % 4):
+        raise ValueError("hyper-synthesis output does not match the latent size (input must be a multiple of 64)")
+    SS, MS = E.new((N, M + support, h, w), dev), E.new((N, M + support, h, w), dev)
+    _h_s_pair(tape, P, "h_scale_s", "h_mean_s", z_hat, SS[:, :M], MS[:, :M])
+    return z, z_hat, z_lik, SS, MS
+
+
+def prologue(tape, P, y, noise_z, num_slices, coding, bucket_marks, support_slices: int = 0):
+    """What both forms do before their slices: shapes from y or from the decoder's z_hat, one aliased gradient buffer each
+    for y and y_hat (consumed whole and by slices), the hyperprior (its two buffers with room for ``support_slices``
+    slices behind the latent channels), and the y_hat / likelihood buffers.  -> a namespace of N, M, h, w, c (channels
+    per slice), dev, z, z_hat, z_lik, SS, MS (``hyperprior``), Y_hat, dYh, Y_lik.  The ``bucket_marks`` [2] and [1] are
+    set here, [0] by ``epilogue``: positions in ``tape.bw`` by which the Trainer buckets its gradient all-reduces."""
+    z_hat = None
+    if coding is not None and coding.decoding:
+        z_hat = coding.z_hat.contiguous()
+        dev, N, M = z_hat.device, z_hat.shape[0], coding.M
+        h, w = z_hat.shape[2] * 4, z_hat.shape[3] * 4
+        if tape.need_grad:
+            raise ValueError("decode mode is inference only")
+    else:
+        dev, (N, M, h, w) = y.device, y.shape
+    if M % num_slices != 0:
+        raise ValueError("latent channels must divide into num_slices")
+    c = M // num_slices
+    if tape.need_grad:
+        dY = E.zeros(y.shape, dev)
+        tape.bind_grad(y, dY, True)
+        for i in range(num_slices):
+            tape.bind_grad(y[:, i * c:(i + 1) * c], dY[:, i * c:(i + 1) * c], True)
+    if bucket_marks is not None:
+        bucket_marks[2] = len(tape.bw)   # backward reaching here => hyper-path gradients are complete
+    z, z_hat, z_lik, SS, MS = hyperprior(tape, P, y, noise_z, z_hat, (N, M, h, w), dev, c * support_slices)
+    Y_hat = E.new((N, M, h, w), dev)
+    Y_lik = E.new((N, M, h, w), dev) if coding is None or coding.likelihoods else None
+    dYh = None
+    if tape.need_grad:
+        dYh = E.zeros(Y_hat.shape, dev)
+        tape.bind_grad(Y_hat, dYh, True)
+        for i in range(num_slices):
+            tape.bind_grad(Y_hat[:, i * c:(i + 1) * c], dYh[:, i * c:(i + 1) * c], True)
+    if bucket_marks is not None:
+        bucket_marks[1] = len(tape.bw)   # => slice-chain gradients complete
+    return SimpleNamespace(N=N, M=M, h=h, w=w, c=c, dev=dev, z=z, z_hat=z_hat, z_lik=z_lik, SS=SS, MS=MS, Y_hat=Y_hat,
+                           dYh=dYh, Y_lik=Y_lik)
+
+
+def epilogue(tape, p, y, mu, scale, keep, bucket_marks):
+    """-> (y_hat, y_likelihoods, z_likelihoods); ``keep`` gets the intermediates the parity tests and compress() read.
+    mu / scale: [N, M, h, w], or their slices in order"""
+    if bucket_marks is not None:
+        bucket_marks[0] = len(tape.bw)   # => synthesis-transform gradients complete
+    if keep is not None:
+        mu, scale = (v if torch.is_tensor(v) else torch.cat(v, 1) for v in (mu, scale))
+        keep.update(y=y, z=p.z, z_hat=p.z_hat, y_hat=p.Y_hat, mu=mu, scale=scale, lat_means=p.MS[:, :p.M],
+                    lat_scales=p.SS[:, :p.M])
+    return p.Y_hat, p.Y_lik, p.z_lik
+
+
+# ------------------------------------------------------------------------------------------------ the per-chain form
+def hyper_slices_unsplit(tape: E.Tape, P: Dict[str, torch.Tensor], y, noise_z, noise_y, num_slices: int,
+                         max_support: int, keep: Optional[dict], bucket_marks: Optional[dict], coding):
+    """torch.cat / chunk become channel-slice views of persistent support buffers: MS / SS hold the latent means / scales
+    followed by the y_hat of the first max_support slices, LS of a slice its mean support followed by its y_hat_pre."""
+    S, ms = num_slices, max_support
+    p = prologue(tape, P, y, noise_z, S, coding, bucket_marks, support_slices=ms)
+    N, M, h, w, c, dev, MS, SS, Y_hat = p.N, p.M, p.h, p.w, p.c, p.dev, p.MS, p.SS, p.Y_hat
+    need = tape.need_grad
+    if need:
+        dMS, dSS = E.zeros(MS.shape, dev), E.zeros(SS.shape, dev)
+        for k in range(ms + 1):
+            tape.bind_grad(MS[:, :M + c * k], dMS[:, :M + c * k], True)
+            tape.bind_grad(SS[:, :M + c * k], dSS[:, :M + c * k], True)
+        for j in range(ms):
+            sl = slice(M + c * j, M + c * (j + 1))
+            tape.bind_grad(MS[:, sl], dMS[:, sl], True)
+            tape.bind_grad(SS[:, sl], dSS[:, sl], True)
+    mus, scs = [], []
+
+    def chains(idx, k, serial):
+        """slices idx, all with the support of k slices: their mean / scale chains as one grouped launch per layer, the
+        Gaussian step of each, their lrp chains (LRP tail fused into the last launch).  serial: one slice, whose lrp
+        chain is a plain launch per layer and whose y_hat joins the support of the next"""
+        nt = len(idx)
+        sup_m, sup_s = MS[:, :M + c * k], SS[:, :M + c * k]
+        names = [f"cc_mean_transforms.{i}" for i in idx] + [f"cc_scale_transforms.{i}" for i in idx]
+        ts = chain_layers(tape, P, names, [VT(sup_m)] * nt + [VT(sup_s)] * nt, (0, 2, 4, 6, 8))
+        LSs, pres = [], []
+        for j, i in enumerate(idx):
+            LS = E.new((N, M + c * (k + 1), h, w), dev)
+            yh_pre = LS[:, M + c * k:]
+            if need:
+                dLS = E.zeros(LS.shape, dev)
+                tape.bind_grad(LS, dLS, True)
+                tape.bind_grad(LS[:, :M + c * k], dLS[:, :M + c * k], True)
+                tape.bind_grad(yh_pre, dLS[:, M + c * k:], True)
+            _copy_op(tape, sup_m, LS[:, :M + c * k])
+            gaussian_step(tape, coding, i, (slice(None), slice(i * c, (i + 1) * c)), y, noise_y, p.Y_lik, ts[j], ts[nt + j],
+                          yh_pre)
+            LSs.append(LS)
+            pres.append(yh_pre)
+        outs = [Y_hat[:, i * c:(i + 1) * c] for i in idx]
+        if serial:
+            _chain(tape, P, f"lrp_transforms.{idx[0]}", VT(LSs[0]), out=outs[0], lrp_aux=pres[0])
+            sl = slice(M + c * k, M + c * (k + 1))
+            _copy_op(tape, outs[0], MS[:, sl])
+            _copy_op(tape, outs[0], SS[:, sl])
+        else:
+            chain_layers(tape, P, [f"lrp_transforms.{i}" for i in idx], [VT(LS) for LS in LSs], (0, 2, 4, 6, 8), outs=outs,
+                         lrp_auxs=pres)
+        mus.extend(ts[:nt])
+        scs.extend(ts[nt:])
+
+    # ---- the support of slice i is y_hat_slices[:max_support] (cnn.py:161): slices 0..max_support-1 form a serial chain,
+    # but every slice >= max_support sees the SAME fixed support (latent + the first max_support slices) and is
+    # independent of its neighbours -> their chains run as grouped launches, in batches
+    n_serial = min(S, ms)
+    for i in range(n_serial):
+        chains([i], i, True)
+    tail = list(range(n_serial, S))
+    for t0 in range(0, len(tail), E.MAX_GROUP // 2):
+        chains(tail[t0:t0 + E.MAX_GROUP // 2], ms, False)
+    return epilogue(tape, p, y, mus, scs, keep, bucket_marks)
+
+
+# ------------------------------------------------------------------------------------------------ the split form
 def _ksplit_dgrad(tape, x, wp, K, Cout, taps, gx, acc, ks, conv_b, tag):
     """Input gradient of a wide first-layer block, x [N, K, h, w] (contiguous channel range) -> gx [N, Cout, h, w], with
     the contraction split into ``ks`` equal channel ranges that run as the members of ONE grouped launch and write
@@ -86,42 +321,13 @@ def _block_grad(tape, w):
 
 
 def hyper_slices_split(tape: E.Tape, P: Dict[str, torch.Tensor], y, noise_z, noise_y, num_slices: int, max_support: int,
-                       keep: Optional[dict], bucket_marks: Optional[dict], codec: Optional[dict], decode: Optional[dict],
-                       h_a, h_s_pair, record_symbols, qstep: int = 0, qmap=None):
-    """see module docstring; h_a / h_s_pair / record_symbols are models.py's helpers (shared with the unsplit path);
-    qstep / qmap: the codec's quantiser step on y or its quality map, as in models.hyper_slices"""
-    if decode is not None:
-        z_hat = decode["z_hat"].contiguous()
-        dev, N, M = z_hat.device, z_hat.shape[0], decode["M"]
-        h, w = z_hat.shape[2] * 4, z_hat.shape[3] * 4
-        if tape.need_grad:
-            raise ValueError("decode mode is inference only")
-    else:
-        dev, N = y.device, y.shape[0]
-        M, h, w = y.shape[1], y.shape[2], y.shape[3]
-    need = tape.need_grad
+                       keep: Optional[dict], bucket_marks: Optional[dict], coding):
+    """see module docstring"""
     S, ms = num_slices, max_support
-    if M % S != 0:
-        raise ValueError("latent channels must divide into num_slices")
-    c = M // S
-    if need:  # y is consumed whole (h_a) and by slices (GaussianConditional): one aliased gradient buffer
-        dY = E.zeros(y.shape, dev)
-        tape.bind_grad(y, dY, True)
-        for i in range(S):
-            tape.bind_grad(y[:, i * c:(i + 1) * c], dY[:, i * c:(i + 1) * c], True)
-    if bucket_marks is not None:
-        bucket_marks[2] = len(tape.bw)   # backward reaching here => hyper-path gradients are complete
-    z = z_lik = None
-    if decode is None:
-        z = h_a(tape, P, y)
-        _, z_lik = E.eb_likelihood(tape, z, P, "entropy_bottleneck", noise_z)
-        z_hat = E.ste_round_medians(tape, z, P["entropy_bottleneck.quantiles"])
-    if (h % 4) or (w % 4):
-        raise ValueError("hyper-synthesis output does not match the latent size (input must be a multiple of 64)")
-    LM, LSC = E.new((N, M, h, w), dev), E.new((N, M, h, w), dev)       # latent_means, latent_scales (cnn.py:154-155)
-    h_s_pair(tape, P, "h_scale_s", "h_mean_s", z_hat, LSC, LM)
-    if bucket_marks is not None:
-        bucket_marks[1] = len(tape.bw)   # => slice-chain gradients complete
+    p = prologue(tape, P, y, noise_z, S, coding, bucket_marks)
+    N, M, h, w, c, dev, Y_hat, dYh = p.N, p.M, p.h, p.w, p.c, p.dev, p.Y_hat, p.dYh
+    LM, LSC = p.MS, p.SS                            # latent_means, latent_scales (cnn.py:154-155)
+    need = tape.need_grad
 
     W0 = {(i, f): P[f"{FAM[f]}.{i}.0.weight"] for i in range(S) for f in range(3)}
     B0 = {(i, f): P[f"{FAM[f]}.{i}.0.bias"] for i in range(S) for f in range(3)}
@@ -149,17 +355,8 @@ def hyper_slices_split(tape: E.Tape, P: Dict[str, torch.Tensor], y, noise_z, noi
         DPRE0 = E.new((N, CT, h, w), dev)
         for k_ in W0:
             tape.bind_grad(pre[k_], DPRE0[:, off(*k_):off(*k_) + D0], False)   # first writer: the second layer's dgrad
-    Y_hat = E.new((N, M, h, w), dev)
     YP = E.new((N, M, h, w), dev)                   # y_hat before the LRP correction, per slice (cnn.py:171-173)
     MU, SC = E.new((N, M, h, w), dev), E.new((N, M, h, w), dev)
-    # the step-aware encoder: one launch per slice, no likelihoods
-    fused = codec is not None and (qstep != 0 or qmap is not None)
-    Y_lik = E.new((N, M, h, w), dev) if decode is None and not fused else None
-    if need:
-        dYh = E.zeros(Y_hat.shape, dev)
-        tape.bind_grad(Y_hat, dYh, True)
-        for i in range(S):
-            tape.bind_grad(Y_hat[:, i * c:(i + 1) * c], dYh[:, i * c:(i + 1) * c], True)
     lib = L.lib()
     conv = dict(KH=KH, KW=KH, stride=1, pad=pad, OH=h, OW=w)
     px = float(N) * h * w
@@ -286,20 +483,6 @@ def hyper_slices_split(tape: E.Tape, P: Dict[str, torch.Tensor], y, noise_z, noi
                                       Cout=c, transposed=1, accum=1, tag="dgrad(C)", **conv_b)
             tape.bw.append(bwd_C)
 
-    def gauss(idx):
-        """GaussianConditional + ste_round per slice (cnn.py:170-173): y_hat_pre -> YP, likelihoods -> Y_lik"""
-        for i in idx:
-            s1 = slice(i * c, (i + 1) * c)
-            if decode is not None:
-                decode["slice"](i, MU[:, s1], SC[:, s1], YP[:, s1])
-            elif fused:
-                record_symbols(codec, i, y[:, s1], MU[:, s1], SC[:, s1], YP[:, s1], qstep, qmap)
-            else:
-                E.gc_likelihood_ste(tape, y[:, s1], MU[:, s1], SC[:, s1], None if noise_y is None else noise_y[:, s1],
-                                    Y_lik[:, s1], YP[:, s1])
-                if codec is not None:
-                    record_symbols(codec, i, y[:, s1], MU[:, s1], SC[:, s1])
-
     def chains(idx, k):
         if k > 0:
             support_block(idx, k)
@@ -308,7 +491,9 @@ def hyper_slices_split(tape: E.Tape, P: Dict[str, torch.Tensor], y, noise_z, noi
         xvs = [VT(pre[(i, 0)], ACT_GELU) for i in idx] + [VT(pre[(i, 2)], ACT_GELU) for i in idx]
         outs = [MU[:, i * c:(i + 1) * c] for i in idx] + [SC[:, i * c:(i + 1) * c] for i in idx]
         chain_layers(tape, P, names, xvs, outs=outs)
-        gauss(idx)
+        for i in idx:                                # GaussianConditional + ste_round: y_hat_pre -> YP, likelihoods -> Y_lik
+            s1 = slice(i * c, (i + 1) * c)
+            gaussian_step(tape, coding, i, (slice(None), s1), y, noise_y, p.Y_lik, MU[:, s1], SC[:, s1], YP[:, s1])
         own_block(idx, k)
         lnames = [f"lrp_transforms.{i}" for i in idx]
         chain_layers(tape, P, lnames, [VT(pre[(i, 1)], ACT_GELU) for i in idx],
@@ -322,8 +507,4 @@ def hyper_slices_split(tape: E.Tape, P: Dict[str, torch.Tensor], y, noise_z, noi
     step = max(1, E.MAX_GROUP // 2)
     for t0 in range(0, len(tail), step):
         chains(tail[t0:t0 + step], ms)
-    if bucket_marks is not None:
-        bucket_marks[0] = len(tape.bw)   # => synthesis-transform gradients complete
-    if keep is not None:
-        keep.update(y=y, z=z, z_hat=z_hat, y_hat=Y_hat, mu=MU, scale=SC, lat_means=LM, lat_scales=LSC)
-    return Y_hat, Y_lik, z_lik
+    return epilogue(tape, p, y, MU, SC, keep, bucket_marks)

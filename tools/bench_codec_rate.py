@@ -74,24 +74,23 @@ def slice_kernels(args, torch, np):
     SC = torch.rand((N, M, h, w), generator=g, device="cuda:0") * 2
     s1 = slice(64, 96)
     tape = E.Tape(need_grad=False)
-    table = gc.scale_table.detach().to("cuda:0", torch.float32).contiguous()
+    args_ = (L.stream(), Y[:, s1], MU[:, s1], SC[:, s1], YP[:, s1])
+    q0, q8 = E.Quantiser(gc), E.Quantiser(gc, 8)
 
     def plain():
         E.gc_likelihood_ste(tape, Y[:, s1], MU[:, s1], SC[:, s1], None, LIK[:, s1], YP[:, s1])
-        sym = torch.empty((N, c, h, w), dtype=torch.int32, device="cuda:0")
-        L.check(L.lib().icm_quantize(L.ptr(Y[:, s1]), L.bs(Y[:, s1]), L.ptr(MU[:, s1]), L.bs(MU[:, s1]), h * w, 1,
-                                     sym.data_ptr(), 0, N, c, h * w, L.stream()), "quantize")
-        return sym, gc.build_indexes(SC[:, s1])
+        return q0.code(*args_)
 
     def fused():
-        return E.gc_code_q(L.stream(), Y[:, s1], MU[:, s1], SC[:, s1], table, gc._scale_bound, 8, YP[:, s1])
+        return q8.code(*args_)
 
     roi = torch.from_numpy(codec.roi_map(H, W, codec.center_pads(H, W), 8, [ROI])).to("cuda:0")
     busy = torch.from_numpy(np.array([-16, -3, 0, 5, 8, 32], dtype=np.int8)[(5 * np.arange(h * w)) % 6].reshape(h, w))
     busy = busy.to("cuda:0")
 
     def mapped(qmap):
-        return lambda: E.gc_code_qmap(L.stream(), Y[:, s1], MU[:, s1], SC[:, s1], table, gc._scale_bound, qmap, YP[:, s1])
+        q = E.Quantiser(gc, 0, qmap)
+        return lambda: q.code(*args_)
 
     res = {"metric": "slice_kernels", "slice": [N, c, h, w], "iters": args.iters}
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
