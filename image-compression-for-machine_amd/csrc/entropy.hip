@@ -279,9 +279,7 @@ __global__ __launch_bounds__(256) void eb_aux_kernel(const EbPtrs P, float* loss
 }
 
 // ------------------------------------------------------------------------------ GaussianConditional
-__device__ __forceinline__ float std_cdf(float t) { return 0.5f * erfcf(-0.70710678118654752440f * t); }
-__device__ __forceinline__ float std_pdf(float t) { return 0.39894228040143267794f * expf(-0.5f * t * t); }
-
+// (std_cdf / std_pdf: icm_common.h, shared with the stepped form in qstep.hip)
 struct GcDesc {
   const float* y; const float* mu; const float* sc; const float* noise;
   float* lik; float* yh; float* yh2;

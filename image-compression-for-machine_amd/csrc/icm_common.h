@@ -79,6 +79,9 @@ __device__ __forceinline__ float dgelu_f(float x) {
   return cdf + x * pdf;
 }
 __device__ __forceinline__ float sigmoid_f(float x) { return 1.0f / (1.0f + expf(-x)); }
+// standard normal CDF and density of the GaussianConditional kernels (entropy.hip, and their stepped form in qstep.hip)
+__device__ __forceinline__ float std_cdf(float t) { return 0.5f * erfcf(-0.70710678118654752440f * t); }
+__device__ __forceinline__ float std_pdf(float t) { return 0.39894228040143267794f * expf(-0.5f * t * t); }
 
 __device__ __forceinline__ float apply_act(float v, int act) {
   if (act == ICM_ACT_GELU) return gelu_f(v);

@@ -681,6 +681,71 @@ __global__ void rd_bwd_kernel(const float* x, const float* xh, long long nx, con
   GRID_STRIDE(i, nz) dlz[i] = cl / lz[i];
 }
 
+// ---- R-D loss with a distortion weight per image (variable-rate training: lmbda_n [N] in DEVICE memory).
+// stage 1, grid (bpi, N): workgroup (b, n) sums the squared error of chunk b of image n -> ws[n * bpi + b]; the
+// log-likelihood sums are not per image: the workgroups take them in flat order f = n * bpi + b -> ws[T + f], ws[2T + f].
+// stage 2 (one workgroup): per image the ordered sum of its bpi partials, then over images in index order, thread 0
+// keeping the plain and the weighted total.  Fixed order throughout, no float atomics (the contract of rd_reduce_kernel).
+__global__ __launch_bounds__(256) void rd_w_reduce_kernel(const float* x, const float* xh, long long per,
+                                                          const float* ly, long long ny, const float* lz, long long nz,
+                                                          float* ws) {
+  __shared__ float red[4];
+  const int bpi = gridDim.x, T = gridDim.x * gridDim.y, f = blockIdx.y * bpi + blockIdx.x;
+  const float* xn = x + (long long)blockIdx.y * per;
+  const float* hn = xh + (long long)blockIdx.y * per;
+  float se = 0.0f, sy = 0.0f, sz = 0.0f;
+  for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < per; i += (long long)bpi * 256) {
+    const float d = hn[i] - xn[i];
+    se += d * d;
+  }
+  for (long long i = (long long)f * 256 + threadIdx.x; i < ny; i += (long long)T * 256) sy += logf(ly[i]);
+  for (long long i = (long long)f * 256 + threadIdx.x; i < nz; i += (long long)T * 256) sz += logf(lz[i]);
+  se = block_sum256(se, red);
+  sy = block_sum256(sy, red);
+  sz = block_sum256(sz, red);
+  if (threadIdx.x == 0) {
+    ws[f] = se;
+    ws[T + f] = sy;
+    ws[2 * T + f] = sz;
+  }
+}
+__global__ __launch_bounds__(256) void rd_w_finish_kernel(const float* ws, int N, int bpi, float* out, long long per,
+                                                          long long npix, const float* __restrict__ lmbda_n) {
+  __shared__ float red[4];
+  const int T = N * bpi;
+  float se = 0.0f, wse = 0.0f;
+  for (int n = 0; n < N; ++n) {
+    const float sn = ordered_sum(ws + (long long)n * bpi, bpi, red);
+    se += sn;
+    wse += lmbda_n[n] * sn;
+  }
+  const float sy = ordered_sum(ws + T, T, red);
+  const float sz = ordered_sum(ws + 2 * T, T, red);
+  if (threadIdx.x == 0) {
+    const float nx = (float)N * (float)per;
+    const float denom = -0.69314718055994530942f * (float)npix;
+    const float bpp = sy / denom + sz / denom;
+    out[0] = bpp;
+    out[1] = se / nx;
+    out[2] = 65025.0f * (wse / nx) + bpp;
+    out[3] = sy;
+    out[4] = sz;
+  }
+}
+// grid (bx, N): image n's gradient carries its own weight
+__global__ void rd_w_bwd_kernel(const float* x, const float* xh, long long per, const float* ly, long long ny,
+                                const float* lz, long long nz, long long npix, const float* __restrict__ lmbda_n,
+                                float gscale, float* dxh, float* dly, float* dlz) {
+  const int N = gridDim.y, T = gridDim.x * gridDim.y, f = blockIdx.y * gridDim.x + blockIdx.x;
+  const float cm = gscale * lmbda_n[blockIdx.y] * 65025.0f * 2.0f / ((float)N * (float)per);
+  const float cl = gscale / (-0.69314718055994530942f * (float)npix);
+  const long long o = (long long)blockIdx.y * per;
+  for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < per; i += (long long)gridDim.x * 256)
+    dxh[o + i] = cm * (xh[o + i] - x[o + i]);
+  for (long long i = (long long)f * 256 + threadIdx.x; i < ny; i += (long long)T * 256) dly[i] = cl / ly[i];
+  for (long long i = (long long)f * 256 + threadIdx.x; i < nz; i += (long long)T * 256) dlz[i] = cl / lz[i];
+}
+
 // ---------------------------------------------------------------- optimiser
 __global__ __launch_bounds__(256) void sqnorm_kernel(const float* g, long long n, float* ws) {
   __shared__ float red[4];
@@ -1036,6 +1101,37 @@ int icm_rd_loss_bwd(const float* x, const float* x_hat, int64_t n_img_elems, con
   hipLaunchKernelGGL(rd_bwd_kernel, dim3(grid_for(n_img_elems)), dim3(256), 0, ST, x, x_hat, (long long)n_img_elems,
                      lik_y, (long long)n_y, lik_z, (long long)n_z, (long long)num_pixels, lmbda, gscale, dx_hat, dlik_y,
                      dlik_z);
+  ICM_CHECK_LAUNCH();
+  return ICM_OK;
+}
+// workgroups per image of the weighted loss: what the scalar form gives one image, held to 2048 in all
+static inline int rd_w_blocks(int N, long long img_elems, int per_thread) {
+  return std::max(1, std::min(grid_for(img_elems, per_thread), 2048 / N));
+}
+int icm_rd_loss_w_fwd(const float* x, const float* x_hat, int N, int64_t img_elems, const float* lik_y, int64_t n_y,
+                      const float* lik_z, int64_t n_z, int64_t num_pixels, const float* lmbda_n, float* out, float* ws,
+                      void* stream) {
+  if (!x || !x_hat || !lik_y || !lik_z || !lmbda_n || !out || !ws || N <= 0 || img_elems <= 0 || num_pixels <= 0)
+    return ICM_ERR_ARG;
+  if (3LL * N > ICM_REDUCE_WS_FLOATS) return ICM_ERR_ARG;   // three partial sums per workgroup, a workgroup per image at least
+  const int bpi = rd_w_blocks(N, img_elems, 8);             // N * bpi <= max(N, 2048): 3 * N * bpi <= ICM_REDUCE_WS_FLOATS
+  hipLaunchKernelGGL(rd_w_reduce_kernel, dim3(bpi, N), dim3(256), 0, ST, x, x_hat, (long long)img_elems, lik_y,
+                     (long long)n_y, lik_z, (long long)n_z, ws);
+  ICM_CHECK_LAUNCH();
+  hipLaunchKernelGGL(rd_w_finish_kernel, dim3(1), dim3(256), 0, ST, ws, N, bpi, out, (long long)img_elems,
+                     (long long)num_pixels, lmbda_n);
+  ICM_CHECK_LAUNCH();
+  return ICM_OK;
+}
+int icm_rd_loss_w_bwd(const float* x, const float* x_hat, int N, int64_t img_elems, const float* lik_y, int64_t n_y,
+                      const float* lik_z, int64_t n_z, int64_t num_pixels, const float* lmbda_n, float gscale,
+                      float* dx_hat, float* dlik_y, float* dlik_z, void* stream) {
+  if (!x || !x_hat || !lik_y || !lik_z || !lmbda_n || !dx_hat || !dlik_y || !dlik_z || N <= 0 || img_elems <= 0 ||
+      num_pixels <= 0 || 3LL * N > ICM_REDUCE_WS_FLOATS)
+    return ICM_ERR_ARG;
+  hipLaunchKernelGGL(rd_w_bwd_kernel, dim3(rd_w_blocks(N, img_elems, 4), N), dim3(256), 0, ST, x, x_hat,
+                     (long long)img_elems, lik_y, (long long)n_y, lik_z, (long long)n_z, (long long)num_pixels, lmbda_n,
+                     gscale, dx_hat, dlik_y, dlik_z);
   ICM_CHECK_LAUNCH();
   return ICM_OK;
 }

@@ -165,6 +165,88 @@ __global__ __launch_bounds__(256) void dequantize_qmap_kernel(const int* __restr
   }
 }
 
+// ---- training and estimation at a step: the likelihood of icm_gc_likelihood_ste_fwd / _bwd (entropy.hip) in symbol
+// units, with a (step, inv) pair per IMAGE read from device memory (`steps` [N] float2: a captured training graph is
+// replayed with fresh steps).  Per element of image n, all f32:
+//     t = (y - mu) * inv;  s = symbol_of(y, mu, inv);  v = noise ? t + noise : (float)s      the noise is in symbol units
+//     se = max(scale, scale_bound) * inv                                                     index_of's own expression
+//     lik = max(Phi((1/2 - |v|) / se) - Phi((-1/2 - |v|) / se), lik_bound)
+//     y_hat = yh_of(s, mu, step)                       the codec's y_hat bit for bit, whether or not there is noise
+// Backward, with pu / pl the densities at the two arguments u, l:  d lik / d|v| = (pl - pu) / se,
+// d lik / d se = (l pl - u pu) / se;  dv / dy = -dv / dmu = inv (with noise; the rounded symbol passes nothing),
+// d se / d scale = inv above the scale bound.  The two LowerBound gates are gc_bwd_kernel's: a gradient passes a bound
+// that is active only if it pushes the value up.  d y_hat passes to y unchanged (straight-through) and not to mu.
+// The same grid-stride shape as the scalar pair: the pair of image n is a wave-uniform 8-byte load per element (N
+// pairs: they stay in cache).
+struct GcQsDesc {
+  const float* y; const float* mu; const float* sc; const float* noise; const float2* steps;
+  float* lik; float* yh; float* yh2;
+  long long y_bs, mu_bs, sc_bs, nz_bs, lik_bs, yh_bs, yh2_bs;
+  int N, C, HW;
+  float scale_bound, lik_bound;
+};
+
+__global__ __launch_bounds__(256) void gc_qs_fwd_kernel(const GcQsDesc d) {
+  const long long per = (long long)d.C * d.HW, total = per * d.N;
+  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total;
+       i += (long long)gridDim.x * blockDim.x) {
+    const long long n = i / per, r = i - n * per;
+    const float2 si = d.steps[n];   // x: step, y: inv
+    const float y = d.y[n * d.y_bs + r], mu = d.mu[n * d.mu_bs + r], sc = d.sc[n * d.sc_bs + r];
+    const int s = symbol_of(y, mu, si.y);
+    const float w = d.noise ? mul_rn(y - mu, si.y) + d.noise[n * d.nz_bs + r] : (float)s;
+    const float v = fabsf(w);
+    const float se = mul_rn(fmaxf(sc, d.scale_bound), si.y);
+    const float up = std_cdf((0.5f - v) / se), lo = std_cdf((-0.5f - v) / se);
+    d.lik[n * d.lik_bs + r] = fmaxf(up - lo, d.lik_bound);
+    const float yh = yh_of(s, mu, si.x);
+    if (d.yh) d.yh[n * d.yh_bs + r] = yh;
+    if (d.yh2) d.yh2[n * d.yh2_bs + r] = yh;
+  }
+}
+
+struct GcQsBwdDesc {
+  const float* y; const float* mu; const float* sc; const float* noise; const float2* steps; const float* dlik;
+  const float* dyh;
+  float* dy; float* dmu; float* dsc;
+  long long y_bs, mu_bs, sc_bs, nz_bs, dl_bs, dyh_bs, dy_bs, dmu_bs, dsc_bs;
+  int N, C, HW, accum_dy;
+  float scale_bound, lik_bound;
+};
+
+__global__ __launch_bounds__(256) void gc_qs_bwd_kernel(const GcQsBwdDesc d) {
+  const long long per = (long long)d.C * d.HW, total = per * d.N;
+  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total;
+       i += (long long)gridDim.x * blockDim.x) {
+    const long long n = i / per, r = i - n * per;
+    const float inv = d.steps[n].y;
+    const float y = d.y[n * d.y_bs + r], mu = d.mu[n * d.mu_bs + r], sc = d.sc[n * d.sc_bs + r];
+    const float w = d.noise ? mul_rn(y - mu, inv) + d.noise[n * d.nz_bs + r] : (float)symbol_of(y, mu, inv);
+    const float v = fabsf(w);
+    const float se = mul_rn(fmaxf(sc, d.scale_bound), inv);
+    const float u = (0.5f - v) / se, l = (-0.5f - v) / se;
+    const float lraw = std_cdf(u) - std_cdf(l);
+    float g = d.dlik[n * d.dl_bs + r];
+    if (!(lraw >= d.lik_bound || g < 0.0f)) g = 0.0f;
+    const float pu = std_pdf(u), pl = std_pdf(l);
+    const float dv = g * (pl - pu) / se;
+    float gs = g * (l * pl - u * pu) / se * inv;
+    if (!(sc >= d.scale_bound || gs < 0.0f)) gs = 0.0f;
+    const float sg = w > 0.0f ? 1.0f : (w < 0.0f ? -1.0f : 0.0f);
+    float gy = 0.0f, gmu = 0.0f;
+    if (d.noise) {
+      gy = dv * sg * inv;
+      gmu = -gy;
+    }
+    if (d.dyh) gy += d.dyh[n * d.dyh_bs + r];
+    float* dyp = d.dy + n * d.dy_bs + r;
+    if (d.accum_dy) gy += *dyp;
+    *dyp = gy;
+    d.dmu[n * d.dmu_bs + r] = gmu;
+    d.dsc[n * d.dsc_bs + r] = gs;
+  }
+}
+
 }  // namespace icm
 
 using namespace icm;
@@ -252,6 +334,37 @@ int icm_dequantize_qmap(const int32_t* symbols, const float* mu, int64_t mu_bs, 
   const QGeom g{0, mu_bs, 0, yh_bs, N, C, HW};
   hipLaunchKernelGGL(dequantize_qmap_kernel, qmap_grid(N, C, HW), dim3(256), 0, (hipStream_t)stream, symbols, mu,
                      (const unsigned char*)qmap, (const float2*)step_table, yh, g);
+  ICM_CHECK_LAUNCH();
+  return ICM_OK;
+}
+
+// the grid of icm_gc_likelihood_ste_fwd / _bwd: a training slice of a 16 x 256 x 256 batch has 131 072 elements
+static inline int qs_blocks(long long total) {
+  return (int)std::max<long long>(1, std::min<long long>((total + 255) / 256, 2048));
+}
+
+int icm_gc_likelihood_ste_qs_fwd(const float* y, int64_t y_bs, const float* mu, int64_t mu_bs, const float* scale,
+                                 int64_t sc_bs, const float* noise, int64_t nz_bs, const float* steps, float* lik,
+                                 int64_t lik_bs, float* yh, int64_t yh_bs, float* yh2, int64_t yh2_bs, int N, int C,
+                                 int HW, float scale_bound, float lik_bound, void* stream) {
+  if (!y || !mu || !scale || !steps || !lik || N <= 0 || C <= 0 || HW <= 0 || scale_bound <= 0) return ICM_ERR_ARG;
+  const GcQsDesc d{y, mu, scale, noise, (const float2*)steps, lik, yh, yh2, y_bs, mu_bs, sc_bs, nz_bs, lik_bs, yh_bs,
+                   yh2_bs, N, C, HW, scale_bound, lik_bound};
+  hipLaunchKernelGGL(gc_qs_fwd_kernel, dim3(qs_blocks((long long)N * C * HW)), dim3(256), 0, (hipStream_t)stream, d);
+  ICM_CHECK_LAUNCH();
+  return ICM_OK;
+}
+
+int icm_gc_likelihood_ste_qs_bwd(const float* y, int64_t y_bs, const float* mu, int64_t mu_bs, const float* scale,
+                                 int64_t sc_bs, const float* noise, int64_t nz_bs, const float* steps, const float* dlik,
+                                 int64_t dl_bs, const float* dyh, int64_t dyh_bs, float* dy, int64_t dy_bs, float* dmu,
+                                 int64_t dmu_bs, float* dscale, int64_t dsc_bs, int N, int C, int HW, float scale_bound,
+                                 float lik_bound, int accum_dy, void* stream) {
+  if (!y || !mu || !scale || !steps || !dlik || !dy || !dmu || !dscale || N <= 0 || C <= 0 || HW <= 0)
+    return ICM_ERR_ARG;
+  const GcQsBwdDesc d{y, mu, scale, noise, (const float2*)steps, dlik, dyh, dy, dmu, dscale, y_bs, mu_bs, sc_bs, nz_bs,
+                      dl_bs, dyh_bs, dy_bs, dmu_bs, dsc_bs, N, C, HW, accum_dy, scale_bound, lik_bound};
+  hipLaunchKernelGGL(gc_qs_bwd_kernel, dim3(qs_blocks((long long)N * C * HW)), dim3(256), 0, (hipStream_t)stream, d);
   ICM_CHECK_LAUNCH();
   return ICM_OK;
 }

@@ -22,7 +22,7 @@ import torch
 from . import _lib as L
 from ._lib import (ACT_GELU, ACT_NONE, ACT_SQUARE, EPI_AXPY2, EPI_GDN, EPI_IGDN, EPI_LRP, EPI_MUL_DGELU, EPI_NONE,
                    EPI_RES, EPI_RES_GELU, EPI_RES_MUL_DGELU, bs, check, ptr)
-from .bitstream import step_of, step_table
+from .bitstream import check_qstep, step_of, step_table
 
 PEDESTAL = 2.0 ** -36
 _SKIP_WGRAD = _os.environ.get("ICM_DEBUG_SKIP_WGRAD", "0") == "1"
@@ -1213,13 +1213,25 @@ def ste_round_medians(tape, z, quantiles):
     return zh
 
 
-def gc_likelihood_ste(tape, y, mu, scale, noise, lik_out, yh_out, yh2_out=None, scale_bound=0.11, lik_bound=1e-9):
-    """GaussianConditional.forward fused with ste_round(y-mu)+mu (entropy_models.py:645-659, cnn.py:171-173)."""
+def gc_likelihood_ste(tape, y, mu, scale, noise, lik_out, yh_out, yh2_out=None, scale_bound=0.11, lik_bound=1e-9,
+                      steps=None):
+    """GaussianConditional.forward fused with ste_round(y-mu)+mu (entropy_models.py:645-659, cnn.py:171-173).
+    ``steps``: a device f32 [N, 2] tensor of (step, inv) pairs (``qstep_steps``), one per image: the likelihood is
+    that of the symbol round((y - mu) / step) under scale / step and y_hat the codec's symbol * step + mu
+    (csrc/qstep.hip); same operands, same tape wiring, the stepped pair of entry points."""
     N, Cc, H, W = y.shape
-    check(L.lib().icm_gc_likelihood_ste_fwd(ptr(y), bs(y), ptr(mu), bs(mu), ptr(scale), bs(scale), ptr(noise),
-                                            bs(noise), ptr(lik_out), bs(lik_out), ptr(yh_out), bs(yh_out),
-                                            ptr(yh2_out), bs(yh2_out), N, Cc, H * W, scale_bound, lik_bound, tape.st),
-          "gc_fwd")
+    lib = L.lib()
+    if steps is None:
+        fwd, bwd_entry, sarg = lib.icm_gc_likelihood_ste_fwd, lib.icm_gc_likelihood_ste_bwd, ()
+    else:
+        if steps.dtype != torch.float32 or tuple(steps.shape) != (N, 2) or not steps.is_contiguous() or \
+                steps.device != y.device:
+            raise ValueError(f"steps: expected a contiguous f32 {(N, 2)} tensor on {y.device}, got {steps.dtype} "
+                             f"{tuple(steps.shape)} on {steps.device}")
+        fwd, bwd_entry, sarg = lib.icm_gc_likelihood_ste_qs_fwd, lib.icm_gc_likelihood_ste_qs_bwd, (ptr(steps),)
+    check(fwd(ptr(y), bs(y), ptr(mu), bs(mu), ptr(scale), bs(scale), ptr(noise), bs(noise), *sarg, ptr(lik_out),
+              bs(lik_out), ptr(yh_out), bs(yh_out), ptr(yh2_out), bs(yh2_out), N, Cc, H * W, scale_bound, lik_bound,
+              tape.st), "gc_fwd")
     if tape.need_grad:
         def bwd():
             dl = tape.grad_of(lik_out)
@@ -1232,11 +1244,44 @@ def gc_likelihood_ste(tape, y, mu, scale, noise, lik_out, yh_out, yh2_out=None, 
             dmu, a1 = tape.grad_for_write(mu)
             dsc, a2 = tape.grad_for_write(scale)
             assert a1 == 0 and a2 == 0
-            check(L.lib().icm_gc_likelihood_ste_bwd(ptr(y), bs(y), ptr(mu), bs(mu), ptr(scale), bs(scale), ptr(noise),
-                                                    bs(noise), ptr(dl), bs(dl), ptr(dyh), bs(dyh), ptr(dy), bs(dy),
-                                                    ptr(dmu), bs(dmu), ptr(dsc), bs(dsc), N, Cc, H * W, scale_bound,
-                                                    lik_bound, acc, tape.st), "gc_bwd")
+            check(bwd_entry(ptr(y), bs(y), ptr(mu), bs(mu), ptr(scale), bs(scale), ptr(noise), bs(noise), *sarg, ptr(dl),
+                            bs(dl), ptr(dyh), bs(dyh), ptr(dy), bs(dy), ptr(dmu), bs(dmu), ptr(dsc), bs(dsc), N, Cc,
+                            H * W, scale_bound, lik_bound, acc, tape.st), "gc_bwd")
         tape.bw.append(bwd)
+
+
+def qstep_indexes(qstep, B: int):
+    """The checked step index of each of B images, from what ``forward(x, qstep=...)`` was given: None for no step
+    (None, 0, or B zeros given as Python ints: today's launches), else a list of B ints.  ``qstep``: a step index, or a
+    sequence / integer tensor of B of them, one per image, each checked by ``bitstream.check_qstep`` (ValueError)."""
+    if qstep is None:
+        return None
+    if torch.is_tensor(qstep):
+        if qstep.dtype.is_floating_point or qstep.dtype == torch.bool or qstep.dim() > 1:
+            raise ValueError(f"qstep: expected an integer tensor of {B} step indexes, got {qstep.dtype} {tuple(qstep.shape)}")
+        ks, zeros_are_none = qstep.reshape(-1).tolist(), False
+    elif isinstance(qstep, (list, tuple)):
+        ks, zeros_are_none = list(qstep), True
+    else:
+        ks, zeros_are_none = [qstep] * B, True
+    if len(ks) != B:
+        raise ValueError(f"qstep: {len(ks)} step indexes for a batch of {B}")
+    ks = [check_qstep(k, "forward: ") for k in ks]
+    if zeros_are_none and not any(ks):
+        return None
+    return ks
+
+
+def qstep_per_image(qstep) -> bool:
+    """was ``qstep`` given per image (a sequence or a tensor) rather than as one index for the batch?"""
+    return torch.is_tensor(qstep) or isinstance(qstep, (list, tuple))
+
+
+def qstep_steps(qstep, B: int, device):
+    """What the slice loop takes for ``qstep`` (``qstep_indexes``): None for no step, else a device f32 [B, 2] tensor of
+    the (step, inv) pairs of ``bitstream.step_of``."""
+    ks = qstep_indexes(qstep, B)
+    return None if ks is None else torch.tensor([step_of(k) for k in ks], dtype=torch.float32).to(device)
 
 
 # ---- the codec's quantiser on y (inference only: compress / decompress)

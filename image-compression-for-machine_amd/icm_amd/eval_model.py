@@ -59,9 +59,8 @@ def load_checkpoint(arch: str, checkpoint_path: str) -> torch.nn.Module:
 def eval_model(model, filepaths: List[str], entropy_estimation: bool = False, recon_path: str = "",
                metric_names=None, qstep: int = 0) -> Dict[str, float]:
     """eval_model/__main__.py:472-487 (per-image metrics averaged over the folder); ``qstep``: the codec's quantiser
-    step index (``utils.inference``; the estimate path has no step)"""
-    if qstep and entropy_estimation:
-        raise ValueError("the entropy estimation has no quantiser step")
+    step index, for the real codec (``utils.inference``) and for the estimate
+    (``utils.inference_entropy_estimation``) alike"""
     device = next(model.parameters()).device
     metrics: Dict[str, float] = defaultdict(float)
     for f in filepaths:

@@ -18,6 +18,9 @@ loss (:438), best-only checkpoints ``<save_path><epoch>.ckpt`` holding epoch / s
 * ``--device-cache GB`` keeps both splits on the device as 8-bit images (decoded once, ``datasets.DeviceImageCache``)
   and cuts every batch there with one kernel launch; the per-step host work left is drawing the crop positions.  The
   crops are the transforms' own (same ``random`` draws); the epoch order comes from ``datasets.EpochSampler``;
+* ``--qstep-range LO,HI`` trains one model across the codec's quantiser steps (``Trainer(qstep_range=...)``: a step per
+  image and iteration, distortion weight ``lambda * step^-E``, ``--qstep-lambda-exp E``); the test loop then reports
+  loss, bpp and mse at K = LO, 0 (if inside the range) and HI, and the checkpoint records ``qstep_range``;
 * checkpoints are read with ``weights_only=True``."""
 from __future__ import annotations
 
@@ -33,7 +36,7 @@ from torch.utils.data import DataLoader
 from .datasets import (CenterCrop, Compose, DeviceCacheLoader, DeviceImageCache, EpochSampler, ImageFolder, RandomCrop,
                        ToTensor)
 from .losses import METRICS, RateDistortionLoss
-from .trainer import Trainer
+from .trainer import Trainer, check_qstep_range, qstep_tables
 from .zoo import models
 
 
@@ -89,6 +92,58 @@ def train_one_epoch(trainer: Trainer, train_dataloader, epoch: int, log_every: i
             print(f"Train epoch {epoch}: [{i * len(x)}/{len(train_dataloader.dataset)} "
                   f"({100. * i / len(train_dataloader):.0f}%)]\tLoss: {v[2]:.3f} |\t{dist} |"
                   f"\tBpp loss: {v[0]:.2f} |\tAux loss: {v[6]:.2f} |\ttime: {dt:.1f}", flush=True)
+
+
+def parse_qstep_range(text):
+    """--qstep-range LO,HI -> (lo, hi), two step indexes with lo <= hi (ValueError otherwise)"""
+    parts = [p.strip() for p in str(text).split(",")]
+    try:
+        lo, hi = (int(p) for p in parts)
+    except ValueError:
+        raise ValueError(f"--qstep-range: expected LO,HI (two integers), got {text!r}")
+    return check_qstep_range((lo, hi))
+
+
+def qstep_test_points(qstep_range):
+    """the step indexes the test loop reports of a variable-rate run: LO, 0 (if inside the range) and HI"""
+    lo, hi = qstep_range
+    return sorted({lo, hi} | ({0} if lo < 0 < hi else set()))
+
+
+@torch.no_grad()
+def qstep_test_epoch(epoch: int, test_dataloader, model, criterion, lmbda: float, lmbda_exp: float, qstep_range,
+                     verbose: bool = True) -> float:
+    """``test_epoch`` of a variable-rate run: loss, bpp and mse at every step index of ``qstep_test_points``, each with the
+    weight training gives that step (``trainer.qstep_tables``); returns the mean of the points' losses, which is what
+    the learning-rate schedule and the best-checkpoint choice then see"""
+    model.eval()
+    device = next(model.parameters()).device
+    points = qstep_test_points(qstep_range)
+    meters = {k: (AverageMeter(), AverageMeter(), AverageMeter()) for k in points}
+    lam = {k: float(qstep_tables((k, k), lmbda, lmbda_exp)[1][0]) for k in points}
+    for d in test_dataloader:
+        x = d.to(device)
+        for k in points:
+            out = criterion(model(x, qstep=k), x, lmbda_n=[lam[k]] * x.shape[0])
+            for m, name in zip(meters[k], ("loss", "bpp_loss", "mse_loss")):
+                m.update(float(out[name]))
+    model.train()
+    if verbose:
+        for k in points:
+            loss, bpp, mse = meters[k]
+            print(f"Test epoch {epoch}: qstep {k}:\tLoss: {loss.avg:.3f} |\tMSE loss: {mse.avg * 255 ** 2:.3f} |"
+                  f"\tBpp loss: {bpp.avg:.2f}", flush=True)
+    return sum(meters[k][0].avg for k in points) / len(points)
+
+
+def checkpoint_state(epoch, state_dict, loss, optimizer, aux_optimizer, lr_scheduler, qstep_range=None,
+                     qstep_lmbda_exp=2.0) -> dict:
+    """what a checkpoint holds (train.py:512-527); "qstep_range" is [lo, hi] of a variable-rate run and None otherwise
+    (a checkpoint without the key is a fixed-rate one)"""
+    return {"epoch": epoch, "state_dict": state_dict, "loss": loss, "optimizer": optimizer,
+            "aux_optimizer": aux_optimizer, "lr_scheduler": lr_scheduler,
+            "qstep_range": None if qstep_range is None else [int(k) for k in qstep_range],
+            "qstep_lambda_exp": float(qstep_lmbda_exp)}
 
 
 @torch.no_grad()
@@ -151,7 +206,29 @@ def parse_args(argv):
     p.add_argument("--device-cache", type=float, default=0.0, metavar="GB",
                    help="keep both splits on the device as 8-bit images, at most GB gigabytes (10^9 bytes), and crop "
                         "batches there (default: 0 = off, DataLoader workers decode every step)")
-    return p.parse_args(argv)
+    p.add_argument("--qstep-range", type=str, default=None, metavar="LO,HI",
+                   help="variable-rate training: draw a quantiser step 2^(K/8) per image, K uniform on LO..HI "
+                        "(integers in -16..32, LO <= HI), and weight its distortion by lambda * step^-E (default: off)")
+    p.add_argument("--qstep-lambda-exp", type=float, default=2.0, metavar="E",
+                   help="exponent E of the per-step distortion weight (default: %(default)s, the high-rate "
+                        "approximation D ~ step^2)")
+    # "--qstep-range -8,16": argparse takes a value that begins with "-" and is no number for an option; hand it the
+    # "--qstep-range=-8,16" form
+    argv = list(argv)
+    for i in range(len(argv) - 1):
+        if argv[i] == "--qstep-range" and argv[i + 1][:1] == "-" and argv[i + 1][1:2].isdigit():
+            argv[i:i + 2] = [f"--qstep-range={argv[i + 1]}"]
+            break
+    args = p.parse_args(argv)
+    try:
+        args.qstep_range = None if args.qstep_range is None else parse_qstep_range(args.qstep_range)
+        if args.qstep_range is not None and args.metric == "ms-ssim":
+            raise ValueError("--qstep-range: the MS-SSIM loss takes a scalar lambda (use --metric mse)")
+        if args.qstep_range is not None and args.model == "stf6":
+            raise ValueError("--qstep-range: stf6 has no codec and so no quantiser step")
+    except ValueError as e:
+        p.error(str(e))   # exit 2, like every other bad argument
+    return args
 
 
 class _Limited:
@@ -231,7 +308,8 @@ def main(argv) -> int:
         last_epoch = int(ck["epoch"]) + 1
         net.load_state_dict(ck["state_dict"])
     trainer = Trainer(net, lr=args.learning_rate, aux_lr=args.aux_learning_rate, lmbda=args.lmbda,
-                      clip_max_norm=args.clip_max_norm, device=device, seed=int(args.seed or 0), metric=args.metric)
+                      clip_max_norm=args.clip_max_norm, device=device, seed=int(args.seed or 0), metric=args.metric,
+                      qstep_range=args.qstep_range, qstep_lmbda_exp=args.qstep_lambda_exp)
     lr_scheduler = PlateauLR(trainer, factor=0.6, patience=6)
     criterion = RateDistortionLoss(lmbda=args.lmbda, metric=args.metric)
     if ck is not None and "optimizer" in ck and isinstance(ck["optimizer"], dict) and "m" in ck["optimizer"]:
@@ -247,14 +325,18 @@ def main(argv) -> int:
             sampler.set_epoch(epoch)
         train_one_epoch(trainer, train_dataloader, epoch)
         if epoch % args.test_every == 0:
-            loss = test_epoch(epoch, test_dataloader, trainer.model, criterion, verbose=rank == 0)
+            if args.qstep_range is not None:
+                loss = qstep_test_epoch(epoch, test_dataloader, trainer.model, criterion, args.lmbda,
+                                        args.qstep_lambda_exp, args.qstep_range, verbose=rank == 0)
+            else:
+                loss = test_epoch(epoch, test_dataloader, trainer.model, criterion, verbose=rank == 0)
             lr_scheduler.step(loss)
             is_best = loss < best_loss
             best_loss = min(loss, best_loss)
             if args.save and is_best and rank == 0:
                 opt, aux = trainer.optimizer_state()
-                save_checkpoint({"epoch": epoch, "state_dict": trainer.model.state_dict(), "loss": loss, "optimizer": opt,
-                                 "aux_optimizer": aux, "lr_scheduler": lr_scheduler.state_dict()},
+                save_checkpoint(checkpoint_state(epoch, trainer.model.state_dict(), loss, opt, aux,
+                                                 lr_scheduler.state_dict(), args.qstep_range, args.qstep_lambda_exp),
                                 os.path.join(args.save_path, f"{epoch}.ckpt"))
     if world > 1:
         import torch.distributed as dist

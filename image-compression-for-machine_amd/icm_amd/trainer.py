@@ -25,6 +25,7 @@ import torch.distributed as dist
 from . import _lib as L
 from . import engine as E
 from ._lib import check, ptr
+from .bitstream import check_qstep, step_of
 from .models import SymmetricalTransFormer, SymmetricalTransFormer3, stf6_forward, stf_forward, wacnn_forward
 
 # bucket -> parameter-name prefixes, in the order their gradients complete during backward
@@ -149,11 +150,49 @@ class GradReducer:
             torch.cuda.current_stream().wait_stream(self.stream)
 
 
+def check_qstep_range(qstep_range) -> Tuple[int, int]:
+    """(lo, hi) of a variable-rate training range: two step indexes (``bitstream.check_qstep``) with lo <= hi"""
+    try:
+        lo, hi = qstep_range
+    except (TypeError, ValueError):
+        raise ValueError(f"qstep_range: expected (lo, hi), got {qstep_range!r}")
+    lo, hi = check_qstep(lo, "qstep_range: "), check_qstep(hi, "qstep_range: ")
+    if lo > hi:
+        raise ValueError(f"qstep_range: lo = {lo} > hi = {hi}")
+    return lo, hi
+
+
+def qstep_tables(qstep_range, lmbda: float, lmbda_exp: float = 2.0) -> Tuple[torch.Tensor, torch.Tensor]:
+    """The two tables a variable-rate step gathers from, entry i for step index k = lo + i (host f32 tensors):
+    the (step, inv) pairs of ``bitstream.step_of`` [n, 2], and lmbda_k = lmbda * step_k^(-lmbda_exp) =
+    lmbda * 2^(-k * lmbda_exp / 8), formed in double [n].  With the default exponent 2 the distortion term
+    lmbda_k * D keeps its weight against the rate as the step grows, under the high-rate approximation D ~ step^2
+    (a default, not a measured optimum)."""
+    lo, hi = check_qstep_range(qstep_range)
+    ks = range(lo, hi + 1)
+    steps = torch.tensor([step_of(k) for k in ks], dtype=torch.float32)
+    lam = torch.tensor([float(lmbda) * 2.0 ** (-k * float(lmbda_exp) / 8.0) for k in ks], dtype=torch.float64)
+    return steps, lam.to(torch.float32)
+
+
 class Trainer:
     def __init__(self, model, lr: float = 1e-4, aux_lr: float = 1e-4, lmbda: float = 0.0067,
-                 clip_max_norm: float = 1.0, device="cuda:0", group=None, seed: int = 0, metric: str = "mse"):
+                 clip_max_norm: float = 1.0, device="cuda:0", group=None, seed: int = 0, metric: str = "mse",
+                 qstep_range=None, qstep_lmbda_exp: float = 2.0):
+        """``qstep_range`` = (lo, hi): variable-rate training -- every step draws a quantiser step index per image,
+        uniform on lo..hi, from this rank's device generator (after the noise and DropPath draws, whose order and
+        values it leaves alone), and trains the entropy model and the transforms at that step
+        (``engine.gc_likelihood_ste(steps=...)``) with the distortion weight lmbda * step^(-qstep_lmbda_exp) of that
+        image (``qstep_tables``).  None (default): today's step, launch for launch and draw for draw."""
         if metric not in ("mse", "ms-ssim"):
             raise NotImplementedError(f"{metric} is not implemented!")
+        self.qstep_range, self.qstep_lmbda_exp = None, float(qstep_lmbda_exp)
+        if qstep_range is not None:
+            self.qstep_range = check_qstep_range(qstep_range)
+            if metric == "ms-ssim":
+                raise ValueError("qstep_range: the MS-SSIM loss takes a scalar lmbda; per-image weights are mse only")
+            if isinstance(model, SymmetricalTransFormer3):
+                raise ValueError("qstep_range: stf6 has no codec and so no quantiser step")
         self.metric = metric
         self.keep_loss_seed = False   # tests: keep (x_hat, dx_hat) of the last step in self.loss_seed
         self.loss_seed = None
@@ -192,16 +231,27 @@ class Trainer:
         self.is_stf = isinstance(model, SymmetricalTransFormer)
         self.is_stf6 = isinstance(model, SymmetricalTransFormer3)
         self.lat_ch = 384 if self.is_stf else 320
+        self.loss_terms = None   # tests (keep_loss_seed, variable rate): likelihoods, drawn step indexes, weights
+        if self.qstep_range is not None:   # built once; a step gathers from them on the device
+            steps, lam = qstep_tables(self.qstep_range, lmbda, self.qstep_lmbda_exp)
+            self._q_steps, self._q_lmbda = steps.to(self.device), lam.to(self.device)
 
     def params(self) -> Dict[str, torch.Tensor]:
         return self.flat.views
+
+    def _draw_qsteps(self, B: int):
+        """(table rows [B] int64, steps [B, 2], lmbda_n [B]) of one step: a step index per image, uniform on the range,
+        from this rank's generator; gathered on the device, nothing comes back to the host"""
+        rows = torch.randint(0, self._q_lmbda.numel(), (B,), device=self.device, generator=self.gen)
+        return rows, self._q_steps.index_select(0, rows), self._q_lmbda.index_select(0, rows)
 
     def step_graphed(self, x: torch.Tensor) -> torch.Tensor:
         """step(x) replayed from a captured hipGraph: one host call per iteration instead of ~1 000 (cnn) to ~8 000
         (stf6) launches issued through Python.  The first two calls per input shape run eagerly (they record the
         weight-packing sequence and set kernel attributes); the third captures.  What changes from step to step lives
         in device memory the graph reads: the input batch, the quantisation noise and DropPath scales (drawn outside the
-        graph from this rank's generator, in the same order as step() draws them) and Adam's step-dependent scalars
+        graph from this rank's generator, in the same order as step() draws them), with ``qstep_range`` the steps and
+        distortion weights of the images (drawn last, as in step()) and Adam's step-dependent scalars
         (icm_adam_step_hyper) -- so a replayed step equals the eager step bit for bit.  Single process only (the RCCL
         reductions are not captured); the side stream of the weight gradients is forked and joined inside the capture."""
         if self.world > 1:
@@ -228,6 +278,9 @@ class Trainer:
             fresh = self.model.draw_drops(B, dev, generator=self.gen)
             for k, v in g["drops"].items():
                 v.copy_(fresh[k])
+        if g["qsteps"] is not None:   # variable rate: the step's last draw, gathered into the buffers the graph reads
+            for buf, fresh in zip(g["qsteps"], self._draw_qsteps(B)):
+                buf.copy_(fresh)
         g["x"].copy_(x)
         g["graph"].replay()
         E.bump_weight_generation()
@@ -243,8 +296,11 @@ class Trainer:
         g = {"key": tuple(x.shape), "x": x.detach().clone().contiguous(),
              "nz": torch.zeros((B, 192, H // 64, W // 64), dtype=torch.float32, device=dev),
              "ny": torch.zeros(ny_shape, dtype=torch.float32, device=dev),
-             "drops": None,
+             "drops": None, "qsteps": None,
              "hyper": (torch.ones(2, dtype=torch.float32, device=dev), torch.ones(2, dtype=torch.float32, device=dev))}
+        if self.qstep_range is not None:   # row 0 of the tables: valid steps for the capture run, replaced per replay
+            rows = torch.zeros(B, dtype=torch.int64, device=dev)
+            g["qsteps"] = (rows, self._q_steps.index_select(0, rows), self._q_lmbda.index_select(0, rows))
         if self.is_stf:
             gen_state = self.gen.get_state()       # shapes / keys only: the capture must not consume random numbers
             g["drops"] = {k: v.clone() for k, v in self.model.draw_drops(B, dev, generator=self.gen).items()}
@@ -253,7 +309,8 @@ class Trainer:
         torch.cuda.synchronize(dev)
         graph = torch.cuda.CUDAGraph()
         with torch.cuda.graph(graph):
-            self.step(g["x"], noise={"z": g["nz"], "y": g["ny"]}, drops=g["drops"], _hyper=g["hyper"])
+            self.step(g["x"], noise={"z": g["nz"], "y": g["ny"]}, drops=g["drops"], _hyper=g["hyper"],
+                      _qsteps=g["qsteps"])
         self.step_no = step_no                      # nothing ran during capture
         self.side = side
         g["graph"] = graph
@@ -298,11 +355,13 @@ class Trainer:
             self.aux_lr = float(aux.get("lr", self.aux_lr))
 
     def step(self, x: torch.Tensor, noise: Optional[dict] = None, drops: Optional[dict] = None,
-             _hyper: Optional[tuple] = None) -> torch.Tensor:
+             _hyper: Optional[tuple] = None, _qsteps: Optional[tuple] = None) -> torch.Tensor:
         """one training iteration on this rank's shard x [B,3,H,W]; returns the device tensor
         [bpp, mse, loss, sumlog_y, sumlog_z, grad_sqnorm, aux_loss, ms_ssim_loss] (no host sync; the last entry is
-        1 - ms_ssim with metric="ms-ssim" and 0 otherwise; loss is lmbda*255^2*mse + bpp or lmbda*(1 - ms_ssim) + bpp).
-        _hyper (step_graphed only): device tensors holding Adam's step-dependent scalars for the two optimisers."""
+        1 - ms_ssim with metric="ms-ssim" and 0 otherwise; loss is lmbda*255^2*mse + bpp or lmbda*(1 - ms_ssim) + bpp;
+        with ``qstep_range`` it is 255^2 * mean_n(lmbda_n * mse_n) + bpp at the steps drawn, mse stays the plain mean).
+        _hyper (step_graphed only): device tensors holding Adam's step-dependent scalars for the two optimisers;
+        _qsteps (step_graphed only): the (rows, steps, lmbda_n) buffers of ``_draw_qsteps`` the graph reads."""
         f, dev = self.flat, self.device
         st = L.stream()
         lib = L.lib()
@@ -334,25 +393,39 @@ class Trainer:
         for n, _ in f.main:   # (the fused EntropyBottleneck backward overwrites its 13 small parameter gradients)
             tape.bind_grad(P[n], f.gviews[n], not n.startswith("entropy_bottleneck."))
         marks = {}
+        if self.is_stf and drops is None:   # stochastic depth, drawn per step like timm's DropPath (stf.py:145)
+            drops = self.model.draw_drops(B, dev, generator=self.gen)
+        # variable rate: the LAST draw of the step, so that the noise and the DropPath scales are those of a plain step
+        qs = None
+        if self.qstep_range is not None:
+            qs = _qsteps if _qsteps is not None else self._draw_qsteps(B)
+        steps = None if qs is None else qs[1]
         if self.is_stf:
-            if drops is None:   # stochastic depth, drawn per step like timm's DropPath (stf.py:145)
-                drops = self.model.draw_drops(B, dev, generator=self.gen)
             drops = {k: v.to(dev, torch.float32).contiguous() for k, v in drops.items()}
             if self.is_stf6:   # zigzag blocks: iid noise, so any layout of the same draw is the same distribution
                 ny6 = ny if ny.dim() == 5 else ny.reshape(B, 24, 64, H // 32, W // 32)
                 x_hat, y_lik, z_lik = stf6_forward(tape, P, x, nz, ny6, drops, bucket_marks=marks)
             else:
-                x_hat, y_lik, z_lik = stf_forward(tape, P, x, nz, ny, drops, bucket_marks=marks)
+                x_hat, y_lik, z_lik = stf_forward(tape, P, x, nz, ny, drops, bucket_marks=marks, steps=steps)
         else:
-            x_hat, y_lik, z_lik = wacnn_forward(tape, P, x, nz, ny, bucket_marks=marks)
+            x_hat, y_lik, z_lik = wacnn_forward(tape, P, x, nz, ny, bucket_marks=marks, steps=steps)
         # ---- R-D loss forward + seeds (train.py:53-76)
-        # metric="ms-ssim": the fused reduction runs with lmbda = 0, i.e. loss = bpp and dx_hat = 0, as the rate part
-        lm = self.lmbda if self.metric == "mse" else 0.0
-        check(lib.icm_rd_loss_fwd(ptr(x), ptr(x_hat), x.numel(), ptr(y_lik), y_lik.numel(), ptr(z_lik), z_lik.numel(),
-                                  B * H * W, lm, ptr(self.scal), ptr(self.red_ws), st), "rd_loss_fwd")
         dxh, dly, dlz = E.new(x_hat), E.new(y_lik), E.new(z_lik)
-        check(lib.icm_rd_loss_bwd(ptr(x), ptr(x_hat), x.numel(), ptr(y_lik), y_lik.numel(), ptr(z_lik), z_lik.numel(),
-                                  B * H * W, lm, 1.0, ptr(dxh), ptr(dly), ptr(dlz), st), "rd_loss_bwd")
+        if qs is not None:   # a distortion weight per image: the weighted pair of reductions
+            lam = qs[2]
+            check(lib.icm_rd_loss_w_fwd(ptr(x), ptr(x_hat), B, x[0].numel(), ptr(y_lik), y_lik.numel(), ptr(z_lik),
+                                        z_lik.numel(), B * H * W, ptr(lam), ptr(self.scal), ptr(self.red_ws), st),
+                  "rd_loss_w_fwd")
+            check(lib.icm_rd_loss_w_bwd(ptr(x), ptr(x_hat), B, x[0].numel(), ptr(y_lik), y_lik.numel(), ptr(z_lik),
+                                        z_lik.numel(), B * H * W, ptr(lam), 1.0, ptr(dxh), ptr(dly), ptr(dlz), st),
+                  "rd_loss_w_bwd")
+        else:
+            # metric="ms-ssim": the fused reduction runs with lmbda = 0, i.e. loss = bpp and dx_hat = 0, as the rate part
+            lm = self.lmbda if self.metric == "mse" else 0.0
+            check(lib.icm_rd_loss_fwd(ptr(x), ptr(x_hat), x.numel(), ptr(y_lik), y_lik.numel(), ptr(z_lik),
+                                      z_lik.numel(), B * H * W, lm, ptr(self.scal), ptr(self.red_ws), st), "rd_loss_fwd")
+            check(lib.icm_rd_loss_bwd(ptr(x), ptr(x_hat), x.numel(), ptr(y_lik), y_lik.numel(), ptr(z_lik),
+                                      z_lik.numel(), B * H * W, lm, 1.0, ptr(dxh), ptr(dly), ptr(dlz), st), "rd_loss_bwd")
         if self.metric == "ms-ssim":
             # loss += lmbda * (1 - ms_ssim(x_hat, x)) on the device; dx_hat = -lmbda * d ms_ssim / d x_hat overwrites
             # the zero the rate part left there
@@ -369,6 +442,9 @@ class Trainer:
                                      mws.numel(), st), "msssim_bwd")
         if self.keep_loss_seed:
             self.loss_seed = (x_hat.detach().clone(), dxh.clone())
+            if qs is not None:
+                self.loss_terms = {"y_lik": y_lik.detach().clone(), "z_lik": z_lik.detach().clone(),
+                                   "qstep": qs[0] + self.qstep_range[0], "lmbda_n": qs[2].clone()}
         tape.bind_grad(x_hat, dxh, True)
         tape.bind_grad(y_lik, dly, True)
         tape.bind_grad(z_lik, dlz, True)

@@ -10,6 +10,7 @@ import torch
 
 from . import _lib as L
 from ._lib import check, ptr
+from .bitstream import check_qstep
 
 
 def pad2d(x: torch.Tensor, left: int, right: int, top: int, bottom: int, value: float = 0.0) -> torch.Tensor:
@@ -111,13 +112,16 @@ def inference(model, x: torch.Tensor, recon=None, metrics: Optional[Sequence[str
 
 @torch.no_grad()
 def inference_entropy_estimation(model, x: torch.Tensor, recon=None,
-                                 metrics: Optional[Sequence[str]] = None) -> Dict[str, float]:
-    """eval_model/__main__.py:143-225: forward pass with estimated rates (no entropy coder)"""
+                                 metrics: Optional[Sequence[str]] = None, qstep: int = 0) -> Dict[str, float]:
+    """eval_model/__main__.py:143-225: forward pass with estimated rates (no entropy coder); ``qstep``: the estimate
+    at the codec's quantiser step of that index (``model.forward(x, qstep=...)``: the reconstruction is the one
+    ``inference(qstep=...)`` decodes, the rate the entropy of the symbols it codes; 0: none)"""
+    qstep = check_qstep(qstep, "inference_entropy_estimation: ")
     if x.dim() == 3:
         x = x.unsqueeze(0)
     xp, pads = pad_to_multiple(x, 64)
     t0 = time.time()
-    out = model(xp)
+    out = model(xp, qstep=qstep) if qstep else model(xp)
     torch.cuda.synchronize() if x.is_cuda else None
     dt = time.time() - t0
     x_hat = crop(out["x_hat"], pads)

@@ -429,6 +429,28 @@ int icm_gc_indexes_qmap(const float* scale, int64_t sc_bs, const float* scale_ta
 int icm_dequantize_qmap(const int32_t* symbols, const float* mu, int64_t mu_bs, const int8_t* qmap,
                         const float* step_table, float* yh, int64_t yh_bs, int N, int C, int HW, void* stream);
 
+/* Training and estimation at a step (variable-rate training; parity unpinned like the rest of this section): the pair
+ * icm_gc_likelihood_ste_fwd / _bwd with a (step, inv) pair per IMAGE, `steps` [N][2] f32 in DEVICE memory, 8-byte
+ * aligned (a captured training graph is replayed with fresh steps; the kernels do not check the pairs).  Per element
+ * of image n, f32, through the device functions of the codec kernels above:
+ *   t = (y - mu) * inv;  s = symbol;  v = noise ? t + noise : (float)s;  se = max(scale, scale_bound) * inv;
+ *   lik = max(Phi((1/2 - |v|) / se) - Phi((-1/2 - |v|) / se), lik_bound);  y_hat = ((float)s * step) + mu
+ * so the likelihood is that of the symbol the codec codes under the scale it codes it with, and y_hat (-> yh, optional
+ * second copy yh2; either may be NULL) is icm_gc_code_q's bit for bit, with or without noise.
+ * bwd: inputs dlik, dyh (gradient wrt y_hat; may be NULL); dy (+)= (accum_dy), dmu =, dscale =.  The likelihood reaches
+ * y and mu through t (factor inv; nothing without noise) and scale through se (factor inv); both LowerBound gates are
+ * those of icm_gc_likelihood_ste_bwd; dyh passes to dy unchanged and not to dmu.
+ * ICM_ERR_ARG before any launch, outputs untouched: what the scalar pair refuses, and a null `steps`. */
+int icm_gc_likelihood_ste_qs_fwd(const float* y, int64_t y_bs, const float* mu, int64_t mu_bs, const float* scale,
+                                 int64_t sc_bs, const float* noise, int64_t nz_bs, const float* steps, float* lik,
+                                 int64_t lik_bs, float* yh, int64_t yh_bs, float* yh2, int64_t yh2_bs, int N, int C,
+                                 int HW, float scale_bound, float lik_bound, void* stream);
+int icm_gc_likelihood_ste_qs_bwd(const float* y, int64_t y_bs, const float* mu, int64_t mu_bs, const float* scale,
+                                 int64_t sc_bs, const float* noise, int64_t nz_bs, const float* steps, const float* dlik,
+                                 int64_t dl_bs, const float* dyh, int64_t dyh_bs, float* dy, int64_t dy_bs, float* dmu,
+                                 int64_t dmu_bs, float* dscale, int64_t dsc_bs, int N, int C, int HW, float scale_bound,
+                                 float lik_bound, int accum_dy, void* stream);
+
 /* ---- R-D loss (train.py:53-61, train_czigzag.py:63,71) --------------------------------------
  * out[0]=bpp, out[1]=mse, out[2]=loss, out[3]=sum log(lik_y), out[4]=sum log(lik_z) (5 floats, overwritten);
  * ws: ICM_REDUCE_WS_FLOATS floats of scratch (per-workgroup partial sums, added in workgroup order). */
@@ -440,6 +462,18 @@ int icm_rd_loss_fwd(const float* x, const float* x_hat, int64_t n_img_elems, con
 int icm_rd_loss_bwd(const float* x, const float* x_hat, int64_t n_img_elems, const float* lik_y, int64_t n_y,
                     const float* lik_z, int64_t n_z, int64_t num_pixels, float lmbda, float gscale,
                     float* dx_hat, float* dlik_y, float* dlik_z, void* stream);
+/* The same with a distortion weight per image (variable-rate training): x / x_hat hold N images of img_elems floats,
+ * lmbda_n [N] f32 in DEVICE memory.  out[0..4] as above, out[1] the plain mse, and
+ *   out[2] = 255^2 * (1/N) * sum_n lmbda_n * mse_n + bpp;   dx_hat of image n = gscale * lmbda_n*255^2*2*(x_hat-x)/(N*img_elems)
+ * Sums are fixed-order per image, then over images in index order (no float atomics: equal inputs give bit-identical
+ * results).  ICM_ERR_ARG: a null pointer, N, img_elems or num_pixels < 1, or 3 * N > ICM_REDUCE_WS_FLOATS (every image
+ * needs a workgroup's three partial sums in ws). */
+int icm_rd_loss_w_fwd(const float* x, const float* x_hat, int N, int64_t img_elems, const float* lik_y, int64_t n_y,
+                      const float* lik_z, int64_t n_z, int64_t num_pixels, const float* lmbda_n, float* out, float* ws,
+                      void* stream);
+int icm_rd_loss_w_bwd(const float* x, const float* x_hat, int N, int64_t img_elems, const float* lik_y, int64_t n_y,
+                      const float* lik_z, int64_t n_z, int64_t num_pixels, const float* lmbda_n, float gscale,
+                      float* dx_hat, float* dlik_y, float* dlik_z, void* stream);
 
 /* ---- MS-SSIM (Wang, Simoncelli, Bovik 2003; the defaults of pytorch_msssim.ms_ssim, which the reference's evaluation
  * CLI imports at compressai/utils/eval_model/__main__.py:32 and reports under the key "ms-ssim", :135) ------------
