@@ -746,6 +746,91 @@ __global__ void rd_w_bwd_kernel(const float* x, const float* xh, long long per, 
   for (long long i = (long long)f * 256 + threadIdx.x; i < nz; i += (long long)T * 256) dlz[i] = cl / lz[i];
 }
 
+// ---- R-D loss with a distortion weight per cell x cell block of pixels (quality-map training): qmap [N][H/cell][W/cell]
+// int8 step indexes, lam[256] the weight of each map byte read as unsigned, both in DEVICE memory.  The weighted sum
+// does not factor per image, so every workgroup carries a plain and a weighted partial sum of squared errors:
+// stage 1, grid (bpi, N): workgroup (b, n) walks rows of image n (a row is one (c, y) line of W pixels: the cell row is
+// found once per row, the cell column is x / cell; with W < 256 a workgroup takes 256 / W rows per pass) and writes
+// ws[f], ws[T + f]; the log-likelihood sums in flat order f = n * bpi + b -> ws[2T + f], ws[3T + f], as in the
+// per-image form.  stage 2 (one workgroup): four ordered sums of T partials.  Fixed order, no float atomics.
+struct RdMGeom {
+  long long per;   // C * H * W
+  int rows, H, W, cell, wc, rpb;   // C * H; W / cell; rows a workgroup takes per pass
+};
+__global__ __launch_bounds__(256) void rd_m_reduce_kernel(const float* x, const float* xh, const RdMGeom g,
+                                                          const unsigned char* __restrict__ qmap,
+                                                          const float* __restrict__ lam, const float* ly, long long ny,
+                                                          const float* lz, long long nz, float* ws) {
+  __shared__ float red[4];
+  const int bpi = gridDim.x, T = gridDim.x * gridDim.y, f = blockIdx.y * bpi + blockIdx.x;
+  const long long o = (long long)blockIdx.y * g.per;
+  const unsigned char* mn = qmap + (long long)blockIdx.y * (g.H / g.cell) * g.wc;
+  const int ty = g.rpb > 1 ? threadIdx.x / g.W : 0, tx = threadIdx.x - ty * g.W;
+  float se = 0.0f, wse = 0.0f, sy = 0.0f, sz = 0.0f;
+  if (ty < g.rpb) {
+    for (int r = blockIdx.x * g.rpb + ty; r < g.rows; r += bpi * g.rpb) {
+      const unsigned char* mrow = mn + (r % g.H) / g.cell * g.wc;
+      const long long ro = o + (long long)r * g.W;
+      for (int xx = tx; xx < g.W; xx += 256) {
+        const float d = xh[ro + xx] - x[ro + xx];
+        const float q = d * d;
+        se += q;
+        wse += lam[mrow[xx / g.cell]] * q;
+      }
+    }
+  }
+  for (long long i = (long long)f * 256 + threadIdx.x; i < ny; i += (long long)T * 256) sy += logf(ly[i]);
+  for (long long i = (long long)f * 256 + threadIdx.x; i < nz; i += (long long)T * 256) sz += logf(lz[i]);
+  se = block_sum256(se, red);
+  wse = block_sum256(wse, red);
+  sy = block_sum256(sy, red);
+  sz = block_sum256(sz, red);
+  if (threadIdx.x == 0) {
+    ws[f] = se;
+    ws[T + f] = wse;
+    ws[2 * T + f] = sy;
+    ws[3 * T + f] = sz;
+  }
+}
+__global__ __launch_bounds__(256) void rd_m_finish_kernel(const float* ws, int T, float* out, float nx, long long npix) {
+  __shared__ float red[4];
+  const float se = ordered_sum(ws, T, red);
+  const float wse = ordered_sum(ws + T, T, red);
+  const float sy = ordered_sum(ws + 2 * T, T, red);
+  const float sz = ordered_sum(ws + 3 * T, T, red);
+  if (threadIdx.x == 0) {
+    const float denom = -0.69314718055994530942f * (float)npix;
+    const float bpp = sy / denom + sz / denom;
+    out[0] = bpp;
+    out[1] = se / nx;
+    out[2] = 65025.0f * (wse / nx) + bpp;
+    out[3] = sy;
+    out[4] = sz;
+  }
+}
+// grid (bx, N), the same walk: a pixel's gradient carries its cell's weight
+__global__ __launch_bounds__(256) void rd_m_bwd_kernel(const float* x, const float* xh, const RdMGeom g,
+                                                       const unsigned char* __restrict__ qmap,
+                                                       const float* __restrict__ lam, const float* ly, long long ny,
+                                                       const float* lz, long long nz, long long npix, float nx,
+                                                       float gscale, float* dxh, float* dly, float* dlz) {
+  const int bx = gridDim.x, T = gridDim.x * gridDim.y, f = blockIdx.y * bx + blockIdx.x;
+  const float c0 = gscale * 65025.0f * 2.0f / nx;
+  const float cl = gscale / (-0.69314718055994530942f * (float)npix);
+  const long long o = (long long)blockIdx.y * g.per;
+  const unsigned char* mn = qmap + (long long)blockIdx.y * (g.H / g.cell) * g.wc;
+  const int ty = g.rpb > 1 ? threadIdx.x / g.W : 0, tx = threadIdx.x - ty * g.W;
+  if (ty < g.rpb) {
+    for (int r = blockIdx.x * g.rpb + ty; r < g.rows; r += bx * g.rpb) {
+      const unsigned char* mrow = mn + (r % g.H) / g.cell * g.wc;
+      const long long ro = o + (long long)r * g.W;
+      for (int xx = tx; xx < g.W; xx += 256) dxh[ro + xx] = c0 * lam[mrow[xx / g.cell]] * (xh[ro + xx] - x[ro + xx]);
+    }
+  }
+  for (long long i = (long long)f * 256 + threadIdx.x; i < ny; i += (long long)T * 256) dly[i] = cl / ly[i];
+  for (long long i = (long long)f * 256 + threadIdx.x; i < nz; i += (long long)T * 256) dlz[i] = cl / lz[i];
+}
+
 // ---------------------------------------------------------------- optimiser
 __global__ __launch_bounds__(256) void sqnorm_kernel(const float* g, long long n, float* ws) {
   __shared__ float red[4];
@@ -1132,6 +1217,47 @@ int icm_rd_loss_w_bwd(const float* x, const float* x_hat, int N, int64_t img_ele
   hipLaunchKernelGGL(rd_w_bwd_kernel, dim3(rd_w_blocks(N, img_elems, 4), N), dim3(256), 0, ST, x, x_hat,
                      (long long)img_elems, lik_y, (long long)n_y, lik_z, (long long)n_z, (long long)num_pixels, lmbda_n,
                      gscale, dx_hat, dlik_y, dlik_z);
+  ICM_CHECK_LAUNCH();
+  return ICM_OK;
+}
+// geometry of the per-cell loss; false: refused (H or W no multiple of cell, or a count outside what the walk indexes)
+static inline bool rd_m_geom(int N, int C, int H, int W, int cell, RdMGeom* g) {
+  if (N <= 0 || C <= 0 || H <= 0 || W <= 0 || cell < 1 || H % cell || W % cell) return false;
+  if ((long long)C * H > (1LL << 30) || 4LL * N > ICM_REDUCE_WS_FLOATS) return false;
+  *g = RdMGeom{(long long)C * H * W, C * H, H, W, cell, W / cell, W >= 256 ? 1 : 256 / W};
+  return true;
+}
+// workgroups per image: rows_per_thread rows of a pass each, held to 2048 in all (N <= 2048: N * bpi <= 2048)
+static inline int rd_m_blocks(int N, const RdMGeom& g, int rows_per_thread) {
+  const int want = (g.rows + g.rpb * rows_per_thread - 1) / (g.rpb * rows_per_thread);
+  return std::max(1, std::min(want, 2048 / N));
+}
+int icm_rd_loss_m_fwd(const float* x, const float* x_hat, int N, int C, int H, int W, int cell, const int8_t* qmap,
+                      const float* lmbda_table, const float* lik_y, int64_t n_y, const float* lik_z, int64_t n_z,
+                      int64_t num_pixels, float* out, float* ws, void* stream) {
+  RdMGeom g;
+  if (!x || !x_hat || !qmap || !lmbda_table || !lik_y || !lik_z || !out || !ws || num_pixels <= 0 ||
+      !rd_m_geom(N, C, H, W, cell, &g))
+    return ICM_ERR_ARG;
+  const int bpi = rd_m_blocks(N, g, 8);   // four partial sums per workgroup: 4 * N * bpi <= ICM_REDUCE_WS_FLOATS
+  hipLaunchKernelGGL(rd_m_reduce_kernel, dim3(bpi, N), dim3(256), 0, ST, x, x_hat, g, (const unsigned char*)qmap,
+                     lmbda_table, lik_y, (long long)n_y, lik_z, (long long)n_z, ws);
+  ICM_CHECK_LAUNCH();
+  hipLaunchKernelGGL(rd_m_finish_kernel, dim3(1), dim3(256), 0, ST, ws, N * bpi, out, (float)N * (float)g.per,
+                     (long long)num_pixels);
+  ICM_CHECK_LAUNCH();
+  return ICM_OK;
+}
+int icm_rd_loss_m_bwd(const float* x, const float* x_hat, int N, int C, int H, int W, int cell, const int8_t* qmap,
+                      const float* lmbda_table, const float* lik_y, int64_t n_y, const float* lik_z, int64_t n_z,
+                      int64_t num_pixels, float gscale, float* dx_hat, float* dlik_y, float* dlik_z, void* stream) {
+  RdMGeom g;
+  if (!x || !x_hat || !qmap || !lmbda_table || !lik_y || !lik_z || !dx_hat || !dlik_y || !dlik_z || num_pixels <= 0 ||
+      !rd_m_geom(N, C, H, W, cell, &g))
+    return ICM_ERR_ARG;
+  hipLaunchKernelGGL(rd_m_bwd_kernel, dim3(rd_m_blocks(N, g, 4), N), dim3(256), 0, ST, x, x_hat, g,
+                     (const unsigned char*)qmap, lmbda_table, lik_y, (long long)n_y, lik_z, (long long)n_z,
+                     (long long)num_pixels, (float)N * (float)g.per, gscale, dx_hat, dlik_y, dlik_z);
   ICM_CHECK_LAUNCH();
   return ICM_OK;
 }

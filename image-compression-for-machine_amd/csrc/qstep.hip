@@ -247,6 +247,95 @@ __global__ __launch_bounds__(256) void gc_qs_bwd_kernel(const GcQsBwdDesc d) {
   }
 }
 
+// ---- the same pair with a step per (image, position): quality-map training.  `qmap` [N][HW] int8 holds a step index
+// per image and latent position, shared by the channels; `d.steps` is the 256-pair table of the codec's map kernels,
+// indexed by the map byte read as unsigned (nothing here clamps the byte or branches on its validity).  Per element
+// the arithmetic is gc_qs_fwd_kernel's / gc_qs_bwd_kernel's, statement for statement, with the pair of the element's
+// position, so a map that is uniform over an image gives that image the bits of the per-image pair.
+// Layout: that of the codec's map kernels (qmap_grid: x over HW, y over c, both grid-stride loops), except that z is
+// the image itself: a training batch is small, and with n fixed per workgroup the nine operand offsets n * bs fold
+// into the base pointers once (with a loop over n the backward kernel ran out of scalar registers).  A lane reads the
+// byte and the pair of (n, p) once and keeps them in registers over the channels it walks; consecutive lanes on
+// consecutive addresses in every operand; no position index is divided out of a flat one.
+__global__ __launch_bounds__(256) void gc_qm_fwd_kernel(const GcQsDesc d, const unsigned char* __restrict__ qmap) {
+  const int n = blockIdx.z;
+  for (long long p = blockIdx.x * 256 + threadIdx.x; p < d.HW; p += gridDim.x * 256) {
+    {
+      const float2 si = d.steps[qmap[(long long)n * d.HW + p]];   // x: step, y: inv
+      for (int c = blockIdx.y; c < d.C; c += gridDim.y) {
+        const long long r = (long long)c * d.HW + p;
+        const float y = d.y[n * d.y_bs + r], mu = d.mu[n * d.mu_bs + r], sc = d.sc[n * d.sc_bs + r];
+        const int s = symbol_of(y, mu, si.y);
+        const float w = d.noise ? mul_rn(y - mu, si.y) + d.noise[n * d.nz_bs + r] : (float)s;
+        const float v = fabsf(w);
+        const float se = mul_rn(fmaxf(sc, d.scale_bound), si.y);
+        const float up = std_cdf((0.5f - v) / se), lo = std_cdf((-0.5f - v) / se);
+        d.lik[n * d.lik_bs + r] = fmaxf(up - lo, d.lik_bound);
+        const float yh = yh_of(s, mu, si.x);
+        if (d.yh) d.yh[n * d.yh_bs + r] = yh;
+        if (d.yh2) d.yh2[n * d.yh2_bs + r] = yh;
+      }
+    }
+  }
+}
+
+__global__ __launch_bounds__(256) void gc_qm_bwd_kernel(const GcQsBwdDesc d, const unsigned char* __restrict__ qmap) {
+  const int n = blockIdx.z;
+  for (long long p = blockIdx.x * 256 + threadIdx.x; p < d.HW; p += gridDim.x * 256) {
+    {
+      const float inv = d.steps[qmap[(long long)n * d.HW + p]].y;
+      for (int c = blockIdx.y; c < d.C; c += gridDim.y) {
+        const long long r = (long long)c * d.HW + p;
+        const float y = d.y[n * d.y_bs + r], mu = d.mu[n * d.mu_bs + r], sc = d.sc[n * d.sc_bs + r];
+        const float w = d.noise ? mul_rn(y - mu, inv) + d.noise[n * d.nz_bs + r] : (float)symbol_of(y, mu, inv);
+        const float v = fabsf(w);
+        const float se = mul_rn(fmaxf(sc, d.scale_bound), inv);
+        const float u = (0.5f - v) / se, l = (-0.5f - v) / se;
+        const float lraw = std_cdf(u) - std_cdf(l);
+        float g = d.dlik[n * d.dl_bs + r];
+        if (!(lraw >= d.lik_bound || g < 0.0f)) g = 0.0f;
+        const float pu = std_pdf(u), pl = std_pdf(l);
+        const float dv = g * (pl - pu) / se;
+        float gs = g * (l * pl - u * pu) / se * inv;
+        if (!(sc >= d.scale_bound || gs < 0.0f)) gs = 0.0f;
+        const float sg = w > 0.0f ? 1.0f : (w < 0.0f ? -1.0f : 0.0f);
+        float gy = 0.0f, gmu = 0.0f;
+        if (d.noise) {
+          gy = dv * sg * inv;
+          gmu = -gy;
+        }
+        if (d.dyh) gy += d.dyh[n * d.dyh_bs + r];
+        float* dyp = d.dy + n * d.dy_bs + r;
+        if (d.accum_dy) gy += *dyp;
+        *dyp = gy;
+        d.dmu[n * d.dmu_bs + r] = gmu;
+        d.dsc[n * d.dsc_bs + r] = gs;
+      }
+    }
+  }
+}
+
+// ---- painting the training maps on the device: qmap [N][h][w] int8; every cell of image n holds base[n], then the R
+// rectangles rects[n][r] = (y0, x0, y1, x1, k) (cells, half open) are painted in order, later ones winning
+// (icm_amd/codec.py: roi_map).  One lane per cell walks the image's rectangles (R is small and the reads are
+// wave-uniform) and stores once; a rectangle is clipped to the map by the test itself, an empty one holds no cell.
+// grid (blocks over h * w, N); k and the coordinates are not range-checked.
+__global__ __launch_bounds__(256) void qmap_paint_kernel(const signed char* __restrict__ base,
+                                                          const int* __restrict__ rects, int R, int h, int w,
+                                                          signed char* __restrict__ qmap) {
+  const int n = blockIdx.y, hw = h * w;
+  const int* rn = rects + (long long)n * R * 5;
+  for (int p = blockIdx.x * 256 + threadIdx.x; p < hw; p += gridDim.x * 256) {   // hw <= 2^30: no overflow
+    const int cy = p / w, cx = p - cy * w;
+    int k = base[n];
+    for (int r = 0; r < R; ++r) {
+      const int* q = rn + 5 * r;
+      if (cy >= q[0] && cx >= q[1] && cy < q[2] && cx < q[3]) k = q[4];
+    }
+    qmap[(long long)n * hw + p] = (signed char)k;
+  }
+}
+
 }  // namespace icm
 
 using namespace icm;
@@ -365,6 +454,56 @@ int icm_gc_likelihood_ste_qs_bwd(const float* y, int64_t y_bs, const float* mu, 
   const GcQsBwdDesc d{y, mu, scale, noise, (const float2*)steps, dlik, dyh, dy, dmu, dscale, y_bs, mu_bs, sc_bs, nz_bs,
                       dl_bs, dyh_bs, dy_bs, dmu_bs, dsc_bs, N, C, HW, accum_dy, scale_bound, lik_bound};
   hipLaunchKernelGGL(gc_qs_bwd_kernel, dim3(qs_blocks((long long)N * C * HW)), dim3(256), 0, (hipStream_t)stream, d);
+  ICM_CHECK_LAUNCH();
+  return ICM_OK;
+}
+
+// grid of the map pair of the training step: qmap_grid's x and y, and z = n (a grid's z holds 65 535)
+constexpr int QM_MAX_N = 65535;
+static inline dim3 qm_grid(int N, int C, int HW) {
+  const dim3 g = qmap_grid(1, C, HW);
+  return dim3(g.x, g.y, N);
+}
+
+int icm_gc_likelihood_ste_qm_fwd(const float* y, int64_t y_bs, const float* mu, int64_t mu_bs, const float* scale,
+                                 int64_t sc_bs, const float* noise, int64_t nz_bs, const int8_t* qmap,
+                                 const float* step_table, float* lik, int64_t lik_bs, float* yh, int64_t yh_bs,
+                                 float* yh2, int64_t yh2_bs, int N, int C, int HW, float scale_bound, float lik_bound,
+                                 void* stream) {
+  if (!y || !mu || !scale || !qmap || !step_table || !lik || N <= 0 || C <= 0 || HW <= 0 || scale_bound <= 0 ||
+      N > QM_MAX_N)
+    return ICM_ERR_ARG;
+  const GcQsDesc d{y, mu, scale, noise, (const float2*)step_table, lik, yh, yh2, y_bs, mu_bs, sc_bs, nz_bs, lik_bs,
+                   yh_bs, yh2_bs, N, C, HW, scale_bound, lik_bound};
+  hipLaunchKernelGGL(gc_qm_fwd_kernel, qm_grid(N, C, HW), dim3(256), 0, (hipStream_t)stream, d,
+                     (const unsigned char*)qmap);
+  ICM_CHECK_LAUNCH();
+  return ICM_OK;
+}
+
+int icm_gc_likelihood_ste_qm_bwd(const float* y, int64_t y_bs, const float* mu, int64_t mu_bs, const float* scale,
+                                 int64_t sc_bs, const float* noise, int64_t nz_bs, const int8_t* qmap,
+                                 const float* step_table, const float* dlik, int64_t dl_bs, const float* dyh,
+                                 int64_t dyh_bs, float* dy, int64_t dy_bs, float* dmu, int64_t dmu_bs, float* dscale,
+                                 int64_t dsc_bs, int N, int C, int HW, float scale_bound, float lik_bound, int accum_dy,
+                                 void* stream) {
+  if (!y || !mu || !scale || !qmap || !step_table || !dlik || !dy || !dmu || !dscale || N <= 0 || C <= 0 || HW <= 0 ||
+      N > QM_MAX_N)
+    return ICM_ERR_ARG;
+  const GcQsBwdDesc d{y, mu, scale, noise, (const float2*)step_table, dlik, dyh, dy, dmu, dscale, y_bs, mu_bs, sc_bs,
+                      nz_bs, dl_bs, dyh_bs, dy_bs, dmu_bs, dsc_bs, N, C, HW, accum_dy, scale_bound, lik_bound};
+  hipLaunchKernelGGL(gc_qm_bwd_kernel, qm_grid(N, C, HW), dim3(256), 0, (hipStream_t)stream, d,
+                     (const unsigned char*)qmap);
+  ICM_CHECK_LAUNCH();
+  return ICM_OK;
+}
+
+int icm_qmap_paint(const int8_t* base, const int32_t* rects, int R, int8_t* qmap, int N, int h, int w, void* stream) {
+  if (!base || !rects || !qmap || N < 1 || h < 1 || w < 1 || R < 0) return ICM_ERR_ARG;
+  if ((long long)h * w > (1LL << 30) || N > 65535) return ICM_ERR_ARG;   // int cell indexes; N is the grid's y
+  const int gx = (int)std::min<long long>(((long long)h * w + 255) / 256, 1024);
+  hipLaunchKernelGGL(qmap_paint_kernel, dim3(gx, N), dim3(256), 0, (hipStream_t)stream, (const signed char*)base, rects,
+                     R, h, w, (signed char*)qmap);
   ICM_CHECK_LAUNCH();
   return ICM_OK;
 }

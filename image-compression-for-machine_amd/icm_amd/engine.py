@@ -1214,14 +1214,26 @@ def ste_round_medians(tape, z, quantiles):
 
 
 def gc_likelihood_ste(tape, y, mu, scale, noise, lik_out, yh_out, yh2_out=None, scale_bound=0.11, lik_bound=1e-9,
-                      steps=None):
+                      steps=None, qmap=None):
     """GaussianConditional.forward fused with ste_round(y-mu)+mu (entropy_models.py:645-659, cnn.py:171-173).
     ``steps``: a device f32 [N, 2] tensor of (step, inv) pairs (``qstep_steps``), one per image: the likelihood is
     that of the symbol round((y - mu) / step) under scale / step and y_hat the codec's symbol * step + mu
-    (csrc/qstep.hip); same operands, same tape wiring, the stepped pair of entry points."""
+    (csrc/qstep.hip); same operands, same tape wiring, the stepped pair of entry points.
+    ``qmap`` (not with ``steps``): a contiguous device int8 [N, H, W] tensor of step indexes the caller has checked, one
+    per image and latent position, shared by the channels: the same at the step of each position (the map pair of
+    entry points, which read the pairs from ``qmap_step_table``)."""
     N, Cc, H, W = y.shape
     lib = L.lib()
-    if steps is None:
+    if steps is not None and qmap is not None:
+        raise ValueError("gc_likelihood_ste: steps and qmap are two forms of one thing; give one")
+    if qmap is not None:
+        if qmap.dtype != torch.int8 or tuple(qmap.shape) != (N, H, W) or not qmap.is_contiguous() or \
+                qmap.device != y.device:
+            raise ValueError(f"qmap: expected a contiguous int8 {(N, H, W)} tensor on {y.device}, got {qmap.dtype} "
+                             f"{tuple(qmap.shape)} on {qmap.device}")
+        fwd, bwd_entry = lib.icm_gc_likelihood_ste_qm_fwd, lib.icm_gc_likelihood_ste_qm_bwd
+        sarg = (ptr(qmap), ptr(qmap_step_table(y.device)))
+    elif steps is None:
         fwd, bwd_entry, sarg = lib.icm_gc_likelihood_ste_fwd, lib.icm_gc_likelihood_ste_bwd, ()
     else:
         if steps.dtype != torch.float32 or tuple(steps.shape) != (N, 2) or not steps.is_contiguous() or \

@@ -57,10 +57,13 @@ def load_checkpoint(arch: str, checkpoint_path: str) -> torch.nn.Module:
 
 @torch.no_grad()
 def eval_model(model, filepaths: List[str], entropy_estimation: bool = False, recon_path: str = "",
-               metric_names=None, qstep: int = 0) -> Dict[str, float]:
+               metric_names=None, qstep: int = 0, qmap=None) -> Dict[str, float]:
     """eval_model/__main__.py:472-487 (per-image metrics averaged over the folder); ``qstep``: the codec's quantiser
     step index, for the real codec (``utils.inference``) and for the estimate
-    (``utils.inference_entropy_estimation``) alike"""
+    (``utils.inference_entropy_estimation``) alike; ``qmap`` (with ``entropy_estimation``, instead of ``qstep``): a
+    quality map of the padded latent's size of every image, the rate estimate under that map"""
+    if qmap is not None and not entropy_estimation:
+        raise ValueError("eval_model: qmap is for the entropy estimation (the codec's map comes from codec.py --roi)")
     device = next(model.parameters()).device
     metrics: Dict[str, float] = defaultdict(float)
     for f in filepaths:
@@ -70,7 +73,8 @@ def eval_model(model, filepaths: List[str], entropy_estimation: bool = False, re
             raise ValueError(f"{f}: {x.shape[-1]}x{x.shape[-2]} is too small for MS-SSIM (both sides must exceed 160 "
                              "pixels: five levels of an 11-tap window)")
         rv = fn(model, x, recon=(lambda xh, name=os.path.basename(f): reconstruct(xh, name, recon_path)) if recon_path else None,
-                **({} if metric_names is None else {"metrics": metric_names}), **({"qstep": qstep} if qstep else {}))
+                **({} if metric_names is None else {"metrics": metric_names}), **({"qstep": qstep} if qstep else {}),
+                **({} if qmap is None else {"qmap": qmap}))
         for k, v in rv.items():
             metrics[k] += v
     return {k: v / len(filepaths) for k, v in metrics.items()}

@@ -9,6 +9,7 @@ from __future__ import annotations
 import math
 from typing import Dict, Optional
 
+import numpy as np
 import torch
 import torch.nn as nn
 
@@ -28,6 +29,15 @@ SCALES_MIN, SCALES_MAX, SCALES_LEVELS = 0.11, 256, 64
 
 def get_scale_table(min=SCALES_MIN, max=SCALES_MAX, levels=SCALES_LEVELS):
     return torch.exp(torch.linspace(math.log(min), math.log(max), levels))
+
+
+def _map_dims(qmap) -> int:
+    return qmap.dim() if torch.is_tensor(qmap) else np.asarray(qmap).ndim
+
+
+def _cat_outputs(outs):
+    return {"x_hat": torch.cat([o["x_hat"] for o in outs]),
+            "likelihoods": {name: torch.cat([o["likelihoods"][name] for o in outs]) for name in ("y", "z")}}
 
 
 class CompressionModel(nn.Module):
@@ -55,20 +65,50 @@ class CompressionModel(nn.Module):
     def forward(self, *args):
         raise NotImplementedError()
 
-    def _forward_each(self, x, qstep):
+    def _forward_each(self, x, qstep, qmap=None):
         """Eval mode with a step per image (``qstep`` a sequence or a tensor, more than one image): every image runs as
         its own batch of one and the results are concatenated -> the forward's dict, or None where this does not apply.
         The codec codes one image per stream, and the convolution plans are chosen by launch size, batch included, so
         only a batch of one gives image n the bits ``decompress(compress(x[n:n+1], qstep=K_n))`` gives it.  Training
-        (and ``Trainer``, which calls the slice loop itself) keeps the batch in one launch sequence."""
+        (and ``Trainer``, which calls the slice loop itself) keeps the batch in one launch sequence.
+        The same for a quality map per image, ``qmap`` [B, h, w].  A step and a map together: ValueError."""
+        if qmap is not None:
+            if E.qstep_indexes(qstep, x.shape[0]) is not None:
+                raise ValueError("forward: qstep and qmap are two forms of one thing; give one (a uniform map is its step)")
+            if self.training or _map_dims(qmap) != 3 or x.shape[0] < 2:
+                return None
+            if len(qmap) != x.shape[0]:
+                raise ValueError(f"forward: qmap holds {len(qmap)} maps for a batch of {x.shape[0]}")
+            return _cat_outputs([self(x[n:n + 1], qmap=qmap[n]) for n in range(x.shape[0])])
         if self.training or not E.qstep_per_image(qstep) or x.shape[0] < 2:
             return None
         ks = E.qstep_indexes(qstep, x.shape[0])
         if ks is None:
             return None
-        outs = [self(x[n:n + 1], qstep=k) for n, k in enumerate(ks)]
-        return {"x_hat": torch.cat([o["x_hat"] for o in outs]),
-                "likelihoods": {name: torch.cat([o["likelihoods"][name] for o in outs]) for name in ("y", "z")}}
+        return _cat_outputs([self(x[n:n + 1], qstep=k) for n, k in enumerate(ks)])
+
+    @staticmethod
+    def _forward_quality(x, qstep, qmap):
+        """(steps, maps) as the slice loop takes them, from what ``forward(x, qstep=, qmap=)`` was given; a map has
+        the size of the latent of ``x`` padded to a multiple of 64 (``_pad_eval_input``).  ``qmap``: one map [h, w] for the
+        batch, or (training, or a batch of one: ``_forward_each`` has taken the others) a map per image [B, h, w]; every
+        map is checked by ``bitstream.check_qmap``.  One map that is uniform is its scalar step."""
+        B, dev = x.shape[0], x.device
+        if qmap is None:
+            return E.qstep_steps(qstep, B, dev), None
+        hw = (-(-x.shape[2] // 64) * 4, -(-x.shape[3] // 64) * 4)
+        if _map_dims(qmap) == 3:
+            if len(qmap) != B:
+                raise ValueError(f"forward: qmap holds {len(qmap)} maps for a batch of {B}")
+            if B > 1:
+                maps = [check_qmap(m, hw, 0, "forward: ") for m in qmap]
+                return None, torch.from_numpy(np.stack(maps)).to(dev)
+            qmap = qmap[0]
+        qmap = check_qmap(qmap, hw, 0, "forward: ")
+        k = uniform_qmap(qmap)
+        if k is not None:
+            return E.qstep_steps(k, B, dev), None
+        return None, torch.from_numpy(qmap).to(dev).unsqueeze(0).expand(B, *hw).contiguous()
 
     def update(self, force=False):
         """models/base.py:43-60: refresh the CDF tables of every EntropyBottleneck child"""
@@ -202,18 +242,19 @@ SLICE_SPLIT = _os.environ.get("ICM_SLICE_SPLIT", "1") != "0"
 
 def hyper_slices(tape: E.Tape, P: Dict[str, torch.Tensor], y: torch.Tensor, noise_z, noise_y, num_slices: int,
                  max_support: int, keep: Optional[dict] = None, bucket_marks: Optional[dict] = None, coding=None,
-                 steps=None):
+                 steps=None, qmap=None):
     """Hyperprior + channel-conditional slice loop shared by the cnn and stf models
     (cnn.py:144-183 == stf.py:596-637) -> (y_hat, y_likelihoods, z_likelihoods), in the form SLICE_SPLIT names (read at
     call time).  coding: None (forward, training), or what compress() / decompress() code the slices with -- a
     ``slices.Encoder`` (y_likelihoods is None if its quantiser is fused) or a ``slices.Decoder`` (y is None, inference
     only, both likelihoods are None).  keep: a dict that receives the intermediates (``slices.epilogue``).
     steps (with coding None): the quantiser step of each image as ``engine.qstep_steps`` gives it -- likelihoods and
-    y_hat are then those of the codec at that step (``engine.gc_likelihood_ste``); z knows no step."""
-    if steps is not None and coding is not None:
+    y_hat are then those of the codec at that step (``engine.gc_likelihood_ste``); z knows no step.
+    qmap (likewise, instead of steps): a device int8 [N, h, w] tensor, a step index per image and latent position."""
+    if (steps is not None or qmap is not None) and coding is not None:
         raise ValueError("hyper_slices: a coding object carries its own quantiser; steps are for the forward pass")
     form = hyper_slices_split if SLICE_SPLIT else hyper_slices_unsplit
-    return form(tape, P, y, noise_z, noise_y, num_slices, max_support, keep, bucket_marks, coding, steps)
+    return form(tape, P, y, noise_z, noise_y, num_slices, max_support, keep, bucket_marks, coding, steps, qmap)
 
 
 def _quality(qstep, qmap, hw, who):
@@ -265,12 +306,12 @@ def _split_lik(tape, Y_lik, num_slices):
 
 def wacnn_forward(tape: E.Tape, P: Dict[str, torch.Tensor], x: torch.Tensor, noise_z=None, noise_y=None,
                   num_slices: int = 10, max_support: int = 5, keep: Optional[dict] = None,
-                  bucket_marks: Optional[dict] = None, steps=None):
+                  bucket_marks: Optional[dict] = None, steps=None, qmap=None):
     """WACNN.forward (models/cnn.py:141-189) on the HIP engine -> (x_hat, y_likelihoods, z_likelihoods).
-    steps: a quantiser step per image (``hyper_slices``)."""
+    steps: a quantiser step per image, or qmap: one per image and latent position (``hyper_slices``)."""
     y = wacnn_g_a(tape, P, x)
     Y_hat, Y_lik, z_lik = hyper_slices(tape, P, y, noise_z, noise_y, num_slices, max_support, keep, bucket_marks,
-                                       steps=steps)
+                                       steps=steps, qmap=qmap)
     x_hat = wacnn_g_s(tape, P, Y_hat)
     if tape.need_grad:
         _split_lik(tape, Y_lik, num_slices)
@@ -340,14 +381,15 @@ def _basic_layer(tape, P, p, t, depth, heads, ws, down, drops):
 
 def stf_forward(tape: E.Tape, P: Dict[str, torch.Tensor], x: torch.Tensor, noise_z=None, noise_y=None,
                 drops: Optional[Dict[str, torch.Tensor]] = None, num_slices: int = 12, max_support: int = 6,
-                window: int = 4, keep: Optional[dict] = None, bucket_marks: Optional[dict] = None, steps=None):
+                window: int = 4, keep: Optional[dict] = None, bucket_marks: Optional[dict] = None, steps=None,
+                qmap=None):
     """SymmetricalTransFormer.forward (models/stf.py:582-645) on the HIP engine.  Tokens stay NCHW end to end:
     [B, L, C] <-> [B, C, H, W] transposes of the reference vanish, Linear layers are 1x1 implicit GEMMs,
     LayerNorm normalises the channel axis per pixel.  drops: {"<layer>.blocks.<j>": [2,B] DropPath scales};
-    steps: a quantiser step per image (``hyper_slices``)."""
+    steps: a quantiser step per image, or qmap: one per image and latent position (``hyper_slices``)."""
     y = stf_analysis(tape, P, x, drops, window)
     Y_hat, Y_lik, z_lik = hyper_slices(tape, P, y, noise_z, noise_y, num_slices, max_support, keep, bucket_marks,
-                                       steps=steps)
+                                       steps=steps, qmap=qmap)
     x_hat = stf_synthesis(tape, P, Y_hat, drops, window)
     if tape.need_grad:
         _split_lik(tape, Y_lik, num_slices)
@@ -590,21 +632,25 @@ class WACNN(CompressionModel):
         """testing hook: {"z": [B,192,h/4,w/4], "y": [B,320,h,w]} U(-1/2,1/2) samples used in train mode"""
         self._noise = noise
 
-    def forward(self, x, qstep=None):
+    def forward(self, x, qstep=None, qmap=None):
         """``qstep``: None, or the step index k of a quantiser step 2^(k/8) on y -- an int, or a sequence / integer
         tensor of B of them, one per image (``engine.qstep_steps``).  The likelihoods of y are then the codec's at that
         step and, in eval mode on a 64-multiple input, x_hat.clamp(0, 1) is what ``decompress(compress(x, qstep=k))``
         returns, bit for bit -- of the whole batch for one k, of each image alone for a k per image (``_forward_each``);
-        in train mode the noise is added in symbol units (parity unpinned, like ``compress``)."""
+        in train mode the noise is added in symbol units (parity unpinned, like ``compress``).
+        ``qmap`` (instead of ``qstep``): a quality map, a 2-D integer array or tensor [h, w] of step indexes of the padded
+        latent's size, one map for the batch as in the codec (``bitstream.check_qmap``); in eval mode on a 64-multiple
+        input x_hat.clamp(0, 1) is ``decompress(compress(x, qmap=M), qmap=M)`` bit for bit, and a uniform map is its
+        scalar step.  [B, h, w]: a map per image, each image its own batch of one in eval mode."""
         if x.dim() != 4 or x.shape[1] != 3:
             raise ValueError("WACNN.forward expects [B,3,H,W]")
-        each = self._forward_each(x, qstep)
+        each = self._forward_each(x, qstep, qmap)
         if each is not None:
             return each
         names, params = _named(self)
         training = self.training
         dev = x.device
-        steps = E.qstep_steps(qstep, x.shape[0], dev)
+        steps, maps = self._forward_quality(x, qstep, qmap)
         x, pads = _pad_eval_input(x, training)
         nz = ny = None
         if training:
@@ -612,7 +658,7 @@ class WACNN(CompressionModel):
         ns, ms = self.num_slices, self.max_support_slices
 
         def runner(tape, xin, *ps):
-            return wacnn_forward(tape, dict(zip(names, ps)), xin, nz, ny, ns, ms, steps=steps)
+            return wacnn_forward(tape, dict(zip(names, ps)), xin, nz, ny, ns, ms, steps=steps, qmap=maps)
 
         x_hat, y_lik, z_lik = E.tape_function(runner, [x.contiguous(), *params], self._pack_cache())
         return {"x_hat": _crop_eval_output(x_hat, pads), "likelihoods": {"y": y_lik, "z": z_lik}}
@@ -843,16 +889,16 @@ class SymmetricalTransFormer(CompressionModel):
                 out[k] = d
         return out
 
-    def forward(self, x, qstep=None):
-        """``qstep``: as for ``WACNN.forward``"""
+    def forward(self, x, qstep=None, qmap=None):
+        """``qstep``, ``qmap``: as for ``WACNN.forward``"""
         if x.dim() != 4 or x.shape[1] != 3:
             raise ValueError("SymmetricalTransFormer.forward expects [B,3,H,W]")
-        each = self._forward_each(x, qstep)
+        each = self._forward_each(x, qstep, qmap)
         if each is not None:
             return each
         names, params = _named(self)
         dev = x.device
-        steps = E.qstep_steps(qstep, x.shape[0], dev)
+        steps, maps = self._forward_quality(x, qstep, qmap)
         x, pads = _pad_eval_input(x, self.training)
         nz = ny = drops = None
         if self.training:
@@ -862,7 +908,7 @@ class SymmetricalTransFormer(CompressionModel):
         ns, ms, ws = self.num_slices, self.max_support_slices, self.window_size
 
         def runner(tape, xin, *ps):
-            return stf_forward(tape, dict(zip(names, ps)), xin, nz, ny, drops, ns, ms, ws, steps=steps)
+            return stf_forward(tape, dict(zip(names, ps)), xin, nz, ny, drops, ns, ms, ws, steps=steps, qmap=maps)
 
         x_hat, y_lik, z_lik = E.tape_function(runner, [x.contiguous(), *params], self._pack_cache())
         return {"x_hat": _crop_eval_output(x_hat, pads), "likelihoods": {"y": y_lik, "z": z_lik}}
@@ -948,9 +994,11 @@ class SymmetricalTransFormer3(SymmetricalTransFormer):
                 out[k] = d
         return out
 
-    def forward(self, x, qstep=None):
+    def forward(self, x, qstep=None, qmap=None):
         if x.dim() != 4 or x.shape[1] != 3:
             raise ValueError("SymmetricalTransFormer3.forward expects [B,3,H,W]")
+        if qmap is not None:
+            raise ValueError("stf6 has no codec and so no quantiser step: it takes no quality map")
         if E.qstep_steps(qstep, x.shape[0], "cpu") is not None:
             raise ValueError("stf6 has no codec and so no quantiser step: qstep must be None or 0")
         if x.shape[2] % 128 or x.shape[3] % 128:

@@ -142,14 +142,15 @@ class Decoder:
         self.dec.close()
 
 
-def gaussian_step(tape, coding, i, sel, y, noise_y, Y_lik, mu, sc, yh_pre, steps=None):
+def gaussian_step(tape, coding, i, sel, y, noise_y, Y_lik, mu, sc, yh_pre, steps=None, qmap=None):
     """GaussianConditional + ste_round of slice i (cnn.py:170-173), the one such step of every loop: likelihoods ->
     Y_lik[sel] and y_hat_pre -> yh_pre from y[sel] (``sel`` indexes the slice in y, the noise and Y_lik), then whatever
     ``coding`` does with the slice.  A fused encoder and the decoder make no likelihood launch: they write yh_pre.
-    ``steps`` (forward and training, not with ``coding``): a quantiser step per image, ``engine.gc_likelihood_ste``."""
+    ``steps`` (forward and training, not with ``coding``): a quantiser step per image, ``engine.gc_likelihood_ste``;
+    ``qmap`` (likewise, instead of ``steps``): a step index per image and latent position."""
     if coding is None or coding.likelihoods:
         E.gc_likelihood_ste(tape, y[sel], mu, sc, None if noise_y is None else noise_y[sel], Y_lik[sel], yh_pre,
-                            steps=steps)
+                            steps=steps, qmap=qmap)
     if coding is not None:
         coding.slice(tape, i, None if y is None else y[sel], mu, sc, yh_pre)
 
@@ -226,7 +227,8 @@ def epilogue(tape, p, y, mu, scale, keep, bucket_marks):
 
 # ------------------------------------------------------------------------------------------------ the per-chain form
 def hyper_slices_unsplit(tape: E.Tape, P: Dict[str, torch.Tensor], y, noise_z, noise_y, num_slices: int,
-                         max_support: int, keep: Optional[dict], bucket_marks: Optional[dict], coding, steps=None):
+                         max_support: int, keep: Optional[dict], bucket_marks: Optional[dict], coding, steps=None,
+                         qmap=None):
     """torch.cat / chunk become channel-slice views of persistent support buffers: MS / SS hold the latent means / scales
     followed by the y_hat of the first max_support slices, LS of a slice its mean support followed by its y_hat_pre."""
     S, ms = num_slices, max_support
@@ -263,7 +265,7 @@ def hyper_slices_unsplit(tape: E.Tape, P: Dict[str, torch.Tensor], y, noise_z, n
                 tape.bind_grad(yh_pre, dLS[:, M + c * k:], True)
             _copy_op(tape, sup_m, LS[:, :M + c * k])
             gaussian_step(tape, coding, i, (slice(None), slice(i * c, (i + 1) * c)), y, noise_y, p.Y_lik, ts[j], ts[nt + j],
-                          yh_pre, steps)
+                          yh_pre, steps, qmap)
             LSs.append(LS)
             pres.append(yh_pre)
         outs = [Y_hat[:, i * c:(i + 1) * c] for i in idx]
@@ -323,7 +325,7 @@ def _block_grad(tape, w):
 
 
 def hyper_slices_split(tape: E.Tape, P: Dict[str, torch.Tensor], y, noise_z, noise_y, num_slices: int, max_support: int,
-                       keep: Optional[dict], bucket_marks: Optional[dict], coding, steps=None):
+                       keep: Optional[dict], bucket_marks: Optional[dict], coding, steps=None, qmap=None):
     """see module docstring"""
     S, ms = num_slices, max_support
     p = prologue(tape, P, y, noise_z, S, coding, bucket_marks)
@@ -495,7 +497,8 @@ def hyper_slices_split(tape: E.Tape, P: Dict[str, torch.Tensor], y, noise_z, noi
         chain_layers(tape, P, names, xvs, outs=outs)
         for i in idx:                                # GaussianConditional + ste_round: y_hat_pre -> YP, likelihoods -> Y_lik
             s1 = slice(i * c, (i + 1) * c)
-            gaussian_step(tape, coding, i, (slice(None), s1), y, noise_y, p.Y_lik, MU[:, s1], SC[:, s1], YP[:, s1], steps)
+            gaussian_step(tape, coding, i, (slice(None), s1), y, noise_y, p.Y_lik, MU[:, s1], SC[:, s1], YP[:, s1], steps,
+                          qmap)
         own_block(idx, k)
         lnames = [f"lrp_transforms.{i}" for i in idx]
         chain_layers(tape, P, lnames, [VT(pre[(i, 1)], ACT_GELU) for i in idx],

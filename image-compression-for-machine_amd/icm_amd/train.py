@@ -21,6 +21,10 @@ loss (:438), best-only checkpoints ``<save_path><epoch>.ckpt`` holding epoch / s
 * ``--qstep-range LO,HI`` trains one model across the codec's quantiser steps (``Trainer(qstep_range=...)``: a step per
   image and iteration, distortion weight ``lambda * step^-E``, ``--qstep-lambda-exp E``); the test loop then reports
   loss, bpp and mse at K = LO, 0 (if inside the range) and HI, and the checkpoint records ``qstep_range``;
+* ``--qmap-rects R`` (with ``--qstep-range``) trains with a quality map per image and iteration
+  (``Trainer(qmap_rects=R)``: R random rectangles over the drawn background, a step per latent position, a distortion
+  weight per 16 x 16 cell); the test loop adds one fixed pattern labelled ``roi`` (``roi_test_map``), the checkpoint
+  records ``qmap_rects`` and a resumed run without the flag keeps the checkpoint's;
 * checkpoints are read with ``weights_only=True``."""
 from __future__ import annotations
 
@@ -36,7 +40,7 @@ from torch.utils.data import DataLoader
 from .datasets import (CenterCrop, Compose, DeviceCacheLoader, DeviceImageCache, EpochSampler, ImageFolder, RandomCrop,
                        ToTensor)
 from .losses import METRICS, RateDistortionLoss
-from .trainer import Trainer, check_qstep_range, qstep_tables
+from .trainer import Trainer, check_qmap_rects, check_qstep_range, qstep_tables
 from .zoo import models
 
 
@@ -110,22 +114,41 @@ def qstep_test_points(qstep_range):
     return sorted({lo, hi} | ({0} if lo < 0 < hi else set()))
 
 
+def roi_test_map(h: int, w: int, lo: int, hi: int):
+    """the fixed pattern the test loop of a quality-map run reports as ``roi``: background HI, and at LO a centred
+    rectangle of half the map's height and width (rounded down, one cell at least) -> int8 [h, w] host array"""
+    import numpy as np
+    m = np.full((h, w), hi, dtype=np.int8)
+    rh, rw = max(h // 2, 1), max(w // 2, 1)
+    y0, x0 = (h - rh) // 2, (w - rw) // 2
+    m[y0:y0 + rh, x0:x0 + rw] = lo
+    return m
+
+
 @torch.no_grad()
 def qstep_test_epoch(epoch: int, test_dataloader, model, criterion, lmbda: float, lmbda_exp: float, qstep_range,
-                     verbose: bool = True) -> float:
+                     verbose: bool = True, qmap_rects: int = 0) -> float:
     """``test_epoch`` of a variable-rate run: loss, bpp and mse at every step index of ``qstep_test_points``, each with the
     weight training gives that step (``trainer.qstep_tables``); returns the mean of the points' losses, which is what
-    the learning-rate schedule and the best-checkpoint choice then see"""
+    the learning-rate schedule and the best-checkpoint choice then see.  With ``qmap_rects`` one more line, ``roi``: the
+    pattern of ``roi_test_map`` under the per-cell loss (it is reported, and stays out of the returned mean, so runs
+    with and without maps are compared by the same figure)"""
     model.eval()
     device = next(model.parameters()).device
     points = qstep_test_points(qstep_range)
     meters = {k: (AverageMeter(), AverageMeter(), AverageMeter()) for k in points}
     lam = {k: float(qstep_tables((k, k), lmbda, lmbda_exp)[1][0]) for k in points}
+    roi_meters = (AverageMeter(), AverageMeter(), AverageMeter())
     for d in test_dataloader:
         x = d.to(device)
         for k in points:
             out = criterion(model(x, qstep=k), x, lmbda_n=[lam[k]] * x.shape[0])
             for m, name in zip(meters[k], ("loss", "bpp_loss", "mse_loss")):
+                m.update(float(out[name]))
+        if qmap_rects:
+            roi = roi_test_map(x.shape[2] // 16, x.shape[3] // 16, qstep_range[0], qstep_range[1])
+            out = criterion(model(x, qmap=roi), x, qmap=roi, lmbda_exp=lmbda_exp)
+            for m, name in zip(roi_meters, ("loss", "bpp_loss", "mse_loss")):
                 m.update(float(out[name]))
     model.train()
     if verbose:
@@ -133,17 +156,25 @@ def qstep_test_epoch(epoch: int, test_dataloader, model, criterion, lmbda: float
             loss, bpp, mse = meters[k]
             print(f"Test epoch {epoch}: qstep {k}:\tLoss: {loss.avg:.3f} |\tMSE loss: {mse.avg * 255 ** 2:.3f} |"
                   f"\tBpp loss: {bpp.avg:.2f}", flush=True)
+        if qmap_rects:
+            loss, bpp, mse = roi_meters
+            print(f"Test epoch {epoch}: qstep roi:\tLoss: {loss.avg:.3f} |\tMSE loss: {mse.avg * 255 ** 2:.3f} |"
+                  f"\tBpp loss: {bpp.avg:.4f}", flush=True)
     return sum(meters[k][0].avg for k in points) / len(points)
 
 
 def checkpoint_state(epoch, state_dict, loss, optimizer, aux_optimizer, lr_scheduler, qstep_range=None,
-                     qstep_lmbda_exp=2.0) -> dict:
+                     qstep_lmbda_exp=2.0, qmap_rects=0) -> dict:
     """what a checkpoint holds (train.py:512-527); "qstep_range" is [lo, hi] of a variable-rate run and None otherwise
-    (a checkpoint without the key is a fixed-rate one)"""
-    return {"epoch": epoch, "state_dict": state_dict, "loss": loss, "optimizer": optimizer,
-            "aux_optimizer": aux_optimizer, "lr_scheduler": lr_scheduler,
-            "qstep_range": None if qstep_range is None else [int(k) for k in qstep_range],
-            "qstep_lambda_exp": float(qstep_lmbda_exp)}
+    (a checkpoint without the key is a fixed-rate one); "qmap_rects" is the rectangle count of a quality-map run, and
+    only such a run has the key"""
+    ck = {"epoch": epoch, "state_dict": state_dict, "loss": loss, "optimizer": optimizer,
+          "aux_optimizer": aux_optimizer, "lr_scheduler": lr_scheduler,
+          "qstep_range": None if qstep_range is None else [int(k) for k in qstep_range],
+          "qstep_lambda_exp": float(qstep_lmbda_exp)}
+    if qmap_rects:
+        ck["qmap_rects"] = int(qmap_rects)
+    return ck
 
 
 @torch.no_grad()
@@ -212,6 +243,10 @@ def parse_args(argv):
     p.add_argument("--qstep-lambda-exp", type=float, default=2.0, metavar="E",
                    help="exponent E of the per-step distortion weight (default: %(default)s, the high-rate "
                         "approximation D ~ step^2)")
+    p.add_argument("--qmap-rects", type=int, default=None, metavar="R",
+                   help="quality-map training (needs --qstep-range): R random rectangles per image, 0..8, each with its "
+                        "own step, over the drawn background; distortion weight per 16x16 cell (default: 0 = off, or "
+                        "what the --checkpoint resumed from records)")
     # "--qstep-range -8,16": argparse takes a value that begins with "-" and is no number for an option; hand it the
     # "--qstep-range=-8,16" form
     argv = list(argv)
@@ -226,6 +261,8 @@ def parse_args(argv):
             raise ValueError("--qstep-range: the MS-SSIM loss takes a scalar lambda (use --metric mse)")
         if args.qstep_range is not None and args.model == "stf6":
             raise ValueError("--qstep-range: stf6 has no codec and so no quantiser step")
+        if args.qmap_rects is not None and check_qmap_rects(args.qmap_rects) and args.qstep_range is None:
+            raise ValueError("--qmap-rects: quality-map training draws its step indexes from --qstep-range; give one")
     except ValueError as e:
         p.error(str(e))   # exit 2, like every other bad argument
     return args
@@ -307,9 +344,11 @@ def main(argv) -> int:
         ck = torch.load(args.checkpoint, map_location="cpu", weights_only=True)
         last_epoch = int(ck["epoch"]) + 1
         net.load_state_dict(ck["state_dict"])
+    if args.qmap_rects is None:   # a resumed quality-map run keeps its rectangle count
+        args.qmap_rects = int(ck.get("qmap_rects", 0) or 0) if ck is not None and args.qstep_range is not None else 0
     trainer = Trainer(net, lr=args.learning_rate, aux_lr=args.aux_learning_rate, lmbda=args.lmbda,
                       clip_max_norm=args.clip_max_norm, device=device, seed=int(args.seed or 0), metric=args.metric,
-                      qstep_range=args.qstep_range, qstep_lmbda_exp=args.qstep_lambda_exp)
+                      qstep_range=args.qstep_range, qstep_lmbda_exp=args.qstep_lambda_exp, qmap_rects=args.qmap_rects)
     lr_scheduler = PlateauLR(trainer, factor=0.6, patience=6)
     criterion = RateDistortionLoss(lmbda=args.lmbda, metric=args.metric)
     if ck is not None and "optimizer" in ck and isinstance(ck["optimizer"], dict) and "m" in ck["optimizer"]:
@@ -327,7 +366,8 @@ def main(argv) -> int:
         if epoch % args.test_every == 0:
             if args.qstep_range is not None:
                 loss = qstep_test_epoch(epoch, test_dataloader, trainer.model, criterion, args.lmbda,
-                                        args.qstep_lambda_exp, args.qstep_range, verbose=rank == 0)
+                                        args.qstep_lambda_exp, args.qstep_range, verbose=rank == 0,
+                                        qmap_rects=args.qmap_rects)
             else:
                 loss = test_epoch(epoch, test_dataloader, trainer.model, criterion, verbose=rank == 0)
             lr_scheduler.step(loss)
@@ -336,7 +376,8 @@ def main(argv) -> int:
             if args.save and is_best and rank == 0:
                 opt, aux = trainer.optimizer_state()
                 save_checkpoint(checkpoint_state(epoch, trainer.model.state_dict(), loss, opt, aux,
-                                                 lr_scheduler.state_dict(), args.qstep_range, args.qstep_lambda_exp),
+                                                 lr_scheduler.state_dict(), args.qstep_range, args.qstep_lambda_exp,
+                                                 args.qmap_rects),
                                 os.path.join(args.save_path, f"{epoch}.ckpt"))
     if world > 1:
         import torch.distributed as dist

@@ -26,6 +26,7 @@ from . import _lib as L
 from . import engine as E
 from ._lib import check, ptr
 from .bitstream import check_qstep, step_of
+from .losses import qmap_lmbda_table
 from .models import SymmetricalTransFormer, SymmetricalTransFormer3, stf6_forward, stf_forward, wacnn_forward
 
 # bucket -> parameter-name prefixes, in the order their gradients complete during backward
@@ -175,15 +176,63 @@ def qstep_tables(qstep_range, lmbda: float, lmbda_exp: float = 2.0) -> Tuple[tor
     return steps, lam.to(torch.float32)
 
 
+QMAP_RECTS_MAX = 8
+
+
+def check_qmap_rects(qmap_rects) -> int:
+    """the rectangle count of quality-map training: an integer in 0..QMAP_RECTS_MAX (ValueError otherwise)"""
+    if isinstance(qmap_rects, bool) or not isinstance(qmap_rects, int) and not hasattr(qmap_rects, "__index__"):
+        raise ValueError(f"qmap_rects must be an integer, got {qmap_rects!r}")
+    if not 0 <= int(qmap_rects) <= QMAP_RECTS_MAX:
+        raise ValueError(f"qmap_rects = {int(qmap_rects)} outside [0, {QMAP_RECTS_MAX}]")
+    return int(qmap_rects)
+
+
+def qmap_rects_of(u: torch.Tensor, h: int, w: int, lo: int, hi: int) -> torch.Tensor:
+    """The rectangles of a draw: ``u`` [..., 5] uniform on [0, 1) -> int32 [..., 5] = (y0, x0, y1, x1, k), in cells of an
+    h x w map, half open.  A pure function of its arguments that runs on the device of ``u``:
+        y0 = min(floor(u0 h), h - 1)        y1 = y0 + 1 + min(floor(u2 (h - y0)), h - y0 - 1)
+        x0 = min(floor(u1 w), w - 1)        x1 = x0 + 1 + min(floor(u3 (w - x0)), w - x0 - 1)
+        k  = lo + min(floor(u4 (hi - lo + 1)), hi - lo)
+    so every rectangle is non-empty and inside the map, the corner is uniform over the cells, the extent uniform over
+    what fits from there, and k uniform on lo..hi.  (The minima only matter where a float32 product rounds up to its
+    bound.)"""
+    u = u.to(torch.float32)
+
+    def cells(v, n):       # floor(v n) held to n - 1, as a float tensor of integers (exact: a map side is far below
+        c = torch.floor(v * n)                                                   # 2^24); n an int or such a tensor
+        return torch.minimum(c, n - 1) if torch.is_tensor(n) else c.clamp(max=n - 1)   # no constant goes to the device
+    y0, x0 = cells(u[..., 0], h), cells(u[..., 1], w)
+    y1 = y0 + 1 + cells(u[..., 2], h - y0)
+    x1 = x0 + 1 + cells(u[..., 3], w - x0)
+    k = lo + cells(u[..., 4], hi - lo + 1)
+    return torch.stack([y0, x0, y1, x1, k], dim=-1).to(torch.int32)
+
+
 class Trainer:
     def __init__(self, model, lr: float = 1e-4, aux_lr: float = 1e-4, lmbda: float = 0.0067,
                  clip_max_norm: float = 1.0, device="cuda:0", group=None, seed: int = 0, metric: str = "mse",
-                 qstep_range=None, qstep_lmbda_exp: float = 2.0):
+                 qstep_range=None, qstep_lmbda_exp: float = 2.0, qmap_rects: int = 0):
         """``qstep_range`` = (lo, hi): variable-rate training -- every step draws a quantiser step index per image,
         uniform on lo..hi, from this rank's device generator (after the noise and DropPath draws, whose order and
         values it leaves alone), and trains the entropy model and the transforms at that step
         (``engine.gc_likelihood_ste(steps=...)``) with the distortion weight lmbda * step^(-qstep_lmbda_exp) of that
-        image (``qstep_tables``).  None (default): today's step, launch for launch and draw for draw."""
+        image (``qstep_tables``).  None (default): today's step, launch for launch and draw for draw.
+        ``qmap_rects`` = R in 1..8 (with ``qstep_range``): quality-map training -- every image and step gets its own map
+        of step indexes over the latent positions.  The background is the index the step draws anyway (the same draw in
+        the same place); ONE further draw from the same generator, uniform [B, R, 5], gives R rectangles per image
+        (``qmap_rects_of``), painted in order over the background on the device (``icm_qmap_paint``).  The slice loop
+        then trains with a step per position (``engine.gc_likelihood_ste(qmap=...)``) and every 16 x 16 cell of pixels
+        weighs its distortion by lmbda * step^(-qstep_lmbda_exp) of its position (``icm_rd_loss_m_fwd/bwd``,
+        ``losses.qmap_lmbda_table``).  0 (default): the ``qstep_range`` step, launch for launch."""
+        self.qmap_rects = check_qmap_rects(qmap_rects)
+        if self.qmap_rects:
+            if qstep_range is None:
+                raise ValueError("qmap_rects: quality-map training draws its step indexes from qstep_range; give one")
+            if metric == "ms-ssim":
+                raise ValueError("qmap_rects: the MS-SSIM loss takes a scalar lmbda; per-cell weights are mse only")
+            if isinstance(model, SymmetricalTransFormer3):
+                raise ValueError("qmap_rects: stf6 has no codec and so no quantiser step")
         if metric not in ("mse", "ms-ssim"):
             raise NotImplementedError(f"{metric} is not implemented!")
         self.qstep_range, self.qstep_lmbda_exp = None, float(qstep_lmbda_exp)
@@ -235,6 +284,8 @@ class Trainer:
         if self.qstep_range is not None:   # built once; a step gathers from them on the device
             steps, lam = qstep_tables(self.qstep_range, lmbda, self.qstep_lmbda_exp)
             self._q_steps, self._q_lmbda = steps.to(self.device), lam.to(self.device)
+        if self.qmap_rects:
+            self._qm_lmbda = qmap_lmbda_table(lmbda, self.qstep_lmbda_exp).to(self.device)
 
     def params(self) -> Dict[str, torch.Tensor]:
         return self.flat.views
@@ -245,13 +296,22 @@ class Trainer:
         rows = torch.randint(0, self._q_lmbda.numel(), (B,), device=self.device, generator=self.gen)
         return rows, self._q_steps.index_select(0, rows), self._q_lmbda.index_select(0, rows)
 
+    def _draw_qmaps(self, B: int, h: int, w: int):
+        """(table rows [B] int64, base [B] int8, rects [B, R, 5] int32) of one quality-map step: the background index of
+        each image from the draw of ``_draw_qsteps``, then one more draw for the rectangles; all on the device"""
+        lo, hi = self.qstep_range
+        rows = torch.randint(0, self._q_lmbda.numel(), (B,), device=self.device, generator=self.gen)
+        u = torch.rand((B, self.qmap_rects, 5), dtype=torch.float32, device=self.device, generator=self.gen)
+        return rows, (rows + lo).to(torch.int8), qmap_rects_of(u, h, w, lo, hi)
+
     def step_graphed(self, x: torch.Tensor) -> torch.Tensor:
         """step(x) replayed from a captured hipGraph: one host call per iteration instead of ~1 000 (cnn) to ~8 000
         (stf6) launches issued through Python.  The first two calls per input shape run eagerly (they record the
         weight-packing sequence and set kernel attributes); the third captures.  What changes from step to step lives
         in device memory the graph reads: the input batch, the quantisation noise and DropPath scales (drawn outside the
         graph from this rank's generator, in the same order as step() draws them), with ``qstep_range`` the steps and
-        distortion weights of the images (drawn last, as in step()) and Adam's step-dependent scalars
+        distortion weights of the images (drawn last, as in step(); with ``qmap_rects`` the background indexes and the
+        rectangles instead, which the graph paints into its map buffer) and Adam's step-dependent scalars
         (icm_adam_step_hyper) -- so a replayed step equals the eager step bit for bit.  Single process only (the RCCL
         reductions are not captured); the side stream of the weight gradients is forked and joined inside the capture."""
         if self.world > 1:
@@ -279,8 +339,9 @@ class Trainer:
             for k, v in g["drops"].items():
                 v.copy_(fresh[k])
         if g["qsteps"] is not None:   # variable rate: the step's last draw, gathered into the buffers the graph reads
-            for buf, fresh in zip(g["qsteps"], self._draw_qsteps(B)):
-                buf.copy_(fresh)
+            fresh = self._draw_qmaps(B, H // 16, W // 16) if self.qmap_rects else self._draw_qsteps(B)
+            for buf, v in zip(g["qsteps"], fresh):   # (the map buffer, a fourth entry, is written by the graph)
+                buf.copy_(v)
         g["x"].copy_(x)
         g["graph"].replay()
         E.bump_weight_generation()
@@ -301,6 +362,11 @@ class Trainer:
         if self.qstep_range is not None:   # row 0 of the tables: valid steps for the capture run, replaced per replay
             rows = torch.zeros(B, dtype=torch.int64, device=dev)
             g["qsteps"] = (rows, self._q_steps.index_select(0, rows), self._q_lmbda.index_select(0, rows))
+        if self.qmap_rects:   # background and one-cell rectangles at lo for the capture run, replaced per replay
+            lo = self.qstep_range[0]
+            rects = torch.tensor([0, 0, 1, 1, lo], dtype=torch.int32, device=dev).repeat(B, self.qmap_rects, 1)
+            g["qsteps"] = (rows, torch.full((B,), lo, dtype=torch.int8, device=dev), rects.contiguous(),
+                           torch.zeros((B, H // 16, W // 16), dtype=torch.int8, device=dev))
         if self.is_stf:
             gen_state = self.gen.get_state()       # shapes / keys only: the capture must not consume random numbers
             g["drops"] = {k: v.clone() for k, v in self.model.draw_drops(B, dev, generator=self.gen).items()}
@@ -361,7 +427,8 @@ class Trainer:
         1 - ms_ssim with metric="ms-ssim" and 0 otherwise; loss is lmbda*255^2*mse + bpp or lmbda*(1 - ms_ssim) + bpp;
         with ``qstep_range`` it is 255^2 * mean_n(lmbda_n * mse_n) + bpp at the steps drawn, mse stays the plain mean).
         _hyper (step_graphed only): device tensors holding Adam's step-dependent scalars for the two optimisers;
-        _qsteps (step_graphed only): the (rows, steps, lmbda_n) buffers of ``_draw_qsteps`` the graph reads."""
+        _qsteps (step_graphed only): the (rows, steps, lmbda_n) buffers of ``_draw_qsteps`` the graph reads, or with
+        ``qmap_rects`` the (rows, base, rects) buffers of ``_draw_qmaps`` and the map buffer the graph paints."""
         f, dev = self.flat, self.device
         st = L.stream()
         lib = L.lib()
@@ -396,22 +463,36 @@ class Trainer:
         if self.is_stf and drops is None:   # stochastic depth, drawn per step like timm's DropPath (stf.py:145)
             drops = self.model.draw_drops(B, dev, generator=self.gen)
         # variable rate: the LAST draw of the step, so that the noise and the DropPath scales are those of a plain step
-        qs = None
-        if self.qstep_range is not None:
+        qs = maps = None
+        if self.qmap_rects:   # ... followed by the one draw of the rectangles; the maps are painted on the device
+            qs = _qsteps if _qsteps is not None else self._draw_qmaps(B, H // 16, W // 16)
+            maps = qs[3] if len(qs) > 3 else torch.empty((B, H // 16, W // 16), dtype=torch.int8, device=dev)
+            check(lib.icm_qmap_paint(ptr(qs[1]), ptr(qs[2]), self.qmap_rects, ptr(maps), B, H // 16, W // 16, st),
+                  "qmap_paint")
+        elif self.qstep_range is not None:
             qs = _qsteps if _qsteps is not None else self._draw_qsteps(B)
-        steps = None if qs is None else qs[1]
+        steps = None if qs is None or maps is not None else qs[1]
         if self.is_stf:
             drops = {k: v.to(dev, torch.float32).contiguous() for k, v in drops.items()}
             if self.is_stf6:   # zigzag blocks: iid noise, so any layout of the same draw is the same distribution
                 ny6 = ny if ny.dim() == 5 else ny.reshape(B, 24, 64, H // 32, W // 32)
                 x_hat, y_lik, z_lik = stf6_forward(tape, P, x, nz, ny6, drops, bucket_marks=marks)
             else:
-                x_hat, y_lik, z_lik = stf_forward(tape, P, x, nz, ny, drops, bucket_marks=marks, steps=steps)
+                x_hat, y_lik, z_lik = stf_forward(tape, P, x, nz, ny, drops, bucket_marks=marks, steps=steps,
+                                                  qmap=maps)
         else:
-            x_hat, y_lik, z_lik = wacnn_forward(tape, P, x, nz, ny, bucket_marks=marks, steps=steps)
+            x_hat, y_lik, z_lik = wacnn_forward(tape, P, x, nz, ny, bucket_marks=marks, steps=steps, qmap=maps)
         # ---- R-D loss forward + seeds (train.py:53-76)
         dxh, dly, dlz = E.new(x_hat), E.new(y_lik), E.new(z_lik)
-        if qs is not None:   # a distortion weight per image: the weighted pair of reductions
+        if maps is not None:   # a distortion weight per 16 x 16 cell: the map pair of reductions
+            tab = self._qm_lmbda
+            check(lib.icm_rd_loss_m_fwd(ptr(x), ptr(x_hat), B, 3, H, W, 16, ptr(maps), ptr(tab), ptr(y_lik),
+                                        y_lik.numel(), ptr(z_lik), z_lik.numel(), B * H * W, ptr(self.scal),
+                                        ptr(self.red_ws), st), "rd_loss_m_fwd")
+            check(lib.icm_rd_loss_m_bwd(ptr(x), ptr(x_hat), B, 3, H, W, 16, ptr(maps), ptr(tab), ptr(y_lik),
+                                        y_lik.numel(), ptr(z_lik), z_lik.numel(), B * H * W, 1.0, ptr(dxh), ptr(dly),
+                                        ptr(dlz), st), "rd_loss_m_bwd")
+        elif qs is not None:   # a distortion weight per image: the weighted pair of reductions
             lam = qs[2]
             check(lib.icm_rd_loss_w_fwd(ptr(x), ptr(x_hat), B, x[0].numel(), ptr(y_lik), y_lik.numel(), ptr(z_lik),
                                         z_lik.numel(), B * H * W, ptr(lam), ptr(self.scal), ptr(self.red_ws), st),
@@ -442,7 +523,10 @@ class Trainer:
                                      mws.numel(), st), "msssim_bwd")
         if self.keep_loss_seed:
             self.loss_seed = (x_hat.detach().clone(), dxh.clone())
-            if qs is not None:
+            if maps is not None:
+                self.loss_terms = {"y_lik": y_lik.detach().clone(), "z_lik": z_lik.detach().clone(),
+                                   "qstep": qs[0] + self.qstep_range[0], "qmap": maps.clone(), "rects": qs[2].clone()}
+            elif qs is not None:
                 self.loss_terms = {"y_lik": y_lik.detach().clone(), "z_lik": z_lik.detach().clone(),
                                    "qstep": qs[0] + self.qstep_range[0], "lmbda_n": qs[2].clone()}
         tape.bind_grad(x_hat, dxh, True)

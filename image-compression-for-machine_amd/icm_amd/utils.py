@@ -112,16 +112,20 @@ def inference(model, x: torch.Tensor, recon=None, metrics: Optional[Sequence[str
 
 @torch.no_grad()
 def inference_entropy_estimation(model, x: torch.Tensor, recon=None,
-                                 metrics: Optional[Sequence[str]] = None, qstep: int = 0) -> Dict[str, float]:
+                                 metrics: Optional[Sequence[str]] = None, qstep: int = 0,
+                                 qmap=None) -> Dict[str, float]:
     """eval_model/__main__.py:143-225: forward pass with estimated rates (no entropy coder); ``qstep``: the estimate
     at the codec's quantiser step of that index (``model.forward(x, qstep=...)``: the reconstruction is the one
-    ``inference(qstep=...)`` decodes, the rate the entropy of the symbols it codes; 0: none)"""
+    ``inference(qstep=...)`` decodes, the rate the entropy of the symbols it codes; 0: none); ``qmap`` (instead of
+    ``qstep``): the estimate under a quality map of the padded latent's size (``model.forward(x, qmap=...)``)"""
     qstep = check_qstep(qstep, "inference_entropy_estimation: ")
+    if qmap is not None and qstep:
+        raise ValueError("inference_entropy_estimation: qstep and qmap are two forms of one thing; give one")
     if x.dim() == 3:
         x = x.unsqueeze(0)
     xp, pads = pad_to_multiple(x, 64)
     t0 = time.time()
-    out = model(xp, qstep=qstep) if qstep else model(xp)
+    out = model(xp, qmap=qmap) if qmap is not None else model(xp, qstep=qstep) if qstep else model(xp)
     torch.cuda.synchronize() if x.is_cuda else None
     dt = time.time() - t0
     x_hat = crop(out["x_hat"], pads)

@@ -451,6 +451,34 @@ int icm_gc_likelihood_ste_qs_bwd(const float* y, int64_t y_bs, const float* mu, 
                                  int64_t dmu_bs, float* dscale, int64_t dsc_bs, int N, int C, int HW, float scale_bound,
                                  float lik_bound, int accum_dy, void* stream);
 
+/* The same pair with a step per (image, latent position) (quality-map training): `steps` is replaced by
+ *   qmap        [N][HW] int8, dense, DEVICE memory: a step index per image and position, shared by the channels;
+ *   step_table  the 256 (step, inv) pairs of icm_gc_code_qmap, indexed by the map byte read as unsigned.
+ * Per element the arithmetic is that of the _qs pair with the pair of the element's position: a map that is uniform
+ * over an image gives that image the _qs pair's bits, and y_hat is icm_gc_code_qmap's bit for bit.  No kernel clamps
+ * the map byte or branches on its validity: the caller checks maps.
+ * ICM_ERR_ARG before any launch, outputs untouched: what the _qs pair refuses, a null `qmap`, a null `step_table`
+ * (and N > 65535: an image is a workgroup row of the grid). */
+int icm_gc_likelihood_ste_qm_fwd(const float* y, int64_t y_bs, const float* mu, int64_t mu_bs, const float* scale,
+                                 int64_t sc_bs, const float* noise, int64_t nz_bs, const int8_t* qmap,
+                                 const float* step_table, float* lik, int64_t lik_bs, float* yh, int64_t yh_bs,
+                                 float* yh2, int64_t yh2_bs, int N, int C, int HW, float scale_bound, float lik_bound,
+                                 void* stream);
+int icm_gc_likelihood_ste_qm_bwd(const float* y, int64_t y_bs, const float* mu, int64_t mu_bs, const float* scale,
+                                 int64_t sc_bs, const float* noise, int64_t nz_bs, const int8_t* qmap,
+                                 const float* step_table, const float* dlik, int64_t dl_bs, const float* dyh,
+                                 int64_t dyh_bs, float* dy, int64_t dy_bs, float* dmu, int64_t dmu_bs, float* dscale,
+                                 int64_t dsc_bs, int N, int C, int HW, float scale_bound, float lik_bound, int accum_dy,
+                                 void* stream);
+
+/* Painting quality maps on the device (quality-map training), one launch: qmap [N][h][w] int8 (written); every cell of
+ * image n holds base[n] ([N] int8), then the R rectangles rects[n][r] = (y0, x0, y1, x1, k) ([N][R][5] int32; cells,
+ * half open) of image n are painted in order, later ones winning.  All three in DEVICE memory.  R = 0 paints the
+ * base alone (rects is still non-null); an empty rectangle paints nothing; a rectangle is clipped to the map; k and
+ * the coordinates are not range-checked otherwise.
+ * ICM_ERR_ARG before the launch: a null pointer, N, h or w < 1, R < 0 (and h * w > 2^30 or N > 65535). */
+int icm_qmap_paint(const int8_t* base, const int32_t* rects, int R, int8_t* qmap, int N, int h, int w, void* stream);
+
 /* ---- R-D loss (train.py:53-61, train_czigzag.py:63,71) --------------------------------------
  * out[0]=bpp, out[1]=mse, out[2]=loss, out[3]=sum log(lik_y), out[4]=sum log(lik_z) (5 floats, overwritten);
  * ws: ICM_REDUCE_WS_FLOATS floats of scratch (per-workgroup partial sums, added in workgroup order). */
@@ -474,6 +502,21 @@ int icm_rd_loss_w_fwd(const float* x, const float* x_hat, int N, int64_t img_ele
 int icm_rd_loss_w_bwd(const float* x, const float* x_hat, int N, int64_t img_elems, const float* lik_y, int64_t n_y,
                       const float* lik_z, int64_t n_z, int64_t num_pixels, const float* lmbda_n, float gscale,
                       float* dx_hat, float* dlik_y, float* dlik_z, void* stream);
+/* The same with a distortion weight per cell x cell block of pixels (quality-map training): x / x_hat are [N][C][H][W],
+ * qmap [N][H/cell][W/cell] int8 step indexes and lmbda_table 256 f32 weights indexed by the map byte read as unsigned,
+ * both in DEVICE memory.  With lmbda_i the table entry of the cell that holds pixel i:
+ *   out[2] = 255^2 * (sum_i lmbda_i * (x_hat_i - x_i)^2) / (N*C*H*W) + bpp;   out[1] the plain mse;
+ *   dx_hat_i = gscale * lmbda_i * 255^2 * 2 / (N*C*H*W) * (x_hat_i - x_i);   dlik as above.
+ * Sums are fixed-order (no float atomics: equal inputs give bit-identical results).  Every workgroup writes four
+ * partial sums to ws (plain and weighted squared error, the two log-likelihood sums), and every image has a workgroup
+ * at least, so ICM_ERR_ARG for 4 * N > ICM_REDUCE_WS_FLOATS; also for a null pointer, N, C, H, W or num_pixels < 1,
+ * cell < 1, H or W no multiple of cell, C * H > 2^30 -- all before any launch. */
+int icm_rd_loss_m_fwd(const float* x, const float* x_hat, int N, int C, int H, int W, int cell, const int8_t* qmap,
+                      const float* lmbda_table, const float* lik_y, int64_t n_y, const float* lik_z, int64_t n_z,
+                      int64_t num_pixels, float* out, float* ws, void* stream);
+int icm_rd_loss_m_bwd(const float* x, const float* x_hat, int N, int C, int H, int W, int cell, const int8_t* qmap,
+                      const float* lmbda_table, const float* lik_y, int64_t n_y, const float* lik_z, int64_t n_z,
+                      int64_t num_pixels, float gscale, float* dx_hat, float* dlik_y, float* dlik_z, void* stream);
 
 /* ---- MS-SSIM (Wang, Simoncelli, Bovik 2003; the defaults of pytorch_msssim.ms_ssim, which the reference's evaluation
  * CLI imports at compressai/utils/eval_model/__main__.py:32 and reports under the key "ms-ssim", :135) ------------
