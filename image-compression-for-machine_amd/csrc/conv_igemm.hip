@@ -17,6 +17,7 @@
 //   * pointwise neighbours are fused: operand activation on the LDS staging path (virtual GELU,
 //     x^2 for GDN) and the epilogues listed in icm_hip.h (bias, residual, GDN rsqrt, GELU', LRP tanh,
 //     PixelShuffle store, gradient accumulation), defined once for all conv kernels in conv_common.h.
+#include <climits>
 #include <cstdlib>
 #include <vector>
 #include "conv_common.h"
@@ -273,104 +274,130 @@ struct PackDesc {
   int dst_ncot, dst_cot_off;    // concatenation along GEMM-M: tiles per step of the destination, first tile of this job
   int wino;                     // 0: spatial taps; 1 / 2: Winograd F(2x2,3x3) weights U = G g G^T of the 3x3 kernel (2: of
                                 // the 180-degree rotated kernel = input-gradient orientation): 16 "taps" = transform points
+  int cg, ngroups;              // an item = (32-co tile, cg consecutive 8-ci chunks); ngroups = ceil(nchunks / cg)
+  int vec;                      // every source row of every item starts on a 16-byte boundary
   short tapidx[ICM_MAX_TAPS];
 };
 
-// One unit = (32-co tile, 8-ci chunk): the 8 x 32 x KHW source block is read with coalesced row segments into LDS
-// (row stride padded to an odd number of words: conflict-free transposed reads), then written out in fragment order
-// with one 16-byte store per lane per tap.  The canonical layouts differ only in which index is the contiguous row:
-// W[co][ci][khw] (src_out_major: 32 rows of 8*KHW) or W[ci][co][khw] (8 rows of 32*KHW).
-#define ICM_PACK_LDS (8 * 32 * ICM_MAX_TAPS + 64)
-__device__ __forceinline__ void pack_unit(const PackDesc& d, int cot, int chunk, float* lds) {
+// One item = one workgroup = (32-co tile, cg 8-ci chunks): the source block is read row by row into LDS (row stride
+// padded to an odd number of words), then written out in fragment order.  The canonical layouts differ only in which index
+// is the contiguous row: W[co][ci][khw] (src_out_major: 32 rows of 8*cg*KHW) or W[ci][co][khw] (8*cg rows of 32*KHW).
+//   * every row goes to 256 / rows threads: no division in the loop, 16-byte loads where the job's rows are aligned
+//     (dwords otherwise and for a row's last 1-3 floats), four (vector) or eight (dword) independent loads in flight;
+//   * thread p owns the weight pair (co = (p >> 2) & 31, ci = 2 (p & 3) + (p >> 7)) of each chunk: float p of the 1 KB
+//     fragment block of every tap, so a tap's block leaves as 256 consecutive dwords -- four per 16-byte fragment entry --
+//     and the Winograd transform of a pair is formed once, by its thread, from nine LDS reads;
+//   * nothing loops over items: a launch's items go to the hardware dispatcher one workgroup each, LDS sized by the
+//     launch's largest source block, so small and large jobs of one launch fill the CUs together.
+__host__ __device__ inline int pack_lds_floats(int cg, int KHW) { return 256 * cg * KHW + 32; }
+
+__device__ __forceinline__ float pack_nonneg(float x, float bound, float pedestal) {
+  x = fmaxf(x, bound);
+  x = x * x - pedestal;
+  return x;
+}
+
+// U[a][b] = sum_pq G[a][p] g[p][q] G[b][q],  G = [[1,0,0],[1/2,1/2,1/2],[1/2,-1/2,1/2],[0,0,1]]   (u[4 a + b]) of one
+// 3x3 kernel g (wino == 2: of the kernel rotated by 180 degrees).  Every product and sum is rounded on its own: with the
+// row and the column half in one expression tree the compiler would fuse 0.5 * x of the row half into the column sums.
+__device__ __forceinline__ void pack_wino_points(const float* g, int wino, float (&u)[16]) {
+#pragma clang fp contract(off)
+  float row[3][4];   // (g G^T)[p][b]
+#pragma unroll
+  for (int p = 0; p < 3; ++p) {
+    const float g0 = g[wino == 2 ? (2 - p) * 3 + 2 : p * 3 + 0];
+    const float g1 = g[wino == 2 ? (2 - p) * 3 + 1 : p * 3 + 1];
+    const float g2 = g[wino == 2 ? (2 - p) * 3 + 0 : p * 3 + 2];
+    row[p][0] = g0;
+    row[p][1] = 0.5f * ((g0 + g2) + g1);
+    row[p][2] = 0.5f * ((g0 + g2) - g1);
+    row[p][3] = g2;
+  }
+#pragma unroll
+  for (int b = 0; b < 4; ++b) {
+    u[0 * 4 + b] = row[0][b];
+    u[1 * 4 + b] = 0.5f * ((row[0][b] + row[2][b]) + row[1][b]);
+    u[2 * 4 + b] = 0.5f * ((row[0][b] + row[2][b]) - row[1][b]);
+    u[3 * 4 + b] = row[2][b];
+  }
+}
+
+__device__ __forceinline__ void pack_item(const PackDesc& d, int item, float* lds) {
   const int KHW = d.KHW, tid = threadIdx.x;
-  const int co0 = cot * 32, ci0 = chunk * 8;
-  int rows, rlen, rstride;
-  if (d.src_out_major) { rows = 32; rlen = 8 * KHW; } else { rows = 8; rlen = 32 * KHW; }
-  rstride = rlen | 1;
-  // batches of 8 independent loads per thread (a plain load -> LDS-store loop waits for every load before the next
-  // one is issued: 25 dependent round trips per 5x5 unit made the packing latency-bound at a fifth of its traffic rate)
-  const int total = rows * rlen;
-  for (int e0 = tid; e0 < total; e0 += 8 * (int)blockDim.x) {
-    float v[8];
-    int lo[8];
+  const int cot = item % d.ncot, grp = item / d.ncot;
+  const int co0 = cot * 32, chunk0 = grp * d.cg, ci0 = chunk0 * 8;
+  const int nch = min(d.cg, d.nchunks - chunk0);            // chunks of this item
+  const int som = d.src_out_major;
+  const int rows = som ? 32 : 8 * d.cg;                     // 8 or 32
+  const int lgt = rows == 32 ? 3 : 5, tpr = 1 << lgt;       // threads per row
+  const int rlen = som ? 8 * d.cg * KHW : 32 * KHW, rstride = rlen | 1;
+  {
+    const int r = tid >> lgt, c0 = tid & (tpr - 1);
+    const int outer = (som ? co0 : ci0) + r, inner0 = som ? ci0 : co0;
+    const bool rok = outer < (som ? d.Co : d.Ci);
+    const int len = rok ? min(som ? 8 * nch : 32, (som ? d.Ci : d.Co) - inner0) * KHW : 0;   // floats of the row that exist
+    const float* src = d.w + ((long long)outer * d.src_ld + d.src_off + inner0) * KHW;
+    float* dst = lds + r * rstride;
+    const int n4 = d.vec ? len >> 2 : 0;
+    for (int b = c0; b < n4; b += 4 * tpr) {
+      f32x4 v[4];
 #pragma unroll
-    for (int u = 0; u < 8; ++u) {
-      const int e = e0 + u * (int)blockDim.x;
-      v[u] = 0.0f;
-      lo[u] = -1;
-      if (e < total) {
-        const int r = e / rlen, c = e - r * rlen;
-        lo[u] = r * rstride + c;
-        if (d.src_out_major) {
-          const int co = co0 + r, ci = ci0 + c / KHW;
-          if (co < d.Co && ci < d.Ci) v[u] = d.w[((long long)co * d.src_ld + d.src_off + ci0) * KHW + c];
-        } else {
-          const int ci = ci0 + r, co = co0 + c / KHW;
-          if (ci < d.Ci && co < d.Co) v[u] = d.w[((long long)ci * d.src_ld + d.src_off + co0) * KHW + c];
+      for (int u = 0; u < 4; ++u)
+        if (b + u * tpr < n4) v[u] = *reinterpret_cast<const f32x4*>(src + 4 * (b + u * tpr));
+#pragma unroll
+      for (int u = 0; u < 4; ++u)
+        if (b + u * tpr < n4) {
+#pragma unroll
+          for (int i = 0; i < 4; ++i) dst[4 * (b + u * tpr) + i] = d.nonneg ? pack_nonneg(v[u][i], d.bound, d.pedestal) : v[u][i];
         }
-      }
     }
+    for (int b = 4 * n4 + c0; b < len; b += 8 * tpr) {
+      float v[8];
 #pragma unroll
-    for (int u = 0; u < 8; ++u) {
-      if (lo[u] >= 0) {
-        float x = v[u];
-        if (d.nonneg) {
-          x = fmaxf(x, d.bound);
-          x = x * x - d.pedestal;
-        }
-        lds[lo[u]] = x;
-      }
+      for (int u = 0; u < 8; ++u)
+        if (b + u * tpr < len) v[u] = src[b + u * tpr];
+#pragma unroll
+      for (int u = 0; u < 8; ++u)
+        if (b + u * tpr < len) dst[b + u * tpr] = d.nonneg ? pack_nonneg(v[u], d.bound, d.pedestal) : v[u];
     }
   }
   __syncthreads();
-  f32x4* out = reinterpret_cast<f32x4*>(d.wp);
-  for (int e = tid; e < d.ntaps * 64; e += blockDim.x) {
-    const int t = e >> 6, lane = e & 63;
-    const int col = lane & 31, hh = lane >> 5, k = d.tapidx[t];
-    f32x4 o;
+  const int col = (tid >> 2) & 31, cil = 2 * (tid & 3) + (tid >> 7);
+  const long long tstride = (long long)d.dst_ncot * 256;   // floats between the blocks of consecutive taps
+  for (int cc = 0; cc < nch; ++cc) {
+    const int cl = cc * 8 + cil;
+    const float* gsrc = som ? lds + col * rstride + cl * KHW : lds + cl * rstride + col * KHW;
+    const bool valid = (co0 + col < d.Co) && (ci0 + cl < d.Ci);   // padded rows / channels are exact zeros (also under nonneg)
+    float* out = d.wp + ((long long)(chunk0 + cc) * d.ntaps * d.dst_ncot + d.dst_cot_off + cot) * 256 + tid;
+    if (d.wino) {
+      float u[16];
+      pack_wino_points(gsrc, d.wino, u);
 #pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const int cil = 2 * j + hh;
-      const float* gsrc = d.src_out_major ? lds + col * rstride + cil * KHW : lds + cil * rstride + col * KHW;
-      float v;
-      if (d.wino) {
-        // U[a][b] = sum_pq G[a][p] g[p][q] G[b][q],  G = [[1,0,0],[1/2,1/2,1/2],[1/2,-1/2,1/2],[0,0,1]]   (t = 4 a + b)
-        const int wa = t >> 2, wb = t & 3;
-        float row[3];   // (g G^T)[p][wb]
-#pragma unroll
-        for (int p = 0; p < 3; ++p) {
-          const float g0 = gsrc[d.wino == 2 ? (2 - p) * 3 + 2 : p * 3 + 0];
-          const float g1 = gsrc[d.wino == 2 ? (2 - p) * 3 + 1 : p * 3 + 1];
-          const float g2 = gsrc[d.wino == 2 ? (2 - p) * 3 + 0 : p * 3 + 2];
-          row[p] = wb == 0 ? g0 : (wb == 3 ? g2 : (wb == 1 ? 0.5f * ((g0 + g2) + g1) : 0.5f * ((g0 + g2) - g1)));
-        }
-        v = wa == 0 ? row[0] : (wa == 3 ? row[2] : (wa == 1 ? 0.5f * ((row[0] + row[2]) + row[1]) : 0.5f * ((row[0] + row[2]) - row[1])));
-      } else {
-        v = gsrc[k];
-      }
-      const bool valid = (co0 + col < d.Co) && (ci0 + cil < d.Ci);
-      o[j] = valid ? v : 0.0f;   // padded rows / channels are exact zeros (also under the nonneg transform)
+      for (int t = 0; t < 16; ++t) out[t * tstride] = valid ? u[t] : 0.0f;
+    } else {
+      for (int t = 0; t < d.ntaps; ++t) out[t * tstride] = valid ? gsrc[d.tapidx[t]] : 0.0f;
     }
-    out[((long long)(chunk * d.ntaps + t) * d.dst_ncot + d.dst_cot_off + cot) * 64 + lane] = o;
   }
-  __syncthreads();
 }
 
 __global__ __launch_bounds__(256) void pack_weights_kernel(const PackDesc d) {
-  __shared__ float lds[ICM_PACK_LDS];
-  const int units = d.ncot * d.nchunks;
-  for (int u = blockIdx.x; u < units; u += gridDim.x) pack_unit(d, u % d.ncot, u / d.ncot, lds);
+  extern __shared__ float pack_lds[];
+  pack_item(d, blockIdx.x, pack_lds);
 }
 
 #define ICM_PACK_NB 24
 struct PackMulti {
   PackDesc g[ICM_PACK_NB];
+  int first[ICM_PACK_NB];   // first item of job i in the launch's flat item list (INT_MAX behind the last job)
 };
+static_assert(sizeof(PackMulti) <= 4096, "kernel arguments are passed by value");
 __global__ __launch_bounds__(256) void pack_weights_multi_kernel(const PackMulti m) {
-  __shared__ float lds[ICM_PACK_LDS];
-  const PackDesc& d = m.g[blockIdx.y];
-  const int units = d.ncot * d.nchunks;
-  for (int u = blockIdx.x; u < units; u += gridDim.x) pack_unit(d, u % d.ncot, u / d.ncot, lds);
+  extern __shared__ float pack_lds[];
+  const int item = blockIdx.x;
+  int job = 0;
+#pragma unroll
+  for (int i = 1; i < ICM_PACK_NB; ++i) job += item >= m.first[i];
+  pack_item(m.g[job], item - m.first[job], pack_lds);
 }
 
 // ---------------------------------------------------------------------------------- host planning
@@ -740,9 +767,16 @@ static PackDesc make_pack_desc(const icm_pack_job& J, const ConvClass& cls, long
   d.bound = J.bound; d.pedestal = J.pedestal;
   d.src_ld = J.src_ld > 0 ? J.src_ld : (J.src_out_major ? J.Cin : J.Cout); d.src_off = J.src_off;
   d.dst_ncot = J.dst_ncot > 0 ? J.dst_ncot : ncot; d.dst_cot_off = J.dst_cot_off; d.wino = J.wino;
+  d.cg = d.KHW == 1 ? 4 : 1;   // a 1x1 weight's item spans 32 input channels: 128-byte source rows in either layout
+  d.ngroups = cdiv(d.nchunks, d.cg);
+  // first float of a row = (outer * src_ld + src_off + a multiple of 8) * KHW
+  d.vec = (reinterpret_cast<uintptr_t>(J.w) & 15) == 0 && ((long long)d.src_ld * d.KHW) % 4 == 0 &&
+          ((long long)d.src_off * d.KHW) % 4 == 0;
   for (int t = 0; t < ntaps; ++t) d.tapidx[t] = (short)cls.taps[t].kidx;
   return d;
 }
+static int pack_items(const PackDesc& d) { return d.ncot * d.ngroups; }
+static size_t pack_lds_bytes(const PackDesc& d) { return sizeof(float) * pack_lds_floats(d.cg, d.KHW); }
 
 }  // namespace icm
 
@@ -832,7 +866,7 @@ int icm_pack_weights(const float* w, float* wp, int Cout, int Cin, int KH, int K
   for (const ConvClass& cls : build_classes(KH, KW, stride, pad, transposed)) {
     if (cls.taps.empty()) continue;
     const PackDesc d = make_pack_desc(J, cls, off);
-    hipLaunchKernelGGL(pack_weights_kernel, dim3(std::min(d.nchunks * d.ncot, 2048)), dim3(256), 0, (hipStream_t)stream, d);
+    hipLaunchKernelGGL(pack_weights_kernel, dim3(pack_items(d)), dim3(256), pack_lds_bytes(d), (hipStream_t)stream, d);
     ICM_CHECK_LAUNCH();
     off += class_packed_floats(Cin, d.ntaps, d.dst_ncot);
   }
@@ -846,8 +880,16 @@ int icm_pack_weights_batch(const icm_pack_job* jobs, int n, void* stream) {
   int nb = 0;
   auto flush = [&]() -> int {
     if (nb == 0) return ICM_OK;
-    for (int i = nb; i < ICM_PACK_NB; ++i) m.g[i] = m.g[0];
-    hipLaunchKernelGGL(pack_weights_multi_kernel, dim3(128, nb), dim3(256), 0, (hipStream_t)stream, m);
+    long long items = 0;
+    size_t lds = 0;
+    for (int i = 0; i < ICM_PACK_NB; ++i) {
+      m.first[i] = i < nb ? (int)items : INT_MAX;
+      if (i >= nb) continue;
+      items += pack_items(m.g[i]);
+      lds = std::max(lds, pack_lds_bytes(m.g[i]));
+    }
+    if (items > INT_MAX) return ICM_ERR_UNSUPPORTED;
+    hipLaunchKernelGGL(pack_weights_multi_kernel, dim3((unsigned)items), dim3(256), lds, (hipStream_t)stream, m);
     ICM_CHECK_LAUNCH();
     nb = 0;
     return ICM_OK;

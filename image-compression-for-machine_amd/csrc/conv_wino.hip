@@ -60,6 +60,48 @@ __device__ __forceinline__ void wino_finish(const WinoDesc& d, const ConvPtrs& P
   P.y[off] = v;
 }
 
+// Two horizontally adjacent output elements (off, off + 1) of one channel with 8-byte operand accesses; the caller has
+// checked that both exist and that off is even in 8-byte aligned operands.  Per element it is wino_finish: the same
+// epi_apply, the same order of bias, epilogue, accumulation and activation.
+typedef float f32x2 __attribute__((ext_vector_type(2)));
+template <int EPI>
+__device__ __forceinline__ void wino_finish2(const WinoDesc& d, const ConvPtrs& P, float v0, float v1, int co, long long off,
+                                             bool ok) {
+  if (!ok) return;
+  if (P.bias) {
+    const float b = P.bias[co];
+    v0 += b;
+    v1 += b;
+  }
+  f32x2 rv = {0.0f, 0.0f}, av = {0.0f, 0.0f};
+  if constexpr (epi_reads_res(EPI)) rv = *reinterpret_cast<const f32x2*>(P.res + off);
+  if constexpr (epi_reads_aux(EPI)) av = *reinterpret_cast<const f32x2*>(P.aux + off);
+  float s0, s1;
+  v0 = epi_apply<EPI>(v0, rv[0], av[0], s0);
+  v1 = epi_apply<EPI>(v1, rv[1], av[1], s1);
+  if constexpr (epi_writes_side(EPI))
+    if (P.y2) *reinterpret_cast<f32x2*>(P.y2 + off) = f32x2{s0, s1};
+  if (d.accum) {
+    const f32x2 old = *reinterpret_cast<const f32x2*>(P.y + off);
+    v0 += old[0];
+    v1 += old[1];
+  }
+  if constexpr (epi_may_gelu(EPI))
+    if (P.y2) {
+      // epi_materialise in its in-place form (y2 == y) turns the value into its activation and stores nothing
+      float g0 = v0, g1 = v1;
+      epi_materialise(g0, P.y, P.y, off, false);
+      epi_materialise(g1, P.y, P.y, off, false);
+      if (P.y2 == P.y) {
+        v0 = g0;
+        v1 = g1;
+      } else {
+        *reinterpret_cast<f32x2*>(P.y2 + off) = f32x2{g0, g1};
+      }
+    }
+  *reinterpret_cast<f32x2*>(P.y + off) = f32x2{v0, v1};
+}
+
 template <int TCO>
 __global__ __launch_bounds__(512, 2) void conv_wino_kernel(const WinoDesc d) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
@@ -351,7 +393,14 @@ __global__ __launch_bounds__(512, 2) void conv_wino8_kernel(const WinoDesc d) {
     const int qq = min((g >> 1) * 16 + xi0 + (g & 1), lastq);
     return wbase + qq * qstride;
   };
+  // V ring in the 128 KB the epilogue needs anyway.  AHEAD = 2 (four slots): the DMAs of step s + 2 are issued during
+  // step s, so the slot of step s + 1 landed and was published a step earlier and its first B fragment is read before the
+  // barrier that ends step s; slot (s + 2) & 3 was last read in step s - 2, two barriers ago for every wave.  AHEAD = 1
+  // (two slots): the next slot is published by the barrier itself, the first fragment is read behind it.  Measured per
+  // co-block width in the training step: four slots win for TCO 2 and 4 and lose 1 % for TCO 3.
+  constexpr int AHEAD = TCO == 3 ? 1 : 2, SLOTM = 2 * AHEAD - 1;
   dma(0, 0);
+  if (AHEAD == 2 && d.nsteps > 1) dma(1, 1);
   f32x4 aq[4][TCO];
 #pragma unroll
   for (int u = 0; u < 3; ++u)
@@ -359,18 +408,25 @@ __global__ __launch_bounds__(512, 2) void conv_wino8_kernel(const WinoDesc d) {
     for (int a = 0; a < TCO; ++a) aq[u][a] = *reinterpret_cast<const f32x4*>(wptr(min(u, nunits - 1)) + wl[a]);
   const int boff = xi0 * 256 + lane;
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  __syncthreads();   // step 0 landed
-  for (int s = 0; s < d.nsteps; ++s) {
-    if (s + 1 < d.nsteps) dma(s + 1, (s + 1) & 1);   // issued first: older than every weight load of this step
-    const float* vb = smem + (s & 1) * WINO_STEP_FLOATS + boff;
-    float bv[2][4];
+  __syncthreads();   // the first AHEAD steps landed
+  float bv[2][4];
+  if constexpr (AHEAD == 2) {
 #pragma unroll
-    for (int j = 0; j < 4; ++j) bv[0][j] = vb[j * 64];
+    for (int j = 0; j < 4; ++j) bv[0][j] = (smem + boff)[j * 64];
+  }
+  for (int s = 0; s < d.nsteps; ++s) {
+    if (s + AHEAD < d.nsteps) dma(s + AHEAD, (s + AHEAD) & SLOTM);   // issued first: older than every weight load of this step
+    const float* vb = smem + (s & SLOTM) * WINO_STEP_FLOATS + boff;
+    if constexpr (AHEAD == 1) {
+#pragma unroll
+      for (int j = 0; j < 4; ++j) bv[0][j] = vb[j * 64];
+    }
 #pragma unroll
     for (int u = 0; u < 4; ++u) {
       const int g = s * 4 + u;
-      if (u + 1 < 4) {
-        const float* nb = vb + ((u + 1) >> 1) * (16 * 256) + ((u + 1) & 1) * 256;
+      if (u + 1 < 4 || AHEAD == 2) {   // next unit's B fragment; behind the last unit, the first one of the next step's slot
+        const float* nb = u + 1 < 4 ? vb + ((u + 1) >> 1) * (16 * 256) + ((u + 1) & 1) * 256
+                                    : smem + ((s + 1) & SLOTM) * WINO_STEP_FLOATS + boff;
 #pragma unroll
         for (int j = 0; j < 4; ++j) bv[(u + 1) & 1][j] = nb[j * 64];
       }
@@ -383,11 +439,13 @@ __global__ __launch_bounds__(512, 2) void conv_wino8_kernel(const WinoDesc d) {
         aq[(u + 3) & 3][a] = *reinterpret_cast<const f32x4*>(sp + wl[a]);
       }
     }
-    // the DMAs of the next step are older than the 3 * TCO weight loads still in flight: wait for them only
+    // the DMAs issued in this step are older than the 3 * TCO weight loads still in flight: wait for them only.  This
+    // wave's LDS reads of slot s fed the MFMAs above; with four slots the read of slot s + 1 may cross the barrier, with
+    // two the barrier frees the slot that the next step's DMAs overwrite, so every LDS read is drained first.
     if constexpr (TCO == 4) asm volatile("s_waitcnt vmcnt(12)" ::: "memory");
     else if constexpr (TCO == 3) asm volatile("s_waitcnt vmcnt(9)" ::: "memory");
     else asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // this wave's LDS reads of the buffer are complete
+    if constexpr (AHEAD == 1) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();
   }
 
@@ -403,8 +461,14 @@ __global__ __launch_bounds__(512, 2) void conv_wino8_kernel(const WinoDesc d) {
   if (P.y2) P.y2 += (long long)n * d.y2_bs;
   if (P.res) P.res += (long long)n * d.res_bs;
   if (P.aux) P.aux += (long long)n * d.aux_bs;
-#pragma unroll
-  for (int a0 = 0; a0 < TCO; a0 += 2) {
+  // the two adjacent outputs of a lane leave as one 8-byte access when every element pair of every operand is 8-byte
+  // aligned: even W (plane, row and column offsets are then even), even batch strides, 8-byte aligned bases
+  const ConvPtrs& P0 = d.g[blockIdx.y];
+  const bool pair = ((d.W | d.y_bs | d.y2_bs | d.res_bs | d.aux_bs) & 1) == 0 &&
+                    ((reinterpret_cast<uintptr_t>(P0.y) | reinterpret_cast<uintptr_t>(P0.y2) |
+                      reinterpret_cast<uintptr_t>(P0.res) | reinterpret_cast<uintptr_t>(P0.aux)) & 7) == 0;
+  auto pass = [&](auto a0_tag) {   // (a constant, not a loop: both epilogue forms of every kind are too much to unroll)
+    constexpr int a0 = decltype(a0_tag)::value;
     __syncthreads();   // staging buffers / the previous pass are free
 #pragma unroll
     for (int al = 0; al < 2; ++al) {
@@ -438,19 +502,31 @@ __global__ __launch_bounds__(512, 2) void conv_wino8_kernel(const WinoDesc d) {
                           zb[((((al * 4 + rr) * 2 + 1) * 2 + cp) * 16 + e) * 64 + lane];
           const bool cok = nok && co < d.Cout;
           const long long base = (long long)co * HW + (long long)oy * d.W + ox;
+          float y0[2], y1[2];
 #pragma unroll
           for (int cp = 0; cp < 2; ++cp) {
-            const float y0 = (z[0][cp] + z[1][cp]) + z[2][cp];
-            const float y1 = (z[1][cp] - z[2][cp]) - z[3][cp];
-            const bool xok = cok && ox + cp < d.W;
-            wino_finish<EPI>(d, P, y0, co, base + cp, xok && oy < d.H);
-            wino_finish<EPI>(d, P, y1, co, base + d.W + cp, xok && oy + 1 < d.H);
+            y0[cp] = (z[0][cp] + z[1][cp]) + z[2][cp];
+            y1[cp] = (z[1][cp] - z[2][cp]) - z[3][cp];
+          }
+          if (pair) {   // even W: ox + 1 < W whenever ox < W
+            const bool xok = cok && ox < d.W;
+            wino_finish2<EPI>(d, P, y0[0], y0[1], co, base, xok && oy < d.H);
+            wino_finish2<EPI>(d, P, y1[0], y1[1], co, base + d.W, xok && oy + 1 < d.H);
+          } else {
+#pragma unroll
+            for (int cp = 0; cp < 2; ++cp) {
+              const bool xok = cok && ox + cp < d.W;
+              wino_finish<EPI>(d, P, y0[cp], co, base + cp, xok && oy < d.H);
+              wino_finish<EPI>(d, P, y1[cp], co, base + d.W + cp, xok && oy + 1 < d.H);
+            }
           }
         }
       }
     };
     EpiWino::dispatch(d.epi, finish_all);
-  }
+  };
+  pass(std::integral_constant<int, 0>{});
+  if constexpr (TCO > 2) pass(std::integral_constant<int, 2>{});
 }
 
 bool wino_supported(const icm_conv_args& a);
