@@ -22,6 +22,13 @@
 // elements: the grid is capped at one 256-thread workgroup per CU, which covers it in a few passes (measured: 19 us
 // for the fused kernel on the 786 432 elements of a 2048x3072 image's slice, against 45 us for the three launches it
 // replaces).
+//
+// Rate-distortion optimised quantisation (icm_gc_code_rdo) is the same fused launch with a choice of symbol, for the
+// scalar pair and for a quality map alike.  It runs on the map kernels' 3-D grid (x over HW, y over c, z over n) in
+// both forms, not on the flat grid above: a map is read by position, which the 3-D grid never divides out of a flat
+// index, the scalar form is the same loop with one pair for every position, and the 3-D grid is no slower (a kernel
+// trace has this kernel at 10.4 us on the slice above, where the flat grid's cap of 256 workgroups holds the scalar
+// kernel at 18.4 us), so a second copy of the decision on a flat grid would buy nothing.
 #include <algorithm>
 #include <cmath>
 #include "icm_common.h"
@@ -135,6 +142,67 @@ __global__ __launch_bounds__(256) void gc_code_qmap_kernel(const float* __restri
     }
   }
 }
+// ---- rate-distortion optimised quantisation: the encoder's fused launch with a choice between the nearest symbol s0
+// and its neighbour toward zero, s1 = s0 - sign(s0).  The coder tables say what each costs: `bits` has
+// the shape of the CDF table, bits[r][v] = 16 - log2(cdf[r][v + 1] - cdf[r][v]) in f32, built on the host
+// (icm_amd/bitstream.py: code_length_table), so nothing here is transcendental.  Per element, all f32, one rounding per
+// operation:
+//     u = (y - mu) * inv;  v_j = s_j - offsets[idx];  e_j = u - (float)s_j;  J_j = (w * (e_j * e_j)) + bits[idx][v_j]
+// and s1 is coded iff s0 != 0, both v_j lie in the table proper, 0 .. cdf_sizes[idx] - 3 (an escaped symbol is never
+// touched and none becomes one), and J1 < J0 strictly.  y_hat is yh_of of the symbol coded; idx does not depend on it,
+// so the decoder needs to know nothing.  symbol_of / index_of / yh_of are the ones above: with a weight so large that
+// J1 < J0 never holds, the outputs are gc_code_q_kernel's / gc_code_qmap_kernel's bit for bit.
+// Layout: the map kernels' 3-D grid for both forms (`qmap` null: the scalar pair for every position), with z the
+// image itself as in gc_qm_fwd_kernel (qm_grid: a codec batch is small, and with n fixed per workgroup the operand
+// offsets n * bs fold into the base pointers; with a loop over n the kernel spilled scalar registers).  The scalar
+// kernel's flat grid would have to divide the position out of the flat index to read a map; here the pair is read
+// once per position and held over the channels, and one kernel serves both.  Consecutive lanes on consecutive addresses in every operand.  Beside the
+// map kernel's traffic a lane reads offsets[idx] and cdf_sizes[idx] (64 rows: cache-resident) and, where both
+// candidates are in the table, two neighbouring entries of one bits row (a gather, mostly out of L2).  The row bound
+// is also held to cdf_stride - 2, so no table the caller passes makes a lane read outside `bits`.
+struct RdoTables {
+  const int* sizes; const int* offsets; const float* bits;
+  int stride;
+  float w;
+};
+
+__global__ __launch_bounds__(256) void gc_code_rdo_kernel(const float* __restrict__ y, const float* __restrict__ mu,
+                                                           const float* __restrict__ sc,
+                                                           const float* __restrict__ table, int ns, float bound,
+                                                           float step, float inv,
+                                                           const unsigned char* __restrict__ qmap,
+                                                           const float2* __restrict__ steps, const RdoTables t,
+                                                           int* __restrict__ sym, int* __restrict__ idx,
+                                                           float* __restrict__ yh, const QGeom g) {
+  const int n = blockIdx.z;
+  for (long long p = blockIdx.x * 256 + threadIdx.x; p < g.HW; p += gridDim.x * 256) {
+    const float2 si = qmap ? steps[qmap[p]] : make_float2(step, inv);   // x: step, y: inv
+    for (int c = blockIdx.y; c < g.C; c += gridDim.y) {
+      const long long r = (long long)c * g.HW + p;
+      const long long i = (long long)n * g.C * g.HW + r;
+      const float m = mu[n * g.mu_bs + r], yv = y[n * g.y_bs + r];
+      const float u = mul_rn(yv - m, si.y);
+      const int ix = index_of(sc[n * g.sc_bs + r], bound, si.y, table, ns);
+      int s = symbol_of(yv, m, si.y);
+      if (s != 0) {
+        const int s1 = s > 0 ? s - 1 : s + 1;
+        const int off = t.offsets[ix], ov = min(t.sizes[ix], t.stride) - 2;
+        const int v0 = s - off, v1 = s1 - off;   // |s| <= 2^30 and a table offset is small: no overflow
+        if (v0 >= 0 && v0 < ov && v1 >= 0 && v1 < ov) {
+          const float* row = t.bits + (long long)ix * t.stride;
+          const float e0 = add_rn(u, -(float)s), e1 = add_rn(u, -(float)s1);
+          const float j0 = add_rn(mul_rn(t.w, mul_rn(e0, e0)), row[v0]);
+          const float j1 = add_rn(mul_rn(t.w, mul_rn(e1, e1)), row[v1]);
+          if (j1 < j0) s = s1;
+        }
+      }
+      sym[i] = s;
+      idx[i] = ix;
+      yh[n * g.yh_bs + r] = yh_of(s, m, si.x);
+    }
+  }
+}
+
 __global__ __launch_bounds__(256) void gc_indexes_qmap_kernel(const float* __restrict__ sc,
                                                                const float* __restrict__ table, int ns, float bound,
                                                                const unsigned char* __restrict__ qmap,
@@ -355,6 +423,14 @@ static inline dim3 qmap_grid(int N, int C, int HW) {
   return dim3(gx, gy, gz);
 }
 
+// grid of the map pair of the training step and of the RDOQ kernel: qmap_grid's x and y, and z = n (a grid's z holds
+// 65 535)
+constexpr int QM_MAX_N = 65535;
+static inline dim3 qm_grid(int N, int C, int HW) {
+  const dim3 g = qmap_grid(1, C, HW);
+  return dim3(g.x, g.y, N);
+}
+
 extern "C" {
 
 int icm_gc_code_q(const float* y, int64_t y_bs, const float* mu, int64_t mu_bs, const float* scale, int64_t sc_bs,
@@ -400,6 +476,25 @@ int icm_gc_code_qmap(const float* y, int64_t y_bs, const float* mu, int64_t mu_b
   hipLaunchKernelGGL(gc_code_qmap_kernel, qmap_grid(N, C, HW), dim3(256), 0, (hipStream_t)stream, y, mu, scale,
                      scale_table, ns, scale_bound, (const unsigned char*)qmap, (const float2*)step_table, symbols,
                      indexes, yh, g);
+  ICM_CHECK_LAUNCH();
+  return ICM_OK;
+}
+
+int icm_gc_code_rdo(const float* y, int64_t y_bs, const float* mu, int64_t mu_bs, const float* scale, int64_t sc_bs,
+                    const float* scale_table, int ns, float scale_bound, float step, float inv, const int8_t* qmap,
+                    const float* step_table, const int32_t* cdfs, int cdf_stride, const int32_t* cdf_sizes,
+                    const int32_t* offsets, int ncdf, const float* bits, float w, int32_t* symbols, int32_t* indexes,
+                    float* yh, int64_t yh_bs, int N, int C, int HW, void* stream) {
+  if (!y || !mu || !scale || !scale_table || !symbols || !indexes || !yh) return ICM_ERR_ARG;
+  if (!cdfs || !cdf_sizes || !offsets || !bits) return ICM_ERR_ARG;
+  if ((qmap == nullptr) != (step_table == nullptr)) return ICM_ERR_ARG;
+  if (!step_ok(step) || !step_ok(inv) || !step_ok(w) || !dims_ok(N, C, HW)) return ICM_ERR_ARG;
+  if (ns < 1 || ns != ncdf || cdf_stride < 3 || N > QM_MAX_N) return ICM_ERR_ARG;
+  const QGeom g{y_bs, mu_bs, sc_bs, yh_bs, N, C, HW};
+  const RdoTables t{cdf_sizes, offsets, bits, cdf_stride, w};
+  hipLaunchKernelGGL(gc_code_rdo_kernel, qm_grid(N, C, HW), dim3(256), 0, (hipStream_t)stream, y, mu, scale,
+                     scale_table, ns, scale_bound, step, inv, (const unsigned char*)qmap, (const float2*)step_table, t,
+                     symbols, indexes, yh, g);
   ICM_CHECK_LAUNCH();
   return ICM_OK;
 }
@@ -456,13 +551,6 @@ int icm_gc_likelihood_ste_qs_bwd(const float* y, int64_t y_bs, const float* mu, 
   hipLaunchKernelGGL(gc_qs_bwd_kernel, dim3(qs_blocks((long long)N * C * HW)), dim3(256), 0, (hipStream_t)stream, d);
   ICM_CHECK_LAUNCH();
   return ICM_OK;
-}
-
-// grid of the map pair of the training step: qmap_grid's x and y, and z = n (a grid's z holds 65 535)
-constexpr int QM_MAX_N = 65535;
-static inline dim3 qm_grid(int N, int C, int HW) {
-  const dim3 g = qmap_grid(1, C, HW);
-  return dim3(g.x, g.y, N);
 }
 
 int icm_gc_likelihood_ste_qm_fwd(const float* y, int64_t y_bs, const float* mu, int64_t mu_bs, const float* scale,

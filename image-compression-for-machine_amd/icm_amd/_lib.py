@@ -89,7 +89,7 @@ SYMBOLS = [
     "icm_eb_table_bounds", "icm_eb_pmf_table", "icm_gc_table_centers", "icm_gc_pmf_table", "icm_gc_build_indexes",
     "icm_quantize", "icm_dequantize", "icm_clamp", "icm_pad2d",
     "icm_gc_code_q", "icm_gc_indexes_q", "icm_dequantize_q",
-    "icm_gc_code_qmap", "icm_gc_indexes_qmap", "icm_dequantize_qmap",
+    "icm_gc_code_qmap", "icm_gc_indexes_qmap", "icm_dequantize_qmap", "icm_gc_code_rdo",
     "icm_gc_likelihood_ste_qs_fwd", "icm_gc_likelihood_ste_qs_bwd", "icm_rd_loss_w_fwd", "icm_rd_loss_w_bwd",
     "icm_gc_likelihood_ste_qm_fwd", "icm_gc_likelihood_ste_qm_bwd", "icm_rd_loss_m_fwd", "icm_rd_loss_m_bwd",
     "icm_qmap_paint",
@@ -242,6 +242,8 @@ def lib():
         L.icm_gc_code_qmap.argtypes = [vp, i64, vp, i64, vp, i64, vp, i32, f32, vp, vp, vp, vp, vp, i64, i32, i32, i32, vp]
         L.icm_gc_indexes_qmap.argtypes = [vp, i64, vp, i32, f32, vp, vp, vp, i32, i32, i32, vp]
         L.icm_dequantize_qmap.argtypes = [vp, vp, i64, vp, vp, vp, i64, i32, i32, i32, vp]
+        L.icm_gc_code_rdo.argtypes = [vp, i64, vp, i64, vp, i64, vp, i32, f32, f32, f32, vp, vp, vp, i32, vp, vp, i32, vp,
+                                      f32, vp, vp, vp, i64, i32, i32, i32, vp]
         L.icm_clamp.argtypes = [vp, i64, f32, f32, vp]
         L.icm_pad2d.argtypes = [vp, i32, i32, i32, i32, vp, i32, i32, i32, i32, f32, vp]
         L.icm_image_workspace_bytes.argtypes = [i32, i32]

@@ -51,6 +51,9 @@ trailing bytes, a non-maximal run, a k outside the range or a single distinct k 
 what it was: a reader from before the map refuses a mapped stream there ("must be one byte", exit code 4 of the CLI).
 The kernels take a map byte as an index into a table of 256 (step, inv) pairs, ``step_table``, built from ``step_of``.
 
+Rate-distortion optimised quantisation (``check_rdoq``, ``code_length_table``) is the encoder's own business: it picks
+between two ordinary symbols per element, so nothing of it is stored and every stream above reads as it did.
+
 A tiled image is a second container with its own magic: a grid of independently coded tiles (``tile_grid`` below gives
 the grid), each of them one complete ``ICMB`` stream.  ``ICMB`` and ``unpack`` are unchanged by it, and each reader
 refuses the other's files for their magic.
@@ -107,6 +110,7 @@ an escape whose symbol does not fit int32 is an error.  The format costs about 4
 """
 from __future__ import annotations
 
+import math
 import struct
 import zlib
 from typing import Dict, List, Optional, Sequence, Tuple
@@ -278,6 +282,45 @@ def qstep_from_strings(strings: Sequence[bytes]) -> int:
     if k == 0:
         raise ValueError("bitstream: a stored qstep of 0 (a stream without a step has two strings)")
     return k
+
+
+# ------------------------------------------------------------------------------ rate-distortion optimised quantisation
+def check_rdoq(w, who: str = "") -> Optional[float]:
+    """The weight of the encoder's rate-distortion optimised quantisation: None (off) passes through; otherwise ``w``
+    must be a real number, not a bool, that is finite and > 0 once rounded to f32, and that f32 value comes back as a
+    Python float (what the kernel is given).  ValueError otherwise.  Nothing of it travels in a stream."""
+    if w is None:
+        return None
+    if isinstance(w, bool) or not isinstance(w, (int, float, np.integer, np.floating)):
+        raise ValueError(f"{who}rdoq must be a positive number, got {w!r}")
+    try:
+        v = struct.unpack("<f", struct.pack("<f", float(w)))[0]
+    except (OverflowError, struct.error):
+        v = math.inf
+    if not (math.isfinite(v) and v > 0.0):
+        raise ValueError(f"{who}rdoq must be finite and > 0 as an f32, got {w!r}")
+    return v
+
+
+def code_length_table(cdf, sizes) -> np.ndarray:
+    """The code lengths the entropy coder's tables imply, as the encoder's RDOQ kernel reads them: float32 of the shape
+    of ``cdf`` ([rows, stride], the quantised CDFs out of 2^16), bits[r][v] = f32(16 - log2(f64(cdf[r][v + 1] -
+    cdf[r][v]))) for v < sizes[r] - 2 -- the table proper without its escape bin -- and 0 elsewhere (never read).
+    Computed in float64 and rounded once.  Pure host code; ValueError for shapes that do not fit or a bin of no width."""
+    cdf = np.asarray(cdf)
+    sizes = np.asarray(sizes).reshape(-1)
+    if cdf.ndim != 2 or cdf.dtype.kind not in "iu" or sizes.dtype.kind not in "iu" or len(sizes) != cdf.shape[0]:
+        raise ValueError(f"bitstream: code_length_table takes integer CDFs [rows, stride] and a size per row, got "
+                         f"{cdf.dtype} {cdf.shape} and {sizes.dtype} {sizes.shape}")
+    if cdf.shape[0] and (int(sizes.min()) < 2 or int(sizes.max()) > cdf.shape[1]):
+        raise ValueError(f"bitstream: CDF sizes must lie in 2 .. {cdf.shape[1]}, the stride")
+    width = np.diff(cdf.astype(np.int64), axis=1)
+    inside = np.arange(cdf.shape[1] - 1)[None, :] < (sizes.astype(np.int64) - 2)[:, None]
+    if bool((width[inside] < 1).any()):
+        raise ValueError("bitstream: a CDF holds a bin of no width inside its table")
+    bits = np.zeros(cdf.shape, dtype=np.float32)
+    bits[:, :-1][inside] = (16.0 - np.log2(width[inside].astype(np.float64))).astype(np.float32)
+    return bits
 
 
 # ------------------------------------------------------------------------------------------------- quality map

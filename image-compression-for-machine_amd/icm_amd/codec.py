@@ -1,7 +1,7 @@
 """``python -m icm_amd.codec`` -- image file to bit-stream file and back, in two processes that share a checkpoint.
 
     python -m icm_amd.codec encode IMAGE -o FILE -a cnn -p CKPT [--tile N [--overlap M]] [--coder {host,lanes}]
-                                   [--qstep K | --target-bytes N | --target-bpp F] [--roi Y0,X0,H,W:D ...]
+                                   [--qstep K | --target-bytes N | --target-bpp F] [--roi Y0,X0,H,W:D ...] [--rdoq W]
     python -m icm_amd.codec decode FILE -o IMAGE.png -p CKPT [--reference IMAGE] [--region Y0,X0,H,W]
 
 Parity unpinned: no counterpart in the reference (upstream CompressAI's ``examples/codec.py`` is not in its tree).  The
@@ -36,7 +36,12 @@ that hold a pixel of the rectangle are coded with the step index K + D instead o
 range; later rectangles win.  K is ``--qstep``, the step a budget search finds (it runs over K as without rectangles,
 the map rebuilt per probe), or 0.  The per-position map travels in the stream (``icm_amd.bitstream``, "Quality map"),
 per tile in a tiled one, and ``decode`` needs no flag; rectangles that change no cell leave the file what it is without
-them.  Parity unpinned: no counterpart in the reference, whose own answer is a task loss at training time."""
+them.  Parity unpinned: no counterpart in the reference, whose own answer is a task loss at training time.
+
+``--rdoq W`` turns on rate-distortion optimised quantisation in the encoder: each latent element is coded as the nearest
+integer or, where W x the added squared error in quantiser steps is less than the bits the coder's tables say it saves,
+as its neighbour toward zero (``icm_gc_code_rdo`` in csrc/qstep.hip).  It combines with every other flag, changes
+nothing in the stream's format, and ``decode`` neither has nor needs a flag.  Parity unpinned."""
 from __future__ import annotations
 
 import argparse
@@ -181,12 +186,18 @@ def _pack_one(arch: str, fp: int, H: int, W: int, pads, enc: Dict, coder: str) -
     return B.pack(header, strings, coder=coder)
 
 
+def _rdoq_kw(rdoq) -> Dict:
+    """the keyword of ``compress`` / ``compress_latent`` for a checked RDOQ weight; none at all when it is off"""
+    return {} if rdoq is None else {"rdoq": rdoq}
+
+
 def _encode_one(model, arch: str, fp: int, u8: torch.Tensor, coder: str = "host",
-                symbols_per_wave: Optional[int] = None, qstep: int = 0, qmap=None) -> bytes:
+                symbols_per_wave: Optional[int] = None, qstep: int = 0, qmap=None,
+                rdoq: Optional[float] = None) -> bytes:
     H, W = u8.size(0), u8.size(1)
     pads = center_pads(H, W)
     enc = model.compress(image_u8_to_f32(u8, pads), coder=coder, symbols_per_wave=symbols_per_wave, qstep=qstep,
-                         qmap=qmap)
+                         qmap=qmap, **_rdoq_kw(rdoq))
     return _pack_one(arch, fp, H, W, pads, enc, coder)
 
 
@@ -274,12 +285,16 @@ def search_qstep(fits, lo: int = B.QSTEP_MIN, hi: int = B.QSTEP_MAX) -> Tuple[in
 @torch.no_grad()
 def encode_image_info(model, img, tile: Optional[int] = None, overlap: int = 0, coder: str = "host",
                       symbols_per_wave: Optional[int] = None, qstep: int = 0,
-                      max_bytes: Optional[int] = None, roi: Optional[Sequence] = None) -> Tuple[bytes, Dict]:
+                      max_bytes: Optional[int] = None, roi: Optional[Sequence] = None,
+                      rdoq: Optional[float] = None) -> Tuple[bytes, Dict]:
     """``encode_image`` with its outcome: (stream, {"qstep": k, "step": 2^(k/8), "probes": encodes made}); k is the
     background step.  With ``roi`` also "roi_cells", the number of latent cells (summed over the tiles) whose step
-    index differs from k, and "qmap_range": [smallest, largest step index in the maps]."""
+    index differs from k, and "qmap_range": [smallest, largest step index in the maps].  With ``rdoq`` also "rdoq", the
+    weight as the kernel took it."""
     B.check_coder(coder, "codec: ")
     qstep = B.check_qstep(qstep, "codec: ")
+    rdoq = B.check_rdoq(rdoq, "codec: ")
+    rd = _rdoq_kw(rdoq)
     if max_bytes is not None:
         if qstep != 0:
             raise ValueError("codec: give a quantiser step or a byte budget, not both")
@@ -317,9 +332,9 @@ def encode_image_info(model, img, tile: Optional[int] = None, overlap: int = 0, 
 
     if max_bytes is None:
         ms, extra = maps(qstep)
-        data = wrap([_encode_one(model, arch, fp, c, coder, symbols_per_wave, 0 if m is not None else qstep, m)
+        data = wrap([_encode_one(model, arch, fp, c, coder, symbols_per_wave, 0 if m is not None else qstep, m, rdoq)
                      for c, m in zip(crops, ms)])
-        return data, {"qstep": qstep, "step": B.step_of(qstep)[0], "probes": 1, **extra}
+        return data, {"qstep": qstep, "step": B.step_of(qstep)[0], "probes": 1, **extra, **rd}
     # encode to size: the analysis transform once per tile, then only the latent coder per probe; a probe is the very
     # container that would be written (headers, CRCs and the lanes coder's flushes included), and the answer is the
     # stream of its probe, not a second encode
@@ -333,7 +348,7 @@ def encode_image_info(model, img, tile: Optional[int] = None, overlap: int = 0, 
         ms, extra = maps(k)
         data = wrap([_pack_one(arch, fp, h, w, pads,
                                model.compress_latent(y, coder=coder, symbols_per_wave=symbols_per_wave,
-                                                     qstep=0 if m is not None else k, qmap=m), coder)
+                                                     qstep=0 if m is not None else k, qmap=m, **rd), coder)
                      for (h, w, pads, y), m in zip(tiles, ms)])
         sizes[k] = len(data)
         if len(data) <= max_bytes:
@@ -347,12 +362,12 @@ def encode_image_info(model, img, tile: Optional[int] = None, overlap: int = 0, 
     except ValueError:
         raise ValueError(f"codec: {max_bytes} bytes are out of reach: the coarsest step (qstep {B.QSTEP_MAX}) still "
                          f"takes {min(sizes.values())} bytes")
-    return kept[k][0], {"qstep": k, "step": B.step_of(k)[0], "probes": probes, **kept[k][1]}
+    return kept[k][0], {"qstep": k, "step": B.step_of(k)[0], "probes": probes, **kept[k][1], **rd}
 
 
 def encode_image(model, img, tile: Optional[int] = None, overlap: int = 0, coder: str = "host",
                  symbols_per_wave: Optional[int] = None, qstep: int = 0, max_bytes: Optional[int] = None,
-                 roi: Optional[Sequence] = None) -> bytes:
+                 roi: Optional[Sequence] = None, rdoq: Optional[float] = None) -> bytes:
     """8-bit [H, W, 3] image (tensor on any device, or anything ``numpy.asarray`` accepts) -> one bit-stream.  With
     ``tile``, an image of more than one tile (``plan_tiles``) becomes an ICMT stream whose tile k is
     ``encode_image(model, crop k)``, the tiles coded one after another; an image of one tile is written untiled.
@@ -364,8 +379,11 @@ def encode_image(model, img, tile: Optional[int] = None, overlap: int = 0, coder
     ``roi``: regions of interest [(y0, x0, h, w, d), ...], rectangles of image pixels inside the image, each with an
     integer offset d to the background step index (negative: finer): the latent cells they touch are coded with
     clamp(k + d) (``roi_map``), k being ``qstep`` or the step the search finds; the map travels in the stream, per
-    tile in a tiled one.  No rectangle, or none that changes a cell, gives byte for byte the stream without ``roi``."""
-    return encode_image_info(model, img, tile, overlap, coder, symbols_per_wave, qstep, max_bytes, roi)[0]
+    tile in a tiled one.  No rectangle, or none that changes a cell, gives byte for byte the stream without ``roi``.
+    ``rdoq``: weight of rate-distortion optimised quantisation (``model.compress``; None, the default: off, and the
+    stream is what it is without).  Every tile and, with ``max_bytes``, every probe of the unchanged search is coded
+    with it.  The stream says nothing of it and decodes as any other."""
+    return encode_image_info(model, img, tile, overlap, coder, symbols_per_wave, qstep, max_bytes, roi, rdoq)[0]
 
 
 def _check_model(header: Dict, arch: str, fp: int, what: str = "the stream") -> None:
@@ -562,6 +580,10 @@ def setup_args() -> argparse.ArgumentParser:
     enc.add_argument("--roi", default=None, type=_roi, action="append", metavar="Y0,X0,H,W:D",
                      help="region of interest, repeatable: the latent cells this rectangle of image pixels touches are "
                           "coded with the step index K + D (D < 0: finer), K the background step; later ones win")
+    enc.add_argument("--rdoq", default=None, type=float, metavar="W",
+                     help="rate-distortion optimised quantisation: code a latent element one symbol nearer zero where "
+                          "W x the added squared error (in quantiser steps) is less than the bits it saves; W > 0, "
+                          "smaller: smaller file (default: off)")
     for s in (enc, dec):
         s.add_argument("-o", "--output", required=True, help="file to write")
         s.add_argument("-p", "--path", dest="paths", required=True, type=str, help="checkpoint path")
@@ -602,6 +624,7 @@ def main(argv) -> int:
                 raise ValueError(f"--target-bytes must be at least 1, got {args.target_bytes}")
             if args.target_bpp is not None and not (args.target_bpp > 0 and math.isfinite(args.target_bpp)):
                 raise ValueError(f"--target-bpp must be a positive number, got {args.target_bpp}")
+            B.check_rdoq(args.rdoq, "--")
         except ValueError as e:
             print(f"Error: {e}", file=sys.stderr)
             return 2
@@ -639,7 +662,7 @@ def main(argv) -> int:
             h, w = payload.shape[:2]
             budget = args.target_bytes if args.target_bpp is None else int(math.floor(args.target_bpp * h * w / 8))
             data, found = encode_image_info(model, payload, args.tile, args.overlap, coder=args.coder,
-                                            qstep=args.qstep or 0, max_bytes=budget, roi=args.roi)
+                                            qstep=args.qstep or 0, max_bytes=budget, roi=args.roi, rdoq=args.rdoq)
             torch.cuda.synchronize()
             dt = time.perf_counter() - t0
             with open(args.output, "wb") as f:

@@ -1331,9 +1331,14 @@ class Quantiser:
     ``code`` is the encoder's side, ``indexes`` and ``dequantize`` the decoder's, before and after the entropy decoder's
     run; ``st`` is the stream to launch on.  Symbols and indexes are dense int32 tensors of the slice's shape.
     ``fused``: ``code`` is ONE launch that also writes y_hat_pre = symbols * step + mu, the decoder's bit for bit, so the
-    encoder makes no likelihood launch (compress() never reads the likelihoods)."""
+    encoder makes no likelihood launch (compress() never reads the likelihoods).
 
-    def __init__(self, gc, qstep: int = 0, qmap: Optional[torch.Tensor] = None):
+    ``rdoq``: None, or the weight of rate-distortion optimised quantisation as ``bitstream.check_rdoq`` returns it.  With
+    a weight, ``code`` of all three kinds is the one launch of ``icm_gc_code_rdo`` (kind "none" with the pair (1, 1)),
+    which codes an element one symbol nearer zero where the coder's own tables say that pays, and ``fused`` is true.
+    The symbols stay ordinary symbols: ``indexes`` and ``dequantize``, the decoder's side, are what they are without."""
+
+    def __init__(self, gc, qstep: int = 0, qmap: Optional[torch.Tensor] = None, rdoq: Optional[float] = None):
         self.gc, self._table = gc, None
         # _kind: suffix of the three entry points; _steps: what each of them (code, indexes, dequantize) takes as its step
         if qmap is not None:
@@ -1346,6 +1351,15 @@ class Quantiser:
             self._kind = None
             self.code, self.indexes, self.dequantize = self._code_plain, self._indexes_plain, self._dequantize_plain
         self.fused = self._kind is not None
+        if rdoq is not None:
+            gc._check_tables()          # the decision reads the coder's tables: they must exist before the first slice
+            # _rdo_steps: (step, inv, qmap, step table) of icm_gc_code_rdo; a map overrides the pair per position
+            if qmap is not None:
+                self._rdo_steps = lambda H, W, dev: (1.0, 1.0, _qmap_ptr(qmap, H, W), ptr(qmap_step_table(dev)))
+            else:
+                pair = step_of(qstep) if qstep else (1.0, 1.0)
+                self._rdo_steps = lambda H, W, dev: (*pair, 0, 0)
+            self._w, self._rdo_tables, self.code, self.fused = float(rdoq), None, self._code_rdo, True
 
     def _entry(self, name):
         return getattr(L.lib(), name + self._kind)
@@ -1379,6 +1393,21 @@ class Quantiser:
         N, Cc, H, W = mu.shape
         check(self._entry("icm_dequantize")(sym.data_ptr(), ptr(mu), bs(mu), *self._steps(H, W, mu.device)[2],
                                             ptr(yh_out), bs(yh_out), N, Cc, H * W, st), "dequantize" + self._kind)
+
+    # ---- any kind, with rate-distortion optimised quantisation
+    def _code_rdo(self, st, y, mu, sc, yh_out):
+        N, Cc, H, W = y.shape
+        sym, idx, table = _int32_like(y), _int32_like(y), self._scale_table(y.device)
+        if self._rdo_tables is None:        # once per call of compress(): (tensors kept alive, the entry point's arguments)
+            keep = (*self.gc._device_tables(), self.gc._code_lengths())
+            cdf, sizes, offsets, bits = keep
+            self._rdo_tables = (keep, (cdf.data_ptr(), int(cdf.shape[1]), sizes.data_ptr(), offsets.data_ptr(),
+                                       int(cdf.shape[0]), bits.data_ptr()))
+        check(L.lib().icm_gc_code_rdo(ptr(y), bs(y), ptr(mu), bs(mu), ptr(sc), bs(sc), ptr(table), int(table.numel()),
+                                      self.gc._scale_bound, *self._rdo_steps(H, W, y.device), *self._rdo_tables[1],
+                                      self._w, sym.data_ptr(), idx.data_ptr(), ptr(yh_out), bs(yh_out), N, Cc, H * W, st),
+              "gc_code_rdo")
+        return sym, idx
 
     # ---- none
     def _code_plain(self, st, y, mu, sc, yh_out):

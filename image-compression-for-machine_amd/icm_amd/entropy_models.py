@@ -137,13 +137,27 @@ class EntropyModel(nn.Module):
             if t.dim() != ndim:
                 raise ValueError(f"Invalid {name} size {t.size()}")
 
+    def _table_key(self):
+        return (getattr(self, "_tab_gen", 0), self._quantized_cdf.data_ptr(), self._quantized_cdf._version,
+                tuple(self._quantized_cdf.shape), self._offset.data_ptr(), self._cdf_length.data_ptr())
+
+    def _code_lengths(self):
+        """``bitstream.code_length_table`` of the coder tables on their device (f32, the shape of ``_quantized_cdf``):
+        what the encoder's RDOQ kernel reads.  Built on the host and uploaded once, kept under the key of ``_tables()``."""
+        from .bitstream import code_length_table
+        key = self._table_key()
+        if getattr(self, "_bits_key", None) != key:
+            bits = code_length_table(self._quantized_cdf.detach().cpu().numpy(), self._cdf_length.detach().cpu().numpy())
+            self._bits = torch.from_numpy(bits).to(self._quantized_cdf.device).contiguous()
+            self._bits_key = key
+        return self._bits
+
     def _tables(self):
         """host copies of the coder tables, cached until the buffers change"""
         from .ans import _Tables
         # keyed on a counter that update() / load_state_dict() bump, plus the buffers' identity: the caching allocator can
         # hand a freed block back, so (data_ptr, _version, shape) alone would serve stale tables after update(force=True)
-        key = (getattr(self, "_tab_gen", 0), self._quantized_cdf.data_ptr(), self._quantized_cdf._version,
-               tuple(self._quantized_cdf.shape), self._offset.data_ptr(), self._cdf_length.data_ptr())
+        key = self._table_key()
         if getattr(self, "_tab_key", None) != key:
             self._tab = _Tables(self._quantized_cdf.detach().cpu().numpy(), self._cdf_length.detach().cpu().numpy(),
                                 self._offset.detach().cpu().numpy())
@@ -196,10 +210,11 @@ class EntropyModel(nn.Module):
         return self.dequantize(sym, means)
 
     def _invalidate_tables(self):
-        """drop the host copies of the coder tables (called by every update() and by load_state_dict)"""
+        """drop the host copies of the coder tables and the code lengths made from them (called by every update() and by
+        load_state_dict)"""
         self._tab_gen = getattr(self, "_tab_gen", 0) + 1
-        self._tab_key = None
-        self._tab = None
+        self._tab_key = self._bits_key = None
+        self._tab = self._bits = None
 
     def _load_from_state_dict(self, *args, **kwargs):
         self._invalidate_tables()

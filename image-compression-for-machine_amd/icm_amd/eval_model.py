@@ -20,7 +20,7 @@ from typing import Dict, List
 import torch
 
 from . import utils as U
-from .bitstream import check_qstep
+from .bitstream import check_qstep, check_rdoq
 from .datasets import IMG_EXTENSIONS, ToTensor, to_pil_image
 from .zoo import models
 
@@ -57,11 +57,15 @@ def load_checkpoint(arch: str, checkpoint_path: str) -> torch.nn.Module:
 
 @torch.no_grad()
 def eval_model(model, filepaths: List[str], entropy_estimation: bool = False, recon_path: str = "",
-               metric_names=None, qstep: int = 0, qmap=None) -> Dict[str, float]:
+               metric_names=None, qstep: int = 0, qmap=None, rdoq=None) -> Dict[str, float]:
     """eval_model/__main__.py:472-487 (per-image metrics averaged over the folder); ``qstep``: the codec's quantiser
     step index, for the real codec (``utils.inference``) and for the estimate
     (``utils.inference_entropy_estimation``) alike; ``qmap`` (with ``entropy_estimation``, instead of ``qstep``): a
-    quality map of the padded latent's size of every image, the rate estimate under that map"""
+    quality map of the padded latent's size of every image, the rate estimate under that map; ``rdoq`` (real codec
+    only): weight of the encoder's rate-distortion optimised quantisation (``utils.inference``)"""
+    rdoq = check_rdoq(rdoq, "eval_model: ")
+    if rdoq is not None and entropy_estimation:
+        raise ValueError("eval_model: rdoq needs the real codec: the entropy estimation's kernels know no RDOQ")
     if qmap is not None and not entropy_estimation:
         raise ValueError("eval_model: qmap is for the entropy estimation (the codec's map comes from codec.py --roi)")
     device = next(model.parameters()).device
@@ -74,7 +78,7 @@ def eval_model(model, filepaths: List[str], entropy_estimation: bool = False, re
                              "pixels: five levels of an 11-tap window)")
         rv = fn(model, x, recon=(lambda xh, name=os.path.basename(f): reconstruct(xh, name, recon_path)) if recon_path else None,
                 **({} if metric_names is None else {"metrics": metric_names}), **({"qstep": qstep} if qstep else {}),
-                **({} if qmap is None else {"qmap": qmap}))
+                **({} if qmap is None else {"qmap": qmap}), **({} if rdoq is None else {"rdoq": rdoq}))
         for k, v in rv.items():
             metrics[k] += v
     return {k: v / len(filepaths) for k, v in metrics.items()}
@@ -108,6 +112,8 @@ def setup_args() -> argparse.ArgumentParser:
                    help="quality metric(s) of the report; repeat the flag or separate by commas (default: psnr)")
     p.add_argument("--qstep", type=int, default=0, metavar="K",
                    help="quantiser step 2^(K/8) on the latent of the real codec, K in -16..32 (default 0: none)")
+    p.add_argument("--rdoq", type=float, default=None, metavar="W",
+                   help="rate-distortion optimised quantisation in the real codec's encoder, weight W > 0 (default: off)")
     p.add_argument("--limit", type=int, default=0, help="evaluate only the first N images (0 = all)")
     return p
 
@@ -126,6 +132,9 @@ def main(argv) -> int:
         check_qstep(args.qstep, "--")
         if args.qstep and args.entropy_estimation:
             raise ValueError("--qstep needs the real codec: the entropy estimation has no quantiser step")
+        check_rdoq(args.rdoq, "--")
+        if args.rdoq is not None and args.entropy_estimation:
+            raise ValueError("--rdoq needs the real codec: the entropy estimation's kernels know no RDOQ")
     except ValueError as e:
         print(f"Error: {e}", file=sys.stderr)
         return 2
@@ -145,7 +154,8 @@ def main(argv) -> int:
         sys.stderr.write(f"Evaluating {args.paths or '<initial weights>'} on {len(filepaths)} images\n")
     try:
         metrics = eval_model(model, filepaths, args.entropy_estimation, args.recon_path,
-                             metric_names=metric_names if args.metric else None, qstep=args.qstep)
+                             metric_names=metric_names if args.metric else None, qstep=args.qstep,
+                             rdoq=args.rdoq)
     except ValueError as e:
         print(f"Error: {e}", file=sys.stderr)
         return 4

@@ -16,7 +16,7 @@ import torch.nn as nn
 from . import _lib as L
 from . import engine as E
 from .ans import coder_for
-from .bitstream import check_qmap, check_qstep, uniform_qmap
+from .bitstream import check_qmap, check_qstep, check_rdoq, uniform_qmap
 from .engine import VT
 from .entropy_models import EntropyBottleneck, GaussianConditional
 from .layers import (GDN, Conv2d, Win_noShift_Attention, WindowAttention, conv, conv3x3, deconv, subpel_conv3x3,
@@ -131,14 +131,16 @@ class CompressionModel(nn.Module):
         names, params = _named(self)
         return dict(zip(names, [p.detach() for p in params]))
 
-    def _compress_latent(self, tape, P, y, coder, debug=None, qstep=0, qmap=None):
+    def _compress_latent(self, tape, P, y, coder, debug=None, qstep=0, qmap=None, rdoq=None):
         """cnn.py:214-266 from ``y`` on: {"strings": [[y_string], z_strings], "shape": z spatial size, "qstep"}.
         ``coder`` (``icm_amd.ans.coder_for``) codes the recorded device tensors of all slices as one y string, a run
         per slice, and the z strings as single-run strings.  ``qstep``: step index of the quantiser step on y (0: none;
         z and its EntropyBottleneck know no step).  ``qmap``: a non-uniform quality map as ``_quality`` returns it (a
-        checked int8 host array; ``qstep`` is then 0), returned under "qmap" with "qstep": None."""
+        checked int8 host array; ``qstep`` is then 0), returned under "qmap" with "qstep": None.  ``rdoq``: the checked
+        weight of rate-distortion optimised quantisation (``bitstream.check_rdoq``) or None; it changes which symbols
+        are coded, not the result's keys, and the decoder is not told."""
         gc = self.gaussian_conditional
-        codec = Encoder(E.Quantiser(gc, qstep, _qmap_on(qmap, y.device)))
+        codec = Encoder(E.Quantiser(gc, qstep, _qmap_on(qmap, y.device), rdoq))
         keep = {}
         hyper_slices(tape, P, y, None, None, self.num_slices, self.max_support_slices, keep=keep, coding=codec)
         z = keep["z"]
@@ -154,16 +156,17 @@ class CompressionModel(nn.Module):
         return {"strings": [[y_string], z_strings], "shape": z.size()[-2:], "qstep": qstep}
 
     @torch.no_grad()
-    def compress_latent(self, y, _debug=None, coder="host", symbols_per_wave=None, qstep=0, qmap=None):
+    def compress_latent(self, y, _debug=None, coder="host", symbols_per_wave=None, qstep=0, qmap=None, rdoq=None):
         """``compress`` from the latent on: ``y`` is what ``analysis(x)`` returned.  A rate search runs the analysis
         transform once per image and this once per probe."""
         qstep = check_qstep(qstep, "compress: ")
+        rdoq = check_rdoq(rdoq, "compress: ")
         coder = coder_for(coder, symbols_per_wave)
         if not isinstance(y, torch.Tensor) or y.dim() != 4 or y.dtype != torch.float32:
             raise ValueError("compress_latent: expected the f32 [B,M,h,w] latent of analysis()")
         qstep, qmap = _quality(qstep, qmap, y.shape[2:], "compress: ")
         tape = E.Tape(need_grad=False, packed_cache=self._pack_cache())
-        return self._compress_latent(tape, self._params(), y.contiguous(), coder, _debug, qstep, qmap)
+        return self._compress_latent(tape, self._params(), y.contiguous(), coder, _debug, qstep, qmap, rdoq)
 
     def _decompress_latent(self, tape, P, strings, shape, coder, qstep=0, qmap=None):
         """cnn.py:289-328: y_hat from the two streams"""
@@ -183,7 +186,7 @@ class CompressionModel(nn.Module):
         return self._g_a(tape, self._params(), x.contiguous())
 
     @torch.no_grad()
-    def compress(self, x, _debug=None, coder="host", symbols_per_wave=None, qstep=0, qmap=None):
+    def compress(self, x, _debug=None, coder="host", symbols_per_wave=None, qstep=0, qmap=None, rdoq=None):
         """cnn.py:210-266 -> {"strings": [[y_string], z_strings], "shape": z.shape[-2:], "qstep"}; ``coder``: "host"
         (the reference's scalar stream) or "lanes" (lane streams coded on the device, ``symbols_per_wave`` symbols of
         a slice per wave body, None: ``icm_amd.ans.SYMBOLS_PER_WAVE``); ``qstep``: step index k of a quantiser step
@@ -192,14 +195,19 @@ class CompressionModel(nn.Module):
         ``qmap`` (instead of ``qstep``): a quality map, a 2-D integer array or tensor of the latent's spatial size
         (H / 16, W / 16) holding a step index per position, shared by the batch and all channels.  A map whose
         entries are all k is ``qstep=k``, and that is what is returned; any other comes back, as an int8 host array,
-        under "qmap" with "qstep": None, and the decoder must be given it."""
+        under "qmap" with "qstep": None, and the decoder must be given it.
+        ``rdoq``: None, or the weight w > 0 of rate-distortion optimised quantisation: an element of y is coded one
+        symbol nearer zero where w x the added squared error (in symbol units) is less than the bits the coder's tables
+        say it saves (csrc/qstep.hip: ``icm_gc_code_rdo``; a smaller w trades more error for bits).  Encoder only: the
+        strings are ordinary strings, and ``decompress`` takes the same arguments as without.  z knows no such choice."""
         qstep = check_qstep(qstep, "compress: ")
+        rdoq = check_rdoq(rdoq, "compress: ")
         coder = coder_for(coder, symbols_per_wave)
         _check_codec_input(x)
         qstep, qmap = _quality(qstep, qmap, (x.shape[2] // 16, x.shape[3] // 16), "compress: ")
         P = self._params()
         tape = E.Tape(need_grad=False, packed_cache=self._pack_cache())
-        return self._compress_latent(tape, P, self._g_a(tape, P, x.contiguous()), coder, _debug, qstep, qmap)
+        return self._compress_latent(tape, P, self._g_a(tape, P, x.contiguous()), coder, _debug, qstep, qmap, rdoq)
 
     @torch.no_grad()
     def decompress(self, strings, shape, coder="host", qstep=0, qmap=None):
@@ -1024,10 +1032,10 @@ class SymmetricalTransFormer3(SymmetricalTransFormer):
     def update(self, scale_table=None, force=False):
         return self._update_tables(scale_table, force)
 
-    def compress(self, x, _debug=None, coder="host", symbols_per_wave=None, qstep=0, qmap=None):
+    def compress(self, x, _debug=None, coder="host", symbols_per_wave=None, qstep=0, qmap=None, rdoq=None):
         raise NotImplementedError("stf6: the zigzag entropy coder loop (stf6.py:898-1057) is not mirrored")
 
-    def compress_latent(self, y, _debug=None, coder="host", symbols_per_wave=None, qstep=0, qmap=None):
+    def compress_latent(self, y, _debug=None, coder="host", symbols_per_wave=None, qstep=0, qmap=None, rdoq=None):
         raise NotImplementedError("stf6: the zigzag entropy coder loop (stf6.py:898-1057) is not mirrored")
 
     def decompress(self, strings, shape, coder="host", qstep=0, qmap=None):

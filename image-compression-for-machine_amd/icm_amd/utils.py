@@ -10,7 +10,7 @@ import torch
 
 from . import _lib as L
 from ._lib import check, ptr
-from .bitstream import check_qstep
+from .bitstream import check_qstep, check_rdoq
 
 
 def pad2d(x: torch.Tensor, left: int, right: int, top: int, bottom: int, value: float = 0.0) -> torch.Tensor:
@@ -87,16 +87,18 @@ def _quality(x: torch.Tensor, x_hat: torch.Tensor, metrics: Optional[Sequence[st
 
 @torch.no_grad()
 def inference(model, x: torch.Tensor, recon=None, metrics: Optional[Sequence[str]] = None,
-              qstep: int = 0) -> Dict[str, float]:
+              qstep: int = 0, rdoq: Optional[float] = None) -> Dict[str, float]:
     """eval_model/__main__.py:96-139: actual bit-stream size and reconstruction quality of one image x [3,H,W] or
     [1,3,H,W] in [0,1]; ``recon(x_hat)`` (optional) receives the cropped reconstruction (the reference saves it, :130);
     ``metrics`` (optional) lists the quality entries to report (EVAL_METRICS; default: "psnr" alone); ``qstep``: step
-    index of the codec's quantiser step on the latent (``model.compress``; 0: none, the reference's codec)"""
+    index of the codec's quantiser step on the latent (``model.compress``; 0: none, the reference's codec); ``rdoq``:
+    weight of the encoder's rate-distortion optimised quantisation (``model.compress``; None: off)"""
+    rdoq = check_rdoq(rdoq, "inference: ")
     if x.dim() == 3:
         x = x.unsqueeze(0)
     xp, pads = pad_to_multiple(x, 64)
     t0 = time.time()
-    enc = model.compress(xp, qstep=qstep)
+    enc = model.compress(xp, qstep=qstep, **({} if rdoq is None else {"rdoq": rdoq}))
     torch.cuda.synchronize() if x.is_cuda else None
     t1 = time.time()
     dec = model.decompress(enc["strings"], enc["shape"], qstep=qstep)

@@ -428,6 +428,27 @@ int icm_gc_indexes_qmap(const float* scale, int64_t sc_bs, const float* scale_ta
                         void* stream);
 int icm_dequantize_qmap(const int32_t* symbols, const float* mu, int64_t mu_bs, const int8_t* qmap,
                         const float* step_table, float* yh, int64_t yh_bs, int N, int C, int HW, void* stream);
+/* Rate-distortion optimised quantisation: icm_gc_code_q / icm_gc_code_qmap with a choice, per element, between the
+ * nearest symbol s0 and its neighbour toward zero s1 = s0 - sign(s0).  Encoder only: the symbols are ordinary symbols
+ * and indexes_q / dequantize_q (or the map pair, or the plain pair at step = inv = 1) decode them.  `qmap` and
+ * `step_table` are both NULL (the scalar pair `step`, `inv` for every position) or both set (the pair of each
+ * position, as icm_gc_code_qmap; `step` and `inv` are then unused but still checked).  `cdfs` [ncdf][cdf_stride],
+ * `cdf_sizes` [ncdf] and `offsets` [ncdf] are the coder's device tables (int32; `cdfs` fixes the layout of `bits` and
+ * is not read); `bits` [ncdf][cdf_stride] f32 is the code-length table of icm_amd/bitstream.py:code_length_table,
+ * bits[r][v] = 16 - log2(cdfs[r][v + 1] - cdfs[r][v]) for v < cdf_sizes[r] - 2; `w` weighs the squared error in symbol
+ * units.  With u = (y - mu) * inv, off = offsets[index], ov = cdf_sizes[index] - 2, v_j = s_j - off, all f32, one
+ * rounding per operation, no FMA:
+ *   e_j = u - (float)s_j;  J_j = (w * (e_j * e_j)) + bits[index][v_j]
+ * and s1 is coded iff s0 != 0, all of v0, v1 lie in 0 .. ov - 1 (an escaped symbol is kept, no candidate becomes one)
+ * and J1 < J0 strictly; y_hat is that of the symbol coded, the index is unchanged.  One launch.
+ * ICM_ERR_ARG before any launch, outputs untouched: a null pointer (qmap / step_table excepted as above, one of the two
+ * without the other included), N, C or HW < 1, N > 65535 (an image is a workgroup row of the grid), ns != ncdf or < 1,
+ * cdf_stride < 3, step, inv or w not finite or <= 0. */
+int icm_gc_code_rdo(const float* y, int64_t y_bs, const float* mu, int64_t mu_bs, const float* scale, int64_t sc_bs,
+                    const float* scale_table, int ns, float scale_bound, float step, float inv, const int8_t* qmap,
+                    const float* step_table, const int32_t* cdfs, int cdf_stride, const int32_t* cdf_sizes,
+                    const int32_t* offsets, int ncdf, const float* bits, float w, int32_t* symbols, int32_t* indexes,
+                    float* yh, int64_t yh_bs, int N, int C, int HW, void* stream);
 
 /* Training and estimation at a step (variable-rate training; parity unpinned like the rest of this section): the pair
  * icm_gc_likelihood_ste_fwd / _bwd with a (step, inv) pair per IMAGE, `steps` [N][2] f32 in DEVICE memory, 8-byte

@@ -15,6 +15,13 @@
                     of the image at offset -16: a quality map, the map-reading kernel per slice), alternated, with both
                     file sizes.
 
+    rdoq_kernel     the encoder's rate-distortion optimised quantisation kernel (``icm_gc_code_rdo``) on that same
+                    slice against the scalar fused kernel (``icm_gc_code_q``, k = 8) in the same run, the forms
+                    alternated: with the scalar pair, with the centred region's map and with the busy map, at weight
+                    0.25, microseconds per slice.
+    rdoq_points     file bytes and latent squared error sum((y - y_hat)^2) without RDOQ and at the weights 4 and
+                    0.25, at qstep -16 and -8 (``analysis()`` once, ``compress_latent`` with ``_debug`` per point).
+
 ``slice_kernels`` also times the map-reading fused kernel (``icm_gc_code_qmap``) against the scalar one
 (``icm_gc_code_q``) on the same operands in the same run, with the map of that centred region and with a map that
 changes its step at every position.
@@ -39,7 +46,9 @@ for p in (ROOT, os.path.join(ROOT, "image-compression-for-machine_amd")):
 
 H, W = 2048, 3072
 RATE_POINTS = (-16, -8, 0, 8, 16, 24, 32)
-PARTS = ("slice_kernels", "step_vs_plain", "rate_points", "target_bpp", "roi_encode")
+PARTS = ("slice_kernels", "step_vs_plain", "rate_points", "target_bpp", "roi_encode", "rdoq_kernel", "rdoq_points")
+RDOQ_WEIGHTS = (4.0, 0.25)
+RDOQ_STEPS = (-16, -8)
 ROI = (H // 4, W // 4, H // 2, W // 2, -16)        # the centred quarter of the image, two octaves finer
 
 
@@ -110,6 +119,65 @@ def slice_kernels(args, torch, np):
     print(json.dumps(res), flush=True)
 
 
+def rdoq_kernel(args, torch, np):
+    """``icm_gc_code_rdo`` against ``icm_gc_code_q`` on the slice of ``slice_kernels``, the forms alternated"""
+    from icm_amd import _lib as L
+    from icm_amd import codec
+    from icm_amd import engine as E
+    from icm_amd.zoo import models
+    model = models["cnn"]().to("cuda:0").eval()
+    model.update(force=True)
+    gc = model.gaussian_conditional
+    g = torch.Generator(device="cuda:0").manual_seed(0)
+    N, M, c, h, w = 1, 320, 32, H // 16, W // 16
+    Y, MU, YP = (torch.randn((N, M, h, w), generator=g, device="cuda:0") for _ in range(3))
+    SC = torch.rand((N, M, h, w), generator=g, device="cuda:0") * 2
+    s1 = slice(64, 96)
+    args_ = (L.stream(), Y[:, s1], MU[:, s1], SC[:, s1], YP[:, s1])
+    roi = torch.from_numpy(codec.roi_map(H, W, codec.center_pads(H, W), 8, [ROI])).to("cuda:0")
+    busy = torch.from_numpy(np.array([-16, -3, 0, 5, 8, 32], dtype=np.int8)[(5 * np.arange(h * w)) % 6].reshape(h, w))
+    busy = busy.to("cuda:0")
+    weight = RDOQ_WEIGHTS[1]
+    qs = {"scalar": E.Quantiser(gc, 8), "rdo": E.Quantiser(gc, 8, rdoq=weight),
+          "rdo_roi": E.Quantiser(gc, 0, roi, rdoq=weight), "rdo_busy": E.Quantiser(gc, 0, busy, rdoq=weight),
+          "rdo_huge": E.Quantiser(gc, 8, rdoq=1e30)}
+    sym0, sym1 = qs["scalar"].code(*args_)[0], qs["rdo"].code(*args_)[0]
+    res = {"metric": "rdoq_kernel", "slice": [N, c, h, w], "iters": args.iters, "weight": weight,
+           "symbols_moved": int((sym0 != sym1).sum().item()), "symbols_nonzero": int((sym0 != 0).sum().item())}
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    order = ("scalar", "rdo", "scalar", "rdo", "scalar", "rdo_roi", "scalar", "rdo_busy", "scalar", "rdo_huge", "scalar",
+             "rdo", "rdo_roi", "rdo_busy")
+    for name in order:
+        fn = (lambda q: lambda: q.code(*args_))(qs[name])
+        for _ in range(10):
+            fn()
+        torch.cuda.synchronize()
+        e0.record()
+        for _ in range(args.iters):
+            fn()
+        e1.record()
+        torch.cuda.synchronize()
+        res.setdefault(name + "_us", []).append(round(e0.elapsed_time(e1) / args.iters * 1e3, 2))
+    print(json.dumps(res), flush=True)
+
+
+def rdoq_points(args, coder, torch, np, codec, B, model, a, base):
+    """bytes and latent squared error with and without RDOQ: the mechanism on a randomly initialised model"""
+    pads = codec.center_pads(H, W)
+    y = model.analysis(codec.image_u8_to_f32(torch.from_numpy(a).to("cuda:0"), pads))
+    arch, fp = codec.arch_of(model), B.fingerprint(model)
+    pts = []
+    for k in RDOQ_STEPS:
+        for weight in (None,) + RDOQ_WEIGHTS:
+            d = {}
+            enc = model.compress_latent(y, _debug=d, coder=coder, qstep=k, **({} if weight is None else {"rdoq": weight}))
+            data = codec._pack_one(arch, fp, H, W, pads, enc, coder)
+            sse = float(((y.double() - d["y_hat"].double()) ** 2).sum().item())
+            pts.append({"qstep": k, "rdoq": weight, "bytes": len(data), "latent_sse": round(sse, 1),
+                        "symbols_nonzero": int((d["symbols"] != 0).sum())})
+    print(json.dumps({"metric": "rdoq_points", **base, "latent_elements": int(y.numel()), "points": pts}), flush=True)
+
+
 def run(args, coder, torch, np, codec, B):
     from icm_amd.zoo import models
     torch.manual_seed(0)
@@ -120,6 +188,9 @@ def run(args, coder, torch, np, codec, B):
 
     def encode(**kw):
         return codec.encode_image_info(model, a, coder=coder, **kw)
+
+    if "rdoq_points" in args.parts:
+        rdoq_points(args, coder, torch, np, codec, B, model, a, base)
 
     # ---- (d) one centred region of interest against the scalar step, alternated
     if "roi_encode" in args.parts:
@@ -214,7 +285,9 @@ def main():
     from icm_amd import codec
     if "slice_kernels" in args.parts:
         slice_kernels(args, torch, np)
-    if not set(args.parts) - {"slice_kernels"}:
+    if "rdoq_kernel" in args.parts:
+        rdoq_kernel(args, torch, np)
+    if not set(args.parts) - {"slice_kernels", "rdoq_kernel"}:
         return
     for coder in (("host", "lanes") if args.coder == "both" else (args.coder,)):
         run(args, coder, torch, np, codec, B)
