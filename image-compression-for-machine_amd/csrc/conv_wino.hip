@@ -346,6 +346,74 @@ __global__ __launch_bounds__(512, 2) void conv_wino_kernel(const WinoDesc d) {
 // tiles: every staged V byte feeds twice the MFMAs, a step is twice as long (half the barriers), two MFMA waves per
 // SIMD cover each other's waits, and each wave issues 4 of the step's 32 DMA instructions itself.  The column half of
 // the output transform is split between the two waves of a row (partial sums through LDS, fixed order).
+//
+// The step loop's vector-memory queue, per wave and in order.  The compiler waits vmcnt(0) for any register load it knows
+// of while an LDS-DMA is outstanding, which made every step open with a full drain: each wave waited for the DMAs it
+// had just issued, whatever the ring depth.  So the weight fragments are inline-asm loads the compiler does not count,
+// and every wait on that queue is written by hand.  A unit is the TCO 16-byte fragment loads of one (chunk, column); w(s, u)
+// are those of unit u of step s, D(s) the 4 DMAs issued in step s (the V of step s + AHEAD).  Fragments are fetched three
+// units ahead, and the loads of a step sit behind its first wait, DMAs first:
+//
+//   prologue          D(0) [D(1)]  w(0,0) w(0,1) w(0,2)      wait 3 TCO: the DMAs, nothing younger; barrier
+//   step s  unit 0    wait for w(s,0);  issue D(s), w(s,3)     younger at the wait: w(s,1) w(s,2)              = 2 TCO
+//           unit 1    wait for w(s,1);  issue w(s+1,0)         younger: w(s,2) D(s) w(s,3)                     = 2 TCO + 4
+//           unit 2    wait for w(s,2);  issue w(s+1,1)         younger: D(s) w(s,3) w(s+1,0)                   = 2 TCO + 4
+//           unit 3    wait for w(s,3);  issue w(s+1,2)         younger: w(s+1,0) w(s+1,1)                      = 2 TCO
+//           barrier   D(s) must have landed                     younger: w(s,3) w(s+1,0) w(s+1,1) w(s+1,2)      = 4 TCO
+//
+// so TCO 2: 4, 8, 8, 4 and 8;  TCO 3: 6, 10, 10, 6 and 12;  TCO 4: 8, 12, 12, 8 and 16.  (Unit 3's wait retires D(s) too,
+// it is older than w(s,3), and leaves at most 3 TCO in flight at the barrier: the barrier's count never blocks; it is
+// there so that the barrier does not depend on that.)  The weight loads are clamped at the end (min(g + 3, nunits - 1)),
+// so their part of the queue is the same in every step.  The last AHEAD steps issue no DMA: the tail is handled with its
+// own counts, not with dummy DMAs -- there units 1 and 2 have 2 TCO younger loads, and the 2 TCO + 4 of the other steps
+// would return with the fragment still in flight (no fault, wrong values), so these steps wait for 2 TCO first.  Units 0
+// and 3 and the barrier do not have D(s) among the younger loads and are the same in every step, nsteps = 1, 2, 3 included.
+// Behind the loop 3 TCO clamped loads are in flight into aq[0..2]: they are drained before the registers are reused.
+template <int TCO>
+struct Wino8Pipe {
+  // Ring depth: four slots.  The DMAs of step s + 2 are issued during step s, so the slot of step s + 1 landed and was
+  // published a step earlier and its first B fragment is read before the barrier that ends step s; slot (s + 2) & 3 was
+  // last read in step s - 2, two barriers ago for every wave.  Measured per co-block width.
+  static constexpr int AHEAD = 2;
+  static constexpr int SLOTM = 2 * AHEAD - 1;
+  static constexpr int W_PROLOGUE = 3 * TCO;      // the prologue's DMAs
+  static constexpr int W_EDGE = 2 * TCO;          // units 0 and 3; units 1 and 2 of a step without DMAs
+  static constexpr int W_MID = 2 * TCO + 4;       // units 1 and 2 of a step that issued its 4 DMAs
+  static constexpr int W_BARRIER = 4 * TCO;       // the step's DMAs, in front of the barrier
+};
+
+// One unit's weight fragments: TCO loads in the saddr + 32-bit voffset form, one statement.  The base may come straight
+// from v_readfirstlane (5 wait states before a VMEM instruction reads it), hence the s_nop.
+template <int TCO>
+__device__ __forceinline__ void wino8_wload(f32x4 (&q)[TCO], const char* base, const unsigned (&wl)[TCO]) {
+  if constexpr (TCO == 2)
+    asm volatile("s_nop 4\n\tglobal_load_dwordx4 %0, %2, %4\n\tglobal_load_dwordx4 %1, %3, %4"
+                 : "=&v"(q[0]), "=&v"(q[1]) : "v"(wl[0]), "v"(wl[1]), "s"(base) : "memory");
+  else if constexpr (TCO == 3)
+    asm volatile("s_nop 4\n\tglobal_load_dwordx4 %0, %3, %6\n\tglobal_load_dwordx4 %1, %4, %6\n\tglobal_load_dwordx4 %2, %5, %6"
+                 : "=&v"(q[0]), "=&v"(q[1]), "=&v"(q[2]) : "v"(wl[0]), "v"(wl[1]), "v"(wl[2]), "s"(base) : "memory");
+  else
+    asm volatile("s_nop 4\n\tglobal_load_dwordx4 %0, %4, %8\n\tglobal_load_dwordx4 %1, %5, %8\n\t"
+                 "global_load_dwordx4 %2, %6, %8\n\tglobal_load_dwordx4 %3, %7, %8"
+                 : "=&v"(q[0]), "=&v"(q[1]), "=&v"(q[2]), "=&v"(q[3])
+                 : "v"(wl[0]), "v"(wl[1]), "v"(wl[2]), "v"(wl[3]), "s"(base) : "memory");
+}
+// The wait that retires a unit's fragments names them, so no MFMA that reads them is scheduled above it; the s_nop covers
+// the wait states between a VGPR written under an asm statement and an MFMA reading it.
+template <int N, int TCO>
+__device__ __forceinline__ void wino8_wwait(f32x4 (&q)[TCO]) {
+  if constexpr (TCO == 2)
+    asm volatile("s_waitcnt vmcnt(%2)\n\ts_nop 1" : "+v"(q[0]), "+v"(q[1]) : "n"(N) : "memory");
+  else if constexpr (TCO == 3)
+    asm volatile("s_waitcnt vmcnt(%3)\n\ts_nop 1" : "+v"(q[0]), "+v"(q[1]), "+v"(q[2]) : "n"(N) : "memory");
+  else
+    asm volatile("s_waitcnt vmcnt(%4)\n\ts_nop 1" : "+v"(q[0]), "+v"(q[1]), "+v"(q[2]), "+v"(q[3]) : "n"(N) : "memory");
+}
+template <int N>
+__device__ __forceinline__ void wino8_vmwait() {
+  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
+}
+
 template <int TCO>
 __global__ __launch_bounds__(512, 2) void conv_wino8_kernel(const WinoDesc d) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
@@ -364,6 +432,8 @@ __global__ __launch_bounds__(512, 2) void conv_wino8_kernel(const WinoDesc d) {
   const int HW = d.H * d.W;
   const int r = wave >> 1, ch = wave & 1;
   const int cot0 = cb * TCO;
+  using PL = Wino8Pipe<TCO>;
+  constexpr int AHEAD = PL::AHEAD, SLOTM = PL::SLOTM;
 
   const float* vsrc = P.x + (long long)pblk * (d.nsteps * 2) * 4096;
   auto dma = [&](int step, int buf) {   // this wave's 4 of the 32 one-KB pieces of the step
@@ -393,61 +463,58 @@ __global__ __launch_bounds__(512, 2) void conv_wino8_kernel(const WinoDesc d) {
     const int qq = min((g >> 1) * 16 + xi0 + (g & 1), lastq);
     return wbase + qq * qstride;
   };
-  // V ring in the 128 KB the epilogue needs anyway.  AHEAD = 2 (four slots): the DMAs of step s + 2 are issued during
-  // step s, so the slot of step s + 1 landed and was published a step earlier and its first B fragment is read before the
-  // barrier that ends step s; slot (s + 2) & 3 was last read in step s - 2, two barriers ago for every wave.  AHEAD = 1
-  // (two slots): the next slot is published by the barrier itself, the first fragment is read behind it.  Measured per
-  // co-block width in the training step: four slots win for TCO 2 and 4 and lose 1 % for TCO 3.
-  constexpr int AHEAD = TCO == 3 ? 1 : 2, SLOTM = 2 * AHEAD - 1;
+  // V ring in the 128 KB the epilogue needs anyway (depth and wait counts: Wino8Pipe above)
   dma(0, 0);
-  if (AHEAD == 2 && d.nsteps > 1) dma(1, 1);
+  if (d.nsteps > 1) dma(1, 1);
   f32x4 aq[4][TCO];
 #pragma unroll
-  for (int u = 0; u < 3; ++u)
-#pragma unroll
-    for (int a = 0; a < TCO; ++a) aq[u][a] = *reinterpret_cast<const f32x4*>(wptr(min(u, nunits - 1)) + wl[a]);
+  for (int u = 0; u < 3; ++u) wino8_wload<TCO>(aq[u], wptr(min(u, nunits - 1)), wl);
   const int boff = xi0 * 256 + lane;
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  __syncthreads();   // the first AHEAD steps landed
+  wino8_vmwait<PL::W_PROLOGUE>();
+  __builtin_amdgcn_s_barrier();   // the first AHEAD steps landed
   float bv[2][4];
-  if constexpr (AHEAD == 2) {
 #pragma unroll
-    for (int j = 0; j < 4; ++j) bv[0][j] = (smem + boff)[j * 64];
-  }
+  for (int j = 0; j < 4; ++j) bv[0][j] = (smem + boff)[j * 64];
   for (int s = 0; s < d.nsteps; ++s) {
-    if (s + AHEAD < d.nsteps) dma(s + AHEAD, (s + AHEAD) & SLOTM);   // issued first: older than every weight load of this step
+    const bool more = s + AHEAD < d.nsteps;   // this step issues DMAs
     const float* vb = smem + (s & SLOTM) * WINO_STEP_FLOATS + boff;
-    if constexpr (AHEAD == 1) {
-#pragma unroll
-      for (int j = 0; j < 4; ++j) bv[0][j] = vb[j * 64];
-    }
 #pragma unroll
     for (int u = 0; u < 4; ++u) {
       const int g = s * 4 + u;
-      if (u + 1 < 4 || AHEAD == 2) {   // next unit's B fragment; behind the last unit, the first one of the next step's slot
-        const float* nb = u + 1 < 4 ? vb + ((u + 1) >> 1) * (16 * 256) + ((u + 1) & 1) * 256
-                                    : smem + ((s + 1) & SLOTM) * WINO_STEP_FLOATS + boff;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) bv[(u + 1) & 1][j] = nb[j * 64];
+      if (u == 0 || u == 3) {
+        wino8_wwait<PL::W_EDGE>(aq[u]);
+      } else {
+        if (!more) wino8_vmwait<PL::W_EDGE>();
+        wino8_wwait<PL::W_MID>(aq[u]);
       }
-      const char* sp = wptr(min(g + 3, nunits - 1));
+      // behind the step's first wait, which so covers fragments only, and older than every weight load of the step
+      if (u == 0 && more) dma(s + AHEAD, (s + AHEAD) & SLOTM);
+      wino8_wload<TCO>(aq[(u + 3) & 3], wptr(min(g + 3, nunits - 1)), wl);
+      // next unit's B fragment; behind the last unit, the first one of the next step's slot
+      const float* nb = u + 1 < 4 ? vb + ((u + 1) >> 1) * (16 * 256) + ((u + 1) & 1) * 256
+                                  : smem + ((s + 1) & SLOTM) * WINO_STEP_FLOATS + boff;
 #pragma unroll
-      for (int a = 0; a < TCO; ++a) {
+      for (int j = 0; j < 4; ++j) bv[(u + 1) & 1][j] = nb[j * 64];
+#pragma unroll
+      for (int a = 0; a < TCO; ++a)
 #pragma unroll
         for (int j = 0; j < 4; ++j)
           acc[u & 1][a] = __builtin_amdgcn_mfma_f32_32x32x2f32(aq[u][a][j], bv[u & 1][j], acc[u & 1][a], 0, 0, 0);
-        aq[(u + 3) & 3][a] = *reinterpret_cast<const f32x4*>(sp + wl[a]);
-      }
     }
-    // the DMAs issued in this step are older than the 3 * TCO weight loads still in flight: wait for them only.  This
-    // wave's LDS reads of slot s fed the MFMAs above; with four slots the read of slot s + 1 may cross the barrier, with
-    // two the barrier frees the slot that the next step's DMAs overwrite, so every LDS read is drained first.
-    if constexpr (TCO == 4) asm volatile("s_waitcnt vmcnt(12)" ::: "memory");
-    else if constexpr (TCO == 3) asm volatile("s_waitcnt vmcnt(9)" ::: "memory");
-    else asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
-    if constexpr (AHEAD == 1) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    // This wave's LDS reads of slot s fed the MFMAs above; the read of slot s + 1 may cross the barrier.
+    wino8_vmwait<PL::W_BARRIER>();
     __builtin_amdgcn_s_barrier();
   }
+  // the clamped loads of the last step are still in flight into aq[0..2]
+  if constexpr (TCO == 2)
+    asm volatile("s_waitcnt vmcnt(0)" : "+v"(aq[0][0]), "+v"(aq[0][1]), "+v"(aq[1][0]), "+v"(aq[1][1]), "+v"(aq[2][0]), "+v"(aq[2][1])
+                 :: "memory");
+  else if constexpr (TCO == 3)
+    asm volatile("s_waitcnt vmcnt(0)" : "+v"(aq[0][0]), "+v"(aq[0][1]), "+v"(aq[0][2]), "+v"(aq[1][0]), "+v"(aq[1][1]), "+v"(aq[1][2]),
+                   "+v"(aq[2][0]), "+v"(aq[2][1]), "+v"(aq[2][2]) :: "memory");
+  else
+    asm volatile("s_waitcnt vmcnt(0)" : "+v"(aq[0][0]), "+v"(aq[0][1]), "+v"(aq[0][2]), "+v"(aq[0][3]), "+v"(aq[1][0]), "+v"(aq[1][1]),
+                   "+v"(aq[1][2]), "+v"(aq[1][3]), "+v"(aq[2][0]), "+v"(aq[2][1]), "+v"(aq[2][2]), "+v"(aq[2][3]) :: "memory");
 
   // ---- output transform.  Column half per wave pair of a row: ch 0 holds M0, M1; ch 1 holds M2, M3
   //      Z[.][0] = (M0 + M1) + M2,   Z[.][1] = M1 + (-M2 - M3):  each wave contributes one partial per Z
