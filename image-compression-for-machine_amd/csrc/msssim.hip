@@ -7,9 +7,12 @@
 // filters the five products along the rows into LDS, along the columns out of LDS into registers, forms cs_map /
 // ssim_map there, writes the three coefficient maps the backward needs, and leaves one (cs, ssim) partial sum per
 // workgroup in the workspace.  The 2x2 average pooling that feeds the next level is done by the same workgroup from
-// the staged tile.  msssim_finish_kernel then adds the partials in tile order and forms ms[n, c], the mean and the
-// per-level upstream factors w_l * ms / v_l (0 where v_l <= 0).  No float atomics anywhere: equal inputs give
-// bit-identical results.
+// the staged tile.  The moments are those of the images minus data_range / 2: variances and covariances do not change
+// under a shift, and E[xx] - mu^2 then cancels at the scale of the centred pixels instead of at mu^2 ~ data_range^2 / 4
+// (in f32 that cancellation, compared with C2 on the smooth coarse levels, was the largest error of the whole value);
+// the luminance term adds the shift back.  msssim_finish_kernel then adds the partials in tile order and forms
+// ms[n, c], the mean and the per-level upstream factors w_l * ms / v_l (0 where v_l <= 0).  No float atomics anywhere:
+// equal inputs give bit-identical results.
 //
 // Backward, one launch per level, last level first (msssim_bwd_level_kernel): the transpose of a valid filter is the
 // full filter with the same (symmetric) window, so a workgroup that owns 32 x 32 INPUT pixels stages the 42 x 42
@@ -166,7 +169,8 @@ __device__ __forceinline__ void pool_range(int t0, int last, int pad, int n2, in
 }
 
 __global__ __launch_bounds__(256) void msssim_level_kernel(const float* __restrict__ X, const float* __restrict__ Y,
-                                                           int h, int w, float C1, float C2, int last_level,
+                                                           int h, int w, float C1, float C2, float shift,
+                                                           int last_level,
                                                            float* __restrict__ Xn, float* __restrict__ Yn,
                                                            float* __restrict__ coef, double* __restrict__ part, int vec,
                                                            const Window wd) {
@@ -182,12 +186,17 @@ __global__ __launch_bounds__(256) void msssim_level_kernel(const float* __restri
   stage_tile(Y + plane, h, w, ty0, tx0, 1.0f, vec, ys);
   __syncthreads();
 
-  // rows: mu1, mu2, E[xx], E[yy], E[xy]
+  // rows: mu1, mu2, E[xx], E[yy], E[xy] of the centred images
   for (int it = threadIdx.x; it < TIN * (T / 4); it += 256) {
     const int r = it >> 3, c = (it & 7) * 4;
     float xv[16], yv[16], t[16];
     load16(xs + r * XS + c, xv);
     load16(ys + r * XS + c, yv);
+#pragma unroll
+    for (int i = 0; i < 14; ++i) {
+      xv[i] -= shift;
+      yv[i] -= shift;
+    }
     *reinterpret_cast<f32x4*>(&hb[0][r * T + c]) = row4(xv, wd);
     *reinterpret_cast<f32x4*>(&hb[1][r * T + c]) = row4(yv, wd);
 #pragma unroll
@@ -245,14 +254,15 @@ __global__ __launch_bounds__(256) void msssim_level_kernel(const float* __restri
   for (int j = 0; j < 4; ++j) {
     const int sy = ty0 + r0 + j, sx = tx0 + c;
     if (sy < sh && sx < sw) {
-      const float m1 = mu1[j], m2 = mu2[j];
-      const float s1 = exx[j] - m1 * m1, s2 = eyy[j] - m2 * m2, s12 = exy[j] - m1 * m2;
+      const float d1 = mu1[j], d2 = mu2[j];   // centred means
+      const float s1 = exx[j] - d1 * d1, s2 = eyy[j] - d2 * d2, s12 = exy[j] - d1 * d2;
+      const float m1 = d1 + shift, m2 = d2 + shift;
       const float rB2 = 1.0f / (s1 + s2 + C2), rB1 = 1.0f / (m1 * m1 + m2 * m2 + C1);
       const float cs = (2.0f * s12 + C2) * rB2;
       const float lum = (2.0f * m1 * m2 + C1) * rB1;
       cs_sum += (double)cs;
       ss_sum += (double)(lum * cs);
-      // derivatives of the level's map with respect to mu1 (a), g*(X*X) (b), g*(X*Y) (c)
+      // derivatives of the level's map with respect to mu1 (a), g*(X*X) (b), g*(X*Y) (c) of the images as given
       float a = 2.0f * (cs * m1 - m2) * rB2, b = -cs * rB2, cc = 2.0f * rB2;
       if (last_level) {
         a = lum * a + cs * 2.0f * (m2 - m1 * lum) * rB1;
@@ -393,7 +403,7 @@ int icm_msssim_fwd(const float* x, const float* y, int N, int C, int H, int W, f
     const int vec = (p.w[l] % 4 == 0) && ((reinterpret_cast<uintptr_t>(xl) | reinterpret_cast<uintptr_t>(yl)) & 15) == 0 &&
                     ((long long)p.h[l] * p.w[l]) % 4 == 0;
     hipLaunchKernelGGL(msssim_level_kernel, dim3(p.tx[l], p.ty[l], NC), dim3(256), 0, ST, xl, yl, p.h[l], p.w[l], C1, C2,
-                       last, xn, yn, ws + p.coef[l], reinterpret_cast<double*>(ws + p.part[l]), vec, wd);
+                       0.5f * data_range, last, xn, yn, ws + p.coef[l], reinterpret_cast<double*>(ws + p.part[l]), vec, wd);
     ICM_CHECK_LAUNCH();
     fa.part[l] = p.part[l];
     fa.tiles[l] = p.ty[l] * p.tx[l];

@@ -1,10 +1,12 @@
-"""The float64 CPU restatement of MS-SSIM (tests/_msssim_ref.py) against hand-checkable cases, and the host-side
-surface of the feature that exists without a GPU (loss constructor, CLI parsers)."""
+"""The float64 CPU restatement of MS-SSIM (tests/_msssim_ref.py) against hand-checkable cases, the conditions
+that the inputs of the GPU numerics tests (tests/_msssim_inputs.py) must meet, and the host-side surface of the
+feature that exists without a GPU (loss constructor, CLI parsers)."""
 import pytest
 import torch
 
 import _msssim_ref as R
-from _msssim_inputs import make_pair
+from _msssim_inputs import (LOWQ_CASES, NUMERICS_CASES, ONE_LEVEL_CLAMP_PLANE, make_pair, numerics_pair,
+                            one_level_clamp_pair)
 
 
 def test_identical_images_give_exactly_one():
@@ -59,6 +61,80 @@ def test_window():
     g = R.window()
     assert g.sum().item() == pytest.approx(1.0, abs=1e-15)
     assert torch.equal(g, g.flip(0)) and g.argmax().item() == 5
+
+
+# ---- input conditions of tests/test_gpu_msssim_numerics.py, in float64
+@pytest.mark.parametrize("name", list(NUMERICS_CASES))
+def test_numerics_inputs_keep_relu_inactive(name):
+    # every level value well above 0: the gradient is smooth there and "4x the f32-vs-f64 distance" means something
+    t, xh, dr = numerics_pair(name)
+    assert tuple(t.shape) == tuple(xh.shape) == NUMERICS_CASES[name]
+    assert t.dtype == xh.dtype == torch.float32
+    assert min(t.min().item(), xh.min().item()) >= 0.0 and max(t.max().item(), xh.max().item()) <= dr
+    lv = R.level_values(xh.double(), t.double(), dr)
+    assert lv.min().item() > 0.05
+    if name in LOWQ_CASES:
+        w = torch.tensor(R.WEIGHTS, dtype=torch.float64).view(-1, 1, 1)
+        ms = torch.prod(lv ** w, dim=0).mean().item()
+        assert 0.5 <= ms <= 0.85 and lv.min().item() < 0.35
+
+
+def test_numerics_shapes_sit_where_they_claim():
+    T, HALO = 32, 10                                  # tile edge and window halo of csrc/msssim.hip
+    N, C, H, W = NUMERICS_CASES["planes258"]
+    assert N * C > 256 and min(H, W) == 161           # the finish kernel has 256 threads
+    _, _, H, W = NUMERICS_CASES["tile_exact"]
+    assert (H - HALO) % T == 0 and (W - HALO) % T == 0
+    _, _, H, W = NUMERICS_CASES["tile_plus1"]
+    assert (H - HALO) % T == 1 and (W - HALO) % T == 1
+    for name, long_side, short_side in (("wide", 3, 2), ("tall", 2, 3)):
+        s = NUMERICS_CASES[name]
+        assert -(-(s[long_side] - HALO) // T) >= 20 and -(-(s[short_side] - HALO) // T) == 5
+    assert NUMERICS_CASES["stage192x224"][3] % 4 == 0
+    assert NUMERICS_CASES["range255"] == NUMERICS_CASES["odd175x201"]
+
+
+def test_flat_blocks_are_exactly_flat():
+    for name, bright in (("flat_blocks", 1.0), ("flat_blocks_dim", 0.98)):
+        t, xh, _ = numerics_pair(name)
+        assert (t[:, :, :64, :80] == 1.0).all() and (xh[:, :, :64, :80] == torch.tensor(bright)).all()
+        assert (t[:, :, 100:, 120:] == 0.0).all() and (xh[:, :, 100:, 120:] == 0.0).all()
+        assert t[:, :, 64:100].std().item() > 0.05     # and the rest is not
+
+
+def test_range255_is_the_unscaled_pair():
+    # MS-SSIM does not change when data_range scales with the images
+    t, xh, _ = numerics_pair("odd175x201")
+    t, xh = t.double(), xh.double()
+    x = xh.clone().requires_grad_(True)
+    y = t.clone().requires_grad_(True)
+    one = R.ms_ssim(x, y, size_average=False)
+    one.sum().backward()
+    scaled = R.ms_ssim(xh * 255.0, t * 255.0, data_range=255.0, size_average=False)
+    assert (scaled - one.detach()).abs().max().item() <= 1e-12
+    # the case itself holds the product rounded to float32: each pixel moves by at most 2^-24 of itself, which to
+    # first order moves a plane's value by at most 2^-24 * sum |pixel * d ms / d pixel| (twice that is allowed here)
+    t255, x255, dr = numerics_pair("range255")
+    assert dr == 255.0
+    got = R.ms_ssim(x255.double(), t255.double(), data_range=255.0, size_average=False)
+    first_order = 2.0 ** -24 * ((x.grad * xh).abs().sum((2, 3)) + (y.grad * t).abs().sum((2, 3)))
+    assert ((got - one.detach()).abs() <= 2.0 * first_order).all() and first_order.max().item() < 1e-7
+    # data_range matters: the same images at data_range = 1 are further away than any bound of the GPU tests (which
+    # ask for 100x the case's value bound, 1.1e-4)
+    assert (R.ms_ssim(x255.double(), t255.double(), size_average=False) - got).abs().min().item() > 2e-4
+
+
+def test_one_level_clamp_pair_clamps_exactly_one_level():
+    t, xh = one_level_clamp_pair()
+    assert min(t.min().item(), xh.min().item()) >= 0.0 and max(t.max().item(), xh.max().item()) <= 1.0
+    p = ONE_LEVEL_CLAMP_PLANE
+    others = [q for q in range(3) if q != p]
+    _, cs0 = R.ssim_level(xh.double(), t.double(), R.window())
+    assert cs0[0, p].item() < -0.05                   # clearly negative before the relu, not a rounding away from 0
+    lv = R.level_values(xh.double(), t.double())[:, 0]
+    assert lv[0, p].item() == 0.0 and lv[1:, p].min().item() > 0.05
+    assert lv[:, others].min().item() > 0.05
+    assert R.ms_ssim(xh.double(), t.double(), size_average=False)[0, p].item() == 0.0
 
 
 # ---- host-side surface (no GPU needed)
