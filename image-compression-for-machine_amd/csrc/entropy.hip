@@ -279,7 +279,7 @@ __global__ __launch_bounds__(256) void eb_aux_kernel(const EbPtrs P, float* loss
 }
 
 // ------------------------------------------------------------------------------ GaussianConditional
-// (std_cdf / std_pdf: icm_common.h, shared with the stepped form in qstep.hip)
+// (std_cdf / std_pdf / gc_bwd_tail: icm_common.h, shared with the stepped form in qstep.hip)
 struct GcDesc {
   const float* y; const float* mu; const float* sc; const float* noise;
   float* lik; float* yh; float* yh2;
@@ -322,29 +322,7 @@ __global__ void gc_bwd_kernel(const GcBwdDesc d) {
     const long long n = i / per, r = i - n * per;
     const float y = d.y[n * d.y_bs + r], mu = d.mu[n * d.mu_bs + r], sc = d.sc[n * d.sc_bs + r];
     const float out = d.noise ? (y + d.noise[n * d.nz_bs + r]) : (rintf(y - mu) + mu);
-    const float w = out - mu;
-    const float v = fabsf(w);
-    const float s = fmaxf(sc, d.scale_bound);
-    const float u = (0.5f - v) / s, l = (-0.5f - v) / s;
-    const float lraw = std_cdf(u) - std_cdf(l);
-    float g = d.dlik[n * d.dl_bs + r];
-    if (!(lraw >= d.lik_bound || g < 0.0f)) g = 0.0f;
-    const float pu = std_pdf(u), pl = std_pdf(l);
-    const float dv = g * (pl - pu) / s;
-    float gs = g * (l * pl - u * pu) / s;
-    if (!(sc >= d.scale_bound || gs < 0.0f)) gs = 0.0f;
-    const float sg = w > 0.0f ? 1.0f : (w < 0.0f ? -1.0f : 0.0f);
-    float gy = 0.0f, gmu = 0.0f;
-    if (d.noise) {
-      gy = dv * sg;
-      gmu = -gy;
-    }
-    if (d.dyh) gy += d.dyh[n * d.dyh_bs + r];
-    float* dyp = d.dy + n * d.dy_bs + r;
-    if (d.accum_dy) gy += *dyp;
-    *dyp = gy;
-    d.dmu[n * d.dmu_bs + r] = gmu;
-    d.dsc[n * d.dsc_bs + r] = gs;
+    gc_bwd_tail(d, n, r, out - mu, fmaxf(sc, d.scale_bound), sc, 1.0f);
   }
 }
 

@@ -82,6 +82,38 @@ __device__ __forceinline__ float sigmoid_f(float x) { return 1.0f / (1.0f + expf
 // standard normal CDF and density of the GaussianConditional kernels (entropy.hip, and their stepped form in qstep.hip)
 __device__ __forceinline__ float std_cdf(float t) { return 0.5f * erfcf(-0.70710678118654752440f * t); }
 __device__ __forceinline__ float std_pdf(float t) { return 0.39894228040143267794f * expf(-0.5f * t * t); }
+// Backward of lik = max(Phi(u) - Phi(l), lik_bound), u = (1/2 - |w|) / se, l = (-1/2 - |w|) / se, for one element (n, r):
+// the only statement of it, behind gc_bwd_kernel (entropy.hip: w = out - mu, se = max(scale, scale_bound), inv = 1.0f,
+// and a product by 1.0f is exact) and the stepped kernels of qstep.hip (w in symbol units, se = max(..) * inv).  With
+// pu / pl the densities at u, l:  d lik / d|w| = (pl - pu) / se,  d lik / d se = (l pl - u pu) / se;  dw / dy =
+// -dw / dmu = inv with noise (the rounded value passes nothing), d se / d scale = inv above the scale bound.  The two
+// LowerBound gates: a gradient passes a bound that is active only if it pushes the value up.  d y_hat passes to y
+// unchanged (straight-through) and not to mu.  D: a descriptor with the members of GcBwdDesc (entropy.hip).
+template <class D>
+__device__ __forceinline__ void gc_bwd_tail(const D& d, long long n, long long r, float w, float se, float sc,
+                                            float inv) {
+  const float v = fabsf(w);
+  const float u = (0.5f - v) / se, l = (-0.5f - v) / se;
+  const float lraw = std_cdf(u) - std_cdf(l);
+  float g = d.dlik[n * d.dl_bs + r];
+  if (!(lraw >= d.lik_bound || g < 0.0f)) g = 0.0f;
+  const float pu = std_pdf(u), pl = std_pdf(l);
+  const float dv = g * (pl - pu) / se;
+  float gs = g * (l * pl - u * pu) / se * inv;
+  if (!(sc >= d.scale_bound || gs < 0.0f)) gs = 0.0f;
+  const float sg = w > 0.0f ? 1.0f : (w < 0.0f ? -1.0f : 0.0f);
+  float gy = 0.0f, gmu = 0.0f;
+  if (d.noise) {
+    gy = dv * sg * inv;
+    gmu = -gy;
+  }
+  if (d.dyh) gy += d.dyh[n * d.dyh_bs + r];
+  float* dyp = d.dy + n * d.dy_bs + r;
+  if (d.accum_dy) gy += *dyp;
+  *dyp = gy;
+  d.dmu[n * d.dmu_bs + r] = gmu;
+  d.dsc[n * d.dsc_bs + r] = gs;
+}
 
 __device__ __forceinline__ float apply_act(float v, int act) {
   if (act == ICM_ACT_GELU) return gelu_f(v);

@@ -3,14 +3,11 @@ latent position) of csrc/qstep.hip (icm_gc_likelihood_ste_qm_fwd / _bwd), the R-
 16 x 16 cell of csrc/pointwise.hip (icm_rd_loss_m_fwd / _bwd) and the map painter (icm_qmap_paint).  CPU only; shared by
 tests/test_qmtrain_ref.py (which asserts what the GPU tests rely on) and the GPU tests.
 
-The rule is tests/_qtrain_ref.py's: the likelihood is restated in torch from its definition, in the dtype of its
-inputs, gradients by autograd through the oracle's LowerBound; on ``.double()`` copies it is the reference, in float32
-the yardstick every limit is formed from (FACTOR times the float32 restatement's own error plus the floor of
-tests/_entropy_ref.py; never anything a kernel returned).  y_hat has no tolerance: tests/_qstep_ref.py's numpy
-arithmetic with the step of each position, bit for bit.
-
-The inputs are ``_qtrain_ref.stepped_inputs`` in units of each POSITION's step D = 2^(k / 8), k the map's entry:
-y = mu + D (j + f), integer j out to 6.5 sigma / D, |f| <= 0.45, so float32 and float64 round to the same symbol."""
+The rule, the input generator and the likelihood references are tests/_qtrain_ref.py's own, read with a (step, inv) pair
+per POSITION where that module's cases carry one per image: the inputs are ``_qtrain_ref.inputs_at`` in units of each
+position's step D = 2^(k / 8), k the map's entry, and y_hat is tests/_qstep_ref.py's numpy arithmetic with the step of
+each position, bit for bit.  This module holds what is the map's own: the maps, the step table, the per-cell loss and
+the painter."""
 import functools
 import math
 
@@ -21,7 +18,6 @@ import _entropy_ref as R
 import _pointwise_ref as P
 import _qstep_ref as Q
 import _qtrain_ref as T
-from oracle import wacnn_oracle as O
 
 MAP_CASES = ("strided", "tiny", "long", "uniform")
 BANDED = ("strided", "long", "uniform")      # 21 elements cannot populate five classes: "tiny" is exempt
@@ -72,24 +68,10 @@ def pairs(m):
 @functools.lru_cache(maxsize=None)
 def inputs(case):
     """{y, mu, scale, noise} float32 [N,C,H,W], "qmap" int8 [N,H,W], "step" / "inv" float32 [N,1,H,W]"""
-    shape = shape_of(case)
-    n = int(np.prod(shape))
-    key = "qmn." + case
     m = maps(case)
-    step_p, inv_p = (torch.from_numpy(a) for a in pairs(m))
-    step, inv = (a.expand(shape).reshape(-1) for a in (step_p, inv_p))
-    table = O.scale_table()
-    scale = table[torch.arange(n) % table.numel()] * R.U(key + ".fac", (n,), 0.8, 1.25)
-    scale[:7] = torch.tensor([0.11, R.SCALE_BELOW, R.SCALE_ABOVE, 0.0, -1.0, 1e-3, 300.0])
-    mu = R.U(key + ".mu", (n,), -3.0, 3.0)
-    reach = torch.clamp(6.5 * torch.clamp(scale, min=O.SCALE_BOUND) * inv, min=0.75)
-    u = R.U(key + ".k", (n,), -1.0, 1.0)
-    j = torch.round(torch.sign(u) * u.abs() ** 1.5 * reach)
-    f = R.U(key + ".f", (n,), -0.45, 0.45)
-    y = mu + step * (j + f)
-    noise = R.U(key + ".noise", (n,), -0.5, 0.5)
-    return {"y": y.reshape(shape), "mu": mu.reshape(shape), "scale": scale.reshape(shape),
-            "noise": noise.reshape(shape), "qmap": torch.from_numpy(m), "step": step_p, "inv": inv_p}
+    step, inv = (torch.from_numpy(a) for a in pairs(m))
+    return {**T.inputs_at("qmn." + case, shape_of(case), step, inv), "qmap": torch.from_numpy(m), "step": step,
+            "inv": inv}
 
 
 def per_image_steps(case):
@@ -99,46 +81,8 @@ def per_image_steps(case):
     return torch.tensor(np.array([Q.step_of(int(k)) for k in m[:, 0, 0]], dtype=np.float32))
 
 
-def symbols(inp):
-    shape = inp["y"].shape
-    return torch.from_numpy(Q.symbols(inp["y"].numpy(), inp["mu"].numpy(), inp["inv"].expand(shape).numpy()))
-
-
-def yhat(inp):
-    shape = inp["y"].shape
-    return torch.from_numpy(Q.dequantize(symbols(inp).numpy(), inp["mu"].numpy(), inp["step"].expand(shape).numpy()))
-
-
-def round_flips(inp):
-    """symbols float64 arithmetic would round differently"""
-    t = (inp["y"].double() - inp["mu"].double()) * inp["inv"].double()
-    return int((torch.round(t) != symbols(inp).double()).sum())
-
-
-def value(inp, mode, dtype, y=None, mu=None):
-    """the value the likelihood is taken at, in symbol units: the float32 symbol (eval), or (y - mu) * inv + noise"""
-    if mode == "eval":
-        return symbols(inp).to(dtype)
-    y = inp["y"].to(dtype) if y is None else y
-    mu = inp["mu"].to(dtype) if mu is None else mu
-    return (y - mu) * inp["inv"].to(dtype) + inp["noise"].to(dtype)
-
-
-def raw(inp, mode):
-    """float64 likelihood before the bound"""
-    s = torch.clamp(inp["scale"].double(), min=O.SCALE_BOUND) * inp["inv"].double()
-    return T._cdf_diff(value(inp, mode, torch.float64), s)
-
-
-def oracle(inp, mode, dtype, dlik=None):
-    """the likelihood in ``dtype``: lik, and with a seed (dy, dmu, dscale) of the likelihood alone"""
-    y, mu, sc = (inp[k].detach().to(dtype).requires_grad_(dlik is not None) for k in ("y", "mu", "scale"))
-    s = O.lower_bound(sc, O.SCALE_BOUND) * inp["inv"].to(dtype)
-    lik = O.lower_bound(T._cdf_diff(value(inp, mode, dtype, y, mu), s), O.LIK_BOUND)
-    if dlik is None:
-        return lik.detach()
-    gs = torch.autograd.grad(lik, [y, mu, sc], dlik.to(dtype), allow_unused=True)
-    return lik.detach(), [torch.zeros_like(y) if g is None else g for g in gs]
+# the references of tests/_qtrain_ref.py read "step" / "inv" where an input set carries them
+symbols, yhat, round_flips, raw, oracle = T.symbols, T.yhat, T.round_flips, T.stepped_raw, T.stepped_oracle
 
 
 # ------------------------------------------------------------------------------------------------ per-cell R-D loss

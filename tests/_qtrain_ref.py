@@ -10,7 +10,10 @@ tolerance: it is tests/_qstep_ref.py's ``dequantize(symbols(...))``, bit for bit
 
 Per image n the inputs are those of ``_entropy_ref.gaussian_inputs`` in units of the image's step D_n = 2^(K_n / 8):
 y = mu + D_n (k + f) with integer k out to 6.5 sigma / D_n and |f| <= 0.45, so that round((y - mu) / D_n) is the same
-symbol in float32 and float64."""
+symbol in float32 and float64.
+
+Everything here reads the (step, inv) pair of an element through ``pair_of``, so it serves a pair per position as well:
+tests/_qmtrain_ref.py builds its inputs with ``inputs_at`` and uses these references as they stand."""
 import functools
 import math
 
@@ -37,17 +40,11 @@ def step_pairs(case):
     return torch.tensor(np.array([Q.step_of(k) for k in QSTEPS[case]], dtype=np.float32))
 
 
-@functools.lru_cache(maxsize=None)
-def stepped_inputs(case):
-    """{y, mu, scale, noise} float32 [N,C,H,W] and "steps" float32 [N, 2]"""
-    shape = shape_of(case)
-    N = shape[0]
+def inputs_at(key, shape, step, inv):
+    """{y, mu, scale, noise} float32 [N,C,H,W] in units of the float32 ``step`` / ``inv``, which broadcast against
+    ``shape``: y = mu + step (k + f), integer k out to 6.5 sigma inv and |f| <= 0.45.  ``key`` prefixes the RNG keys."""
     n = int(np.prod(shape))
-    key = "qtn." + case
-    steps = step_pairs(case)
-    assert steps.shape[0] == N
-    step = steps[:, 0].reshape(N, 1).expand(N, n // N).reshape(-1)
-    inv = steps[:, 1].reshape(N, 1).expand(N, n // N).reshape(-1)
+    step, inv = (a.expand(shape).reshape(-1) for a in (step, inv))
     table = O.scale_table()
     scale = table[torch.arange(n) % table.numel()] * R.U(key + ".fac", (n,), 0.8, 1.25)
     scale[:7] = torch.tensor([0.11, R.SCALE_BELOW, R.SCALE_ABOVE, 0.0, -1.0, 1e-3, 300.0])
@@ -60,31 +57,42 @@ def stepped_inputs(case):
     y = mu + step * (k + f)
     noise = R.U(key + ".noise", (n,), -0.5, 0.5)
     return {"y": y.reshape(shape), "mu": mu.reshape(shape), "scale": scale.reshape(shape),
-            "noise": noise.reshape(shape), "steps": steps}
+            "noise": noise.reshape(shape)}
 
 
-def _per_image(steps, col, dtype):
-    return steps[:, col].to(dtype).reshape(-1, 1, 1, 1)
+def pair_of(inp):
+    """float32 (step, inv) of an input set, broadcasting against [N,C,H,W]: its "step" / "inv" where it carries them
+    ([N,1,H,W], a pair per position: tests/_qmtrain_ref.py), else the columns of "steps" [N, 2] as [N,1,1,1]"""
+    if "inv" in inp:
+        return inp["step"], inp["inv"]
+    return tuple(inp["steps"][:, c].reshape(-1, 1, 1, 1) for c in (0, 1))
+
+
+@functools.lru_cache(maxsize=None)
+def stepped_inputs(case):
+    """{y, mu, scale, noise} float32 [N,C,H,W] and "steps" float32 [N, 2]"""
+    shape = shape_of(case)
+    steps = step_pairs(case)
+    assert steps.shape[0] == shape[0]
+    return {**inputs_at("qtn." + case, shape, *pair_of({"steps": steps})), "steps": steps}
 
 
 def symbols(inp):
-    """the float32 symbols round((y - mu) * inv), int32 [N,C,H,W]: tests/_qstep_ref.py's, image by image"""
-    out = [Q.symbols(inp["y"][n].numpy(), inp["mu"][n].numpy(), inp["steps"][n, 1].item())
-           for n in range(inp["y"].shape[0])]
-    return torch.from_numpy(np.stack(out))
+    """the float32 symbols round((y - mu) * inv), int32 [N,C,H,W]: tests/_qstep_ref.py's, with the pair of each element"""
+    shape = inp["y"].shape
+    return torch.from_numpy(Q.symbols(inp["y"].numpy(), inp["mu"].numpy(), pair_of(inp)[1].expand(shape).numpy()))
 
 
 def yhat(inp):
     """float32 y_hat = (float)symbol * step + mu, two roundings: tests/_qstep_ref.py's dequantize"""
-    sym = symbols(inp).numpy()
-    out = [Q.dequantize(sym[n], inp["mu"][n].numpy(), inp["steps"][n, 0].item()) for n in range(sym.shape[0])]
-    return torch.from_numpy(np.stack(out))
+    shape = inp["y"].shape
+    return torch.from_numpy(Q.dequantize(symbols(inp).numpy(), inp["mu"].numpy(),
+                                         pair_of(inp)[0].expand(shape).numpy()))
 
 
 def round_flips(inp):
     """symbols float64 arithmetic would round differently"""
-    d = R.cast({k: inp[k] for k in ("y", "mu")}, torch.float64)
-    t = (d["y"] - d["mu"]) * _per_image(inp["steps"], 1, torch.float64)
+    t = (inp["y"].double() - inp["mu"].double()) * pair_of(inp)[1].double()
     return int((torch.round(t) != symbols(inp).double()).sum())
 
 
@@ -94,7 +102,7 @@ def stepped_value(inp, mode, dtype, y=None, mu=None):
         return symbols(inp).to(dtype)
     y = inp["y"].to(dtype) if y is None else y
     mu = inp["mu"].to(dtype) if mu is None else mu
-    return (y - mu) * _per_image(inp["steps"], 1, dtype) + inp["noise"].to(dtype)
+    return (y - mu) * pair_of(inp)[1].to(dtype) + inp["noise"].to(dtype)
 
 
 def _cdf_diff(v, s):
@@ -105,14 +113,14 @@ def _cdf_diff(v, s):
 
 def stepped_raw(inp, mode):
     """float64 likelihood before the bound"""
-    s = torch.clamp(inp["scale"].double(), min=O.SCALE_BOUND) * _per_image(inp["steps"], 1, torch.float64)
+    s = torch.clamp(inp["scale"].double(), min=O.SCALE_BOUND) * pair_of(inp)[1].double()
     return _cdf_diff(stepped_value(inp, mode, torch.float64), s)
 
 
 def stepped_oracle(inp, mode, dtype, dlik=None):
     """the stepped likelihood in ``dtype``: lik, and with a seed (dy, dmu, dscale) of the likelihood alone"""
     y, mu, sc = (inp[k].detach().to(dtype).requires_grad_(dlik is not None) for k in ("y", "mu", "scale"))
-    s = O.lower_bound(sc, O.SCALE_BOUND) * _per_image(inp["steps"], 1, dtype)
+    s = O.lower_bound(sc, O.SCALE_BOUND) * pair_of(inp)[1].to(dtype)
     lik = O.lower_bound(_cdf_diff(stepped_value(inp, mode, dtype, y, mu), s), O.LIK_BOUND)
     if dlik is None:
         return lik.detach()
