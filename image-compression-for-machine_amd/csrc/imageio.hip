@@ -10,6 +10,8 @@
 //   image_sse_finish_kernel  adds the partial sums (64-bit integers: exact, whatever the order)
 //   image_tile_blend_kernel  adds one decoded tile's window, weighted by its seam ramps, into the f32 canvas of a
 //                            tiled image (planar [3, PH, PW] -> planar [3, H, W]); a thread owns four pixels of a row
+//   image_cell_stats_kernel  interleaved [H, W, 3] bytes -> (n, sum Y, sum Y^2) of the integer luma over every 16 x 16
+//                            cell of the padded image's grid (the encoder's variance-adaptive quality maps)
 //
 // Pure bandwidth work.  A thread owns a run of 16 pixels of one row: 48 interleaved bytes = three 16-byte accesses,
 // and 16 floats = four 16-byte accesses in each of the three planes.  Whether the 16-byte form may be used is decided
@@ -70,6 +72,27 @@ __device__ __forceinline__ void gather_run(const uint8_t* row, int sx0, int W, u
       }
     }
   }
+}
+
+// the 48 bytes of a run that starts at p, whatever its byte residue, through the dword-aligned window around them (the
+// access image_batch_u8_to_f32_kernel describes and spells out in its own body).  The window may begin up to 3 bytes
+// before the run and end up to 3 bytes after it, so it is read only for a run that lies inside its row (in_row) and
+// whose window lies inside the image's bytes [img, end); false, and w untouched, otherwise
+__device__ __forceinline__ bool load_run_window(bool in_row, const uint8_t* p, const uint8_t* img, const uint8_t* end,
+                                                uint32_t (&w)[12]) {
+  const uint32_t res = (uint32_t)(reinterpret_cast<uintptr_t>(p) & 3);
+  const uint32_t* a = reinterpret_cast<const uint32_t*>(p - res);
+  if (in_row && reinterpret_cast<const uint8_t*>(a) >= img &&
+      reinterpret_cast<const uint8_t*>(a) + (res ? 52 : 48) <= end) {
+    uint32_t t[13];
+#pragma unroll
+    for (int k = 0; k < 12; ++k) t[k] = a[k];
+    t[12] = res ? a[12] : 0u;
+#pragma unroll
+    for (int k = 0; k < 12; ++k) w[k] = __builtin_amdgcn_alignbyte(t[k + 1], t[k], res);
+    return true;
+  }
+  return false;
 }
 
 // a run's 48 interleaved bytes -> 16 floats in each of the three planes, out = the run's first element of plane 0.
@@ -394,6 +417,72 @@ __global__ __launch_bounds__(BLOCK) void image_tile_blend_kernel(const float* __
   }
 }
 
+// Luma statistics of the 16 x 16 cells of a padded image's grid: pixel (y, x) lies in cell ((top + y) / 16,
+// (left + x) / 16), Y = (77 R + 150 G + 29 B + 128) >> 8, and a cell's (n, s1, s2) = (its image pixels, sum Y, sum Y^2);
+// pad pixels are no pixels.  A workgroup takes a strip of STRIP cells of one row of cells: thread t owns the run of 16
+// pixels of row t / 16 of cell t % 16, so a wave reads four image rows of 768 contiguous bytes each -- through the
+// dword window wherever the run lies inside its row (3 W bytes a row and an arbitrary left: 16-byte alignment is the
+// exception, as for the batch crops), byte by byte at the image's edges.  Bytes outside the image stay zero and give
+// Y = 0, so only n has to know about them.  The four rows a wave holds of a cell are added by two shuffles, the four
+// waves' partials through LDS, and 3 STRIP threads store the strip's 3 STRIP contiguous integers: every entry of stats is
+// written once, by plain vector stores.  Integer sums (s2 <= 256 * 255^2 < 2^24): exact in any order.
+constexpr int CELL = 16;
+constexpr int STRIP = BLOCK / CELL;   // cells per workgroup
+static_assert(CELL == RUN && STRIP == 16 && BLOCK == 256, "a thread owns one row of one cell; four waves of four rows");
+
+__global__ __launch_bounds__(BLOCK) void image_cell_stats_kernel(const uint8_t* __restrict__ img, int H, int W, int top,
+                                                                  int left, int gw, int strips,
+                                                                  int32_t* __restrict__ stats) {
+  __shared__ int32_t red[BLOCK / 64][3 * STRIP];
+  const int cy = blockIdx.x / strips;
+  const int cx0 = (blockIdx.x - cy * strips) * STRIP;
+  const int cell = threadIdx.x & (STRIP - 1), r = threadIdx.x / STRIP;
+  const int y = cy * CELL + r - top, x0 = (cx0 + cell) * CELL - left;
+
+  uint32_t w[12];
+#pragma unroll
+  for (int k = 0; k < 12; ++k) w[k] = 0u;
+  int n = 0;
+  if ((unsigned)y < (unsigned)H && x0 + RUN > 0 && x0 < W) {
+    const uint8_t* row = img + ((size_t)y * W) * 3;
+    if (load_run_window(x0 >= 0 && x0 + RUN <= W, row + (size_t)x0 * 3, img, img + (size_t)H * W * 3, w)) {
+      n = RUN;
+    } else {
+      gather_run(row, x0, W, w);
+      n = min(x0 + RUN, W) - max(x0, 0);
+    }
+  }
+  int s1 = 0, s2 = 0;
+#pragma unroll
+  for (int px = 0; px < RUN; ++px) {
+    uint32_t c[3];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+      const int b = 3 * px + k;
+      c[k] = (w[b >> 2] >> (8 * (b & 3))) & 255u;
+    }
+    const int Y = (int)((77u * c[0] + 150u * c[1] + 29u * c[2] + 128u) >> 8);
+    s1 += Y;
+    s2 += Y * Y;
+  }
+#pragma unroll
+  for (int m = STRIP; m < 64; m <<= 1) {   // lanes cell, cell + 16, cell + 32, cell + 48: the wave's four rows
+    n += __shfl_xor(n, m, 64);
+    s1 += __shfl_xor(s1, m, 64);
+    s2 += __shfl_xor(s2, m, 64);
+  }
+  if ((threadIdx.x & 63) < STRIP) {
+    int32_t* o = red[threadIdx.x >> 6] + 3 * cell;
+    o[0] = n;
+    o[1] = s1;
+    o[2] = s2;
+  }
+  __syncthreads();
+  if (threadIdx.x < 3 * STRIP && cx0 + (int)threadIdx.x / 3 < gw)
+    stats[((size_t)cy * gw + cx0) * 3 + threadIdx.x] =
+        (red[0][threadIdx.x] + red[1][threadIdx.x]) + (red[2][threadIdx.x] + red[3][threadIdx.x]);
+}
+
 // runs of a rows x cols image and the workgroups that cover them; false = geometry out of range
 bool run_grid(int rows, int cols, int& runs_per_row, long long& total_runs, int& blocks) {
   if (rows <= 0 || cols <= 0 || rows > MAX_SIDE || cols > MAX_SIDE) return false;
@@ -476,6 +565,20 @@ int icm_image_tile_blend(const float* src, int PH, int PW, int top, int left, in
   const long long total = (long long)h * rpr;                                    // <= 32768 * 8192
   hipLaunchKernelGGL(image_tile_blend_kernel, dim3((unsigned)((total + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, ST, src, PH,
                      PW, top, left, h, w, canvas, H, W, y0, x0, ramp, m, edges, rpr, total);
+  ICM_CHECK_LAUNCH();
+  return ICM_OK;
+}
+
+int icm_image_cell_stats(const uint8_t* img, int H, int W, int top, int left, int gh, int gw, int32_t* stats,
+                         void* stream) {
+  constexpr int MAX_CELLS = 1 << 26;   // 16 x (a cell index, one strip past the grid) stays an int
+  if (!img || !stats || H < 1 || W < 1 || gh < 1 || gw < 1 || top < 0 || left < 0) return ICM_ERR_ARG;
+  if (gh > MAX_CELLS || gw > MAX_CELLS) return ICM_ERR_ARG;
+  if ((long long)top + H > (long long)CELL * gh || (long long)left + W > (long long)CELL * gw) return ICM_ERR_ARG;
+  const int strips = (gw + STRIP - 1) / STRIP;
+  if ((long long)gh * strips > 0x7fffffffLL) return ICM_ERR_ARG;
+  hipLaunchKernelGGL(image_cell_stats_kernel, dim3((unsigned)(gh * strips)), dim3(BLOCK), 0, ST, img, H, W, top, left, gw,
+                     strips, stats);
   ICM_CHECK_LAUNCH();
   return ICM_OK;
 }

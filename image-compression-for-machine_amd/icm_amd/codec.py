@@ -2,6 +2,7 @@
 
     python -m icm_amd.codec encode IMAGE -o FILE -a cnn -p CKPT [--tile N [--overlap M]] [--coder {host,lanes}]
                                    [--qstep K | --target-bytes N | --target-bpp F] [--roi Y0,X0,H,W:D ...] [--rdoq W]
+                                   [--aq S]
     python -m icm_amd.codec decode FILE -o IMAGE.png -p CKPT [--reference IMAGE] [--region Y0,X0,H,W]
 
 Parity unpinned: no counterpart in the reference (upstream CompressAI's ``examples/codec.py`` is not in its tree).  The
@@ -41,7 +42,14 @@ them.  Parity unpinned: no counterpart in the reference, whose own answer is a t
 ``--rdoq W`` turns on rate-distortion optimised quantisation in the encoder: each latent element is coded as the nearest
 integer or, where W x the added squared error in quantiser steps is less than the bits the coder's tables say it saves,
 as its neighbour toward zero (``icm_gc_code_rdo`` in csrc/qstep.hip).  It combines with every other flag, changes
-nothing in the stream's format, and ``decode`` neither has nor needs a flag.  Parity unpinned."""
+nothing in the stream's format, and ``decode`` neither has nor needs a flag.  Parity unpinned.
+
+``--aq S`` derives the quality map from the picture, as video encoders' variance-based adaptive quantisation does: one
+pass over the 8-bit image gives every cell the variance v of its luma (``icm_image_cell_stats`` in csrc/imageio.hip),
+and the cell is coded with the step index K + clip(rint(4 S (log2(1 + v) - the image's mean of it)), -16, 16).  S > 0
+spends bits on flat cells and saves them on busy ones, S < 0 the reverse; |S| <= 4.  S = 1 makes the step follow the
+cell's standard deviation: a rule, not a measured optimum.  ``--roi`` rectangles win over it, a budget search runs over K
+with the offsets fixed, tiles share the image's mean, and ``decode`` needs no flag.  Parity unpinned."""
 from __future__ import annotations
 
 import argparse
@@ -254,6 +262,87 @@ def clip_rois(rois, y0: int, x0: int, h: int, w: int) -> List[Tuple[int, int, in
     return out
 
 
+# ------------------------------------------------------------------------------------ variance-adaptive quantisation
+AQ_STRENGTH_MAX = 4.0  # |strength| of ``--aq``
+AQ_MAX_OFFSET = 16     # |offset| to the background step index: two octaves of the step
+
+
+def check_aq(strength, who: str = "") -> Optional[float]:
+    """The strength of the encoder's variance-adaptive quantisation: None and 0 mean off and come back as None;
+    otherwise a real number, not a bool, finite, with 0 < |strength| <= AQ_STRENGTH_MAX, as a Python float.
+    ValueError otherwise.  Nothing of it travels in a stream."""
+    if strength is None:
+        return None
+    if isinstance(strength, bool) or not isinstance(strength, (int, float, np.integer, np.floating)):
+        raise ValueError(f"{who}aq must be a number, got {strength!r}")
+    s = float(strength)
+    if not (math.isfinite(s) and abs(s) <= AQ_STRENGTH_MAX):
+        raise ValueError(f"{who}aq must be finite with |aq| <= {AQ_STRENGTH_MAX}, got {strength!r}")
+    return s if s else None
+
+
+def cell_stats(u8: torch.Tensor, pads: Tuple[int, int, int, int]) -> np.ndarray:
+    """device 8-bit [H, W, 3] -> host int32 [gh, gw, 3]: per 16 x 16 cell of the grid of the image padded by ``pads`` =
+    (left, right, top, bottom) the number of image pixels in it, the sum of their integer luma and the sum of its
+    squares (``icm_image_cell_stats``; pad pixels are not counted).  gh, gw = ceil((top + H + bottom) / 16), ...: with
+    ``pads`` = (0, 0, 0, 0) the grid anchored at the image's first pixel."""
+    H, W = u8.size(0), u8.size(1)
+    left, right, top, bottom = (int(p) for p in pads)
+    gh, gw = -(-(top + H + bottom) // CELL), -(-(left + W + right) // CELL)
+    out = torch.empty((gh, gw, 3), dtype=torch.int32, device=u8.device)
+    check(L.lib().icm_image_cell_stats(u8.data_ptr(), H, W, top, left, gh, gw, out.data_ptr(), L.stream()),
+          "image_cell_stats")
+    return out.cpu().numpy()
+
+
+def aq_activity(stats) -> np.ndarray:
+    """float64 [gh, gw]: log2(1 + v), v = (n s2 - s1^2) / n^2 the variance of the luma over the cell's image pixels
+    (``cell_stats``; the numerator is an exact integer in float64); nan where the cell holds none.  Host-only."""
+    s = np.asarray(stats).astype(np.float64)
+    n, s1, s2 = s[..., 0], s[..., 1], s[..., 2]
+    with np.errstate(invalid="ignore", divide="ignore"):
+        act = np.log2(1.0 + (n * s2 - s1 * s1) / (n * n))
+    act[n == 0] = np.nan
+    return act
+
+
+def aq_reference(stats) -> float:
+    """what "average" means to ``aq_offsets``: the mean activity over the cells that hold a pixel, of the anchored grid
+    of the whole image (``cell_stats`` with pads (0, 0, 0, 0)), so that all tiles of a tiled image share it.  Host-only."""
+    act = aq_activity(stats)
+    return float(np.mean(act[~np.isnan(act)]))
+
+
+def aq_offsets(stats, strength: float, ref: float) -> np.ndarray:
+    """int8 [gh, gw], the cells' offsets to the background step index: clip(rint(4 strength (activity - ref)),
+    -AQ_MAX_OFFSET, AQ_MAX_OFFSET), ties to even, 0 where the cell holds no pixel.  The step index has 8 steps per octave
+    of the step and a doubled variance is half an octave of amplitude, hence the 4: at strength 1 the step follows the
+    cell's standard deviation relative to the reference's.  A rule, not a measured optimum.  Positive strength: flat
+    cells finer, busy cells coarser.  Host-only."""
+    act = aq_activity(stats)
+    d = np.rint(4.0 * float(strength) * (np.where(np.isnan(act), ref, act) - ref))
+    return np.clip(d, -AQ_MAX_OFFSET, AQ_MAX_OFFSET).astype(np.int8)
+
+
+def quality_map(H: int, W: int, pads, base: int, rois, offsets=None) -> np.ndarray:
+    """``roi_map`` on a background that varies: every cell starts at clamp(base + offsets[cell], QSTEP_MIN, QSTEP_MAX)
+    (``aq_offsets`` of the same grid), then the rectangles are painted as ``roi_map`` paints them, each with
+    clamp(base + d): they win over the offsets.  ``offsets`` None: ``roi_map`` itself.  Host-only."""
+    m = roi_map(H, W, pads, base, rois)
+    if offsets is None:
+        return m
+    offsets = np.asarray(offsets)
+    if offsets.shape != m.shape or offsets.dtype.kind != "i":
+        raise ValueError(f"codec: offsets must be integers of the map's size {m.shape}, got {offsets.dtype} "
+                         f"{offsets.shape}")
+    left, top = int(pads[0]), int(pads[2])
+    m = np.clip(int(base) + offsets.astype(np.int64), B.QSTEP_MIN, B.QSTEP_MAX).astype(np.int8)
+    for y0, x0, h, w, d in check_rois(rois, H, W):
+        k = min(max(int(base) + d, B.QSTEP_MIN), B.QSTEP_MAX)
+        m[(top + y0) // CELL:(top + y0 + h - 1) // CELL + 1, (left + x0) // CELL:(left + x0 + w - 1) // CELL + 1] = k
+    return m
+
+
 def search_qstep(fits, lo: int = B.QSTEP_MIN, hi: int = B.QSTEP_MAX) -> Tuple[int, int]:
     """Smallest step index the bisection finds whose encode fits a budget -> (k, number of probes).  ``fits(k)`` makes
     the encode at k and says whether it fits; the size need not be monotone in k, and the guarantee asks for nothing
@@ -286,14 +375,16 @@ def search_qstep(fits, lo: int = B.QSTEP_MIN, hi: int = B.QSTEP_MAX) -> Tuple[in
 def encode_image_info(model, img, tile: Optional[int] = None, overlap: int = 0, coder: str = "host",
                       symbols_per_wave: Optional[int] = None, qstep: int = 0,
                       max_bytes: Optional[int] = None, roi: Optional[Sequence] = None,
-                      rdoq: Optional[float] = None) -> Tuple[bytes, Dict]:
+                      rdoq: Optional[float] = None, aq: Optional[float] = None) -> Tuple[bytes, Dict]:
     """``encode_image`` with its outcome: (stream, {"qstep": k, "step": 2^(k/8), "probes": encodes made}); k is the
-    background step.  With ``roi`` also "roi_cells", the number of latent cells (summed over the tiles) whose step
-    index differs from k, and "qmap_range": [smallest, largest step index in the maps].  With ``rdoq`` also "rdoq", the
-    weight as the kernel took it."""
+    background step.  With ``roi`` or ``aq`` also "roi_cells", the number of latent cells (summed over the tiles) whose
+    step index differs from k, and "qmap_range": [smallest, largest step index in the maps].  With ``rdoq`` also "rdoq",
+    the weight as the kernel took it.  With ``aq`` also "aq", the strength as checked, "aq_ref", the image's reference
+    activity, and "aq_offset_range": [smallest, largest offset over all tiles]."""
     B.check_coder(coder, "codec: ")
     qstep = B.check_qstep(qstep, "codec: ")
     rdoq = B.check_rdoq(rdoq, "codec: ")
+    aq = check_aq(aq, "codec: ")
     rd = _rdoq_kw(rdoq)
     if max_bytes is not None:
         if qstep != 0:
@@ -317,13 +408,23 @@ def encode_image_info(model, img, tile: Optional[int] = None, overlap: int = 0, 
     # regions of interest: per tile the rectangles clipped to it, in its coordinates; the map of a tile is built from
     # them with the tile's own pads, per probe, and a map that comes out uniform is coded as its scalar step
     rois = None if roi is None else check_rois(roi, H, W)
-    tile_rois = None if roi is None else [clip_rois(rois, *t) for t in plan]
+    tile_rois = [[]] * len(plan) if roi is None else [clip_rois(rois, *t) for t in plan]
+    # variance-adaptive quantisation: once per encode the reference activity of the whole image on the grid anchored at
+    # its first pixel, and per tile the offsets of its own grid (the tile's pads) against that one reference; the
+    # probes of a budget search move k under fixed offsets
+    offsets, told = [None] * len(plan), dict(rd)
+    if aq is not None:
+        aq_ref = aq_reference(cell_stats(u8, (0, 0, 0, 0)))
+        offsets = [aq_offsets(cell_stats(c, center_pads(c.size(0), c.size(1))), aq, aq_ref) for c in crops]
+        told.update(aq=aq, aq_ref=aq_ref, aq_offset_range=[int(min(o.min() for o in offsets)),
+                                                           int(max(o.max() for o in offsets))])
 
     def maps(k):
-        """the tiles' quality maps at the background step k (None: no rectangles were given), and what they hold"""
-        if tile_rois is None:
+        """the tiles' quality maps at the background step k (None: neither rectangles nor offsets were given), and
+        what they hold"""
+        if roi is None and aq is None:
             return [None] * len(plan), {}
-        ms = [roi_map(h, w, center_pads(h, w), k, r) for (_, _, h, w), r in zip(plan, tile_rois)]
+        ms = [quality_map(h, w, center_pads(h, w), k, r, o) for (_, _, h, w), r, o in zip(plan, tile_rois, offsets)]
         return ms, {"roi_cells": int(sum(int((m != k).sum()) for m in ms)),
                     "qmap_range": [int(min(m.min() for m in ms)), int(max(m.max() for m in ms))]}
 
@@ -334,7 +435,7 @@ def encode_image_info(model, img, tile: Optional[int] = None, overlap: int = 0, 
         ms, extra = maps(qstep)
         data = wrap([_encode_one(model, arch, fp, c, coder, symbols_per_wave, 0 if m is not None else qstep, m, rdoq)
                      for c, m in zip(crops, ms)])
-        return data, {"qstep": qstep, "step": B.step_of(qstep)[0], "probes": 1, **extra, **rd}
+        return data, {"qstep": qstep, "step": B.step_of(qstep)[0], "probes": 1, **extra, **told}
     # encode to size: the analysis transform once per tile, then only the latent coder per probe; a probe is the very
     # container that would be written (headers, CRCs and the lanes coder's flushes included), and the answer is the
     # stream of its probe, not a second encode
@@ -362,12 +463,12 @@ def encode_image_info(model, img, tile: Optional[int] = None, overlap: int = 0, 
     except ValueError:
         raise ValueError(f"codec: {max_bytes} bytes are out of reach: the coarsest step (qstep {B.QSTEP_MAX}) still "
                          f"takes {min(sizes.values())} bytes")
-    return kept[k][0], {"qstep": k, "step": B.step_of(k)[0], "probes": probes, **kept[k][1], **rd}
+    return kept[k][0], {"qstep": k, "step": B.step_of(k)[0], "probes": probes, **kept[k][1], **told}
 
 
 def encode_image(model, img, tile: Optional[int] = None, overlap: int = 0, coder: str = "host",
                  symbols_per_wave: Optional[int] = None, qstep: int = 0, max_bytes: Optional[int] = None,
-                 roi: Optional[Sequence] = None, rdoq: Optional[float] = None) -> bytes:
+                 roi: Optional[Sequence] = None, rdoq: Optional[float] = None, aq: Optional[float] = None) -> bytes:
     """8-bit [H, W, 3] image (tensor on any device, or anything ``numpy.asarray`` accepts) -> one bit-stream.  With
     ``tile``, an image of more than one tile (``plan_tiles``) becomes an ICMT stream whose tile k is
     ``encode_image(model, crop k)``, the tiles coded one after another; an image of one tile is written untiled.
@@ -382,8 +483,13 @@ def encode_image(model, img, tile: Optional[int] = None, overlap: int = 0, coder
     tile in a tiled one.  No rectangle, or none that changes a cell, gives byte for byte the stream without ``roi``.
     ``rdoq``: weight of rate-distortion optimised quantisation (``model.compress``; None, the default: off, and the
     stream is what it is without).  Every tile and, with ``max_bytes``, every probe of the unchanged search is coded
-    with it.  The stream says nothing of it and decodes as any other."""
-    return encode_image_info(model, img, tile, overlap, coder, symbols_per_wave, qstep, max_bytes, roi, rdoq)[0]
+    with it.  The stream says nothing of it and decodes as any other.
+    ``aq``: strength of variance-adaptive quantisation, 0 < |aq| <= AQ_STRENGTH_MAX (None or 0, the default: off, and
+    the stream is what it is without): the quality map is derived from the image, each cell's offset to k following the
+    variance of its luma against the image's average (``aq_offsets``; positive: flat cells finer, busy cells coarser).
+    Rectangles of ``roi`` win over it; a budget search moves k under the fixed offsets; the tiles of a tiled image
+    share one reference.  A flat image, or a strength at which every offset rounds to 0, gives the stream without."""
+    return encode_image_info(model, img, tile, overlap, coder, symbols_per_wave, qstep, max_bytes, roi, rdoq, aq)[0]
 
 
 def _check_model(header: Dict, arch: str, fp: int, what: str = "the stream") -> None:
@@ -584,6 +690,11 @@ def setup_args() -> argparse.ArgumentParser:
                      help="rate-distortion optimised quantisation: code a latent element one symbol nearer zero where "
                           "W x the added squared error (in quantiser steps) is less than the bits it saves; W > 0, "
                           "smaller: smaller file (default: off)")
+    enc.add_argument("--aq", default=None, type=float, metavar="S",
+                     help=f"variance-adaptive quantisation: derive the quality map from the image, each 16 x 16 cell's "
+                          f"step index offset by 4 S x (log2 of its luma variance against the image's mean), within "
+                          f"+-{AQ_MAX_OFFSET}; S > 0: flat cells finer, busy cells coarser; |S| <= {AQ_STRENGTH_MAX:g} "
+                          f"(default: off)")
     for s in (enc, dec):
         s.add_argument("-o", "--output", required=True, help="file to write")
         s.add_argument("-p", "--path", dest="paths", required=True, type=str, help="checkpoint path")
@@ -625,6 +736,7 @@ def main(argv) -> int:
             if args.target_bpp is not None and not (args.target_bpp > 0 and math.isfinite(args.target_bpp)):
                 raise ValueError(f"--target-bpp must be a positive number, got {args.target_bpp}")
             B.check_rdoq(args.rdoq, "--")
+            check_aq(args.aq, "--")
         except ValueError as e:
             print(f"Error: {e}", file=sys.stderr)
             return 2
@@ -662,7 +774,8 @@ def main(argv) -> int:
             h, w = payload.shape[:2]
             budget = args.target_bytes if args.target_bpp is None else int(math.floor(args.target_bpp * h * w / 8))
             data, found = encode_image_info(model, payload, args.tile, args.overlap, coder=args.coder,
-                                            qstep=args.qstep or 0, max_bytes=budget, roi=args.roi, rdoq=args.rdoq)
+                                            qstep=args.qstep or 0, max_bytes=budget, roi=args.roi, rdoq=args.rdoq,
+                                            aq=args.aq)
             torch.cuda.synchronize()
             dt = time.perf_counter() - t0
             with open(args.output, "wb") as f:

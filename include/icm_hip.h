@@ -599,6 +599,19 @@ int icm_image_u8_to_f32(const uint8_t* src, int H, int W, float* dst, int OH, in
 int icm_image_f32_to_u8(const float* src, int PH, int PW, int top, int left, uint8_t* dst, int H, int W,
                         const uint8_t* ref, int64_t* sse, void* ws, int64_t ws_bytes, void* stream);
 
+/* ---- luma statistics per latent cell (icm_amd/codec.py, variance-adaptive quality maps of the encoder; no counterpart
+ * in the reference).  img = interleaved [H, W, 3] bytes; the grid of gh x gw cells of 16 x 16 pixels is that of the
+ * image padded by top rows and left columns: pixel (y, x) lies in cell ((top + y) / 16, (left + x) / 16).  With the
+ * integer luma Y = (77 R + 150 G + 29 B + 128) >> 8 (0..255), stats = [gh][gw][3] int32 = (n, s1, s2) per cell: n the
+ * image pixels in the cell (0..256; pad pixels are no pixels, a cell wholly in the padding holds 0, 0, 0), s1 the sum
+ * of Y (<= 65 280), s2 the sum of Y^2 (<= 16 646 400).  Integer sums: exact, whatever the order.  Every entry of stats
+ * is written exactly once, the caller does not clear it.  One launch, no atomics, no allocation, no synchronisation
+ * (graph-capturable); one streaming read of the 3 H W bytes.  No pointer needs more than its natural alignment.
+ * ICM_ERR_ARG before the launch: null pointers, H, W, gh or gw < 1, top or left < 0, a grid that does not cover the
+ * image (top + H > 16 gh or left + W > 16 gw), gh or gw above 2^26 (or more than 2^31 - 1 workgroups). */
+int icm_image_cell_stats(const uint8_t* img, int H, int W, int top, int left, int gh, int gw, int32_t* stats,
+                         void* stream);
+
 /* ---- assembly of a tiled image (icm_amd/codec.py, ICMT streams; no counterpart in the reference).  One decoded tile
  * is added into the zero-filled f32 canvas of the image, its overlap bands weighted by a ramp:
  *   canvas[c][y0 + y][x0 + x] = canvas[c][y0 + y][x0 + x] + (wy(y) * wx(x)) * src[c][top + y][left + x]
