@@ -9,7 +9,7 @@ objs=""
 pids=""
 for f in conv_igemm conv_1x1 conv_ks8 conv_wino conv_wgrad wgrad_wino pointwise entropy qstep msssim imageio rans_lanes winattn winattn_mfma; do
   stale=0
-  for dep in csrc/$f.hip csrc/icm_common.h ../include/icm_hip.h $(for h in conv_common.h winattn_common.h rans_lanes_common.h; do grep -q $h csrc/$f.hip && echo csrc/$h; done); do
+  for dep in csrc/$f.hip csrc/icm_common.h ../include/icm_hip.h $(for h in conv_common.h winattn_common.h rans_lanes_common.h image_u8.h; do grep -q $h csrc/$f.hip && echo csrc/$h; done); do
     if [ ! -f build/$f.o ] || [ $dep -nt build/$f.o ]; then stale=1; fi
   done
   if [ $stale = 1 ]; then

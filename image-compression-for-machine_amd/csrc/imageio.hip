@@ -24,8 +24,11 @@
 // The way back is clamp to [0, 1], one f32 multiplication by 255 (correctly rounded on every target) and truncation.
 // NaN input to image_f32_to_u8 is unspecified.
 #include "icm_common.h"
+#include "image_u8.h"
 
 namespace {
+
+using icm::quantise_u8;   // clamp(0, 1).mul(255).to(uint8): image_u8.h
 
 constexpr int RUN = 16;        // pixels per thread
 constexpr int BLOCK = 256;
@@ -197,10 +200,6 @@ __global__ __launch_bounds__(BLOCK) void image_batch_u8_to_f32_kernel(const uint
   }
   const size_t plane = (size_t)CH * CW;
   store_run(lut, w, dst + (size_t)b * 3 * plane + (size_t)oy * CW + ox0, plane, ox0, CW, dvec);
-}
-
-__device__ __forceinline__ uint32_t quantise_u8(float v) {
-  return (uint32_t)(int)(fminf(fmaxf(v, 0.0f), 1.0f) * 255.0f);   // clamp(0, 1).mul(255).to(uint8)
 }
 
 __global__ __launch_bounds__(BLOCK) void image_f32_to_u8_kernel(const float* __restrict__ src, int PH, int PW, int top,

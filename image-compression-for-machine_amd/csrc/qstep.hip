@@ -50,6 +50,7 @@
 #include <cmath>
 #include <initializer_list>
 #include "icm_common.h"
+#include "image_u8.h"
 
 namespace icm {
 
@@ -326,9 +327,16 @@ __global__ __launch_bounds__(256) void gc_qm_bwd_kernel(const GcQsBwdDesc d, con
 
 // ---- painting the training maps on the device: qmap [N][h][w] int8; every cell of image n holds base[n], then the R
 // rectangles rects[n][r] = (y0, x0, y1, x1, k) (cells, half open) are painted in order, later ones winning
-// (icm_amd/codec.py: roi_map).  One lane per cell walks the image's rectangles (R is small and the reads are
-// wave-uniform) and stores once; a rectangle is clipped to the map by the test itself, an empty one holds no cell.
+// (icm_amd/codec.py: roi_map).  One lane per cell walks the image's rectangles (paint_cell: R is small and the reads
+// are wave-uniform) and stores once; a rectangle is clipped to the map by the test itself, an empty one holds no cell.
 // grid (blocks over h * w, N); k and the coordinates are not range-checked.
+__device__ __forceinline__ int paint_cell(int k, const int* __restrict__ rn, int R, int cy, int cx) {
+  for (int r = 0; r < R; ++r) {
+    const int* q = rn + 5 * r;
+    if (cy >= q[0] && cx >= q[1] && cy < q[2] && cx < q[3]) k = q[4];
+  }
+  return k;
+}
 __global__ __launch_bounds__(256) void qmap_paint_kernel(const signed char* __restrict__ base,
                                                           const int* __restrict__ rects, int R, int h, int w,
                                                           signed char* __restrict__ qmap) {
@@ -336,12 +344,91 @@ __global__ __launch_bounds__(256) void qmap_paint_kernel(const signed char* __re
   const int* rn = rects + (long long)n * R * 5;
   for (int p = blockIdx.x * 256 + threadIdx.x; p < hw; p += gridDim.x * 256) {   // hw <= 2^30: no overflow
     const int cy = p / w, cx = p - cy * w;
-    int k = base[n];
-    for (int r = 0; r < R; ++r) {
-      const int* q = rn + 5 * r;
-      if (cy >= q[0] && cx >= q[1] && cy < q[2] && cx < q[3]) k = q[4];
+    qmap[(long long)n * hw + p] = (signed char)paint_cell(base[n], rn, R, cy, cx);
+  }
+}
+
+// ---- the maps of variance-adaptive quantisation for a training batch (icm_qmap_aq): what icm_amd/codec.py makes of
+// an image for `codec encode --aq S` (cell_stats, aq_activity, aq_reference, aq_offsets, quality_map), restated for
+// planar f32 crops [N][3][H][W] of whole 16 x 16 cells, so n = 256 in every cell and nothing is padding.  Two launches:
+//
+//   qmap_aq_activity_kernel   a wave per cell: lane l owns four pixels of row l / 4 (three 16-byte loads, one per
+//       plane; the four lanes of a row read its 64 contiguous bytes, the four waves of a workgroup four neighbouring
+//       cells).  A sample's 8-bit value is quantise_u8 (image_u8.h: the codec's own rule), Y = (77 R + 150 G + 29 B +
+//       128) >> 8, and s1 = sum Y, s2 = sum Y^2 are integers added across the wave by shuffles: exact in any order.
+//       Lane 0 forms 256 s2 - s1^2 in 64 bits (it passes 2^32), v = that / 65536 (exact in double) and stores
+//       L = log2(1 + v) in DOUBLE into act [N][h w]: a batch has a few thousand cells, and the double is what lets a
+//       test ask for the map cell by cell.
+//   qmap_aq_map_kernel        a workgroup per image.  ref[n] = mean of L over the image's cells, summed in double in an
+//       order fixed by the cell index alone: partial j = L[j] + L[j + 256] + ... in ascending order, then the binary
+//       tree red[t] += red[t + m], m = 128 .. 1, over the 256 partials; no atomics, the same bits on every run and in
+//       every batch.  Then per cell d = clip(rint(4 (double)strength[n] (L - ref[n])), -16, 16) (v_rndne: ties to
+//       even), k = clamp(base[n] + d, -16, 32), and the image's rectangles over it (paint_cell); one store per cell.
+//
+// Every entry of qmap and ref is written once and act is written before it is read, so nothing needs clearing.
+constexpr int AQ_CELL = 16;
+constexpr int AQ_K_MIN = -16, AQ_K_MAX = 32;   // bitstream.py: QSTEP_MIN, QSTEP_MAX
+constexpr double AQ_MAX_OFFSET = 16.0;         // codec.py: AQ_MAX_OFFSET
+
+__global__ __launch_bounds__(256) void qmap_aq_activity_kernel(const float* __restrict__ x, int H, int W, int w,
+                                                                long long per, long long cells,
+                                                                double* __restrict__ act) {
+#pragma clang fp contract(off)
+  const int lane = threadIdx.x & 63, row = lane >> 2, q4 = (lane & 3) * 4;
+  const long long plane = (long long)H * W;
+  for (long long c = (long long)blockIdx.x * 4 + (threadIdx.x >> 6); c < cells; c += (long long)gridDim.x * 4) {
+    const long long n = c / per;
+    const int p = (int)(c - n * per), cy = p / w, cx = p - cy * w;
+    const float* px = x + n * 3 * plane + (long long)(cy * AQ_CELL + row) * W + cx * AQ_CELL + q4;
+    const f32x4 r = *reinterpret_cast<const f32x4*>(px);
+    const f32x4 g = *reinterpret_cast<const f32x4*>(px + plane);
+    const f32x4 b = *reinterpret_cast<const f32x4*>(px + 2 * plane);
+    int s1 = 0, s2 = 0;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const int Y = (int)((77u * quantise_u8(r[j]) + 150u * quantise_u8(g[j]) + 29u * quantise_u8(b[j]) + 128u) >> 8);
+      s1 += Y;
+      s2 += Y * Y;
     }
-    qmap[(long long)n * hw + p] = (signed char)k;
+#pragma unroll
+    for (int m = 1; m < 64; m <<= 1) {   // c is wave-uniform: all 64 lanes are here
+      s1 += __shfl_xor(s1, m, 64);
+      s2 += __shfl_xor(s2, m, 64);
+    }
+    if (lane == 0) {
+      const long long num = 256LL * s2 - (long long)s1 * s1;
+      act[c] = log2(1.0 + (double)num / 65536.0);
+    }
+  }
+}
+
+__global__ __launch_bounds__(256) void qmap_aq_map_kernel(const double* __restrict__ act,
+                                                           const signed char* __restrict__ base,
+                                                           const float* __restrict__ strength,
+                                                           const int* __restrict__ rects, int R, int h, int w,
+                                                           signed char* __restrict__ qmap, double* __restrict__ ref) {
+#pragma clang fp contract(off)
+  __shared__ double red[256];
+  const int n = blockIdx.x, hw = h * w, t = threadIdx.x;   // hw <= 2^30: p + 256 stays an int
+  const double* a = act + (long long)n * hw;
+  const int* rn = rects + (long long)n * R * 5;
+  double s = 0.0;
+  for (int p = t; p < hw; p += 256) s += a[p];
+  red[t] = s;
+  __syncthreads();
+  for (int m = 128; m > 0; m >>= 1) {
+    if (t < m) red[t] += red[t + m];
+    __syncthreads();
+  }
+  const double mean = red[0] / (double)hw;
+  if (t == 0) ref[n] = mean;
+  const double gain = 4.0 * (double)strength[n];
+  const int b = base[n];
+  for (int p = t; p < hw; p += 256) {
+    const int cy = p / w, cx = p - cy * w;
+    const double d = fmin(fmax(rint(gain * (a[p] - mean)), -AQ_MAX_OFFSET), AQ_MAX_OFFSET);
+    const int k = min(max(b + (int)d, AQ_K_MIN), AQ_K_MAX);
+    qmap[(long long)n * hw + p] = (signed char)paint_cell(k, rn, R, cy, cx);
   }
 }
 
@@ -544,6 +631,32 @@ int icm_qmap_paint(const int8_t* base, const int32_t* rects, int R, int8_t* qmap
   const int gx = (int)std::min<long long>(((long long)h * w + 255) / 256, 1024);
   hipLaunchKernelGGL(qmap_paint_kernel, dim3(gx, N), dim3(256), 0, (hipStream_t)stream, (const signed char*)base, rects,
                      R, h, w, (signed char*)qmap);
+  ICM_CHECK_LAUNCH();
+  return ICM_OK;
+}
+
+int64_t icm_qmap_aq_workspace_bytes(int N, int H, int W) {
+  if (N < 1 || H < 1 || W < 1 || H % AQ_CELL || W % AQ_CELL) return 0;
+  const long long hw = (long long)(H / AQ_CELL) * (W / AQ_CELL);
+  if (hw > (1LL << 30) || N > 65535) return 0;
+  return (int64_t)N * hw * (int64_t)sizeof(double);
+}
+
+int icm_qmap_aq(const float* x, int N, int H, int W, const int8_t* base, const float* strength, const int32_t* rects,
+                int R, int8_t* qmap, double* ref, void* ws, int64_t ws_bytes, void* stream) {
+  if (!args_ok({x, base, strength, qmap, ref, ws}, N, H, W) || R < 0 || (R > 0 && !rects)) return ICM_ERR_ARG;
+  const int64_t need = icm_qmap_aq_workspace_bytes(N, H, W);   // 0: no whole cells, or icm_qmap_paint's limits
+  if (need == 0 || ws_bytes < need) return ICM_ERR_ARG;
+  if ((reinterpret_cast<uintptr_t>(x) & 15) || ((reinterpret_cast<uintptr_t>(ws) | reinterpret_cast<uintptr_t>(ref)) & 7))
+    return ICM_ERR_ARG;   // 16-byte loads of whole cell rows (W is a multiple of 16 floats); doubles
+  const int h = H / AQ_CELL, w = W / AQ_CELL;
+  const long long per = (long long)h * w, cells = per * N;
+  const int gx = (int)std::min<long long>((cells + 3) / 4, 65536);
+  hipLaunchKernelGGL(qmap_aq_activity_kernel, dim3(gx), dim3(256), 0, (hipStream_t)stream, x, H, W, w, per, cells,
+                     (double*)ws);
+  ICM_CHECK_LAUNCH();
+  hipLaunchKernelGGL(qmap_aq_map_kernel, dim3(N), dim3(256), 0, (hipStream_t)stream, (const double*)ws,
+                     (const signed char*)base, strength, rects, R, h, w, (signed char*)qmap, ref);
   ICM_CHECK_LAUNCH();
   return ICM_OK;
 }

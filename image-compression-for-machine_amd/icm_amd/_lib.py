@@ -92,7 +92,7 @@ SYMBOLS = [
     "icm_gc_code_qmap", "icm_gc_indexes_qmap", "icm_dequantize_qmap", "icm_gc_code_rdo",
     "icm_gc_likelihood_ste_qs_fwd", "icm_gc_likelihood_ste_qs_bwd", "icm_rd_loss_w_fwd", "icm_rd_loss_w_bwd",
     "icm_gc_likelihood_ste_qm_fwd", "icm_gc_likelihood_ste_qm_bwd", "icm_rd_loss_m_fwd", "icm_rd_loss_m_bwd",
-    "icm_qmap_paint",
+    "icm_qmap_paint", "icm_qmap_aq_workspace_bytes", "icm_qmap_aq",
     "icm_msssim_workspace_floats", "icm_msssim_fwd", "icm_msssim_bwd",
     "icm_image_workspace_bytes", "icm_image_u8_to_f32", "icm_image_f32_to_u8",
     "icm_image_batch_u8_to_f32", "icm_image_tile_blend", "icm_image_cell_stats",
@@ -187,6 +187,9 @@ def lib():
         L.icm_rd_loss_m_bwd.argtypes = [vp, vp, i32, i32, i32, i32, i32, vp, vp, vp, i64, vp, i64, i64, f32, vp, vp, vp,
                                         vp]
         L.icm_qmap_paint.argtypes = [vp, vp, i32, vp, i32, i32, i32, vp]
+        L.icm_qmap_aq_workspace_bytes.argtypes = [i32, i32, i32]
+        L.icm_qmap_aq_workspace_bytes.restype = i64
+        L.icm_qmap_aq.argtypes = [vp, i32, i32, i32, vp, vp, vp, i32, vp, vp, vp, i64, vp]
         L.icm_grad_sqnorm.argtypes = [vp, i64, vp, vp, vp]
         L.icm_adam_step.argtypes = [vp, vp, vp, vp, i64, C.c_double, C.c_double, C.c_double, C.c_double, i32, vp, f32, f32, vp]
         L.icm_adam_step_hyper.argtypes = [vp, vp, vp, vp, i64, C.c_double, C.c_double, C.c_double, vp, vp, f32, f32, vp]

@@ -1296,6 +1296,59 @@ def qstep_steps(qstep, B: int, device):
     return None if ks is None else torch.tensor([step_of(k) for k in ks], dtype=torch.float32).to(device)
 
 
+def qmap_aq_workspace(B: int, H: int, W: int, device) -> torch.Tensor:
+    """the workspace of ``qmap_aq`` for a [B, 3, H, W] batch (``icm_qmap_aq_workspace_bytes``; ValueError for a shape it
+    does not take): a device f64 tensor, never cleared"""
+    nbytes = int(L.lib().icm_qmap_aq_workspace_bytes(B, H, W))
+    if nbytes == 0:
+        raise ValueError(f"qmap_aq: a batch of {B} images of {H}x{W} is not B >= 1 images of whole 16-pixel cells")
+    return torch.empty(nbytes // 8, dtype=torch.float64, device=device)
+
+
+def qmap_aq(x: torch.Tensor, base: torch.Tensor, strength: torch.Tensor, rects: Optional[torch.Tensor] = None,
+            out: Optional[torch.Tensor] = None, ref: Optional[torch.Tensor] = None,
+            ws: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """The quality maps variance-adaptive quantisation (``codec encode --aq``) would make for the images of a batch, on
+    the device (``icm_qmap_aq``, two launches, no host sync): ``x`` contiguous device f32 [B, 3, H, W] with H and W
+    multiples of 16, ``base`` int8 [B] the background step index of each image, ``strength`` f32 [B] its AQ strength,
+    ``rects`` int32 [B, R, 5] = (y0, x0, y1, x1, k) in cells, painted over the offsets as ``icm_qmap_paint`` paints them
+    (None or R = 0: none).  -> (maps int8 [B, H / 16, W / 16], ref f64 [B]: each image's mean activity).  The values
+    are the caller's to check (a step index outside -16..32 in a rectangle goes into the map as given).  ``out``,
+    ``ref``, ``ws`` (``qmap_aq_workspace``): buffers to write into instead of fresh ones, e.g. those a captured graph
+    owns."""
+    if x.dtype != torch.float32 or x.dim() != 4 or x.size(1) != 3 or not x.is_cuda or not x.is_contiguous():
+        raise ValueError(f"qmap_aq: x must be a contiguous device float32 [B, 3, H, W] tensor, got {x.dtype} "
+                         f"{tuple(x.shape)} on {x.device}")
+    B, _, H, W = x.shape
+    dev = x.device
+
+    def want(t, dtype, shape, name):
+        if t.dtype != dtype or tuple(t.shape) != shape or t.device != dev or not t.is_contiguous():
+            raise ValueError(f"qmap_aq: {name} must be a contiguous {dtype} {shape} tensor on {dev}, got {t.dtype} "
+                             f"{tuple(t.shape)} on {t.device}")
+        return t
+    want(base, torch.int8, (B,), "base")
+    want(strength, torch.float32, (B,), "strength")
+    R = 0
+    if rects is not None:
+        if rects.dim() != 3:
+            raise ValueError(f"qmap_aq: rects must be int32 [B, R, 5], got {tuple(rects.shape)}")
+        R = rects.size(1)
+        want(rects, torch.int32, (B, R, 5), "rects")
+    if H % 16 or W % 16:
+        raise ValueError(f"qmap_aq: {H}x{W} is not a whole number of 16-pixel cells")
+    if ws is None:
+        ws = qmap_aq_workspace(B, H, W, dev)
+    elif ws.device != dev or not ws.is_contiguous():
+        raise ValueError("qmap_aq: ws must be a contiguous tensor on the device of x")
+    h, w = H // 16, W // 16
+    out = torch.empty((B, h, w), dtype=torch.int8, device=dev) if out is None else want(out, torch.int8, (B, h, w), "out")
+    ref = torch.empty((B,), dtype=torch.float64, device=dev) if ref is None else want(ref, torch.float64, (B,), "ref")
+    check(L.lib().icm_qmap_aq(ptr(x), B, H, W, ptr(base), ptr(strength), ptr(rects) if R else 0, R, ptr(out), ptr(ref),
+                              ptr(ws), ws.numel() * ws.element_size(), L.stream()), "qmap_aq")
+    return out, ref
+
+
 # ---- the codec's quantiser on y (inference only: compress / decompress)
 _step_tables = {}
 

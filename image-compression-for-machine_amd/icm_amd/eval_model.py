@@ -19,6 +19,7 @@ from typing import Dict, List
 
 import torch
 
+from . import codec
 from . import utils as U
 from .bitstream import check_qstep, check_rdoq
 from .datasets import IMG_EXTENSIONS, ToTensor, to_pil_image
@@ -55,15 +56,34 @@ def load_checkpoint(arch: str, checkpoint_path: str) -> torch.nn.Module:
     return net.eval()
 
 
+def aq_quality_map(filepath: str, device, aq: float, qstep: int = 0):
+    """the quality map ``codec.encode_image(model, img, aq=aq, qstep=qstep)`` builds for the image of a file, untiled:
+    the luma statistics of the 8-bit image on the grid of its centre pads, against the reference of the grid anchored
+    at its first pixel -> int8 [h, w] of the padded latent's size (host)"""
+    u8 = codec._as_u8_image(codec.read_image_u8(filepath), device)
+    H, W = u8.size(0), u8.size(1)
+    pads = codec.center_pads(H, W)
+    ref = codec.aq_reference(codec.cell_stats(u8, (0, 0, 0, 0)))
+    return codec.quality_map(H, W, pads, qstep, [], codec.aq_offsets(codec.cell_stats(u8, pads), aq, ref))
+
+
 @torch.no_grad()
 def eval_model(model, filepaths: List[str], entropy_estimation: bool = False, recon_path: str = "",
-               metric_names=None, qstep: int = 0, qmap=None, rdoq=None) -> Dict[str, float]:
+               metric_names=None, qstep: int = 0, qmap=None, rdoq=None, aq=None) -> Dict[str, float]:
     """eval_model/__main__.py:472-487 (per-image metrics averaged over the folder); ``qstep``: the codec's quantiser
     step index, for the real codec (``utils.inference``) and for the estimate
     (``utils.inference_entropy_estimation``) alike; ``qmap`` (with ``entropy_estimation``, instead of ``qstep``): a
     quality map of the padded latent's size of every image, the rate estimate under that map; ``rdoq`` (real codec
-    only): weight of the encoder's rate-distortion optimised quantisation (``utils.inference``)"""
+    only): weight of the encoder's rate-distortion optimised quantisation (``utils.inference``); ``aq`` (instead of
+    ``qmap``; real codec and estimate alike): strength of variance-adaptive quantisation (``codec.check_aq``; None or
+    0: off) -- every image is coded under the map ``codec.encode_image(aq=aq, qstep=qstep)`` derives from it
+    (``aq_quality_map``), ``qstep`` being the map's background"""
     rdoq = check_rdoq(rdoq, "eval_model: ")
+    aq = codec.check_aq(aq, "eval_model: ")
+    if aq is not None and qmap is not None:
+        raise ValueError("eval_model: aq derives a quality map from every image; give aq or qmap, not both")
+    if aq is not None:
+        qstep = check_qstep(qstep, "eval_model: ")
     if rdoq is not None and entropy_estimation:
         raise ValueError("eval_model: rdoq needs the real codec: the entropy estimation's kernels know no RDOQ")
     if qmap is not None and not entropy_estimation:
@@ -76,9 +96,11 @@ def eval_model(model, filepaths: List[str], entropy_estimation: bool = False, re
         if metric_names is not None and "ms-ssim" in metric_names and min(x.shape[-2:]) <= 160:
             raise ValueError(f"{f}: {x.shape[-1]}x{x.shape[-2]} is too small for MS-SSIM (both sides must exceed 160 "
                              "pixels: five levels of an 11-tap window)")
+        quality = {"qmap": aq_quality_map(f, device, aq, qstep)} if aq is not None else \
+            {**({"qstep": qstep} if qstep else {}), **({} if qmap is None else {"qmap": qmap})}
         rv = fn(model, x, recon=(lambda xh, name=os.path.basename(f): reconstruct(xh, name, recon_path)) if recon_path else None,
-                **({} if metric_names is None else {"metrics": metric_names}), **({"qstep": qstep} if qstep else {}),
-                **({} if qmap is None else {"qmap": qmap}), **({} if rdoq is None else {"rdoq": rdoq}))
+                **({} if metric_names is None else {"metrics": metric_names}), **quality,
+                **({} if rdoq is None else {"rdoq": rdoq}))
         for k, v in rv.items():
             metrics[k] += v
     return {k: v / len(filepaths) for k, v in metrics.items()}
@@ -114,6 +136,10 @@ def setup_args() -> argparse.ArgumentParser:
                    help="quantiser step 2^(K/8) on the latent of the real codec, K in -16..32 (default 0: none)")
     p.add_argument("--rdoq", type=float, default=None, metavar="W",
                    help="rate-distortion optimised quantisation in the real codec's encoder, weight W > 0 (default: off)")
+    p.add_argument("--aq", type=float, default=None, metavar="S",
+                   help="variance-adaptive quantisation as `codec encode --aq S`: every image under the quality map "
+                        "derived from it, --qstep its background; with --entropy-estimation the estimate under that map "
+                        "(0 < |S| <= 4; default: off)")
     p.add_argument("--limit", type=int, default=0, help="evaluate only the first N images (0 = all)")
     return p
 
@@ -130,7 +156,8 @@ def main(argv) -> int:
         return 2
     try:
         check_qstep(args.qstep, "--")
-        if args.qstep and args.entropy_estimation:
+        codec.check_aq(args.aq, "--")
+        if args.qstep and args.entropy_estimation and not args.aq:
             raise ValueError("--qstep needs the real codec: the entropy estimation has no quantiser step")
         check_rdoq(args.rdoq, "--")
         if args.rdoq is not None and args.entropy_estimation:
@@ -155,7 +182,7 @@ def main(argv) -> int:
     try:
         metrics = eval_model(model, filepaths, args.entropy_estimation, args.recon_path,
                              metric_names=metric_names if args.metric else None, qstep=args.qstep,
-                             rdoq=args.rdoq)
+                             rdoq=args.rdoq, aq=args.aq)
     except ValueError as e:
         print(f"Error: {e}", file=sys.stderr)
         return 4

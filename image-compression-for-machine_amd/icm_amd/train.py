@@ -25,6 +25,10 @@ loss (:438), best-only checkpoints ``<save_path><epoch>.ckpt`` holding epoch / s
   (``Trainer(qmap_rects=R)``: R random rectangles over the drawn background, a step per latent position, a distortion
   weight per 16 x 16 cell); the test loop adds one fixed pattern labelled ``roi`` (``roi_test_map``), the checkpoint
   records ``qmap_rects`` and a resumed run without the flag keeps the checkpoint's;
+* ``--qmap-aq SLO,SHI`` (with ``--qstep-range``, with or without ``--qmap-rects``) trains on the maps ``codec encode
+  --aq S`` would make for the crops themselves (``Trainer(qmap_aq=(SLO, SHI))``: S uniform on SLO..SHI per image and
+  iteration, the maps computed on the device inside the step); the test loop adds one line labelled ``aq``
+  (``aq_test_point``), the checkpoint records ``qmap_aq`` and a resumed run without the flag keeps the checkpoint's;
 * checkpoints are read with ``weights_only=True``."""
 from __future__ import annotations
 
@@ -40,7 +44,8 @@ from torch.utils.data import DataLoader
 from .datasets import (CenterCrop, Compose, DeviceCacheLoader, DeviceImageCache, EpochSampler, ImageFolder, RandomCrop,
                        ToTensor)
 from .losses import METRICS, RateDistortionLoss
-from .trainer import Trainer, check_qmap_rects, check_qstep_range, qstep_tables
+from . import engine as E
+from .trainer import Trainer, check_qmap_aq, check_qmap_rects, check_qstep_range, qstep_tables
 from .zoo import models
 
 
@@ -114,6 +119,24 @@ def qstep_test_points(qstep_range):
     return sorted({lo, hi} | ({0} if lo < 0 < hi else set()))
 
 
+def parse_qmap_aq(text):
+    """--qmap-aq SLO,SHI -> (slo, shi) or None for off (``trainer.check_qmap_aq``; ValueError otherwise)"""
+    parts = [p.strip() for p in str(text).split(",")]
+    try:
+        slo, shi = (float(p) for p in parts)
+    except ValueError:
+        raise ValueError(f"--qmap-aq: expected SLO,SHI (two numbers), got {text!r}")
+    return check_qmap_aq((slo, shi))
+
+
+def aq_test_point(qstep_range, qmap_aq):
+    """(K, S) of the line the test loop of an AQ-map run reports as ``aq``: the background of the ``0`` line (LO when 0
+    is outside the range) and whichever of SLO, SHI is larger in magnitude"""
+    lo, hi = qstep_range
+    slo, shi = qmap_aq
+    return (0 if lo < 0 < hi else lo), (shi if abs(shi) >= abs(slo) else slo)
+
+
 def roi_test_map(h: int, w: int, lo: int, hi: int):
     """the fixed pattern the test loop of a quality-map run reports as ``roi``: background HI, and at LO a centred
     rectangle of half the map's height and width (rounded down, one cell at least) -> int8 [h, w] host array"""
@@ -127,18 +150,21 @@ def roi_test_map(h: int, w: int, lo: int, hi: int):
 
 @torch.no_grad()
 def qstep_test_epoch(epoch: int, test_dataloader, model, criterion, lmbda: float, lmbda_exp: float, qstep_range,
-                     verbose: bool = True, qmap_rects: int = 0) -> float:
+                     verbose: bool = True, qmap_rects: int = 0, qmap_aq=None) -> float:
     """``test_epoch`` of a variable-rate run: loss, bpp and mse at every step index of ``qstep_test_points``, each with the
     weight training gives that step (``trainer.qstep_tables``); returns the mean of the points' losses, which is what
     the learning-rate schedule and the best-checkpoint choice then see.  With ``qmap_rects`` one more line, ``roi``: the
     pattern of ``roi_test_map`` under the per-cell loss (it is reported, and stays out of the returned mean, so runs
-    with and without maps are compared by the same figure)"""
+    with and without maps are compared by the same figure).  With ``qmap_aq`` one more line, ``aq``, reported the same
+    way: every test image under the map variance-adaptive quantisation makes for it (``engine.qmap_aq``, the entry point
+    the training step uses) at the background and strength of ``aq_test_point``"""
     model.eval()
     device = next(model.parameters()).device
     points = qstep_test_points(qstep_range)
     meters = {k: (AverageMeter(), AverageMeter(), AverageMeter()) for k in points}
     lam = {k: float(qstep_tables((k, k), lmbda, lmbda_exp)[1][0]) for k in points}
     roi_meters = (AverageMeter(), AverageMeter(), AverageMeter())
+    aq_meters = (AverageMeter(), AverageMeter(), AverageMeter())
     for d in test_dataloader:
         x = d.to(device)
         for k in points:
@@ -150,6 +176,14 @@ def qstep_test_epoch(epoch: int, test_dataloader, model, criterion, lmbda: float
             out = criterion(model(x, qmap=roi), x, qmap=roi, lmbda_exp=lmbda_exp)
             for m, name in zip(roi_meters, ("loss", "bpp_loss", "mse_loss")):
                 m.update(float(out[name]))
+        if qmap_aq is not None:
+            k, s = aq_test_point(qstep_range, qmap_aq)
+            n = x.shape[0]
+            maps = E.qmap_aq(x.contiguous(), torch.full((n,), k, dtype=torch.int8, device=device),
+                             torch.full((n,), s, dtype=torch.float32, device=device))[0].cpu().numpy()
+            out = criterion(model(x, qmap=maps), x, qmap=maps, lmbda_exp=lmbda_exp)
+            for m, name in zip(aq_meters, ("loss", "bpp_loss", "mse_loss")):
+                m.update(float(out[name]))
     model.train()
     if verbose:
         for k in points:
@@ -160,20 +194,26 @@ def qstep_test_epoch(epoch: int, test_dataloader, model, criterion, lmbda: float
             loss, bpp, mse = roi_meters
             print(f"Test epoch {epoch}: qstep roi:\tLoss: {loss.avg:.3f} |\tMSE loss: {mse.avg * 255 ** 2:.3f} |"
                   f"\tBpp loss: {bpp.avg:.4f}", flush=True)
+        if qmap_aq is not None:
+            loss, bpp, mse = aq_meters
+            print(f"Test epoch {epoch}: qstep aq:\tLoss: {loss.avg:.3f} |\tMSE loss: {mse.avg * 255 ** 2:.3f} |"
+                  f"\tBpp loss: {bpp.avg:.4f}", flush=True)
     return sum(meters[k][0].avg for k in points) / len(points)
 
 
 def checkpoint_state(epoch, state_dict, loss, optimizer, aux_optimizer, lr_scheduler, qstep_range=None,
-                     qstep_lmbda_exp=2.0, qmap_rects=0) -> dict:
+                     qstep_lmbda_exp=2.0, qmap_rects=0, qmap_aq=None) -> dict:
     """what a checkpoint holds (train.py:512-527); "qstep_range" is [lo, hi] of a variable-rate run and None otherwise
     (a checkpoint without the key is a fixed-rate one); "qmap_rects" is the rectangle count of a quality-map run, and
-    only such a run has the key"""
+    only such a run has the key; likewise "qmap_aq", [slo, shi] of an AQ-map run"""
     ck = {"epoch": epoch, "state_dict": state_dict, "loss": loss, "optimizer": optimizer,
           "aux_optimizer": aux_optimizer, "lr_scheduler": lr_scheduler,
           "qstep_range": None if qstep_range is None else [int(k) for k in qstep_range],
           "qstep_lambda_exp": float(qstep_lmbda_exp)}
     if qmap_rects:
         ck["qmap_rects"] = int(qmap_rects)
+    if qmap_aq is not None:
+        ck["qmap_aq"] = [float(v) for v in qmap_aq]
     return ck
 
 
@@ -247,13 +287,19 @@ def parse_args(argv):
                    help="quality-map training (needs --qstep-range): R random rectangles per image, 0..8, each with its "
                         "own step, over the drawn background; distortion weight per 16x16 cell (default: 0 = off, or "
                         "what the --checkpoint resumed from records)")
+    p.add_argument("--qmap-aq", type=str, default=None, metavar="SLO,SHI",
+                   help="AQ-map training (needs --qstep-range): the quality map of every crop is the one `codec encode "
+                        "--aq S` would make for it, S uniform on SLO..SHI per image (-4 <= SLO <= SHI <= 4); with "
+                        "--qmap-rects the rectangles win (default: off, or what the --checkpoint resumed from records; "
+                        "0,0 = off)")
     # "--qstep-range -8,16": argparse takes a value that begins with "-" and is no number for an option; hand it the
-    # "--qstep-range=-8,16" form
+    # "--qstep-range=-8,16" form (--qmap-aq likewise)
     argv = list(argv)
-    for i in range(len(argv) - 1):
-        if argv[i] == "--qstep-range" and argv[i + 1][:1] == "-" and argv[i + 1][1:2].isdigit():
-            argv[i:i + 2] = [f"--qstep-range={argv[i + 1]}"]
-            break
+    for flag in ("--qstep-range", "--qmap-aq"):
+        for i in range(len(argv) - 1):
+            if argv[i] == flag and argv[i + 1][:1] == "-" and argv[i + 1][1:2] in tuple("0123456789."):
+                argv[i:i + 2] = [f"{flag}={argv[i + 1]}"]
+                break
     args = p.parse_args(argv)
     try:
         args.qstep_range = None if args.qstep_range is None else parse_qstep_range(args.qstep_range)
@@ -263,6 +309,15 @@ def parse_args(argv):
             raise ValueError("--qstep-range: stf6 has no codec and so no quantiser step")
         if args.qmap_rects is not None and check_qmap_rects(args.qmap_rects) and args.qstep_range is None:
             raise ValueError("--qmap-rects: quality-map training draws its step indexes from --qstep-range; give one")
+        args.qmap_aq_given = args.qmap_aq is not None   # "0,0" turns a resumed run's maps off; no flag keeps them
+        args.qmap_aq = None if args.qmap_aq is None else parse_qmap_aq(args.qmap_aq)
+        if args.qmap_aq is not None:
+            if args.qstep_range is None:
+                raise ValueError("--qmap-aq: quality-map training draws its step indexes from --qstep-range; give one")
+            if args.metric == "ms-ssim":
+                raise ValueError("--qmap-aq: the MS-SSIM loss takes a scalar lambda (use --metric mse)")
+            if args.model == "stf6":
+                raise ValueError("--qmap-aq: stf6 has no codec and so no quantiser step")
     except ValueError as e:
         p.error(str(e))   # exit 2, like every other bad argument
     return args
@@ -346,9 +401,12 @@ def main(argv) -> int:
         net.load_state_dict(ck["state_dict"])
     if args.qmap_rects is None:   # a resumed quality-map run keeps its rectangle count
         args.qmap_rects = int(ck.get("qmap_rects", 0) or 0) if ck is not None and args.qstep_range is not None else 0
+    if not args.qmap_aq_given and ck is not None and args.qstep_range is not None:   # ... and its AQ strengths
+        args.qmap_aq = check_qmap_aq(ck.get("qmap_aq"))
     trainer = Trainer(net, lr=args.learning_rate, aux_lr=args.aux_learning_rate, lmbda=args.lmbda,
                       clip_max_norm=args.clip_max_norm, device=device, seed=int(args.seed or 0), metric=args.metric,
-                      qstep_range=args.qstep_range, qstep_lmbda_exp=args.qstep_lambda_exp, qmap_rects=args.qmap_rects)
+                      qstep_range=args.qstep_range, qstep_lmbda_exp=args.qstep_lambda_exp, qmap_rects=args.qmap_rects,
+                      qmap_aq=args.qmap_aq)
     lr_scheduler = PlateauLR(trainer, factor=0.6, patience=6)
     criterion = RateDistortionLoss(lmbda=args.lmbda, metric=args.metric)
     if ck is not None and "optimizer" in ck and isinstance(ck["optimizer"], dict) and "m" in ck["optimizer"]:
@@ -367,7 +425,7 @@ def main(argv) -> int:
             if args.qstep_range is not None:
                 loss = qstep_test_epoch(epoch, test_dataloader, trainer.model, criterion, args.lmbda,
                                         args.qstep_lambda_exp, args.qstep_range, verbose=rank == 0,
-                                        qmap_rects=args.qmap_rects)
+                                        qmap_rects=args.qmap_rects, qmap_aq=args.qmap_aq)
             else:
                 loss = test_epoch(epoch, test_dataloader, trainer.model, criterion, verbose=rank == 0)
             lr_scheduler.step(loss)
@@ -377,7 +435,7 @@ def main(argv) -> int:
                 opt, aux = trainer.optimizer_state()
                 save_checkpoint(checkpoint_state(epoch, trainer.model.state_dict(), loss, opt, aux,
                                                  lr_scheduler.state_dict(), args.qstep_range, args.qstep_lambda_exp,
-                                                 args.qmap_rects),
+                                                 args.qmap_rects, args.qmap_aq),
                                 os.path.join(args.save_path, f"{epoch}.ckpt"))
     if world > 1:
         import torch.distributed as dist

@@ -16,9 +16,11 @@ with the clip coefficient computed on the device (no host sync anywhere in the s
 from __future__ import annotations
 
 import ctypes as C
+import math
 import os
 from typing import Dict, List, Optional, Tuple
 
+import numpy as np
 import torch
 import torch.distributed as dist
 
@@ -26,6 +28,7 @@ from . import _lib as L
 from . import engine as E
 from ._lib import check, ptr
 from .bitstream import check_qstep, step_of
+from .codec import AQ_STRENGTH_MAX
 from .losses import qmap_lmbda_table
 from .models import SymmetricalTransFormer, SymmetricalTransFormer3, stf6_forward, stf_forward, wacnn_forward
 
@@ -188,6 +191,26 @@ def check_qmap_rects(qmap_rects) -> int:
     return int(qmap_rects)
 
 
+def check_qmap_aq(qmap_aq) -> Optional[Tuple[float, float]]:
+    """(slo, hi) of AQ-map training: the range the per-image strength of variance-adaptive quantisation is drawn from,
+    two real numbers, not bools, finite, with -AQ_STRENGTH_MAX <= slo <= shi <= AQ_STRENGTH_MAX (``codec.check_aq``'s
+    limit), as Python floats.  None and (0, 0) mean off and come back as None.  ValueError otherwise."""
+    if qmap_aq is None:
+        return None
+    try:
+        slo, shi = qmap_aq
+    except (TypeError, ValueError):
+        raise ValueError(f"qmap_aq: expected (slo, shi), got {qmap_aq!r}")
+    for v in (slo, shi):
+        if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or \
+                not math.isfinite(float(v)):
+            raise ValueError(f"qmap_aq: expected two finite numbers, got {qmap_aq!r}")
+    slo, shi = float(slo), float(shi)
+    if not -AQ_STRENGTH_MAX <= slo <= shi <= AQ_STRENGTH_MAX:
+        raise ValueError(f"qmap_aq: need -{AQ_STRENGTH_MAX} <= slo <= shi <= {AQ_STRENGTH_MAX}, got ({slo}, {shi})")
+    return (slo, shi) if slo or shi else None
+
+
 def qmap_rects_of(u: torch.Tensor, h: int, w: int, lo: int, hi: int) -> torch.Tensor:
     """The rectangles of a draw: ``u`` [..., 5] uniform on [0, 1) -> int32 [..., 5] = (y0, x0, y1, x1, k), in cells of an
     h x w map, half open.  A pure function of its arguments that runs on the device of ``u``:
@@ -212,7 +235,7 @@ def qmap_rects_of(u: torch.Tensor, h: int, w: int, lo: int, hi: int) -> torch.Te
 class Trainer:
     def __init__(self, model, lr: float = 1e-4, aux_lr: float = 1e-4, lmbda: float = 0.0067,
                  clip_max_norm: float = 1.0, device="cuda:0", group=None, seed: int = 0, metric: str = "mse",
-                 qstep_range=None, qstep_lmbda_exp: float = 2.0, qmap_rects: int = 0):
+                 qstep_range=None, qstep_lmbda_exp: float = 2.0, qmap_rects: int = 0, qmap_aq=None):
         """``qstep_range`` = (lo, hi): variable-rate training -- every step draws a quantiser step index per image,
         uniform on lo..hi, from this rank's device generator (after the noise and DropPath draws, whose order and
         values it leaves alone), and trains the entropy model and the transforms at that step
@@ -224,8 +247,25 @@ class Trainer:
         (``qmap_rects_of``), painted in order over the background on the device (``icm_qmap_paint``).  The slice loop
         then trains with a step per position (``engine.gc_likelihood_ste(qmap=...)``) and every 16 x 16 cell of pixels
         weighs its distortion by lmbda * step^(-qstep_lmbda_exp) of its position (``icm_rd_loss_m_fwd/bwd``,
-        ``losses.qmap_lmbda_table``).  0 (default): the ``qstep_range`` step, launch for launch."""
+        ``losses.qmap_lmbda_table``).  0 (default): the ``qstep_range`` step, launch for launch.
+        ``qmap_aq`` = (SLO, SHI) (``check_qmap_aq``; with ``qstep_range``): AQ-map training -- the map of every image is
+        the one ``codec encode --aq S`` would make for that crop at the background index the step draws anyway: each
+        cell's offset to it follows the variance of the cell's luma against the crop's mean (``codec.aq_offsets``),
+        computed on the device inside the step (``icm_qmap_aq``, which takes the place of the ``icm_qmap_paint`` launch;
+        no host sync).  The strength S_n = SLO + (SHI - SLO) u_n comes from ONE further draw, uniform [B], the step's
+        last, so every earlier draw keeps its value; with ``qmap_rects`` the rectangles are drawn as they are without
+        and win over the offsets, as in the codec.  Downstream is the map path of ``qmap_rects``, untouched (offsets
+        may leave lo..hi: the weight table covers every step index).  None or (0, 0) (default): off, launch for launch
+        and draw for draw."""
         self.qmap_rects = check_qmap_rects(qmap_rects)
+        self.qmap_aq = check_qmap_aq(qmap_aq)
+        if self.qmap_aq is not None:
+            if qstep_range is None:
+                raise ValueError("qmap_aq: quality-map training draws its step indexes from qstep_range; give one")
+            if metric == "ms-ssim":
+                raise ValueError("qmap_aq: the MS-SSIM loss takes a scalar lmbda; per-cell weights are mse only")
+            if isinstance(model, SymmetricalTransFormer3):
+                raise ValueError("qmap_aq: stf6 has no codec and so no quantiser step")
         if self.qmap_rects:
             if qstep_range is None:
                 raise ValueError("qmap_rects: quality-map training draws its step indexes from qstep_range; give one")
@@ -280,12 +320,14 @@ class Trainer:
         self.is_stf = isinstance(model, SymmetricalTransFormer)
         self.is_stf6 = isinstance(model, SymmetricalTransFormer3)
         self.lat_ch = 384 if self.is_stf else 320
+        self._maps = bool(self.qmap_rects) or self.qmap_aq is not None   # a step index per latent position
         self.loss_terms = None   # tests (keep_loss_seed, variable rate): likelihoods, drawn step indexes, weights
         if self.qstep_range is not None:   # built once; a step gathers from them on the device
             steps, lam = qstep_tables(self.qstep_range, lmbda, self.qstep_lmbda_exp)
             self._q_steps, self._q_lmbda = steps.to(self.device), lam.to(self.device)
-        if self.qmap_rects:
+        if self.qmap_rects or self.qmap_aq is not None:
             self._qm_lmbda = qmap_lmbda_table(lmbda, self.qstep_lmbda_exp).to(self.device)
+        self._aq_bufs = None   # AQ-map training: (batch shape, ref f64 [B], workspace), allocated once per shape
 
     def params(self) -> Dict[str, torch.Tensor]:
         return self.flat.views
@@ -298,11 +340,28 @@ class Trainer:
 
     def _draw_qmaps(self, B: int, h: int, w: int):
         """(table rows [B] int64, base [B] int8, rects [B, R, 5] int32) of one quality-map step: the background index of
-        each image from the draw of ``_draw_qsteps``, then one more draw for the rectangles; all on the device"""
+        each image from the draw of ``_draw_qsteps``, then one more draw for the rectangles; all on the device.  With
+        ``qmap_aq`` a fourth entry, the strengths [B] f32 of the step's last draw (and no rectangle draw where R = 0:
+        ``rects`` is then empty)."""
         lo, hi = self.qstep_range
         rows = torch.randint(0, self._q_lmbda.numel(), (B,), device=self.device, generator=self.gen)
-        u = torch.rand((B, self.qmap_rects, 5), dtype=torch.float32, device=self.device, generator=self.gen)
-        return rows, (rows + lo).to(torch.int8), qmap_rects_of(u, h, w, lo, hi)
+        if self.qmap_rects:
+            u = torch.rand((B, self.qmap_rects, 5), dtype=torch.float32, device=self.device, generator=self.gen)
+            rects = qmap_rects_of(u, h, w, lo, hi)
+        else:
+            rects = torch.empty((B, 0, 5), dtype=torch.int32, device=self.device)
+        if self.qmap_aq is None:
+            return rows, (rows + lo).to(torch.int8), rects
+        slo, shi = self.qmap_aq
+        u = torch.rand((B,), dtype=torch.float32, device=self.device, generator=self.gen)
+        return rows, (rows + lo).to(torch.int8), rects, slo + (shi - slo) * u
+
+    def _aq_buffers(self, B: int, H: int, W: int):
+        """(ref f64 [B], workspace) of ``engine.qmap_aq`` for this batch shape, kept between steps"""
+        if self._aq_bufs is None or self._aq_bufs[0] != (B, H, W):
+            self._aq_bufs = ((B, H, W), torch.empty((B,), dtype=torch.float64, device=self.device),
+                             E.qmap_aq_workspace(B, H, W, self.device))
+        return self._aq_bufs[1], self._aq_bufs[2]
 
     def step_graphed(self, x: torch.Tensor) -> torch.Tensor:
         """step(x) replayed from a captured hipGraph: one host call per iteration instead of ~1 000 (cnn) to ~8 000
@@ -311,7 +370,8 @@ class Trainer:
         in device memory the graph reads: the input batch, the quantisation noise and DropPath scales (drawn outside the
         graph from this rank's generator, in the same order as step() draws them), with ``qstep_range`` the steps and
         distortion weights of the images (drawn last, as in step(); with ``qmap_rects`` the background indexes and the
-        rectangles instead, which the graph paints into its map buffer) and Adam's step-dependent scalars
+        rectangles instead, which the graph paints into its map buffer; with ``qmap_aq`` also the strengths, and the
+        graph derives the maps from its input batch) and Adam's step-dependent scalars
         (icm_adam_step_hyper) -- so a replayed step equals the eager step bit for bit.  Single process only (the RCCL
         reductions are not captured); the side stream of the weight gradients is forked and joined inside the capture."""
         if self.world > 1:
@@ -339,8 +399,8 @@ class Trainer:
             for k, v in g["drops"].items():
                 v.copy_(fresh[k])
         if g["qsteps"] is not None:   # variable rate: the step's last draw, gathered into the buffers the graph reads
-            fresh = self._draw_qmaps(B, H // 16, W // 16) if self.qmap_rects else self._draw_qsteps(B)
-            for buf, v in zip(g["qsteps"], fresh):   # (the map buffer, a fourth entry, is written by the graph)
+            fresh = self._draw_qmaps(B, H // 16, W // 16) if self._maps else self._draw_qsteps(B)
+            for buf, v in zip(g["qsteps"], fresh):   # (the map buffer, the last entry, is written by the graph)
                 buf.copy_(v)
         g["x"].copy_(x)
         g["graph"].replay()
@@ -367,6 +427,13 @@ class Trainer:
             rects = torch.tensor([0, 0, 1, 1, lo], dtype=torch.int32, device=dev).repeat(B, self.qmap_rects, 1)
             g["qsteps"] = (rows, torch.full((B,), lo, dtype=torch.int8, device=dev), rects.contiguous(),
                            torch.zeros((B, H // 16, W // 16), dtype=torch.int8, device=dev))
+        if self.qmap_aq is not None:   # ... and strength 0 (a valid one) for the capture run; the maps stay last
+            lo = self.qstep_range[0]
+            rects = g["qsteps"][2] if self.qmap_rects else torch.empty((B, 0, 5), dtype=torch.int32, device=dev)
+            g["qsteps"] = (rows, torch.full((B,), lo, dtype=torch.int8, device=dev), rects,
+                           torch.zeros((B,), dtype=torch.float32, device=dev),
+                           torch.zeros((B, H // 16, W // 16), dtype=torch.int8, device=dev))
+            self._aq_buffers(B, H, W)   # allocated before the capture, not inside it
         if self.is_stf:
             gen_state = self.gen.get_state()       # shapes / keys only: the capture must not consume random numbers
             g["drops"] = {k: v.clone() for k, v in self.model.draw_drops(B, dev, generator=self.gen).items()}
@@ -428,7 +495,7 @@ class Trainer:
         with ``qstep_range`` it is 255^2 * mean_n(lmbda_n * mse_n) + bpp at the steps drawn, mse stays the plain mean).
         _hyper (step_graphed only): device tensors holding Adam's step-dependent scalars for the two optimisers;
         _qsteps (step_graphed only): the (rows, steps, lmbda_n) buffers of ``_draw_qsteps`` the graph reads, or with
-        ``qmap_rects`` the (rows, base, rects) buffers of ``_draw_qmaps`` and the map buffer the graph paints."""
+        ``qmap_rects`` or ``qmap_aq`` the buffers of ``_draw_qmaps`` followed by the map buffer the graph writes."""
         f, dev = self.flat, self.device
         st = L.stream()
         lib = L.lib()
@@ -464,7 +531,13 @@ class Trainer:
             drops = self.model.draw_drops(B, dev, generator=self.gen)
         # variable rate: the LAST draw of the step, so that the noise and the DropPath scales are those of a plain step
         qs = maps = None
-        if self.qmap_rects:   # ... followed by the one draw of the rectangles; the maps are painted on the device
+        aq_ref = None
+        if self.qmap_aq is not None:   # ... followed by the rectangles' draw (R > 0), then the strengths'; the maps
+            qs = _qsteps if _qsteps is not None else self._draw_qmaps(B, H // 16, W // 16)   # come from x, on the device
+            maps = qs[4] if len(qs) > 4 else torch.empty((B, H // 16, W // 16), dtype=torch.int8, device=dev)
+            aq_ref, aq_ws = self._aq_buffers(B, H, W)
+            E.qmap_aq(x.contiguous(), qs[1], qs[3], qs[2] if self.qmap_rects else None, out=maps, ref=aq_ref, ws=aq_ws)
+        elif self.qmap_rects:   # ... followed by the one draw of the rectangles; the maps are painted on the device
             qs = _qsteps if _qsteps is not None else self._draw_qmaps(B, H // 16, W // 16)
             maps = qs[3] if len(qs) > 3 else torch.empty((B, H // 16, W // 16), dtype=torch.int8, device=dev)
             check(lib.icm_qmap_paint(ptr(qs[1]), ptr(qs[2]), self.qmap_rects, ptr(maps), B, H // 16, W // 16, st),
@@ -526,6 +599,8 @@ class Trainer:
             if maps is not None:
                 self.loss_terms = {"y_lik": y_lik.detach().clone(), "z_lik": z_lik.detach().clone(),
                                    "qstep": qs[0] + self.qstep_range[0], "qmap": maps.clone(), "rects": qs[2].clone()}
+                if aq_ref is not None:
+                    self.loss_terms.update(aq=qs[3].clone(), aq_ref=aq_ref.clone())
             elif qs is not None:
                 self.loss_terms = {"y_lik": y_lik.detach().clone(), "z_lik": z_lik.detach().clone(),
                                    "qstep": qs[0] + self.qstep_range[0], "lmbda_n": qs[2].clone()}

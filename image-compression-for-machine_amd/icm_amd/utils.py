@@ -87,21 +87,25 @@ def _quality(x: torch.Tensor, x_hat: torch.Tensor, metrics: Optional[Sequence[st
 
 @torch.no_grad()
 def inference(model, x: torch.Tensor, recon=None, metrics: Optional[Sequence[str]] = None,
-              qstep: int = 0, rdoq: Optional[float] = None) -> Dict[str, float]:
+              qstep: int = 0, rdoq: Optional[float] = None, qmap=None) -> Dict[str, float]:
     """eval_model/__main__.py:96-139: actual bit-stream size and reconstruction quality of one image x [3,H,W] or
     [1,3,H,W] in [0,1]; ``recon(x_hat)`` (optional) receives the cropped reconstruction (the reference saves it, :130);
     ``metrics`` (optional) lists the quality entries to report (EVAL_METRICS; default: "psnr" alone); ``qstep``: step
     index of the codec's quantiser step on the latent (``model.compress``; 0: none, the reference's codec); ``rdoq``:
-    weight of the encoder's rate-distortion optimised quantisation (``model.compress``; None: off)"""
+    weight of the encoder's rate-distortion optimised quantisation (``model.compress``; None: off); ``qmap`` (instead
+    of ``qstep``): a quality map of the padded latent's size, handed to ``model.compress`` and ``model.decompress``"""
     rdoq = check_rdoq(rdoq, "inference: ")
+    if qmap is not None and qstep:
+        raise ValueError("inference: qstep and qmap are two forms of one thing; give one")
     if x.dim() == 3:
         x = x.unsqueeze(0)
     xp, pads = pad_to_multiple(x, 64)
     t0 = time.time()
-    enc = model.compress(xp, qstep=qstep, **({} if rdoq is None else {"rdoq": rdoq}))
+    quality = {"qstep": qstep} if qmap is None else {"qmap": qmap}
+    enc = model.compress(xp, **quality, **({} if rdoq is None else {"rdoq": rdoq}))
     torch.cuda.synchronize() if x.is_cuda else None
     t1 = time.time()
-    dec = model.decompress(enc["strings"], enc["shape"], qstep=qstep)
+    dec = model.decompress(enc["strings"], enc["shape"], **quality)
     torch.cuda.synchronize() if x.is_cuda else None
     t2 = time.time()
     x_hat = crop(dec["x_hat"], pads)

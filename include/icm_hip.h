@@ -500,6 +500,25 @@ int icm_gc_likelihood_ste_qm_bwd(const float* y, int64_t y_bs, const float* mu, 
  * ICM_ERR_ARG before the launch: a null pointer, N, h or w < 1, R < 0 (and h * w > 2^30 or N > 65535). */
 int icm_qmap_paint(const int8_t* base, const int32_t* rects, int R, int8_t* qmap, int N, int h, int w, void* stream);
 
+/* The quality maps of variance-adaptive quantisation for a training batch, two launches: what `codec encode --aq S`
+ * derives from an image (icm_amd/codec.py: cell_stats, aq_activity, aq_reference, aq_offsets, quality_map), for planar
+ * f32 crops x [N][3][H][W] of whole 16 x 16 cells (H, W multiples of 16; x 16-byte aligned), h = H / 16, w = W / 16:
+ *   8-bit value of a sample: (int)(min(max(v, 0), 1) * 255.0f), the rule of icm_image_f32_to_u8 (NaN unspecified)
+ *   Y = (77 R + 150 G + 29 B + 128) >> 8;  per cell s1 = sum Y, s2 = sum Y^2 over its 256 pixels (integers)
+ *   L = log2(1 + (256 s2 - s1^2) / 65536) in double, the numerator a 64-bit integer
+ *   ref[n] = mean of L over the h w cells of image n, summed in double in an order fixed by the cell index
+ *   d = clip(rint(4 (double)strength[n] (L - ref[n])), -16, 16), ties to even;  cell = clamp(base[n] + d, -16, 32)
+ *   then the R rectangles rects[n][r] of image n over it, exactly as icm_qmap_paint paints them (k as given).
+ * base [N] int8, strength [N] f32, rects [N][R][5] int32 (may be null with R = 0), qmap [N][h][w] int8 and ref [N]
+ * double (8-byte aligned) are DEVICE memory; every entry of qmap and ref is written exactly once, the same bits on
+ * every run and whatever else is in the batch.  ws: icm_qmap_aq_workspace_bytes(N, H, W) bytes, 8-byte aligned, need
+ * not be cleared.  No allocation, synchronisation or host read: the launches can be captured in a graph.
+ * ICM_ERR_ARG before any launch: a null pointer (rects only with R > 0), N, H or W < 1, H or W no multiple of 16,
+ * R < 0, a workspace too small, a misaligned x, ref or ws, and icm_qmap_paint's limits (h w > 2^30, N > 65535). */
+int64_t icm_qmap_aq_workspace_bytes(int N, int H, int W);   /* 0 = bad geometry */
+int icm_qmap_aq(const float* x, int N, int H, int W, const int8_t* base, const float* strength, const int32_t* rects,
+                int R, int8_t* qmap, double* ref, void* ws, int64_t ws_bytes, void* stream);
+
 /* ---- R-D loss (train.py:53-61, train_czigzag.py:63,71) --------------------------------------
  * out[0]=bpp, out[1]=mse, out[2]=loss, out[3]=sum log(lik_y), out[4]=sum log(lik_z) (5 floats, overwritten);
  * ws: ICM_REDUCE_WS_FLOATS floats of scratch (per-workgroup partial sums, added in workgroup order). */
