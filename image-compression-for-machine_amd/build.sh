@@ -7,7 +7,7 @@ HIPCC=${HIPCC:-/opt/rocm/bin/hipcc}
 FLAGS="--offload-arch=gfx950 -O3 -fPIC -std=c++17 -Wno-unused-result"
 objs=""
 pids=""
-for f in conv_igemm conv_1x1 conv_ks8 conv_wino conv_wgrad wgrad_wino pointwise entropy qstep msssim imageio rans_lanes winattn winattn_mfma; do
+for f in conv_igemm conv_1x1 conv_ks8 conv_wino conv_wgrad wgrad_wino pointwise entropy qstep msssim imageio residual rans_lanes winattn winattn_mfma; do
   stale=0
   for dep in csrc/$f.hip csrc/icm_common.h ../include/icm_hip.h $(for h in conv_common.h winattn_common.h rans_lanes_common.h image_u8.h; do grep -q $h csrc/$f.hip && echo csrc/$h; done); do
     if [ ! -f build/$f.o ] || [ $dep -nt build/$f.o ]; then stale=1; fi

@@ -1,0 +1,233 @@
+// The error-bounded residual layer of the codec on the device, gfx950 (icm_amd/residual.py, ICMR streams; parity
+// unpinned: no counterpart in the reference).  x = the original 8-bit image, xhat = what the decoder makes of the base
+// stream, both interleaved [H, W, 3] bytes; D = the bound, s = 2 D + 1.
+//
+//   residual_code_kernel     x, xhat -> q = sign(x - xhat) ((|x - xhat| + D) div s) in plane order [3, H, W], the class of
+//                            every 16 x 16-pixel cell (grid anchored at pixel (0, 0)) and, per sample, its cell's class
+//   residual_indexes_kernel  the decoder's expansion: classes [gh, gw] -> one class per sample, [3, H, W]
+//   residual_apply_kernel    xhat of a window, q -> min(max(xhat + q s, 0), 255), interleaved bytes of the window
+//
+// Integer work only, byte-bound: 6 bytes in and 24 out per pixel for the first, 12 out for the second, 15 in and 3 out
+// for the third.  A thread owns four adjacent pixels of one row: 12 interleaved bytes = three dword accesses where the
+// run lies inside its row and its first byte is dword-aligned, and four int32 per plane = one 16-byte access where its
+// first element is 16-byte aligned; every other run -- row ends, widths that are no multiple of four, odd pointers --
+// moves byte by byte and element by element through the same registers.  No LDS, no scratch, no atomics.
+//
+// The division by s is a multiplication: for n = |r| + D <= 287 and s <= 65, (n m) >> 16 with m = 65536 div s + 1 is
+// n div s, because the error of m / 65536 against 1 / s is below 1 / 65536 and 287 / 65536 < 1 / 65 (the test suite
+// also walks all (n, s)).
+#include "icm_common.h"
+
+namespace {
+
+constexpr int RUN = 4;         // pixels per thread
+constexpr int BLOCK = 256;
+constexpr int MAX_SIDE = 32768;
+constexpr int MAX_D = 32;
+constexpr int CELL = 16;
+constexpr int WAVES = BLOCK / 64;   // cells per workgroup in residual_code_kernel: neighbours in one row of cells
+
+// class thresholds, round(2^(1 + j / 2)): a cell of N coded samples with S = sum |q| has the class
+// #{j : 16 S > N T_j} (icm_amd/residual.py THRESHOLDS; the tests compare the two lists through the classes)
+constexpr int NTHRESH = 18;
+constexpr int THRESH[NTHRESH] = {2, 3, 4, 6, 8, 11, 16, 23, 32, 45, 64, 91, 128, 181, 256, 362, 512, 724};
+
+typedef int32_t i32x4 __attribute__((ext_vector_type(4)));
+
+__device__ __forceinline__ bool aligned_to(const void* p, uintptr_t a) {
+  return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0;
+}
+
+// the 12 interleaved bytes of the run's pixels that lie inside the row (n of them), little-endian words, zero elsewhere
+__device__ __forceinline__ void load_run(const uint8_t* p, bool full, int n, uint32_t (&w)[3]) {
+  if (full && aligned_to(p, 4)) {
+    const uint32_t* q = reinterpret_cast<const uint32_t*>(p);
+#pragma unroll
+    for (int k = 0; k < 3; ++k) w[k] = q[k];
+  } else {
+#pragma unroll
+    for (int k = 0; k < 3; ++k) w[k] = 0u;
+#pragma unroll
+    for (int b = 0; b < 3 * RUN; ++b)
+      if (b < 3 * n) w[b >> 2] |= (uint32_t)p[b] << (8 * (b & 3));
+  }
+}
+
+__device__ __forceinline__ int byte_of(const uint32_t (&w)[3], int b) { return (int)((w[b >> 2] >> (8 * (b & 3))) & 255u); }
+
+// four int32 of one plane, n of them inside the row
+__device__ __forceinline__ void store_run(int32_t* o, bool full, int n, const int (&v)[RUN]) {
+  if (full && aligned_to(o, 16)) {
+    const i32x4 t = {v[0], v[1], v[2], v[3]};
+    *reinterpret_cast<i32x4*>(o) = t;
+  } else {
+#pragma unroll
+    for (int j = 0; j < RUN; ++j)
+      if (j < n) o[j] = v[j];
+  }
+}
+
+// One wave owns a cell: lane l holds the four pixels 4 (l % 4) .. of row l / 4, so a wave reads the cell's two blocks
+// of 16 rows x 48 bytes and the four waves of a workgroup read 192 contiguous bytes of every row.  S is reduced by six
+// shuffles; N is known from the geometry.  Lanes of rows and columns past the image load and store nothing and add 0.
+__global__ __launch_bounds__(BLOCK) void residual_code_kernel(const uint8_t* __restrict__ x,
+                                                               const uint8_t* __restrict__ xhat, int H, int W, int D,
+                                                               int magic, int gw, int strips,
+                                                               int32_t* __restrict__ symbols,
+                                                               int32_t* __restrict__ indexes,
+                                                               int32_t* __restrict__ classes) {
+  const int cy = blockIdx.x / strips;
+  const int cx = (blockIdx.x - cy * strips) * WAVES + (threadIdx.x >> 6);
+  if (cx >= gw) return;   // wave-uniform; the kernel has no barrier
+  const int lane = threadIdx.x & 63;
+  const int y = cy * CELL + (lane >> 2), px0 = cx * CELL + RUN * (lane & 3);
+  const int n = y < H ? min(max(W - px0, 0), RUN) : 0;   // the run's pixels inside the image
+  const bool full = n == RUN;
+
+  int q[3 * RUN];
+  int S = 0;
+#pragma unroll
+  for (int b = 0; b < 3 * RUN; ++b) q[b] = 0;
+  if (n > 0) {
+    const size_t o = ((size_t)y * W + px0) * 3;
+    uint32_t a[3], e[3];
+    load_run(x + o, full, n, a);
+    load_run(xhat + o, full, n, e);
+#pragma unroll
+    for (int b = 0; b < 3 * RUN; ++b) {   // bytes past the row end are zero on both sides: q = 0
+      const int r = byte_of(a, b) - byte_of(e, b);
+      const int m = ((abs(r) + D) * magic) >> 16;
+      q[b] = r < 0 ? -m : m;
+      S += m;
+    }
+  }
+#pragma unroll
+  for (int m = 32; m >= 1; m >>= 1) S += __shfl_xor(S, m, 64);
+  const int N = 3 * min(CELL, H - cy * CELL) * min(CELL, W - cx * CELL);
+  int cls = 0;
+#pragma unroll
+  for (int j = 0; j < NTHRESH; ++j) cls += 16 * S > N * THRESH[j] ? 1 : 0;   // 16 S <= 2^22, N T <= 2^20
+
+  if (n > 0) {
+    const size_t plane = (size_t)H * W, e0 = (size_t)y * W + px0;
+    const int k[RUN] = {cls, cls, cls, cls};
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      const int v[RUN] = {q[c], q[3 + c], q[6 + c], q[9 + c]};
+      store_run(symbols + c * plane + e0, full, n, v);
+      store_run(indexes + c * plane + e0, full, n, k);
+    }
+  }
+  if (lane == 0) classes[(size_t)cy * gw + cx] = cls;
+}
+
+// a thread owns four adjacent samples of one row (they share a cell) in the three planes
+__global__ __launch_bounds__(BLOCK) void residual_indexes_kernel(const int32_t* __restrict__ classes, int H, int W,
+                                                                  int gw, int32_t* __restrict__ indexes,
+                                                                  int runs_per_row, long long total_runs) {
+  const long long g = (long long)blockIdx.x * BLOCK + threadIdx.x;
+  if (g >= total_runs) return;
+  const int y = (int)(g / runs_per_row);
+  const int x0 = ((int)(g - (long long)y * runs_per_row)) * RUN;
+  const int n = min(W - x0, RUN);
+  const int cls = classes[(size_t)(y / CELL) * gw + x0 / CELL];
+  const int k[RUN] = {cls, cls, cls, cls};
+  const size_t plane = (size_t)H * W, e0 = (size_t)y * W + x0;
+#pragma unroll
+  for (int c = 0; c < 3; ++c) store_run(indexes + c * plane + e0, n == RUN, n, k);
+}
+
+// a thread owns four adjacent pixels of one row of the window.  |q| >= 256 saturates whatever s is, so q is clamped
+// to +-256 first and the product stays small: the result is that of the exact integers for every int32 q
+__global__ __launch_bounds__(BLOCK) void residual_apply_kernel(const uint8_t* __restrict__ xhat,
+                                                                const int32_t* __restrict__ symbols, int H, int W,
+                                                                int y0, int x0, int h, int w, int s,
+                                                                uint8_t* __restrict__ out, int runs_per_row,
+                                                                long long total_runs) {
+  const long long g = (long long)blockIdx.x * BLOCK + threadIdx.x;
+  if (g >= total_runs) return;
+  const int y = (int)(g / runs_per_row);
+  const int x = ((int)(g - (long long)y * runs_per_row)) * RUN;
+  const int n = min(w - x, RUN);
+  const bool full = n == RUN;
+  const size_t o = ((size_t)y * w + x) * 3;
+  uint32_t e[3];
+  load_run(xhat + o, full, n, e);
+
+  const size_t plane = (size_t)H * W, e0 = (size_t)(y0 + y) * W + x0 + x;
+  uint32_t r[3] = {0u, 0u, 0u};
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    const int32_t* sp = symbols + c * plane + e0;
+    int q[RUN];
+    if (full && aligned_to(sp, 16)) {
+      const i32x4 t = *reinterpret_cast<const i32x4*>(sp);
+#pragma unroll
+      for (int j = 0; j < RUN; ++j) q[j] = t[j];
+    } else {
+#pragma unroll
+      for (int j = 0; j < RUN; ++j) q[j] = j < n ? sp[j] : 0;
+    }
+#pragma unroll
+    for (int j = 0; j < RUN; ++j) {
+      const int b = 3 * j + c;
+      const int v = min(max(byte_of(e, b) + min(max(q[j], -256), 256) * s, 0), 255);
+      r[b >> 2] |= (uint32_t)v << (8 * (b & 3));
+    }
+  }
+  uint8_t* op = out + o;
+  if (full && aligned_to(op, 4)) {
+    uint32_t* p = reinterpret_cast<uint32_t*>(op);
+#pragma unroll
+    for (int k = 0; k < 3; ++k) p[k] = r[k];
+  } else {
+#pragma unroll
+    for (int b = 0; b < 3 * RUN; ++b)
+      if (b < 3 * n) op[b] = (uint8_t)(r[b >> 2] >> (8 * (b & 3)));
+  }
+}
+
+bool side_ok(int v) { return v >= 1 && v <= MAX_SIDE; }
+
+}  // namespace
+
+#define ST ((hipStream_t)stream)
+
+extern "C" {
+
+int icm_residual_code(const uint8_t* x, const uint8_t* xhat, int H, int W, int D, int32_t* symbols, int32_t* indexes,
+                      int32_t* classes, void* stream) {
+  if (!x || !xhat || !symbols || !indexes || !classes) return ICM_ERR_ARG;
+  if (!side_ok(H) || !side_ok(W) || D < 0 || D > MAX_D) return ICM_ERR_ARG;
+  const int gh = (H + CELL - 1) / CELL, gw = (W + CELL - 1) / CELL;
+  const int strips = (gw + WAVES - 1) / WAVES;                    // gh strips <= 2048 * 512
+  hipLaunchKernelGGL(residual_code_kernel, dim3((unsigned)(gh * strips)), dim3(BLOCK), 0, ST, x, xhat, H, W, D,
+                     65536 / (2 * D + 1) + 1, gw, strips, symbols, indexes, classes);
+  ICM_CHECK_LAUNCH();
+  return ICM_OK;
+}
+
+int icm_residual_indexes(const int32_t* classes, int H, int W, int32_t* indexes, void* stream) {
+  if (!classes || !indexes || !side_ok(H) || !side_ok(W)) return ICM_ERR_ARG;
+  const int rpr = (W + RUN - 1) / RUN;
+  const long long total = (long long)H * rpr;                     // <= 32768 * 8192
+  hipLaunchKernelGGL(residual_indexes_kernel, dim3((unsigned)((total + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, ST, classes,
+                     H, W, (W + CELL - 1) / CELL, indexes, rpr, total);
+  ICM_CHECK_LAUNCH();
+  return ICM_OK;
+}
+
+int icm_residual_apply(const uint8_t* xhat, const int32_t* symbols, int H, int W, int y0, int x0, int h, int w, int D,
+                       uint8_t* out, void* stream) {
+  if (!xhat || !symbols || !out) return ICM_ERR_ARG;
+  if (!side_ok(H) || !side_ok(W) || !side_ok(h) || !side_ok(w) || D < 0 || D > MAX_D) return ICM_ERR_ARG;
+  if (y0 < 0 || x0 < 0 || (long long)y0 + h > H || (long long)x0 + w > W) return ICM_ERR_ARG;
+  const int rpr = (w + RUN - 1) / RUN;
+  const long long total = (long long)h * rpr;
+  hipLaunchKernelGGL(residual_apply_kernel, dim3((unsigned)((total + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, ST, xhat,
+                     symbols, H, W, y0, x0, h, w, 2 * D + 1, out, rpr, total);
+  ICM_CHECK_LAUNCH();
+  return ICM_OK;
+}
+
+}  // extern "C"

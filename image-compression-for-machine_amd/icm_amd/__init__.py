@@ -18,6 +18,7 @@ signatures, state-dict keys and error behaviour):
     icm_amd.graphs           hipGraph capture of the eval forward
     icm_amd.bitstream        container of one compressed image (pack / unpack / fingerprint)  (no counterpart)
     icm_amd.codec            image file <-> bit-stream file: library and CLI                  (no counterpart)
+    icm_amd.residual         error-bounded residual layer: quantiser, classes, static tables  (no counterpart)
 
 All numerics run in hand-written HIP kernels behind the C ABI of include/icm_hip.h (lib/libicm_hip.so); there is no
 CPU or ATen compute fallback: importing works without the library, any op raises if it is missing.

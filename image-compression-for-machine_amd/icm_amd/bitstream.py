@@ -78,6 +78,29 @@ The coder id lives in the tile streams alone: the high byte of the ICMT architec
 quantiser step: every tile stream of a stepped image carries its own byte (the encoder writes the same k in all), and
 every tile of a region-of-interest encode its own map string, or the step byte where its map came out uniform.
 
+An error-bounded image is a third container with its own magic: one ordinary stream, ``ICMB`` or ``ICMT``, the base,
+followed by the string of the residual layer (``icm_amd.residual``: the quantised differences between the original and
+the decoder's reconstruction of the base, which bound the error of every sample by D).
+
+    offset  size  field
+         0     4  magic, the bytes ``ICMR``
+         4     2  format version (u16), ``RESIDUAL_VERSION`` = 1
+         6     1  D (u8), 0..``MAX_ERROR`` = 32: every sample of the decode is within D of the original; 0 = lossless
+         7     1  coder id of the residual string (u8), index into ``CODERS``; the base names its own
+         8     4  image height (u32, 1..32768)
+        12     4  image width (u32, 1..32768)
+        16     4  CRC-32 of the residual layer's static tables (cdf, sizes, offsets as little-endian int32)
+        20     4  length of the base stream (u32)
+        24     4  length of the residual string (u32)
+        28   ...  the base stream, then the residual string
+       end-4     4  CRC-32 of every byte before it
+
+``unpack_residual`` refuses, with ValueError, anything that is not exactly one such stream, a D above 32, a base that
+begins with neither inner magic and -- given the reader's own table CRC -- a file written with other tables, so that a
+reader built with other tables stops instead of decoding garbage.  ``unpack`` and ``unpack_tiled`` are unchanged and
+refuse the magic, as a reader from before this container does (exit code 4 of the CLI).  The residual string is one
+string of four runs under the layer's tables: the class map, then the R, G and B planes.
+
 Lane stream -- the string format of coder id 1, made to be coded by one GPU wave per body (csrc/rans_lanes.hip; the
 executable definition is csrc/rans_lanes_common.h, the arithmetic of a lane's step that host and kernels both compile,
 under the loops of ``icm_rans_lanes_encode`` / ``icm_rans_lanes_decoder_*`` of csrc/rans.cpp).  Parity unpinned: no
@@ -551,3 +574,81 @@ def unpack_tiled(data: bytes) -> Tuple[Dict, List[bytes]]:
     header = {"arch": ARCHS[arch_id], "height": height, "width": width, "tile": tile, "overlap": overlap, "rows": rows,
               "cols": cols, "fingerprint": fp}
     return header, streams
+
+
+# ------------------------------------------------------------------------------------------- error-bounded images
+RESIDUAL_MAGIC = b"ICMR"
+RESIDUAL_VERSION = 1
+MAX_ERROR = 32                              # largest bound D of the residual layer
+RESIDUAL_SIDE_MAX = 32768                   # what the layer's kernels take
+_RFIXED = struct.Struct("<4sHBBIIIII")      # magic .. residual length
+RESIDUAL_FIXED_BYTES = _RFIXED.size         # 28
+assert RESIDUAL_FIXED_BYTES == 28
+RESIDUAL_HEADER_KEYS = ("max_error", "coder", "height", "width", "table_crc")
+
+
+def pack_residual(header: Dict, base: bytes, residual: bytes) -> bytes:
+    """``header``: {"max_error": D in 0..MAX_ERROR, "coder": name in CODERS of the residual string, "height", "width",
+    "table_crc": u32}; ``base``: one complete ICMB or ICMT stream; ``residual``: the residual layer's string."""
+    missing = [k for k in RESIDUAL_HEADER_KEYS if k not in header]
+    if missing:
+        raise ValueError(f"bitstream: residual header lacks {missing}")
+    check_coder(header["coder"], "bitstream: ")
+    base, residual = bytes(base), bytes(residual)
+    if base[:4] not in (MAGIC, TILED_MAGIC):
+        raise ValueError("bitstream: the base of an ICMR stream must be an ICMB or ICMT stream")
+    out = bytearray(_RFIXED.pack(
+        RESIDUAL_MAGIC, RESIDUAL_VERSION, _uint("max_error", header["max_error"], MAX_ERROR),
+        CODERS.index(header["coder"]), _uint("height", header["height"], RESIDUAL_SIDE_MAX, 1),
+        _uint("width", header["width"], RESIDUAL_SIDE_MAX, 1), _uint("table_crc", header["table_crc"], U32_MAX),
+        _uint("base length", len(base), U32_MAX), _uint("residual length", len(residual), U32_MAX)))
+    out += base
+    out += residual
+    out += _U32.pack(zlib.crc32(bytes(out)) & U32_MAX)
+    return bytes(out)
+
+
+def is_residual(data) -> bool:
+    """True if ``data`` begins with the magic of an error-bounded stream (says nothing else about it)"""
+    return isinstance(data, (bytes, bytearray, memoryview)) and bytes(data[:4]) == RESIDUAL_MAGIC
+
+
+def unpack_residual(data: bytes, table_crc: Optional[int] = None) -> Tuple[Dict, bytes, bytes]:
+    """inverse of ``pack_residual``: (header, base stream, residual string).  ValueError for a bad magic, an unknown
+    version or coder id, D above MAX_ERROR, an image side outside 1..32768, declared lengths that run past the data,
+    trailing bytes, a CRC mismatch, a base that begins with neither inner magic and, with ``table_crc`` (the reader's
+    own), a stream written with other tables.  The base is returned as it lies; ``unpack`` / ``unpack_tiled`` check
+    it."""
+    if not isinstance(data, (bytes, bytearray, memoryview)):
+        raise ValueError(f"bitstream: expected bytes, got {type(data).__name__}")
+    data = bytes(data)
+    if not RESIDUAL_MAGIC.startswith(data[:4]):
+        raise ValueError("bitstream: bad magic (not an ICMR stream)")
+    if len(data) < RESIDUAL_FIXED_BYTES + CRC_BYTES:
+        raise ValueError(f"bitstream: truncated: {len(data)} bytes, the fixed residual header and CRC need "
+                         f"{RESIDUAL_FIXED_BYTES + CRC_BYTES}")
+    (_, version, d, coder_id, height, width, tcrc, nbase, nres) = _RFIXED.unpack_from(data, 0)
+    if version != RESIDUAL_VERSION:
+        raise ValueError(f"bitstream: unknown residual format version {version} (this reader knows {RESIDUAL_VERSION})")
+    if d > MAX_ERROR:
+        raise ValueError(f"bitstream: max_error = {d} outside [0, {MAX_ERROR}]")
+    if coder_id >= len(CODERS):
+        raise ValueError(f"bitstream: unknown coder id {coder_id} (this reader knows 0..{len(CODERS) - 1})")
+    if not (1 <= height <= RESIDUAL_SIDE_MAX and 1 <= width <= RESIDUAL_SIDE_MAX):
+        raise ValueError(f"bitstream: image {height}x{width} outside 1..{RESIDUAL_SIDE_MAX} a side")
+    end = RESIDUAL_FIXED_BYTES + nbase + nres
+    if end + CRC_BYTES > len(data):
+        raise ValueError(f"bitstream: truncated: declared lengths {nbase} + {nres} run past the data ({len(data)} "
+                         f"bytes, {end + CRC_BYTES} needed)")
+    if end + CRC_BYTES < len(data):
+        raise ValueError(f"bitstream: {len(data) - end - CRC_BYTES} trailing bytes after the CRC")
+    if _U32.unpack_from(data, end)[0] != zlib.crc32(data[:end]) & U32_MAX:
+        raise ValueError("bitstream: CRC mismatch (corrupt stream)")
+    base = data[RESIDUAL_FIXED_BYTES:RESIDUAL_FIXED_BYTES + nbase]
+    if base[:4] not in (MAGIC, TILED_MAGIC):
+        raise ValueError("bitstream: the base of the ICMR stream is neither an ICMB nor an ICMT stream")
+    if table_crc is not None and tcrc != table_crc & U32_MAX:
+        raise ValueError(f"bitstream: residual table mismatch: the stream was written with tables {tcrc:#010x}, this "
+                         f"reader has {table_crc & U32_MAX:#010x}")
+    header = {"max_error": d, "coder": CODERS[coder_id], "height": height, "width": width, "table_crc": tcrc}
+    return header, base, data[RESIDUAL_FIXED_BYTES + nbase:end]

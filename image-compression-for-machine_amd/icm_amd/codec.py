@@ -2,7 +2,7 @@
 
     python -m icm_amd.codec encode IMAGE -o FILE -a cnn -p CKPT [--tile N [--overlap M]] [--coder {host,lanes}]
                                    [--qstep K | --target-bytes N | --target-bpp F] [--roi Y0,X0,H,W:D ...] [--rdoq W]
-                                   [--aq S]
+                                   [--aq S] [--max-error D]
     python -m icm_amd.codec decode FILE -o IMAGE.png -p CKPT [--reference IMAGE] [--region Y0,X0,H,W]
 
 Parity unpinned: no counterpart in the reference (upstream CompressAI's ``examples/codec.py`` is not in its tree).  The
@@ -49,7 +49,17 @@ pass over the 8-bit image gives every cell the variance v of its luma (``icm_ima
 and the cell is coded with the step index K + clip(rint(4 S (log2(1 + v) - the image's mean of it)), -16, 16).  S > 0
 spends bits on flat cells and saves them on busy ones, S < 0 the reverse; |S| <= 4.  S = 1 makes the step follow the
 cell's standard deviation: a rule, not a measured optimum.  ``--roi`` rectangles win over it, a budget search runs over K
-with the offsets fixed, tiles share the image's mean, and ``decode`` needs no flag.  Parity unpinned."""
+with the offsets fixed, tiles share the image's mean, and ``decode`` needs no flag.  Parity unpinned.
+
+``--max-error D`` gives a guarantee per sample where every flag above steers an average: the file decodes to an image
+whose every 8-bit sample lies within D of the original's, D in 0 .. 32, and D = 0 gives the original back bit for bit.
+The base is coded as without the flag (every flag above applies to it; a byte budget contradicts a bound and is refused);
+the encoder then decodes it on the device, as the decoder will, and codes the quantised differences as a second layer
+(``icm_amd.residual``, csrc/residual.hip: a uniform quantiser of step 2 D + 1, one context class per 16 x 16-pixel cell,
+static two-sided geometric tables, the coder ``--coder`` names), both wrapped in an ``ICMR`` container
+(``icm_amd.bitstream``).  ``decode`` needs no flag; with ``--region`` it decodes the base's region only but the residual
+string whole -- decoding only the window's part of the lane bodies is not built.  Files written without the flag are
+byte for byte what they were.  Parity unpinned: no counterpart in the reference."""
 from __future__ import annotations
 
 import argparse
@@ -65,7 +75,10 @@ import torch
 
 from . import _lib as L
 from . import bitstream as B
+from . import residual as R
 from ._lib import check
+from .ans import coder_for
+from .residual import ResidualTables      # noqa: F401  part of this module's surface
 
 PAD_MULTIPLE = 64      # six stride-2 stages (utils.pad_to_multiple)
 
@@ -375,13 +388,19 @@ def search_qstep(fits, lo: int = B.QSTEP_MIN, hi: int = B.QSTEP_MAX) -> Tuple[in
 def encode_image_info(model, img, tile: Optional[int] = None, overlap: int = 0, coder: str = "host",
                       symbols_per_wave: Optional[int] = None, qstep: int = 0,
                       max_bytes: Optional[int] = None, roi: Optional[Sequence] = None,
-                      rdoq: Optional[float] = None, aq: Optional[float] = None) -> Tuple[bytes, Dict]:
+                      rdoq: Optional[float] = None, aq: Optional[float] = None,
+                      max_error: Optional[int] = None) -> Tuple[bytes, Dict]:
     """``encode_image`` with its outcome: (stream, {"qstep": k, "step": 2^(k/8), "probes": encodes made}); k is the
     background step.  With ``roi`` or ``aq`` also "roi_cells", the number of latent cells (summed over the tiles) whose
     step index differs from k, and "qmap_range": [smallest, largest step index in the maps].  With ``rdoq`` also "rdoq",
     the weight as the kernel took it.  With ``aq`` also "aq", the strength as checked, "aq_ref", the image's reference
-    activity, and "aq_offset_range": [smallest, largest offset over all tiles]."""
+    activity, and "aq_offset_range": [smallest, largest offset over all tiles].  With ``max_error`` also "max_error",
+    "base_bytes" and "residual_bytes" (the base stream and the residual string inside the ICMR container) and
+    "residual_class_range": [smallest, largest context class of the cells]."""
     B.check_coder(coder, "codec: ")
+    max_error = R.check_max_error(max_error, "codec: ")
+    if max_error is not None and max_bytes is not None:
+        raise ValueError("codec: give a byte budget or an error bound, not both: the bound decides the size")
     qstep = B.check_qstep(qstep, "codec: ")
     rdoq = B.check_rdoq(rdoq, "codec: ")
     aq = check_aq(aq, "codec: ")
@@ -396,6 +415,8 @@ def encode_image_info(model, img, tile: Optional[int] = None, overlap: int = 0, 
     device = next(model.parameters()).device
     u8 = _as_u8_image(img, device)
     H, W = u8.size(0), u8.size(1)
+    if max_error is not None and max(H, W) > B.RESIDUAL_SIDE_MAX:
+        raise ValueError(f"codec: max_error takes images of at most {B.RESIDUAL_SIDE_MAX} pixels a side, got {H}x{W}")
     if tile is None:
         if overlap:
             raise ValueError("codec: overlap needs a tile extent")
@@ -435,7 +456,17 @@ def encode_image_info(model, img, tile: Optional[int] = None, overlap: int = 0, 
         ms, extra = maps(qstep)
         data = wrap([_encode_one(model, arch, fp, c, coder, symbols_per_wave, 0 if m is not None else qstep, m, rdoq)
                      for c, m in zip(crops, ms)])
-        return data, {"qstep": qstep, "step": B.step_of(qstep)[0], "probes": 1, **extra, **told}
+        told = {"qstep": qstep, "step": B.step_of(qstep)[0], "probes": 1, **extra, **told}
+        if max_error is not None:
+            # the residual layer: the base decoded on the device as the decoder will decode it, the quantised
+            # differences coded as one string, both wrapped
+            xhat = _decode_device(model, data)[0]
+            string, classes = R.encode_residual(u8, xhat, max_error, coder_for(coder, symbols_per_wave))
+            told.update(max_error=max_error, base_bytes=len(data), residual_bytes=len(string),
+                        residual_class_range=list(classes))
+            data = B.pack_residual({"max_error": max_error, "coder": coder, "height": H, "width": W,
+                                    "table_crc": R.tables().crc}, data, string)
+        return data, told
     # encode to size: the analysis transform once per tile, then only the latent coder per probe; a probe is the very
     # container that would be written (headers, CRCs and the lanes coder's flushes included), and the answer is the
     # stream of its probe, not a second encode
@@ -468,7 +499,8 @@ def encode_image_info(model, img, tile: Optional[int] = None, overlap: int = 0, 
 
 def encode_image(model, img, tile: Optional[int] = None, overlap: int = 0, coder: str = "host",
                  symbols_per_wave: Optional[int] = None, qstep: int = 0, max_bytes: Optional[int] = None,
-                 roi: Optional[Sequence] = None, rdoq: Optional[float] = None, aq: Optional[float] = None) -> bytes:
+                 roi: Optional[Sequence] = None, rdoq: Optional[float] = None, aq: Optional[float] = None,
+                 max_error: Optional[int] = None) -> bytes:
     """8-bit [H, W, 3] image (tensor on any device, or anything ``numpy.asarray`` accepts) -> one bit-stream.  With
     ``tile``, an image of more than one tile (``plan_tiles``) becomes an ICMT stream whose tile k is
     ``encode_image(model, crop k)``, the tiles coded one after another; an image of one tile is written untiled.
@@ -488,8 +520,13 @@ def encode_image(model, img, tile: Optional[int] = None, overlap: int = 0, coder
     the stream is what it is without): the quality map is derived from the image, each cell's offset to k following the
     variance of its luma against the image's average (``aq_offsets``; positive: flat cells finer, busy cells coarser).
     Rectangles of ``roi`` win over it; a budget search moves k under the fixed offsets; the tiles of a tiled image
-    share one reference.  A flat image, or a strength at which every offset rounds to 0, gives the stream without."""
-    return encode_image_info(model, img, tile, overlap, coder, symbols_per_wave, qstep, max_bytes, roi, rdoq, aq)[0]
+    share one reference.  A flat image, or a strength at which every offset rounds to 0, gives the stream without.
+    ``max_error``: an integer D in 0 .. 32 (None, the default: off, and the stream is what it is without): the stream
+    becomes an ICMR container of the very stream the other arguments give, the base, and the residual string that
+    brings every sample of the decode within D of the image's (0: the image itself).  ``coder`` codes that string too.
+    Not with ``max_bytes``: ValueError."""
+    return encode_image_info(model, img, tile, overlap, coder, symbols_per_wave, qstep, max_bytes, roi, rdoq, aq,
+                             max_error)[0]
 
 
 def _check_model(header: Dict, arch: str, fp: int, what: str = "the stream") -> None:
@@ -550,14 +587,52 @@ def _check_region(region, H: int, W: int) -> Tuple[int, int, int, int]:
 
 @torch.no_grad()
 def decode_image(model, data: bytes, reference=None, region=None) -> Tuple[torch.Tensor, Dict]:
-    """one bit-stream, ICMB or ICMT -> (8-bit [H, W, 3] host tensor, info); ``info``: "bpp" = 8 x the whole stream
+    """one bit-stream, ICMB, ICMT or ICMR -> (8-bit [H, W, 3] host tensor, info); ``info``: "bpp" = 8 x the whole stream
     length / (H W), header included, and, given ``reference`` (the original 8-bit image), "psnr" of the two 8-bit
     images.  ``region`` = (y0, x0, h, w): only that window is returned ([h, w, 3]; "sse" / "psnr" are over it, against
     the same window of ``reference``); of a tiled stream only the tiles that touch it are decoded
     (``info["tiles_decoded"]``), and the result is bit for bit the same crop of the full decode.  "qstep": the step
     index the stream was coded with (0: none), or the list per tile should they differ; None for a stream (in the
     list: a tile) coded with a quality map, which "qmap" then holds: the int8 map, or of a tiled stream the list per
-    tile with None for the tiles of a scalar step.  Streams without a map have no "qmap"."""
+    tile with None for the tiles of a scalar step.  Streams without a map have no "qmap".
+    An ICMR stream: the base is decoded as above (with ``region``, only that region), the residual string is decoded
+    whole -- also with ``region``: decoding only the window's part of the lane bodies is not built -- and applied to
+    the window; a region decode is bit for bit the crop of the full decode.  ``info`` is the base's with "bytes" and
+    "bpp" of the whole file, and "max_error", "base_bytes" and "residual_bytes"; with ``reference`` also
+    "max_abs_error", the largest absolute difference of a sample to the reference's, and "sse" / "psnr" of the final
+    image."""
+    if B.is_residual(data):
+        head, base, string = B.unpack_residual(data, R.tables().crc)
+        device = next(model.parameters()).device
+        out, _, info, (ry, rx, rh, rw) = _decode_device(model, base, None, region)
+        H, W, D = head["height"], head["width"], head["max_error"]
+        if (info["height"], info["width"]) != (H, W):
+            raise ValueError(f"codec: the ICMR stream holds a {H}x{W} image, its base a {info['height']}x{info['width']}")
+        sym = R.decode_residual(string, H, W, coder_for(head["coder"]), device)
+        out = R.residual_apply(out, sym, (ry, rx, rh, rw), D)
+        info.update(bytes=len(data), bpp=8.0 * len(data) / (H * W), max_error=D, base_bytes=len(base),
+                    residual_bytes=len(string))
+        if reference is not None:
+            ref = _as_u8_image(reference, device, "reference")
+            if tuple(ref.shape) != (H, W, 3):
+                raise ValueError(f"codec: the reference is {ref.size(0)}x{ref.size(1)}, the stream holds a {H}x{W} image")
+            d = out.to(torch.int32) - ref[ry:ry + rh, rx:rx + rw].to(torch.int32)
+            info["max_abs_error"] = int(d.abs().max().item())
+            info["sse"] = int((d.to(torch.int64) ** 2).sum().item())
+            info["psnr"] = 10.0 * math.log10(255.0 ** 2 / (info["sse"] / (rh * rw * 3))) if info["sse"] else math.inf
+        return out.cpu(), info
+    out, sse, info, (ry, rx, rh, rw) = _decode_device(model, data, reference, region)
+    if sse is not None:
+        info["sse"] = int(sse.item())
+        info["psnr"] = 10.0 * math.log10(255.0 ** 2 / (info["sse"] / (rh * rw * 3))) if info["sse"] else math.inf
+    return out.cpu(), info
+
+
+def _decode_device(model, data: bytes, reference=None, region=None):
+    """the device-side body of ``decode_image`` for an ICMB or ICMT stream, shared with the encoder of the residual
+    layer -> (8-bit [h, w, 3] device tensor of the region, the device scalar of the squared differences to
+    ``reference`` or None, info without "sse" / "psnr", the region as checked (y0, x0, h, w)).  The image stays on the
+    device."""
     arch = _ready(model)
     fp = B.fingerprint(model)
     device = next(model.parameters()).device
@@ -614,10 +689,7 @@ def decode_image(model, data: bytes, reference=None, region=None) -> Tuple[torch
     if region is not None:
         info["region"] = [ry, rx, rh, rw]
     out, sse = image_f32_to_u8(x_hat, (left, x_hat.size(3) - left - rw, top, x_hat.size(2) - top - rh), ref)
-    if sse is not None:
-        info["sse"] = int(sse.item())
-        info["psnr"] = 10.0 * math.log10(255.0 ** 2 / (info["sse"] / (rh * rw * 3))) if info["sse"] else math.inf
-    return out.cpu(), info
+    return out, sse, info, (ry, rx, rh, rw)
 
 
 # ------------------------------------------------------------------------------------------------------------ CLI
@@ -695,6 +767,10 @@ def setup_args() -> argparse.ArgumentParser:
                           f"step index offset by 4 S x (log2 of its luma variance against the image's mean), within "
                           f"+-{AQ_MAX_OFFSET}; S > 0: flat cells finer, busy cells coarser; |S| <= {AQ_STRENGTH_MAX:g} "
                           f"(default: off)")
+    enc.add_argument("--max-error", default=None, type=int, metavar="D",
+                     help=f"error bound: add a residual layer so that every 8-bit sample of the decode lies within D of "
+                          f"the original's, D in 0..{B.MAX_ERROR}; 0: lossless (default: off; not with --target-bytes / "
+                          f"--target-bpp)")
     for s in (enc, dec):
         s.add_argument("-o", "--output", required=True, help="file to write")
         s.add_argument("-p", "--path", dest="paths", required=True, type=str, help="checkpoint path")
@@ -737,6 +813,9 @@ def main(argv) -> int:
                 raise ValueError(f"--target-bpp must be a positive number, got {args.target_bpp}")
             B.check_rdoq(args.rdoq, "--")
             check_aq(args.aq, "--")
+            R.check_max_error(args.max_error, "--")
+            if args.max_error is not None and (args.target_bytes is not None or args.target_bpp is not None):
+                raise ValueError("give --max-error or a byte budget (--target-bytes / --target-bpp), not both")
         except ValueError as e:
             print(f"Error: {e}", file=sys.stderr)
             return 2
@@ -754,7 +833,8 @@ def main(argv) -> int:
                 raise ValueError(f"{args.input}: no such file")
             with open(args.input, "rb") as f:
                 payload = f.read()
-            header, _ = B.unpack_tiled(payload) if B.is_tiled(payload) else B.unpack(payload)
+            inner = B.unpack_residual(payload, R.tables().crc)[1] if B.is_residual(payload) else payload
+            header, _ = B.unpack_tiled(inner) if B.is_tiled(inner) else B.unpack(inner)
             if arch is not None and arch != header["arch"]:
                 print(f"Error: -a {arch} disagrees with the stream, written by {header['arch']!r}.", file=sys.stderr)
                 return 2
@@ -775,7 +855,7 @@ def main(argv) -> int:
             budget = args.target_bytes if args.target_bpp is None else int(math.floor(args.target_bpp * h * w / 8))
             data, found = encode_image_info(model, payload, args.tile, args.overlap, coder=args.coder,
                                             qstep=args.qstep or 0, max_bytes=budget, roi=args.roi, rdoq=args.rdoq,
-                                            aq=args.aq)
+                                            aq=args.aq, max_error=args.max_error)
             torch.cuda.synchronize()
             dt = time.perf_counter() - t0
             with open(args.output, "wb") as f:

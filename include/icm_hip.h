@@ -652,6 +652,32 @@ int icm_image_tile_blend(const float* src, int PH, int PW, int top, int left, in
                          float* canvas, int H, int W, int y0, int x0,
                          const float* ramp, int m, int edges, void* stream);
 
+/* ---- error-bounded residual layer of the codec (icm_amd/residual.py, ICMR streams; no counterpart in the reference).
+ * x = the original image, xhat = the decoder's reconstruction of the base stream, both interleaved [H, W, 3] bytes;
+ * D = the bound, 0..32, s = 2 D + 1.  Integer arithmetic only:
+ *   q = sign(x - xhat) ((|x - xhat| + D) div s),   xtilde = min(max(xhat + q s, 0), 255),   |x - xtilde| <= D.
+ * Symbols, indexes = planar [3, H, W] int32, image pixels only.  Classes = [gh, gw] int32 over the 16 x 16-pixel cells
+ * of the grid anchored at pixel (0, 0), gh = ceil(H / 16), gw = ceil(W / 16), edge cells partial, one class for the
+ * three channels: with N the samples of the cell (3 x its pixels) and S the sum of |q| over them, the class is the
+ * number of thresholds T_j = round(2^(1 + j / 2)), j = 0..17, with 16 S > N T_j (an integer comparison): 0..18.
+ * residual_code: one wave per cell forms q from the cell's two blocks of bytes, reduces S across the wave and writes
+ *   the cell's symbols, its indexes (= its class) and classes[cell].
+ * residual_indexes: the decoder's expansion, indexes[c][y][x] = classes[y / 16][x / 16], the value as found (classes as
+ *   decoded, in device memory; a value outside the tables is the entropy decoder's to flag).
+ * residual_apply: out = interleaved [h, w, 3] bytes, xtilde of the window (y0, x0, h, w) of the image from xhat =
+ *   interleaved [h, w, 3] bytes of that window and the whole image's symbols; the full image is the window
+ *   (0, 0, H, W).  Any int32 symbol gives the value of the exact integers (no overflow).
+ * Each: one launch, no atomics, no allocation, no synchronisation (graph-capturable); every output element is written
+ * exactly once, the caller does not clear it.  No pointer needs more than its natural alignment: runs of four pixels
+ * whose bytes are not dword-aligned, or whose int32 are not 16-byte aligned, move one at a time.
+ * ICM_ERR_ARG before the launch: null pointers, H, W, h or w outside 1..32768, D outside 0..32, y0 or x0 < 0, a window
+ * outside the image. */
+int icm_residual_code(const uint8_t* x, const uint8_t* xhat, int H, int W, int D, int32_t* symbols, int32_t* indexes,
+                      int32_t* classes, void* stream);
+int icm_residual_indexes(const int32_t* classes, int H, int W, int32_t* indexes, void* stream);
+int icm_residual_apply(const uint8_t* xhat, const int32_t* symbols, int H, int W, int y0, int x0, int h, int w, int D,
+                       uint8_t* out, void* stream);
+
 /* ---- device-resident training data (icm_amd/datasets.py DeviceImageCache; stands in for the reference's per-step
  * CenterCrop / RandomCrop(pad_if_needed) + ToTensor + collate on the host, train.py:393-425).  A training batch cut out
  * of an arena of 8-bit images in one launch: sample b is the interleaved [H, W, 3] byte image at arena + offset, and

@@ -1,0 +1,151 @@
+#!/usr/bin/env python
+"""The error-bounded residual layer (``codec encode --max-error``): what its three kernels cost, and what the whole
+encode and decode cost with and without it, on a large synthetic image (2048x3072).
+
+    kernel   icm_residual_code, icm_residual_indexes and icm_residual_apply alone: microseconds per launch (HIP events
+             over --iters launches of the C entry points) and achieved bytes/s.  Bytes are those the algorithm needs:
+             6 in and 24 + 4 / 256 out per pixel for code, 12 out for indexes, 15 in and 3 out for apply.  Launches rotate
+             over two sets of buffers, more than the 256 MiB last-level cache in all.  The yardstick printed next to each
+             is a device-to-device copy that moves the same number of bytes (half of them read, half written), rotated
+             and timed the same way.
+    codec    encode_image / decode_image without and with max_error = --max-error in the same process, alternating,
+             medians of --rounds wall times (device synchronised), the file sizes, and the bound as decoded.
+
+The model is a randomly initialised ``cnn`` (seeded): its base reconstruction is far from the image, so the residual
+dominates the file and the sizes say nothing about a trained codec.  The bound is what is verified, not the rate.  Prints
+one JSON line per part.
+
+    python tools/bench_codec_residual.py [--iters 100] [--rounds 3] [--kernel-only] [--coder {host,lanes}] [--max-error D]
+
+--kernel-only runs the kernel part alone (the run to put under rocprofv3 --kernel-trace --stats).
+"""
+import argparse
+import json
+import os
+import statistics
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+for p in (ROOT, os.path.join(ROOT, "image-compression-for-machine_amd"), os.path.join(ROOT, "tools")):
+    if p not in sys.path:
+        sys.path.insert(0, p)
+
+from bench_codec_tiles import HBM_PEAK, synthetic, wall  # noqa: E402
+
+H, W = 2048, 3072
+SETS = 2
+
+
+def events(fn, iters, torch):
+    for i in range(SETS + 2):
+        fn(i)
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    torch.cuda.synchronize()
+    e0.record()
+    for i in range(iters):
+        fn(i)
+    e1.record()
+    torch.cuda.synchronize()
+    return e0.elapsed_time(e1) / iters * 1e3
+
+
+def kernel_part(args, torch, np, R, L):
+    dev, d = "cuda:0", args.max_error
+    rng = np.random.default_rng(1)
+    x = synthetic(np, H, W, 1)
+    xhat = np.clip(x.astype(np.int64) + rng.integers(-12, 13, size=x.shape), 0, 255).astype(np.uint8)
+    gh, gw = R.grid(H, W)
+    sets = []
+    for _ in range(SETS):
+        s = {"x": torch.from_numpy(x).to(dev), "xhat": torch.from_numpy(xhat).to(dev),
+             "sym": torch.empty((3, H, W), dtype=torch.int32, device=dev),
+             "idx": torch.empty((3, H, W), dtype=torch.int32, device=dev),
+             "cls": torch.empty((gh, gw), dtype=torch.int32, device=dev),
+             "out": torch.empty((H, W, 3), dtype=torch.uint8, device=dev)}
+        sets.append(s)
+    lib, st = L.lib(), L.stream()
+    px = H * W
+    launches = {
+        "icm_residual_code": (6 * px + 24 * px + 4 * gh * gw, lambda s: lib.icm_residual_code(
+            s["x"].data_ptr(), s["xhat"].data_ptr(), H, W, d, s["sym"].data_ptr(), s["idx"].data_ptr(),
+            s["cls"].data_ptr(), st)),
+        "icm_residual_indexes": (12 * px + 4 * gh * gw, lambda s: lib.icm_residual_indexes(
+            s["cls"].data_ptr(), H, W, s["idx"].data_ptr(), st)),
+        "icm_residual_apply": (15 * px + 3 * px, lambda s: lib.icm_residual_apply(
+            s["xhat"].data_ptr(), s["sym"].data_ptr(), H, W, 0, 0, H, W, d, s["out"].data_ptr(), st)),
+    }
+    for name, (nbytes, fn) in launches.items():
+        L.check(fn(sets[0]), name)
+        us = events(lambda i: fn(sets[i % SETS]), args.iters, torch)
+        half = nbytes // 2
+        src = [torch.empty(half, dtype=torch.uint8, device=dev) for _ in range(SETS)]
+        dst = [torch.empty(half, dtype=torch.uint8, device=dev) for _ in range(SETS)]
+        cus = events(lambda i: dst[i % SETS].copy_(src[i % SETS]), args.iters, torch)
+        del src, dst
+        print(json.dumps({"metric": "residual_kernel", "kernel": name, "height": H, "width": W, "max_error": d,
+                          "iters": args.iters, "us_per_launch": round(us, 2), "bytes": nbytes,
+                          "GBps": round(nbytes / us / 1e3, 1),
+                          "pct_of_hbm_peak": round(100.0 * nbytes / (us * 1e-6) / HBM_PEAK, 1),
+                          "copy_same_bytes_us": round(cus, 2), "kernel_over_copy": round(us / cus, 2),
+                          "note": "HIP events around back-to-back launches from Python, two rotating buffer sets: "
+                                  "launch overhead is inside both figures"}), flush=True)
+    s = sets[0]
+    err = (s["out"].to(torch.int16) - s["x"].to(torch.int16)).abs().max().item()
+    assert err <= d, err
+
+
+def codec_part(args, torch, np, codec):
+    from icm_amd.zoo import models
+    torch.manual_seed(0)
+    model = models["cnn"]().to("cuda:0").eval()
+    model.update(force=True)
+    a = synthetic(np, H, W, 1)
+    variants = {"plain": {}, "bounded": {"max_error": args.max_error}}
+    data, info, te, td = {}, {}, {k: [] for k in variants}, {k: [] for k in variants}
+    for k, extra in variants.items():                                       # warm every shape up
+        data[k], info[k] = codec.encode_image_info(model, a, coder=args.coder, **extra)
+        codec.decode_image(model, data[k])
+    for _ in range(args.rounds):                                            # alternating: drift hits both alike
+        for k, extra in variants.items():
+            te[k].append(wall(lambda: codec.encode_image(model, a, coder=args.coder, **extra), torch)[0])
+            td[k].append(wall(lambda: codec.decode_image(model, data[k]), torch)[0])
+    out, dinfo = codec.decode_image(model, data["bounded"], reference=a)
+    assert dinfo["max_abs_error"] <= args.max_error
+    print(json.dumps({"metric": "codec_residual", "coder": args.coder, "height": H, "width": W,
+                      "max_error": args.max_error, "model": "cnn, randomly initialised (seed 0)", "rounds": args.rounds,
+                      "plain_encode_s": round(statistics.median(te["plain"]), 4),
+                      "bounded_encode_s": round(statistics.median(te["bounded"]), 4),
+                      "plain_decode_s": round(statistics.median(td["plain"]), 4),
+                      "bounded_decode_s": round(statistics.median(td["bounded"]), 4),
+                      "plain_encode_s_all": [round(t, 4) for t in te["plain"]],
+                      "bounded_encode_s_all": [round(t, 4) for t in te["bounded"]],
+                      "plain_decode_s_all": [round(t, 4) for t in td["plain"]],
+                      "bounded_decode_s_all": [round(t, 4) for t in td["bounded"]],
+                      "plain_bytes": len(data["plain"]), "bounded_bytes": len(data["bounded"]),
+                      "base_bytes": info["bounded"]["base_bytes"], "residual_bytes": info["bounded"]["residual_bytes"],
+                      "residual_class_range": info["bounded"]["residual_class_range"],
+                      "max_abs_error": dinfo["max_abs_error"], "bpp": round(dinfo["bpp"], 3)}), flush=True)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--iters", type=int, default=100)
+    ap.add_argument("--rounds", type=int, default=3)
+    ap.add_argument("--kernel-only", action="store_true")
+    ap.add_argument("--coder", default="lanes", choices=["host", "lanes"])
+    ap.add_argument("--max-error", type=int, default=2)
+    args = ap.parse_args()
+    import numpy as np
+    import torch
+    if not torch.cuda.is_available():
+        sys.exit("bench_codec_residual: no GPU (there is no CPU fallback)")
+    from icm_amd import _lib as L
+    from icm_amd import codec
+    from icm_amd import residual as R
+    kernel_part(args, torch, np, R, L)
+    if not args.kernel_only:
+        codec_part(args, torch, np, codec)
+
+
+if __name__ == "__main__":
+    main()
