@@ -530,9 +530,6 @@ def flush_wgrads(tape):
     if _SKIP_WGRAD:   # measurement only (ICM_DEBUG_SKIP_WGRAD=1): time the main stream without weight gradients
         tape.wjobs = []
         return
-    groups: Dict[tuple, list] = {}
-    for job in tape.wjobs:
-        groups.setdefault(job[0], []).append(job)
     jobs_all = tape.wjobs
     tape.wjobs = []
     lib = L.lib()
@@ -544,27 +541,45 @@ def flush_wgrads(tape):
         side.wait_event(ev)
         st = side.cuda_stream
         tape._flushed.append(jobs_all)
-    for key, jobs in groups.items():
+    # One launch runs its members side by side, and the launches of one flush are ordered by geometry, not by queue
+    # position.  A weight (or bias) used by two layers has two problems on one buffer, an overwrite and a later add:
+    # the queue is cut into runs in which every output buffer appears once, and the runs are issued in queue order (one
+    # stream), so the overwrite comes first and never shares a launch with the add.  No shared weights: one run.
+    runs, run, seen = [], [], set()
+    for job in jobs_all:
+        outs_ = {job[3].data_ptr()} if job[5] is None else {job[3].data_ptr(), job[5].data_ptr()}
+        if seen & outs_:
+            runs.append(run)
+            run, seen = [], set()
+        run.append(job)
+        seen |= outs_
+    runs.append(run)
+    chunks = []
+    for run in runs:
+        groups: Dict[tuple, list] = {}
+        for job in run:
+            groups.setdefault(job[0], []).append(job)
+        for key, jobs in groups.items():
+            chunks += [(key, jobs[i0:i0 + 32]) for i0 in range(0, len(jobs), 32)]
+    for key, chunk in chunks:
         geom, algo = key[:15], key[-1]
-        for i0 in range(0, len(jobs), 32):
-            chunk = jobs[i0:i0 + 32]
-            arr = (L.WgradArgs * len(chunk))()
-            for a, (_, gs, gb, dw, accum, dbias, accum_bias, dw_ld) in zip(arr, chunk):
-                _wgrad_args(a, gs, gb, dw, geom, accum, dbias, accum_bias, dw_ld, algo)
-            n = (_wgrad_ws_floats(arr, True) + 63) // 64 * 64
-            if side is not None:
-                if tape._side_ws is None or tape._side_ws.numel() < n * len(chunk):
-                    with torch.cuda.stream(side):
-                        tape._side_ws = torch.empty(max(n * len(chunk), 1 << 24), dtype=torch.float32,
-                                                    device=chunk[0][1].device)
-                ws = tape._side_ws
-            else:
-                ws = tape.workspace(n * len(chunk), chunk[0][1].device)
-            for j, a in enumerate(arr):
-                a.ws, a.ws_floats = ptr(ws) + 4 * n * j, n
-            e0 = _prof_begin(side)
-            check(lib.icm_conv_wgrad_grouped(arr, len(chunk), st), "conv_wgrad_grouped")
-            _wgrad_prof_end(e0, key, algo, len(chunk), side)
+        arr = (L.WgradArgs * len(chunk))()
+        for a, (_, gs, gb, dw, accum, dbias, accum_bias, dw_ld) in zip(arr, chunk):
+            _wgrad_args(a, gs, gb, dw, geom, accum, dbias, accum_bias, dw_ld, algo)
+        n = (_wgrad_ws_floats(arr, True) + 63) // 64 * 64
+        if side is not None:
+            if tape._side_ws is None or tape._side_ws.numel() < n * len(chunk):
+                with torch.cuda.stream(side):
+                    tape._side_ws = torch.empty(max(n * len(chunk), 1 << 24), dtype=torch.float32,
+                                                device=chunk[0][1].device)
+            ws = tape._side_ws
+        else:
+            ws = tape.workspace(n * len(chunk), chunk[0][1].device)
+        for j, a in enumerate(arr):
+            a.ws, a.ws_floats = ptr(ws) + 4 * n * j, n
+        e0 = _prof_begin(side)
+        check(lib.icm_conv_wgrad_grouped(arr, len(chunk), st), "conv_wgrad_grouped")
+        _wgrad_prof_end(e0, key, algo, len(chunk), side)
 
 
 def accumulate(tape, dst_t, src, mul_dgelu_of=None):
@@ -575,7 +590,14 @@ def accumulate(tape, dst_t, src, mul_dgelu_of=None):
     if g.is_contiguous() and src.is_contiguous() and (mul_dgelu_of is None or mul_dgelu_of.is_contiguous()):
         check(L.lib().icm_add_grad(ptr(src), ptr(mul_dgelu_of), ptr(g), src.numel(), acc, tape.st), "add_grad")
     else:
-        assert mul_dgelu_of is None
+        if mul_dgelu_of is not None:
+            # a GELU identity-path term into a channel slice (no dgrad could carry it): the product through a
+            # contiguous temporary, then the strided copy / add below
+            sc = src if src.is_contiguous() else src.contiguous()
+            pc = mul_dgelu_of if mul_dgelu_of.is_contiguous() else mul_dgelu_of.contiguous()
+            tmp = new(sc)
+            check(L.lib().icm_add_grad(ptr(sc), ptr(pc), ptr(tmp), sc.numel(), 0, tape.st), "add_grad")
+            src = tmp
         N, Cc = src.shape[0], src.shape[1]
         HW = src.shape[2] * src.shape[3]
         check(L.lib().icm_copy_strided(ptr(src), bs(src), ptr(g), bs(g), N, Cc, HW, acc, tape.st), "copy_strided")
@@ -651,6 +673,9 @@ def _conv_layer(tape: Tape, single: bool, xvs, ws, bs_, outs, ress, lrp_auxs, *,
             y2s = [new(oshape, x0.device) for _ in range(n)]
         for y, y2 in zip(ys, y2s):
             tape.mat[_key(y)] = y2
+    if outs is not None and tape.mat and (lrp or y2s is None):
+        for y in ys:      # this layer overwrites a caller's tensor and stores no gelu(y): an earlier producer's is stale
+            tape.mat.pop(_key(y), None)
     _conv_launch(tape, single, xfs, wps, bs_, ys, Cin=Cin, Cout=Cout, KH=KH, KW=KW, stride=stride, pad=pad,
                  transposed=transposed, OH=OH, OW=OW, pro_act=actf, epi=epi, ress=resf, auxs=lrp_auxs, y2s=y2s,
                  ps=pixel_shuffle, algo=wino)
@@ -1001,10 +1026,17 @@ def layernorm(tape, x, gamma, beta) -> torch.Tensor:
                 return
             gg = gb_ = dx = None
             ap = ax = 0
-            if tape.wants(gamma):
+            want_g, want_b = tape.wants(gamma), tape.wants(beta)
+            if want_g and want_b:
                 gg, ap = tape.grad_for_write(gamma)
                 gb_, ap2 = tape.grad_for_write(beta)
                 assert ap == ap2
+            elif want_g:      # the kernel writes both parameter gradients or neither: the unwanted one into scratch
+                gg, ap = tape.grad_for_write(gamma)
+                gb_ = zeros(beta.shape, x.device)
+            elif want_b:
+                gb_, ap = tape.grad_for_write(beta)
+                gg = zeros(gamma.shape, x.device)
             rg = None
             if tape.wants(x):
                 rg = tape.take_res_grad(x, False)   # x + f(LN(x)): the identity-path term rides on this pass
