@@ -7,6 +7,13 @@
 //   residual_indexes_kernel  the decoder's expansion: classes [gh, gw] -> one class per sample, [3, H, W]
 //   residual_apply_kernel    xhat of a window, q -> min(max(xhat + q s, 0), 255), interleaved bytes of the window
 //
+// The bound is one number for the image (icm_residual_code / icm_residual_apply) or one byte per 16 x 16-pixel cell of
+// the same grid (icm_residual_code_map / icm_residual_apply_map, ICME streams).  Each operation has one element body,
+// code_cell and apply_run, and two thin kernels that differ in where the bound comes from: a kernel argument, or the
+// map -- read once per wave in residual_code_map_kernel, where a wave owns a cell, and once or twice per run in
+// residual_apply_map_kernel, where a run of four window pixels may straddle a cell boundary of the image.  A map byte
+// above 32 counts as 32 in both, so that the reciprocal below always divides.
+//
 // Integer work only, byte-bound: 6 bytes in and 24 out per pixel for the first, 12 out for the second, 15 in and 3 out
 // for the third.  A thread owns four adjacent pixels of one row: 12 interleaved bytes = three dword accesses where the
 // run lies inside its row and its first byte is dword-aligned, and four int32 per plane = one 16-byte access where its
@@ -70,16 +77,13 @@ __device__ __forceinline__ void store_run(int32_t* o, bool full, int n, const in
 // One wave owns a cell: lane l holds the four pixels 4 (l % 4) .. of row l / 4, so a wave reads the cell's two blocks
 // of 16 rows x 48 bytes and the four waves of a workgroup read 192 contiguous bytes of every row.  S is reduced by six
 // shuffles; N is known from the geometry.  Lanes of rows and columns past the image load and store nothing and add 0.
-__global__ __launch_bounds__(BLOCK) void residual_code_kernel(const uint8_t* __restrict__ x,
-                                                               const uint8_t* __restrict__ xhat, int H, int W, int D,
-                                                               int magic, int gw, int strips,
-                                                               int32_t* __restrict__ symbols,
-                                                               int32_t* __restrict__ indexes,
-                                                               int32_t* __restrict__ classes) {
-  const int cy = blockIdx.x / strips;
-  const int cx = (blockIdx.x - cy * strips) * WAVES + (threadIdx.x >> 6);
-  if (cx >= gw) return;   // wave-uniform; the kernel has no barrier
-  const int lane = threadIdx.x & 63;
+// bound(D, magic) gives the cell's D and magic = 65536 div (2 D + 1) + 1, the same in all lanes; it is asked once the
+// loads of the cell's bytes are on their way, so that a bound that is itself loaded does not wait alone.
+template <class Bound>
+__device__ __forceinline__ void code_cell(const uint8_t* __restrict__ x, const uint8_t* __restrict__ xhat, int H, int W,
+                                          Bound bound, int gw, int cy, int cx, int lane,
+                                          int32_t* __restrict__ symbols, int32_t* __restrict__ indexes,
+                                          int32_t* __restrict__ classes) {
   const int y = cy * CELL + (lane >> 2), px0 = cx * CELL + RUN * (lane & 3);
   const int n = y < H ? min(max(W - px0, 0), RUN) : 0;   // the run's pixels inside the image
   const bool full = n == RUN;
@@ -93,6 +97,8 @@ __global__ __launch_bounds__(BLOCK) void residual_code_kernel(const uint8_t* __r
     uint32_t a[3], e[3];
     load_run(x + o, full, n, a);
     load_run(xhat + o, full, n, e);
+    int D, magic;
+    bound(D, magic);
 #pragma unroll
     for (int b = 0; b < 3 * RUN; ++b) {   // bytes past the row end are zero on both sides: q = 0
       const int r = byte_of(a, b) - byte_of(e, b);
@@ -121,6 +127,37 @@ __global__ __launch_bounds__(BLOCK) void residual_code_kernel(const uint8_t* __r
   if (lane == 0) classes[(size_t)cy * gw + cx] = cls;
 }
 
+__global__ __launch_bounds__(BLOCK) void residual_code_kernel(const uint8_t* __restrict__ x,
+                                                               const uint8_t* __restrict__ xhat, int H, int W, int D,
+                                                               int magic, int gw, int strips,
+                                                               int32_t* __restrict__ symbols,
+                                                               int32_t* __restrict__ indexes,
+                                                               int32_t* __restrict__ classes) {
+  const int cy = blockIdx.x / strips;
+  const int cx = (blockIdx.x - cy * strips) * WAVES + (threadIdx.x >> 6);
+  if (cx >= gw) return;   // wave-uniform; the kernel has no barrier
+  code_cell(x, xhat, H, W, [=](int& d, int& m) { d = D; m = magic; }, gw, cy, cx, threadIdx.x & 63, symbols, indexes,
+            classes);
+}
+
+// the cell's bound from the map: one byte per wave, the same address in all lanes, read first and, when the cell's
+// bytes have been asked for, made a scalar so that the division for the reciprocal is done once per wave
+__global__ __launch_bounds__(BLOCK) void residual_code_map_kernel(const uint8_t* __restrict__ x,
+                                                                   const uint8_t* __restrict__ xhat, int H, int W,
+                                                                   const uint8_t* __restrict__ dmap, int gw, int strips,
+                                                                   int32_t* __restrict__ symbols,
+                                                                   int32_t* __restrict__ indexes,
+                                                                   int32_t* __restrict__ classes) {
+  const int cy = blockIdx.x / strips;
+  const int cx = (blockIdx.x - cy * strips) * WAVES + (threadIdx.x >> 6);
+  if (cx >= gw) return;   // wave-uniform; the kernel has no barrier
+  const int byte = dmap[(size_t)cy * gw + cx];
+  code_cell(x, xhat, H, W, [=](int& d, int& m) {
+    d = __builtin_amdgcn_readfirstlane(min(byte, MAX_D));
+    m = 65536 / (2 * d + 1) + 1;
+  }, gw, cy, cx, threadIdx.x & 63, symbols, indexes, classes);
+}
+
 // a thread owns four adjacent samples of one row (they share a cell) in the three planes
 __global__ __launch_bounds__(BLOCK) void residual_indexes_kernel(const int32_t* __restrict__ classes, int H, int W,
                                                                   int gw, int32_t* __restrict__ indexes,
@@ -137,17 +174,12 @@ __global__ __launch_bounds__(BLOCK) void residual_indexes_kernel(const int32_t* 
   for (int c = 0; c < 3; ++c) store_run(indexes + c * plane + e0, n == RUN, n, k);
 }
 
-// a thread owns four adjacent pixels of one row of the window.  |q| >= 256 saturates whatever s is, so q is clamped
-// to +-256 first and the product stays small: the result is that of the exact integers for every int32 q
-__global__ __launch_bounds__(BLOCK) void residual_apply_kernel(const uint8_t* __restrict__ xhat,
-                                                                const int32_t* __restrict__ symbols, int H, int W,
-                                                                int y0, int x0, int h, int w, int s,
-                                                                uint8_t* __restrict__ out, int runs_per_row,
-                                                                long long total_runs) {
-  const long long g = (long long)blockIdx.x * BLOCK + threadIdx.x;
-  if (g >= total_runs) return;
-  const int y = (int)(g / runs_per_row);
-  const int x = ((int)(g - (long long)y * runs_per_row)) * RUN;
+// a thread owns four adjacent pixels of one row of the window; s[j] is the step 2 D + 1 of pixel j's cell.  |q| >= 256
+// saturates whatever s is, so q is clamped to +-256 first and the product stays small: the result is that of the exact
+// integers for every int32 q
+__device__ __forceinline__ void apply_run(const uint8_t* __restrict__ xhat, const int32_t* __restrict__ symbols, int H,
+                                          int W, int y0, int x0, int w, int y, int x, const int (&s)[RUN],
+                                          uint8_t* __restrict__ out) {
   const int n = min(w - x, RUN);
   const bool full = n == RUN;
   const size_t o = ((size_t)y * w + x) * 3;
@@ -171,7 +203,7 @@ __global__ __launch_bounds__(BLOCK) void residual_apply_kernel(const uint8_t* __
 #pragma unroll
     for (int j = 0; j < RUN; ++j) {
       const int b = 3 * j + c;
-      const int v = min(max(byte_of(e, b) + min(max(q[j], -256), 256) * s, 0), 255);
+      const int v = min(max(byte_of(e, b) + min(max(q[j], -256), 256) * s[j], 0), 255);
       r[b >> 2] |= (uint32_t)v << (8 * (b & 3));
     }
   }
@@ -185,6 +217,44 @@ __global__ __launch_bounds__(BLOCK) void residual_apply_kernel(const uint8_t* __
     for (int b = 0; b < 3 * RUN; ++b)
       if (b < 3 * n) op[b] = (uint8_t)(r[b >> 2] >> (8 * (b & 3)));
   }
+}
+
+__global__ __launch_bounds__(BLOCK) void residual_apply_kernel(const uint8_t* __restrict__ xhat,
+                                                                const int32_t* __restrict__ symbols, int H, int W,
+                                                                int y0, int x0, int h, int w, int s,
+                                                                uint8_t* __restrict__ out, int runs_per_row,
+                                                                long long total_runs) {
+  const long long g = (long long)blockIdx.x * BLOCK + threadIdx.x;
+  if (g >= total_runs) return;
+  const int y = (int)(g / runs_per_row);
+  const int x = ((int)(g - (long long)y * runs_per_row)) * RUN;
+  const int sj[RUN] = {s, s, s, s};
+  apply_run(xhat, symbols, H, W, y0, x0, w, y, x, sj, out);
+}
+
+// The cell of a pixel is that of its image position (y0 + y, x0 + x + j).  The run's pixels inside the window span at
+// most two cells of one row of cells (4 <= 16): the first pixel's and the last one's.  Their bytes are read, the second
+// only where it is another cell, and every pixel takes the one of its own column.  Both lie inside the map: the window
+// lies inside the image.
+__global__ __launch_bounds__(BLOCK) void residual_apply_map_kernel(const uint8_t* __restrict__ xhat,
+                                                                    const int32_t* __restrict__ symbols, int H, int W,
+                                                                    int y0, int x0, int h, int w,
+                                                                    const uint8_t* __restrict__ dmap, int gw,
+                                                                    uint8_t* __restrict__ out, int runs_per_row,
+                                                                    long long total_runs) {
+  const long long g = (long long)blockIdx.x * BLOCK + threadIdx.x;
+  if (g >= total_runs) return;
+  const int y = (int)(g / runs_per_row);
+  const int x = ((int)(g - (long long)y * runs_per_row)) * RUN;
+  const int px = x0 + x, last = px + min(w - x, RUN) - 1;
+  const int c0 = px / CELL, c1 = last / CELL;
+  const uint8_t* row = dmap + (size_t)((y0 + y) / CELL) * gw;
+  const int s0 = 2 * min((int)row[c0], MAX_D) + 1;
+  const int s1 = c1 != c0 ? 2 * min((int)row[c1], MAX_D) + 1 : s0;
+  int sj[RUN];
+#pragma unroll
+  for (int j = 0; j < RUN; ++j) sj[j] = (px + j) / CELL == c0 ? s0 : s1;   // pixels past the window are not stored
+  apply_run(xhat, symbols, H, W, y0, x0, w, y, x, sj, out);
 }
 
 bool side_ok(int v) { return v >= 1 && v <= MAX_SIDE; }
@@ -203,6 +273,18 @@ int icm_residual_code(const uint8_t* x, const uint8_t* xhat, int H, int W, int D
   const int strips = (gw + WAVES - 1) / WAVES;                    // gh strips <= 2048 * 512
   hipLaunchKernelGGL(residual_code_kernel, dim3((unsigned)(gh * strips)), dim3(BLOCK), 0, ST, x, xhat, H, W, D,
                      65536 / (2 * D + 1) + 1, gw, strips, symbols, indexes, classes);
+  ICM_CHECK_LAUNCH();
+  return ICM_OK;
+}
+
+int icm_residual_code_map(const uint8_t* x, const uint8_t* xhat, int H, int W, const uint8_t* dmap, int32_t* symbols,
+                          int32_t* indexes, int32_t* classes, void* stream) {
+  if (!x || !xhat || !dmap || !symbols || !indexes || !classes) return ICM_ERR_ARG;
+  if (!side_ok(H) || !side_ok(W)) return ICM_ERR_ARG;
+  const int gh = (H + CELL - 1) / CELL, gw = (W + CELL - 1) / CELL;
+  const int strips = (gw + WAVES - 1) / WAVES;
+  hipLaunchKernelGGL(residual_code_map_kernel, dim3((unsigned)(gh * strips)), dim3(BLOCK), 0, ST, x, xhat, H, W, dmap,
+                     gw, strips, symbols, indexes, classes);
   ICM_CHECK_LAUNCH();
   return ICM_OK;
 }
@@ -226,6 +308,19 @@ int icm_residual_apply(const uint8_t* xhat, const int32_t* symbols, int H, int W
   const long long total = (long long)h * rpr;
   hipLaunchKernelGGL(residual_apply_kernel, dim3((unsigned)((total + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, ST, xhat,
                      symbols, H, W, y0, x0, h, w, 2 * D + 1, out, rpr, total);
+  ICM_CHECK_LAUNCH();
+  return ICM_OK;
+}
+
+int icm_residual_apply_map(const uint8_t* xhat, const int32_t* symbols, int H, int W, int y0, int x0, int h, int w,
+                           const uint8_t* dmap, uint8_t* out, void* stream) {
+  if (!xhat || !symbols || !dmap || !out) return ICM_ERR_ARG;
+  if (!side_ok(H) || !side_ok(W) || !side_ok(h) || !side_ok(w)) return ICM_ERR_ARG;
+  if (y0 < 0 || x0 < 0 || (long long)y0 + h > H || (long long)x0 + w > W) return ICM_ERR_ARG;
+  const int rpr = (w + RUN - 1) / RUN;
+  const long long total = (long long)h * rpr;
+  hipLaunchKernelGGL(residual_apply_map_kernel, dim3((unsigned)((total + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, ST, xhat,
+                     symbols, H, W, y0, x0, h, w, dmap, (W + CELL - 1) / CELL, out, rpr, total);
   ICM_CHECK_LAUNCH();
   return ICM_OK;
 }

@@ -97,6 +97,7 @@ SYMBOLS = [
     "icm_image_workspace_bytes", "icm_image_u8_to_f32", "icm_image_f32_to_u8",
     "icm_image_batch_u8_to_f32", "icm_image_tile_blend", "icm_image_cell_stats",
     "icm_residual_code", "icm_residual_indexes", "icm_residual_apply",
+    "icm_residual_code_map", "icm_residual_apply_map",
 ]
 REDUCE_WS_FLOATS = 8192   # ICM_REDUCE_WS_FLOATS
 
@@ -260,6 +261,8 @@ def lib():
         L.icm_residual_code.argtypes = [vp, vp, i32, i32, i32, vp, vp, vp, vp]
         L.icm_residual_indexes.argtypes = [vp, i32, i32, vp, vp]
         L.icm_residual_apply.argtypes = [vp, vp, i32, i32, i32, i32, i32, i32, i32, vp, vp]
+        L.icm_residual_code_map.argtypes = [vp, vp, i32, i32, vp, vp, vp, vp, vp]
+        L.icm_residual_apply_map.argtypes = [vp, vp, i32, i32, i32, i32, i32, i32, vp, vp, vp]
         L.icm_zigzag_order.argtypes = [i32, i32, i32, vp, i32]
         L.icm_zigzag_splits.argtypes = [vp, i64, vp, i32, i32, i32, i32, i32, i32, i32, vp]
         L.icm_zigzag_reverse.argtypes = [vp, vp, i64, i32, i32, i32, i32, i32, i32, i32, vp]

@@ -101,6 +101,39 @@ reader built with other tables stops instead of decoding garbage.  ``unpack`` an
 refuse the magic, as a reader from before this container does (exit code 4 of the CLI).  The residual string is one
 string of four runs under the layer's tables: the class map, then the R, G and B planes.
 
+An error-bounded image whose bound varies over the picture is a fourth container with its own magic: the bound is one
+byte per 16 x 16-pixel cell of the residual layer's grid (``error_grid``: anchored at pixel (0, 0) of the whole image,
+tiled base or not; edge cells partial), every sample of the decode lies within its own cell's bound, and the cells at
+0 come back bit for bit.  ``ICMR``, ``pack_residual`` and ``unpack_residual`` are unchanged by it.
+
+    offset  size  field
+         0     4  magic, the bytes ``ICME``
+         4     2  format version (u16), ``RESIDUAL_MAP_VERSION`` = 1
+         6     1  the largest bound in the map (u8, <= ``MAX_ERROR``): the file's overall guarantee
+         7     1  coder id of the residual string (u8), index into ``CODERS``; the base names its own
+         8     4  image height (u32, 1..32768)
+        12     4  image width (u32, 1..32768)
+        16     4  CRC-32 of the residual layer's static tables
+        20     4  length of the base stream (u32)
+        24     4  length of the bound-map string (u32)
+        28     4  length of the residual string (u32)
+        32   ...  the base stream, the bound-map string, the residual string
+       end-4     4  CRC-32 of every byte before it
+
+The bound-map string is run-length coded like the quality map (``error_map_string`` / ``error_map_from_string``):
+
+    u16 gh, u16 gw                     the grid; must be ``error_grid`` of the header's height and width
+    then runs (u16 count >= 1, u8 d)   row-major, covering gh gw cells exactly
+
+and canonical in the same way: runs are maximal (except after a run of 65535), every d is at most 32, and at least two
+distinct d occur -- ``pack_residual_map`` writes a map whose entries are all D as the ``ICMR`` stream of D, byte for
+byte, so one content keeps one encoding.  ``unpack_residual_map`` refuses, with ValueError, what ``unpack_residual``
+refuses and a wrong grid against the header, a header maximum that is not the map's, a count of 0, runs short of or
+past the grid, a non-maximal run, a d above 32, a single distinct d and trailing bytes.  ``unpack_residual`` refuses
+the new magic, as a reader from before this container does (exit code 4 of the CLI), and ``unpack_residual_map`` an
+``ICMR`` stream.  The residual string is what it is in an ``ICMR`` stream; only the quantiser behind its symbols
+differs from cell to cell.
+
 Lane stream -- the string format of coder id 1, made to be coded by one GPU wave per body (csrc/rans_lanes.hip; the
 executable definition is csrc/rans_lanes_common.h, the arithmetic of a lane's step that host and kernels both compile,
 under the loops of ``icm_rans_lanes_encode`` / ``icm_rans_lanes_decoder_*`` of csrc/rans.cpp).  Parity unpinned: no
@@ -652,3 +685,179 @@ def unpack_residual(data: bytes, table_crc: Optional[int] = None) -> Tuple[Dict,
                          f"reader has {table_crc & U32_MAX:#010x}")
     header = {"max_error": d, "coder": CODERS[coder_id], "height": height, "width": width, "table_crc": tcrc}
     return header, base, data[RESIDUAL_FIXED_BYTES + nbase:end]
+
+
+# -------------------------------------------------------------------------- error-bounded images, a bound per cell
+RESIDUAL_MAP_MAGIC = b"ICME"
+RESIDUAL_MAP_VERSION = 1
+ERROR_CELL = 16                             # pixels per cell and axis of the bound map: the residual layer's grid
+_EFIXED = struct.Struct("<4sHBBIIIIII")     # magic .. residual length
+RESIDUAL_MAP_FIXED_BYTES = _EFIXED.size     # 32
+assert RESIDUAL_MAP_FIXED_BYTES == 32
+RESIDUAL_MAP_HEADER_KEYS = ("coder", "height", "width", "table_crc")
+_EMAP_RUN = struct.Struct("<HB")            # count, d
+
+
+def error_grid(height: int, width: int) -> Tuple[int, int]:
+    """(gh, gw): the 16 x 16-pixel cells of the image, anchored at pixel (0, 0), edge cells partial"""
+    return -(-int(height) // ERROR_CELL), -(-int(width) // ERROR_CELL)
+
+
+def check_error_map(dmap, height: int, width: int, who: str = "") -> np.ndarray:
+    """``dmap`` as a uint8 [gh, gw] array of bounds in 0 .. MAX_ERROR over ``error_grid``; ValueError otherwise
+    (another dtype is not cast)"""
+    a = np.asarray(dmap)
+    if a.dtype != np.uint8:
+        raise ValueError(f"{who}the bound map must be uint8, got {a.dtype}")
+    if a.shape != error_grid(height, width):
+        raise ValueError(f"{who}the bound map of a {height}x{width} image is {error_grid(height, width)}, got {a.shape}")
+    if int(a.max()) > MAX_ERROR:
+        raise ValueError(f"{who}the bound map holds max_error = {int(a.max())} outside [0, {MAX_ERROR}]")
+    return a
+
+
+def error_map_string(dmap) -> bytes:
+    """the bound-map string of an ICME stream.  A uniform map has none (ValueError): it is written as an ICMR stream."""
+    a = np.asarray(dmap)
+    if a.ndim != 2 or a.dtype != np.uint8:
+        raise ValueError(f"bitstream: the bound map must be a uint8 [gh, gw] array, got {a.dtype} {a.shape}")
+    gh, gw = _uint("map height", a.shape[0], U16_MAX, 1), _uint("map width", a.shape[1], U16_MAX, 1)
+    flat = a.reshape(-1)
+    if int(flat.max()) > MAX_ERROR:
+        raise ValueError(f"bitstream: the bound map holds max_error = {int(flat.max())} outside [0, {MAX_ERROR}]")
+    if bool((flat == flat[0]).all()):
+        raise ValueError(f"bitstream: a uniform bound map (every entry {int(flat[0])}) is written as an ICMR stream, "
+                         f"not as a map string")
+    starts = np.flatnonzero(np.concatenate(([True], flat[1:] != flat[:-1])))
+    ends = np.append(starts[1:], flat.size)
+    out = bytearray(_MAP_HEAD.pack(gh, gw))
+    for s, e in zip(starts.tolist(), ends.tolist()):
+        n, d = e - s, int(flat[s])
+        while n > 0:                                # a maximal run longer than a count holds: full counts first
+            c = min(n, U16_MAX)
+            out += _EMAP_RUN.pack(c, d)
+            n -= c
+    return bytes(out)
+
+
+def error_map_from_string(data: bytes, height: int, width: int) -> np.ndarray:
+    """inverse of ``error_map_string`` -> uint8 [gh, gw]; the grid must be that of the height x width image.
+    ValueError, naming the condition, for anything that is not the one canonical string of such a map."""
+    data = bytes(data)
+    if len(data) < _MAP_HEAD.size:
+        raise ValueError(f"bitstream: truncated: a bound-map string begins with {_MAP_HEAD.size} bytes of grid, this one "
+                         f"has {len(data)}")
+    gh, gw = _MAP_HEAD.unpack_from(data, 0)
+    if (gh, gw) != error_grid(height, width):
+        want = error_grid(height, width)
+        raise ValueError(f"bitstream: the bound map's grid is {gh}x{gw}, a {height}x{width} image has {want[0]}x{want[1]} "
+                         f"cells")
+    if (len(data) - _MAP_HEAD.size) % _EMAP_RUN.size:
+        raise ValueError(f"bitstream: {(len(data) - _MAP_HEAD.size) % _EMAP_RUN.size} trailing bytes after the last "
+                         f"whole run of the bound map")
+    total, flat, pos, prev = gh * gw, np.empty(gh * gw, dtype=np.uint8), 0, None
+    for off in range(_MAP_HEAD.size, len(data), _EMAP_RUN.size):
+        if pos == total:
+            raise ValueError(f"bitstream: {len(data) - off} trailing bytes after the bound map's {total} cells")
+        count, d = _EMAP_RUN.unpack_from(data, off)
+        if count == 0:
+            raise ValueError("bitstream: a run of the bound map has a count of 0")
+        if d > MAX_ERROR:
+            raise ValueError(f"bitstream: bound map: stored max_error = {d} outside [0, {MAX_ERROR}]")
+        if prev is not None and prev[1] == d and prev[0] != U16_MAX:
+            raise ValueError(f"bitstream: the bound map's runs are not maximal: a run of {prev[0]} is followed by "
+                             f"another of the same d = {d}")
+        if pos + count > total:
+            raise ValueError(f"bitstream: the bound map's runs go past its {total} cells")
+        flat[pos:pos + count] = d
+        pos, prev = pos + count, (count, d)
+    if pos != total:
+        raise ValueError(f"bitstream: the bound map's runs cover {pos} of its {total} cells")
+    if bool((flat == flat[0]).all()):
+        raise ValueError(f"bitstream: the bound map holds a single d = {int(flat[0])} (a uniform map is written as an "
+                         f"ICMR stream)")
+    return flat.reshape(gh, gw)
+
+
+def pack_residual_map(header: Dict, base: bytes, dmap, residual: bytes) -> bytes:
+    """``header``: {"coder": name in CODERS of the residual string, "height", "width", "table_crc": u32} ("max_error",
+    if given, must be the map's largest entry); ``base``: one complete ICMB or ICMT stream; ``dmap``: the bounds of the
+    image's cells (``check_error_map``); ``residual``: the residual layer's string under that map.  A uniform map gives
+    the ICMR stream of its one bound, ``pack_residual``'s bytes: one content keeps one encoding."""
+    missing = [k for k in RESIDUAL_MAP_HEADER_KEYS if k not in header]
+    if missing:
+        raise ValueError(f"bitstream: residual header lacks {missing}")
+    check_coder(header["coder"], "bitstream: ")
+    height = _uint("height", header["height"], RESIDUAL_SIDE_MAX, 1)
+    width = _uint("width", header["width"], RESIDUAL_SIDE_MAX, 1)
+    a = check_error_map(dmap, height, width, "bitstream: ")
+    top = int(a.max())
+    if header.get("max_error", top) != top:
+        raise ValueError(f"bitstream: header says max_error = {header['max_error']}, the largest bound in the map is {top}")
+    if int(a.min()) == top:
+        return pack_residual({**{k: header[k] for k in RESIDUAL_MAP_HEADER_KEYS}, "max_error": top}, base, residual)
+    base, residual, string = bytes(base), bytes(residual), error_map_string(a)
+    if base[:4] not in (MAGIC, TILED_MAGIC):
+        raise ValueError("bitstream: the base of an ICME stream must be an ICMB or ICMT stream")
+    out = bytearray(_EFIXED.pack(
+        RESIDUAL_MAP_MAGIC, RESIDUAL_MAP_VERSION, top, CODERS.index(header["coder"]), height, width,
+        _uint("table_crc", header["table_crc"], U32_MAX), _uint("base length", len(base), U32_MAX),
+        _uint("map length", len(string), U32_MAX), _uint("residual length", len(residual), U32_MAX)))
+    out += base
+    out += string
+    out += residual
+    out += _U32.pack(zlib.crc32(bytes(out)) & U32_MAX)
+    return bytes(out)
+
+
+def is_residual_map(data) -> bool:
+    """True if ``data`` begins with the magic of an error-bounded stream with a bound map (says nothing else about it)"""
+    return isinstance(data, (bytes, bytearray, memoryview)) and bytes(data[:4]) == RESIDUAL_MAP_MAGIC
+
+
+def unpack_residual_map(data: bytes, table_crc: Optional[int] = None) -> Tuple[Dict, bytes, np.ndarray, bytes]:
+    """inverse of ``pack_residual_map`` for a map of more than one value: (header with "max_error" = the largest bound,
+    base stream, bound map uint8 [gh, gw], residual string).  ValueError for a bad magic, an unknown version or coder
+    id, a maximum above MAX_ERROR, an image side outside 1..32768, declared lengths that run past the data, trailing
+    bytes, a CRC mismatch, a base that begins with neither inner magic, with ``table_crc`` (the reader's own) a stream
+    written with other tables, a bound-map string ``error_map_from_string`` refuses, and a header maximum that is not
+    the map's.  The base is returned as it lies; ``unpack`` / ``unpack_tiled`` check it."""
+    if not isinstance(data, (bytes, bytearray, memoryview)):
+        raise ValueError(f"bitstream: expected bytes, got {type(data).__name__}")
+    data = bytes(data)
+    if not RESIDUAL_MAP_MAGIC.startswith(data[:4]):
+        raise ValueError("bitstream: bad magic (not an ICME stream)")
+    if len(data) < RESIDUAL_MAP_FIXED_BYTES + CRC_BYTES:
+        raise ValueError(f"bitstream: truncated: {len(data)} bytes, the fixed bound-map header and CRC need "
+                         f"{RESIDUAL_MAP_FIXED_BYTES + CRC_BYTES}")
+    (_, version, top, coder_id, height, width, tcrc, nbase, nmap, nres) = _EFIXED.unpack_from(data, 0)
+    if version != RESIDUAL_MAP_VERSION:
+        raise ValueError(f"bitstream: unknown bound-map format version {version} (this reader knows "
+                         f"{RESIDUAL_MAP_VERSION})")
+    if top > MAX_ERROR:
+        raise ValueError(f"bitstream: max_error = {top} outside [0, {MAX_ERROR}]")
+    if coder_id >= len(CODERS):
+        raise ValueError(f"bitstream: unknown coder id {coder_id} (this reader knows 0..{len(CODERS) - 1})")
+    if not (1 <= height <= RESIDUAL_SIDE_MAX and 1 <= width <= RESIDUAL_SIDE_MAX):
+        raise ValueError(f"bitstream: image {height}x{width} outside 1..{RESIDUAL_SIDE_MAX} a side")
+    end = RESIDUAL_MAP_FIXED_BYTES + nbase + nmap + nres
+    if end + CRC_BYTES > len(data):
+        raise ValueError(f"bitstream: truncated: declared lengths {nbase} + {nmap} + {nres} run past the data "
+                         f"({len(data)} bytes, {end + CRC_BYTES} needed)")
+    if end + CRC_BYTES < len(data):
+        raise ValueError(f"bitstream: {len(data) - end - CRC_BYTES} trailing bytes after the CRC")
+    if _U32.unpack_from(data, end)[0] != zlib.crc32(data[:end]) & U32_MAX:
+        raise ValueError("bitstream: CRC mismatch (corrupt stream)")
+    p0 = RESIDUAL_MAP_FIXED_BYTES
+    base = data[p0:p0 + nbase]
+    if base[:4] not in (MAGIC, TILED_MAGIC):
+        raise ValueError("bitstream: the base of the ICME stream is neither an ICMB nor an ICMT stream")
+    if table_crc is not None and tcrc != table_crc & U32_MAX:
+        raise ValueError(f"bitstream: residual table mismatch: the stream was written with tables {tcrc:#010x}, this "
+                         f"reader has {table_crc & U32_MAX:#010x}")
+    dmap = error_map_from_string(data[p0 + nbase:p0 + nbase + nmap], height, width)
+    if int(dmap.max()) != top:
+        raise ValueError(f"bitstream: the header says max_error = {top}, the largest bound in the map is "
+                         f"{int(dmap.max())}")
+    header = {"max_error": top, "coder": CODERS[coder_id], "height": height, "width": width, "table_crc": tcrc}
+    return header, base, dmap, data[p0 + nbase + nmap:end]

@@ -2,7 +2,7 @@
 
     python -m icm_amd.codec encode IMAGE -o FILE -a cnn -p CKPT [--tile N [--overlap M]] [--coder {host,lanes}]
                                    [--qstep K | --target-bytes N | --target-bpp F] [--roi Y0,X0,H,W:D ...] [--rdoq W]
-                                   [--aq S] [--max-error D]
+                                   [--aq S] [--max-error D [--error-roi Y0,X0,H,W:D' ...]]
     python -m icm_amd.codec decode FILE -o IMAGE.png -p CKPT [--reference IMAGE] [--region Y0,X0,H,W]
 
 Parity unpinned: no counterpart in the reference (upstream CompressAI's ``examples/codec.py`` is not in its tree).  The
@@ -59,7 +59,15 @@ the encoder then decodes it on the device, as the decoder will, and codes the qu
 static two-sided geometric tables, the coder ``--coder`` names), both wrapped in an ``ICMR`` container
 (``icm_amd.bitstream``).  ``decode`` needs no flag; with ``--region`` it decodes the base's region only but the residual
 string whole -- decoding only the window's part of the lane bodies is not built.  Files written without the flag are
-byte for byte what they were.  Parity unpinned: no counterpart in the reference."""
+byte for byte what they were.  Parity unpinned: no counterpart in the reference.
+
+``--error-roi Y0,X0,H,W:D'`` (repeatable, with ``--max-error``) gives the bound the form every other knob has: the
+16 x 16-pixel cells of the residual layer's grid that hold a pixel of the rectangle are held to the absolute bound D'
+instead of D -- D' = 0: that part of the picture comes back bit for bit -- and later rectangles win (``error_map``).
+The map of bounds travels in an ``ICME`` container (``icm_amd.bitstream``), ``decode`` needs no flag and reports the
+map's range and, with ``--reference``, the number of samples outside their cell's bound, which is 0.  Rectangles that
+change no cell leave the ``ICMR`` file what it is without them.  What a loose background saves in bytes depends on the
+base model and is not measured against trained weights.  Parity unpinned."""
 from __future__ import annotations
 
 import argparse
@@ -275,6 +283,30 @@ def clip_rois(rois, y0: int, x0: int, h: int, w: int) -> List[Tuple[int, int, in
     return out
 
 
+# ------------------------------------------------------------------------------------------- error bounds per cell
+def check_error_rois(rois, H: int, W: int) -> List[Tuple[int, int, int, int, int]]:
+    """``rois`` as a list of (y0, x0, h, w, d) of ints: rectangles of image pixels inside the H x W image, each with
+    an absolute error bound d in 0 .. 32 (not an offset).  ValueError otherwise.  Host-only."""
+    out = []
+    for y0, x0, h, w, d in check_rois(rois, H, W):
+        out.append((y0, x0, h, w, R.check_max_error(d, f"codec: error region {(y0, x0, h, w)}: ")))
+    return out
+
+
+def error_map(H: int, W: int, base: int, rois) -> np.ndarray:
+    """The bound map of an H x W image: uint8 [gh, gw] over the residual layer's grid (``residual.grid``: 16 x 16-pixel
+    cells anchored at pixel (0, 0), no padding).  Every cell starts at the bound ``base``; the rectangles
+    (``check_error_rois``) are painted in list order, each onto every cell that holds at least one of its pixels, with
+    its own d; later rectangles win.  ``roi_map``'s rules on the unpadded grid.  Host-only."""
+    base = R.check_max_error(base, "codec: ")
+    if base is None:
+        raise ValueError("codec: error_map needs a background bound")
+    m = np.full(R.grid(H, W), base, dtype=np.uint8)
+    for y0, x0, h, w, d in check_error_rois(rois, H, W):
+        m[y0 // R.CELL:(y0 + h - 1) // R.CELL + 1, x0 // R.CELL:(x0 + w - 1) // R.CELL + 1] = d
+    return m
+
+
 # ------------------------------------------------------------------------------------ variance-adaptive quantisation
 AQ_STRENGTH_MAX = 4.0  # |strength| of ``--aq``
 AQ_MAX_OFFSET = 16     # |offset| to the background step index: two octaves of the step
@@ -389,16 +421,20 @@ def encode_image_info(model, img, tile: Optional[int] = None, overlap: int = 0, 
                       symbols_per_wave: Optional[int] = None, qstep: int = 0,
                       max_bytes: Optional[int] = None, roi: Optional[Sequence] = None,
                       rdoq: Optional[float] = None, aq: Optional[float] = None,
-                      max_error: Optional[int] = None) -> Tuple[bytes, Dict]:
+                      max_error: Optional[int] = None, error_roi: Optional[Sequence] = None) -> Tuple[bytes, Dict]:
     """``encode_image`` with its outcome: (stream, {"qstep": k, "step": 2^(k/8), "probes": encodes made}); k is the
     background step.  With ``roi`` or ``aq`` also "roi_cells", the number of latent cells (summed over the tiles) whose
     step index differs from k, and "qmap_range": [smallest, largest step index in the maps].  With ``rdoq`` also "rdoq",
     the weight as the kernel took it.  With ``aq`` also "aq", the strength as checked, "aq_ref", the image's reference
     activity, and "aq_offset_range": [smallest, largest offset over all tiles].  With ``max_error`` also "max_error",
     "base_bytes" and "residual_bytes" (the base stream and the residual string inside the ICMR container) and
-    "residual_class_range": [smallest, largest context class of the cells]."""
+    "residual_class_range": [smallest, largest context class of the cells].  With ``error_roi`` (``max_error`` is then
+    the background's bound) also "max_error_range": [smallest, largest bound in the map] and "error_roi_cells", the
+    number of cells whose bound differs from ``max_error``."""
     B.check_coder(coder, "codec: ")
     max_error = R.check_max_error(max_error, "codec: ")
+    if error_roi is not None and max_error is None:
+        raise ValueError("codec: error_roi gives the exceptions to max_error, the background's bound: give max_error")
     if max_error is not None and max_bytes is not None:
         raise ValueError("codec: give a byte budget or an error bound, not both: the bound decides the size")
     qstep = B.check_qstep(qstep, "codec: ")
@@ -417,6 +453,7 @@ def encode_image_info(model, img, tile: Optional[int] = None, overlap: int = 0, 
     H, W = u8.size(0), u8.size(1)
     if max_error is not None and max(H, W) > B.RESIDUAL_SIDE_MAX:
         raise ValueError(f"codec: max_error takes images of at most {B.RESIDUAL_SIDE_MAX} pixels a side, got {H}x{W}")
+    dmap = None if error_roi is None else error_map(H, W, max_error, error_roi)
     if tile is None:
         if overlap:
             raise ValueError("codec: overlap needs a tile extent")
@@ -459,13 +496,19 @@ def encode_image_info(model, img, tile: Optional[int] = None, overlap: int = 0, 
         told = {"qstep": qstep, "step": B.step_of(qstep)[0], "probes": 1, **extra, **told}
         if max_error is not None:
             # the residual layer: the base decoded on the device as the decoder will decode it, the quantised
-            # differences coded as one string, both wrapped
+            # differences coded as one string, both wrapped.  A bound map that came out uniform gives the symbols of
+            # its one bound, and ``pack_residual_map`` writes it as that bound's ICMR stream
             xhat = _decode_device(model, data)[0]
-            string, classes = R.encode_residual(u8, xhat, max_error, coder_for(coder, symbols_per_wave))
+            string, classes = R.encode_residual(u8, xhat, max_error if dmap is None else dmap,
+                                                coder_for(coder, symbols_per_wave))
             told.update(max_error=max_error, base_bytes=len(data), residual_bytes=len(string),
                         residual_class_range=list(classes))
-            data = B.pack_residual({"max_error": max_error, "coder": coder, "height": H, "width": W,
-                                    "table_crc": R.tables().crc}, data, string)
+            head = {"coder": coder, "height": H, "width": W, "table_crc": R.tables().crc}
+            if dmap is not None:
+                told.update(max_error_range=[int(dmap.min()), int(dmap.max())],
+                            error_roi_cells=int((dmap != max_error).sum()))
+            data = (B.pack_residual({**head, "max_error": max_error}, data, string) if dmap is None else
+                    B.pack_residual_map(head, data, dmap, string))
         return data, told
     # encode to size: the analysis transform once per tile, then only the latent coder per probe; a probe is the very
     # container that would be written (headers, CRCs and the lanes coder's flushes included), and the answer is the
@@ -500,7 +543,7 @@ def encode_image_info(model, img, tile: Optional[int] = None, overlap: int = 0, 
 def encode_image(model, img, tile: Optional[int] = None, overlap: int = 0, coder: str = "host",
                  symbols_per_wave: Optional[int] = None, qstep: int = 0, max_bytes: Optional[int] = None,
                  roi: Optional[Sequence] = None, rdoq: Optional[float] = None, aq: Optional[float] = None,
-                 max_error: Optional[int] = None) -> bytes:
+                 max_error: Optional[int] = None, error_roi: Optional[Sequence] = None) -> bytes:
     """8-bit [H, W, 3] image (tensor on any device, or anything ``numpy.asarray`` accepts) -> one bit-stream.  With
     ``tile``, an image of more than one tile (``plan_tiles``) becomes an ICMT stream whose tile k is
     ``encode_image(model, crop k)``, the tiles coded one after another; an image of one tile is written untiled.
@@ -524,9 +567,14 @@ def encode_image(model, img, tile: Optional[int] = None, overlap: int = 0, coder
     ``max_error``: an integer D in 0 .. 32 (None, the default: off, and the stream is what it is without): the stream
     becomes an ICMR container of the very stream the other arguments give, the base, and the residual string that
     brings every sample of the decode within D of the image's (0: the image itself).  ``coder`` codes that string too.
-    Not with ``max_bytes``: ValueError."""
+    Not with ``max_bytes``: ValueError.
+    ``error_roi``: exceptions to that bound [(y0, x0, h, w, d), ...], rectangles of image pixels inside the image, each
+    with an absolute bound d in 0 .. 32: the 16 x 16-pixel cells of the residual layer's grid they touch are coded under
+    d instead of D (``error_map``; later rectangles win), and every sample of the decode lies within its cell's bound
+    -- the rectangle bit for bit at d = 0.  The stream is an ICME container, which carries the map; no rectangle, or
+    none that changes a cell, gives byte for byte the ICMR stream of D.  Needs ``max_error``: ValueError without."""
     return encode_image_info(model, img, tile, overlap, coder, symbols_per_wave, qstep, max_bytes, roi, rdoq, aq,
-                             max_error)[0]
+                             max_error, error_roi)[0]
 
 
 def _check_model(header: Dict, arch: str, fp: int, what: str = "the stream") -> None:
@@ -587,7 +635,7 @@ def _check_region(region, H: int, W: int) -> Tuple[int, int, int, int]:
 
 @torch.no_grad()
 def decode_image(model, data: bytes, reference=None, region=None) -> Tuple[torch.Tensor, Dict]:
-    """one bit-stream, ICMB, ICMT or ICMR -> (8-bit [H, W, 3] host tensor, info); ``info``: "bpp" = 8 x the whole stream
+    """one bit-stream, ICMB, ICMT, ICMR or ICME -> (8-bit [H, W, 3] host tensor, info); ``info``: "bpp" = 8 x the whole stream
     length / (H W), header included, and, given ``reference`` (the original 8-bit image), "psnr" of the two 8-bit
     images.  ``region`` = (y0, x0, h, w): only that window is returned ([h, w, 3]; "sse" / "psnr" are over it, against
     the same window of ``reference``); of a tiled stream only the tiles that touch it are decoded
@@ -600,24 +648,40 @@ def decode_image(model, data: bytes, reference=None, region=None) -> Tuple[torch
     the window; a region decode is bit for bit the crop of the full decode.  ``info`` is the base's with "bytes" and
     "bpp" of the whole file, and "max_error", "base_bytes" and "residual_bytes"; with ``reference`` also
     "max_abs_error", the largest absolute difference of a sample to the reference's, and "sse" / "psnr" of the final
-    image."""
-    if B.is_residual(data):
-        head, base, string = B.unpack_residual(data, R.tables().crc)
+    image.
+    An ICME stream, an ICMR stream with a bound per 16 x 16-pixel cell, decodes the same way, each sample under its own
+    cell's bound.  "max_error" is then the largest bound in the map, the file's overall guarantee; "max_error_range":
+    [smallest, largest bound]; "max_error_map": the uint8 [gh, gw] map; and with ``reference`` also "bound_violations",
+    the number of returned samples farther from the reference's than their cell's bound: 0 for a file that is what it
+    says."""
+    if B.is_residual(data) or B.is_residual_map(data):
+        if B.is_residual_map(data):
+            head, base, dmap, string = B.unpack_residual_map(data, R.tables().crc)
+        else:
+            (head, base, string), dmap = B.unpack_residual(data, R.tables().crc), None
         device = next(model.parameters()).device
         out, _, info, (ry, rx, rh, rw) = _decode_device(model, base, None, region)
         H, W, D = head["height"], head["width"], head["max_error"]
         if (info["height"], info["width"]) != (H, W):
             raise ValueError(f"codec: the ICMR stream holds a {H}x{W} image, its base a {info['height']}x{info['width']}")
         sym = R.decode_residual(string, H, W, coder_for(head["coder"]), device)
-        out = R.residual_apply(out, sym, (ry, rx, rh, rw), D)
+        out = R.residual_apply(out, sym, (ry, rx, rh, rw), D if dmap is None else dmap)
         info.update(bytes=len(data), bpp=8.0 * len(data) / (H * W), max_error=D, base_bytes=len(base),
                     residual_bytes=len(string))
+        if dmap is not None:
+            info.update(max_error_range=[int(dmap.min()), int(dmap.max())], max_error_map=dmap)
         if reference is not None:
             ref = _as_u8_image(reference, device, "reference")
             if tuple(ref.shape) != (H, W, 3):
                 raise ValueError(f"codec: the reference is {ref.size(0)}x{ref.size(1)}, the stream holds a {H}x{W} image")
             d = out.to(torch.int32) - ref[ry:ry + rh, rx:rx + rw].to(torch.int32)
             info["max_abs_error"] = int(d.abs().max().item())
+            if dmap is not None:
+                # every returned sample against the bound of the cell of its image position
+                cells = torch.from_numpy(dmap.astype(np.int32)).to(device)
+                ys = torch.arange(ry, ry + rh, device=device) // R.CELL
+                xs = torch.arange(rx, rx + rw, device=device) // R.CELL
+                info["bound_violations"] = int((d.abs() > cells[ys][:, xs][..., None]).sum().item())
             info["sse"] = int((d.to(torch.int64) ** 2).sum().item())
             info["psnr"] = 10.0 * math.log10(255.0 ** 2 / (info["sse"] / (rh * rw * 3))) if info["sse"] else math.inf
         return out.cpu(), info
@@ -724,6 +788,13 @@ def _roi(text: str) -> Tuple[int, int, int, int, int]:
     return v
 
 
+def _residual_base(payload: bytes) -> bytes:
+    """the base stream of an ICMR or ICME file, checked; any other payload as it is"""
+    if B.is_residual_map(payload):
+        return B.unpack_residual_map(payload, R.tables().crc)[1]
+    return B.unpack_residual(payload, R.tables().crc)[1] if B.is_residual(payload) else payload
+
+
 def _qmap_range(qmap) -> List[int]:
     ms = [m for m in (qmap if isinstance(qmap, list) else [qmap]) if m is not None]
     return [int(min(m.min() for m in ms)), int(max(m.max() for m in ms))]
@@ -771,6 +842,10 @@ def setup_args() -> argparse.ArgumentParser:
                      help=f"error bound: add a residual layer so that every 8-bit sample of the decode lies within D of "
                           f"the original's, D in 0..{B.MAX_ERROR}; 0: lossless (default: off; not with --target-bytes / "
                           f"--target-bpp)")
+    enc.add_argument("--error-roi", default=None, type=_roi, action="append", metavar="Y0,X0,H,W:D",
+                     help=f"exception to --max-error, repeatable: the 16 x 16-pixel cells this rectangle of image pixels "
+                          f"touches are held to the absolute bound D in 0..{B.MAX_ERROR} instead (0: bit-exact); later ones "
+                          f"win (needs --max-error)")
     for s in (enc, dec):
         s.add_argument("-o", "--output", required=True, help="file to write")
         s.add_argument("-p", "--path", dest="paths", required=True, type=str, help="checkpoint path")
@@ -816,6 +891,11 @@ def main(argv) -> int:
             R.check_max_error(args.max_error, "--")
             if args.max_error is not None and (args.target_bytes is not None or args.target_bpp is not None):
                 raise ValueError("give --max-error or a byte budget (--target-bytes / --target-bpp), not both")
+            if args.error_roi is not None:
+                if args.max_error is None:
+                    raise ValueError("--error-roi gives the exceptions to --max-error: give --max-error")
+                for r in args.error_roi:
+                    R.check_max_error(r[4], f"--error-roi {r[0]},{r[1]},{r[2]},{r[3]}: ")
         except ValueError as e:
             print(f"Error: {e}", file=sys.stderr)
             return 2
@@ -828,12 +908,18 @@ def main(argv) -> int:
                 except ValueError as e:
                     print(f"Error: --roi: {e}", file=sys.stderr)
                     return 2
+            if args.error_roi is not None:
+                try:
+                    check_error_rois(args.error_roi, *payload.shape[:2])
+                except ValueError as e:
+                    print(f"Error: --error-roi: {e}", file=sys.stderr)
+                    return 2
         else:
             if not os.path.isfile(args.input):
                 raise ValueError(f"{args.input}: no such file")
             with open(args.input, "rb") as f:
                 payload = f.read()
-            inner = B.unpack_residual(payload, R.tables().crc)[1] if B.is_residual(payload) else payload
+            inner = _residual_base(payload)
             header, _ = B.unpack_tiled(inner) if B.is_tiled(inner) else B.unpack(inner)
             if arch is not None and arch != header["arch"]:
                 print(f"Error: -a {arch} disagrees with the stream, written by {header['arch']!r}.", file=sys.stderr)
@@ -855,7 +941,7 @@ def main(argv) -> int:
             budget = args.target_bytes if args.target_bpp is None else int(math.floor(args.target_bpp * h * w / 8))
             data, found = encode_image_info(model, payload, args.tile, args.overlap, coder=args.coder,
                                             qstep=args.qstep or 0, max_bytes=budget, roi=args.roi, rdoq=args.rdoq,
-                                            aq=args.aq, max_error=args.max_error)
+                                            aq=args.aq, max_error=args.max_error, error_roi=args.error_roi)
             torch.cuda.synchronize()
             dt = time.perf_counter() - t0
             with open(args.output, "wb") as f:
@@ -868,7 +954,7 @@ def main(argv) -> int:
             dt = time.perf_counter() - t0
             from PIL import Image
             Image.fromarray(img.numpy()).save(args.output)
-            report = {"command": "decode", **{k: v for k, v in info.items() if k not in ("sse", "qmap")},
+            report = {"command": "decode", **{k: v for k, v in info.items() if k not in ("sse", "qmap", "max_error_map")},
                       "decode_time": dt}
             if "qmap" in info:
                 report["qmap_range"] = _qmap_range(info["qmap"])

@@ -27,6 +27,12 @@ the range that function's 32-bit counts hold -- and come out as the usual (cdf, 
 and answers ``_tables()`` / ``_device_tables()``, which is all ``ans.HostCoder`` / ``ans.LanesCoder`` ask of an entropy
 model.
 
+Bound map -- the bound may also be one byte per cell of the same grid (``check_error_map``; ICME streams): a sample of
+cell (cy, cx) is coded by the rule above under D[cy, cx], and the class of a cell is taken from its own q, so classes,
+thresholds and tables are untouched.  ``residual_code``, ``residual_apply`` and ``encode_residual`` take either the int
+or a host map, which is checked here and then uploaded (``icm_residual_code_map`` / ``icm_residual_apply_map``); the
+decode is within D[cy, cx] of the original in every sample of the cell, bit-exact where the byte is 0.
+
 String -- one string of four runs: the class map (gh gw symbols, all with index 19), then the R, G and B planes (H W
 symbols each, the index of a sample being the class of its cell)."""
 from __future__ import annotations
@@ -40,6 +46,7 @@ import torch
 from . import _lib as L
 from ._lib import check
 from .bitstream import MAX_ERROR        # the largest D, defined with the container that stores it
+from .bitstream import check_error_map as _check_error_map
 
 CELL = 16
 THRESHOLDS = (2, 3, 4, 6, 8, 11, 16, 23, 32, 45, 64, 91, 128, 181, 256, 362, 512, 724)
@@ -65,6 +72,21 @@ def check_max_error(d, who: str = ""):
 def grid(H: int, W: int) -> Tuple[int, int]:
     """(gh, gw): the cells of an H x W image"""
     return -(-H // CELL), -(-W // CELL)
+
+
+def check_error_map(dmap, H: int, W: int, who: str = "") -> np.ndarray:
+    """``dmap`` as a contiguous host uint8 [gh, gw] array: the bounds of the cells of an H x W image, each in
+    0 .. MAX_ERROR (``bitstream.check_error_map``, the one check).  ValueError for a device tensor, another dtype
+    (nothing is cast), another shape or a larger entry.  Host-only."""
+    if isinstance(dmap, torch.Tensor):
+        if dmap.is_cuda:
+            raise ValueError(f"{who}the bound map must be a host array: it is checked before it is uploaded")
+        dmap = dmap.numpy()
+    return np.ascontiguousarray(_check_error_map(dmap, H, W, who))
+
+
+def _is_map(d) -> bool:
+    return isinstance(d, (np.ndarray, torch.Tensor)) and d.ndim > 0
 
 
 def class_weights(k: int) -> np.ndarray:
@@ -136,9 +158,10 @@ def _u8(t: torch.Tensor, what: str) -> torch.Tensor:
     return t.contiguous()
 
 
-def residual_code(x: torch.Tensor, xhat: torch.Tensor, d: int):
+def residual_code(x: torch.Tensor, xhat: torch.Tensor, d):
     """device 8-bit [H, W, 3] original and reconstruction -> (symbols int32 [3, H, W], indexes int32 [3, H, W], classes
-    int32 [gh, gw]) on the device (``icm_residual_code``)"""
+    int32 [gh, gw]) on the device.  ``d``: the bound, an int (``icm_residual_code``) or a host map of bounds per cell
+    (``check_error_map``; ``icm_residual_code_map``)"""
     x, xhat = _u8(x, "the image"), _u8(xhat, "the reconstruction")
     if x.shape != xhat.shape:
         raise ValueError(f"residual: image {tuple(x.shape)} and reconstruction {tuple(xhat.shape)} differ in size")
@@ -146,8 +169,13 @@ def residual_code(x: torch.Tensor, xhat: torch.Tensor, d: int):
     sym = torch.empty((3, H, W), dtype=torch.int32, device=x.device)
     idx = torch.empty_like(sym)
     cls = torch.empty(grid(H, W), dtype=torch.int32, device=x.device)
-    check(L.lib().icm_residual_code(x.data_ptr(), xhat.data_ptr(), H, W, d, sym.data_ptr(), idx.data_ptr(),
-                                    cls.data_ptr(), L.stream()), "residual_code")
+    if _is_map(d):
+        dmap = torch.from_numpy(check_error_map(d, H, W, "residual: ")).to(x.device)
+        check(L.lib().icm_residual_code_map(x.data_ptr(), xhat.data_ptr(), H, W, dmap.data_ptr(), sym.data_ptr(),
+                                            idx.data_ptr(), cls.data_ptr(), L.stream()), "residual_code_map")
+    else:
+        check(L.lib().icm_residual_code(x.data_ptr(), xhat.data_ptr(), H, W, d, sym.data_ptr(), idx.data_ptr(),
+                                        cls.data_ptr(), L.stream()), "residual_code")
     return sym, idx, cls
 
 
@@ -161,9 +189,11 @@ def residual_indexes(classes: torch.Tensor, H: int, W: int) -> torch.Tensor:
     return idx
 
 
-def residual_apply(xhat: torch.Tensor, symbols: torch.Tensor, window, d: int) -> torch.Tensor:
+def residual_apply(xhat: torch.Tensor, symbols: torch.Tensor, window, d) -> torch.Tensor:
     """device 8-bit [h, w, 3] reconstruction of the window (y0, x0, h, w) and the image's symbols int32 [3, H, W] -> the
-    window with the residual applied, 8-bit [h, w, 3] (``icm_residual_apply``)"""
+    window with the residual applied, 8-bit [h, w, 3].  ``d``: the bound, an int (``icm_residual_apply``) or the host
+    map of the whole image's cells (``icm_residual_apply_map``): a window pixel takes the bound of the cell of its image
+    position"""
     xhat = _u8(xhat, "the reconstruction")
     y0, x0, h, w = window
     if symbols.dtype != torch.int32 or symbols.dim() != 3 or symbols.size(0) != 3 or tuple(xhat.shape[:2]) != (h, w):
@@ -171,14 +201,20 @@ def residual_apply(xhat: torch.Tensor, symbols: torch.Tensor, window, d: int) ->
                          f"{tuple(xhat.shape)} do not fit")
     symbols = symbols.contiguous()
     out = torch.empty_like(xhat)
-    check(L.lib().icm_residual_apply(xhat.data_ptr(), symbols.data_ptr(), symbols.size(1), symbols.size(2), y0, x0, h, w,
-                                     d, out.data_ptr(), L.stream()), "residual_apply")
+    H, W = symbols.size(1), symbols.size(2)
+    if _is_map(d):
+        dmap = torch.from_numpy(check_error_map(d, H, W, "residual: ")).to(xhat.device)
+        check(L.lib().icm_residual_apply_map(xhat.data_ptr(), symbols.data_ptr(), H, W, y0, x0, h, w, dmap.data_ptr(),
+                                             out.data_ptr(), L.stream()), "residual_apply_map")
+    else:
+        check(L.lib().icm_residual_apply(xhat.data_ptr(), symbols.data_ptr(), H, W, y0, x0, h, w, d, out.data_ptr(),
+                                         L.stream()), "residual_apply")
     return out
 
 
-def encode_residual(x: torch.Tensor, xhat: torch.Tensor, d: int, coder) -> Tuple[bytes, Tuple[int, int]]:
-    """the residual string of x against xhat under ``coder`` (an object of ``ans.coder_for``) -> (string, (smallest,
-    largest class in the map))"""
+def encode_residual(x: torch.Tensor, xhat: torch.Tensor, d, coder) -> Tuple[bytes, Tuple[int, int]]:
+    """the residual string of x against xhat under the bound ``d`` (an int, or a host map per cell) and ``coder`` (an
+    object of ``ans.coder_for``) -> (string, (smallest, largest class in the map))"""
     sym, idx, cls = residual_code(x, xhat, d)
     n, cells = sym[0].numel(), cls.numel()
     symbols = torch.cat([cls.reshape(-1), sym.reshape(-1)])

@@ -677,6 +677,19 @@ int icm_residual_code(const uint8_t* x, const uint8_t* xhat, int H, int W, int D
 int icm_residual_indexes(const int32_t* classes, int H, int W, int32_t* indexes, void* stream);
 int icm_residual_apply(const uint8_t* xhat, const int32_t* symbols, int H, int W, int y0, int x0, int h, int w, int D,
                        uint8_t* out, void* stream);
+/* The same two operations under a bound per cell (ICME streams): dmap = [gh, gw] bytes in DEVICE memory over the grid
+ * of the classes, anchored at pixel (0, 0) of the whole image; a sample of cell (cy, cx) is coded and applied with
+ * D = min(dmap[cy][cx], 32) by the rule above, and the class of a cell is taken from its own q.  The entries cannot
+ * look into a device map before the launch, hence the min: a byte above 32 counts as 32 in both kernels.  A uniform
+ * map gives bit for bit the outputs of the scalar entries of that D.
+ * residual_code_map: a wave owns a cell and reads its byte once.
+ * residual_apply_map: the cell of a window pixel is that of its image position (y0 + y, x0 + x); a run of four window
+ *   pixels that straddles a cell boundary of the image takes each pixel's own bound.
+ * Launch, alignment and ICM_ERR_ARG as above (no D to check; dmap must not be null). */
+int icm_residual_code_map(const uint8_t* x, const uint8_t* xhat, int H, int W, const uint8_t* dmap, int32_t* symbols,
+                          int32_t* indexes, int32_t* classes, void* stream);
+int icm_residual_apply_map(const uint8_t* xhat, const int32_t* symbols, int H, int W, int y0, int x0, int h, int w,
+                           const uint8_t* dmap, uint8_t* out, void* stream);
 
 /* ---- device-resident training data (icm_amd/datasets.py DeviceImageCache; stands in for the reference's per-step
  * CenterCrop / RandomCrop(pad_if_needed) + ToTensor + collate on the host, train.py:393-425).  A training batch cut out

@@ -11,11 +11,17 @@ encode and decode cost with and without it, on a large synthetic image (2048x307
     codec    encode_image / decode_image without and with max_error = --max-error in the same process, alternating,
              medians of --rounds wall times (device synchronised), the file sizes, and the bound as decoded.
 
+With --error-roi Y0,X0,H,W:D' (repeatable; the rectangles of ``codec encode --error-roi``, D the background) the kernel
+part also times icm_residual_code_map and icm_residual_apply_map under that map, which adds one byte per cell to code
+and one or two per run of four pixels to apply, and the codec part also encodes the mapped file and the uniform
+lossless one (max_error = 0) and reports their sizes next to the uniform D's.
+
 The model is a randomly initialised ``cnn`` (seeded): its base reconstruction is far from the image, so the residual
 dominates the file and the sizes say nothing about a trained codec.  The bound is what is verified, not the rate.  Prints
 one JSON line per part.
 
     python tools/bench_codec_residual.py [--iters 100] [--rounds 3] [--kernel-only] [--coder {host,lanes}] [--max-error D]
+                                          [--error-roi Y0,X0,H,W:D' ...]
 
 --kernel-only runs the kernel part alone (the run to put under rocprofv3 --kernel-trace --stats).
 """
@@ -49,7 +55,7 @@ def events(fn, iters, torch):
     return e0.elapsed_time(e1) / iters * 1e3
 
 
-def kernel_part(args, torch, np, R, L):
+def kernel_part(args, torch, np, R, L, dmap=None):
     dev, d = "cuda:0", args.max_error
     rng = np.random.default_rng(1)
     x = synthetic(np, H, W, 1)
@@ -62,6 +68,8 @@ def kernel_part(args, torch, np, R, L):
              "idx": torch.empty((3, H, W), dtype=torch.int32, device=dev),
              "cls": torch.empty((gh, gw), dtype=torch.int32, device=dev),
              "out": torch.empty((H, W, 3), dtype=torch.uint8, device=dev)}
+        if dmap is not None:
+            s["dmap"] = torch.from_numpy(dmap).to(dev)
         sets.append(s)
     lib, st = L.lib(), L.stream()
     px = H * W
@@ -74,6 +82,13 @@ def kernel_part(args, torch, np, R, L):
         "icm_residual_apply": (15 * px + 3 * px, lambda s: lib.icm_residual_apply(
             s["xhat"].data_ptr(), s["sym"].data_ptr(), H, W, 0, 0, H, W, d, s["out"].data_ptr(), st)),
     }
+    if dmap is not None:
+        runs = H * -(-W // 4)
+        launches["icm_residual_code_map"] = (6 * px + 24 * px + 5 * gh * gw, lambda s: lib.icm_residual_code_map(
+            s["x"].data_ptr(), s["xhat"].data_ptr(), H, W, s["dmap"].data_ptr(), s["sym"].data_ptr(),
+            s["idx"].data_ptr(), s["cls"].data_ptr(), st))
+        launches["icm_residual_apply_map"] = (15 * px + 3 * px + runs, lambda s: lib.icm_residual_apply_map(
+            s["xhat"].data_ptr(), s["sym"].data_ptr(), H, W, 0, 0, H, W, s["dmap"].data_ptr(), s["out"].data_ptr(), st))
     for name, (nbytes, fn) in launches.items():
         L.check(fn(sets[0]), name)
         us = events(lambda i: fn(sets[i % SETS]), args.iters, torch)
@@ -82,6 +97,12 @@ def kernel_part(args, torch, np, R, L):
         dst = [torch.empty(half, dtype=torch.uint8, device=dev) for _ in range(SETS)]
         cus = events(lambda i: dst[i % SETS].copy_(src[i % SETS]), args.iters, torch)
         del src, dst
+        if name.startswith("icm_residual_apply"):        # what the launches left: every sample within its cell's bound
+            cells = sets[0]["dmap"].to(torch.int16) if name.endswith("_map") else \
+                torch.full((gh, gw), d, dtype=torch.int16, device=dev)
+            bound = cells.repeat_interleave(16, 0).repeat_interleave(16, 1)[:H, :W, None]
+            err = (sets[0]["out"].to(torch.int16) - sets[0]["x"].to(torch.int16)).abs()
+            assert bool((err <= bound).all()), name
         print(json.dumps({"metric": "residual_kernel", "kernel": name, "height": H, "width": W, "max_error": d,
                           "iters": args.iters, "us_per_launch": round(us, 2), "bytes": nbytes,
                           "GBps": round(nbytes / us / 1e3, 1),
@@ -89,18 +110,18 @@ def kernel_part(args, torch, np, R, L):
                           "copy_same_bytes_us": round(cus, 2), "kernel_over_copy": round(us / cus, 2),
                           "note": "HIP events around back-to-back launches from Python, two rotating buffer sets: "
                                   "launch overhead is inside both figures"}), flush=True)
-    s = sets[0]
-    err = (s["out"].to(torch.int16) - s["x"].to(torch.int16)).abs().max().item()
-    assert err <= d, err
 
 
-def codec_part(args, torch, np, codec):
+def codec_part(args, torch, np, codec, rois=None):
     from icm_amd.zoo import models
     torch.manual_seed(0)
     model = models["cnn"]().to("cuda:0").eval()
     model.update(force=True)
     a = synthetic(np, H, W, 1)
     variants = {"plain": {}, "bounded": {"max_error": args.max_error}}
+    if rois:
+        variants["mapped"] = {"max_error": args.max_error, "error_roi": rois}
+        variants["lossless"] = {"max_error": 0}
     data, info, te, td = {}, {}, {k: [] for k in variants}, {k: [] for k in variants}
     for k, extra in variants.items():                                       # warm every shape up
         data[k], info[k] = codec.encode_image_info(model, a, coder=args.coder, **extra)
@@ -125,6 +146,22 @@ def codec_part(args, torch, np, codec):
                       "base_bytes": info["bounded"]["base_bytes"], "residual_bytes": info["bounded"]["residual_bytes"],
                       "residual_class_range": info["bounded"]["residual_class_range"],
                       "max_abs_error": dinfo["max_abs_error"], "bpp": round(dinfo["bpp"], 3)}), flush=True)
+    if rois:
+        out, minfo = codec.decode_image(model, data["mapped"], reference=a)
+        assert minfo["bound_violations"] == 0
+        print(json.dumps({"metric": "codec_residual_map", "coder": args.coder, "height": H, "width": W,
+                          "max_error": args.max_error, "error_roi": [list(r) for r in rois],
+                          "max_error_range": info["mapped"]["max_error_range"],
+                          "error_roi_cells": info["mapped"]["error_roi_cells"], "cells": int(minfo["max_error_map"].size),
+                          "mapped_bytes": len(data["mapped"]), "bounded_bytes": len(data["bounded"]),
+                          "lossless_bytes": len(data["lossless"]), "base_bytes": info["mapped"]["base_bytes"],
+                          "mapped_encode_s": round(statistics.median(te["mapped"]), 4),
+                          "mapped_decode_s": round(statistics.median(td["mapped"]), 4),
+                          "bounded_encode_s": round(statistics.median(te["bounded"]), 4),
+                          "bounded_decode_s": round(statistics.median(td["bounded"]), 4),
+                          "bound_violations": minfo["bound_violations"], "max_abs_error": minfo["max_abs_error"],
+                          "note": "randomly initialised model: the sizes exercise the mechanism, nothing more"}),
+              flush=True)
 
 
 def main():
@@ -134,6 +171,9 @@ def main():
     ap.add_argument("--kernel-only", action="store_true")
     ap.add_argument("--coder", default="lanes", choices=["host", "lanes"])
     ap.add_argument("--max-error", type=int, default=2)
+    ap.add_argument("--error-roi", action="append", default=None, metavar="Y0,X0,H,W:D",
+                    help="rectangle with its own absolute bound, repeatable: also time the map kernels and encode the "
+                         "mapped file")
     args = ap.parse_args()
     import numpy as np
     import torch
@@ -142,9 +182,13 @@ def main():
     from icm_amd import _lib as L
     from icm_amd import codec
     from icm_amd import residual as R
-    kernel_part(args, torch, np, R, L)
+    rois = dmap = None
+    if args.error_roi:
+        rois = [codec._roi(t) for t in args.error_roi]
+        dmap = codec.error_map(H, W, args.max_error, rois)
+    kernel_part(args, torch, np, R, L, dmap)
     if not args.kernel_only:
-        codec_part(args, torch, np, codec)
+        codec_part(args, torch, np, codec, rois)
 
 
 if __name__ == "__main__":
