@@ -203,16 +203,25 @@ struct LaneDecoder {
   std::vector<Body> body;
   std::vector<uint32_t> x;                     // [G][64]
   std::vector<int64_t> cur;                    // [G] word cursor
-  int status = 0;                              // ICM_LANES_ST_* bits, sticky
+  std::vector<int> status;                     // [G] ICM_LANES_ST_* bits of each wave, sticky
   inline uint32_t word(int g, int64_t k) {
-    if (k >= body[g].words) { status |= ICM_LANES_ST_OVERRUN; return 0; }
+    if (k >= body[g].words) { status[g] |= ICM_LANES_ST_OVERRUN; return 0; }
     return le16(data.data() + body[g].off + kBodyMin + 2 * k);
+  }
+  inline int status_of(int g0, int g1) const {
+    int st = 0;
+    for (int g = g0; g < g1; ++g) st |= status[g];
+    return st;
   }
 };
 
-void lanes_decode_run(LaneDecoder& D, const int32_t* indexes, int64_t n, const Tables& T, int32_t* out) {
+// waves g0 <= g < g1 decode their elements of a run of n (the whole run's length: it fixes c); element e reads
+// indexes[e - elem0] and writes out[e - elem0].  The whole run is (0, G, 0).  No other wave is touched.
+void lanes_decode_run(LaneDecoder& D, int g0, int g1, int64_t elem0, const int32_t* indexes, int64_t n, const Tables& T,
+                      int32_t* out) {
   const int64_t c = chunk(n, D.G);
-  for (int g = 0; g < D.G; ++g) {
+  for (int g = g0; g < g1; ++g) {
+    int& status = D.status[g];
     uint32_t* x = D.x.data() + (size_t)g * kLanes;
     const int64_t e0 = (int64_t)g * c, e1 = std::min(n, e0 + c);
     for (int64_t base = e0; base < e1; base += kLanes) {
@@ -221,21 +230,23 @@ void lanes_decode_run(LaneDecoder& D, const int32_t* indexes, int64_t n, const T
       uint64_t raw[kLanes];
       int32_t overflow[kLanes];
       int64_t k = D.cur[g];
+      const int32_t* ix = indexes + (base - elem0);   // base >= g0 c >= elem0
+      int32_t* o = out + (base - elem0);
       for (int l = 0; l < act; ++l) {              // phase 0: the table symbol
         esc[l] = false;
         raw[l] = 0;
-        out[base + l] = 0;
-        const int idx = indexes[base + l], size = ICM_LANES_SIZE(T, idx);
-        if (!ICM_LANES_FITS(T, size)) { D.status |= ICM_LANES_ST_INDEX; overflow[l] = -1; continue; }
+        o[l] = 0;
+        const int idx = ix[l], size = ICM_LANES_SIZE(T, idx);
+        if (!ICM_LANES_FITS(T, size)) { status |= ICM_LANES_ST_INDEX; overflow[l] = -1; continue; }
         const int32_t* cdf = T.cdfs + (int64_t)idx * T.stride;
         overflow[l] = size - 2;
         const int cum = (int)(x[l] & 0xFFFF);
         const int32_t s = (int32_t)(std::upper_bound(cdf, cdf + size, (int32_t)cum) - cdf) - 1;
-        if (s < 0 || s > overflow[l] || cdf[s + 1] <= cdf[s]) { D.status |= ICM_LANES_ST_SYMBOL; overflow[l] = -1; continue; }
+        if (s < 0 || s > overflow[l] || cdf[s + 1] <= cdf[s]) { status |= ICM_LANES_ST_SYMBOL; overflow[l] = -1; continue; }
         x[l] = advance(x[l], cum, cdf[s], cdf[s + 1]);
         if (x[l] < kL) x[l] = (x[l] << 16) | D.word(g, k++);
         esc[l] = s == overflow[l];
-        out[base + l] = s + T.offsets[idx];
+        o[l] = s + T.offsets[idx];
       }
       for (int ph = 0; ph < 3; ++ph)               // phases 1..3: raw 16-bit groups of the lanes that escaped
         for (int l = 0; l < act; ++l)
@@ -245,9 +256,9 @@ void lanes_decode_run(LaneDecoder& D, const int32_t* indexes, int64_t n, const T
           }
       for (int l = 0; l < act; ++l)
         if (esc[l]) {
-          const int64_t v = unescape(raw[l], overflow[l], T.offsets[indexes[base + l]]);
-          if (is_int32(v)) out[base + l] = (int32_t)v;
-          else { D.status |= ICM_LANES_ST_ESCAPE; out[base + l] = 0; }
+          const int64_t v = unescape(raw[l], overflow[l], T.offsets[ix[l]]);
+          if (is_int32(v)) o[l] = (int32_t)v;
+          else { status |= ICM_LANES_ST_ESCAPE; o[l] = 0; }
         }
       D.cur[g] = k;
     }
@@ -341,6 +352,7 @@ void* icm_rans_lanes_decoder_create(const uint8_t* stream, int64_t nbytes) {
     if (parse(D->data.data(), nbytes, D->body)) {
       D->G = (int)D->body.size();
       D->cur.assign((size_t)D->G, 0);
+      D->status.assign((size_t)D->G, 0);
       D->x.resize((size_t)D->G * kLanes);
       for (int g = 0; g < D->G; ++g)
         for (int l = 0; l < kLanes; ++l) D->x[(size_t)g * kLanes + l] = le32(D->data.data() + D->body[g].off + 4 * l);
@@ -358,20 +370,42 @@ int icm_rans_lanes_decoder_decode_run(void* handle, const int32_t* indexes, int6
   const Tables T{cdfs, cdf_sizes, offsets, cdf_stride, ncdf};
   if (!handle || n < 0 || (n > 0 && (!indexes || !out)) || !T.ok()) return ICM_ERR_ARG;
   LaneDecoder& D = *static_cast<LaneDecoder*>(handle);
-  lanes_decode_run(D, indexes, n, T, out);
-  return D.status ? ICM_ERR_ARG : ICM_OK;
+  return icm_rans_lanes_decoder_decode_run_waves(handle, 0, D.G, 0, indexes, n, cdfs, cdf_stride, cdf_sizes, offsets, ncdf,
+                                                 out);
+}
+
+int icm_rans_lanes_decoder_decode_run_waves(void* handle, int g0, int g1, int64_t elem0, const int32_t* indexes,
+                                            int64_t n, const int32_t* cdfs, int cdf_stride, const int32_t* cdf_sizes,
+                                            const int32_t* offsets, int ncdf, int32_t* out) {
+  const Tables T{cdfs, cdf_sizes, offsets, cdf_stride, ncdf};
+  if (!handle || n < 0 || !T.ok()) return ICM_ERR_ARG;
+  LaneDecoder& D = *static_cast<LaneDecoder*>(handle);
+  const int64_t c = chunk(n, D.G);
+  if (g0 < 0 || g0 > g1 || g1 > D.G || elem0 < 0 || elem0 > (int64_t)g0 * c) return ICM_ERR_ARG;
+  const bool owns = g0 < g1 && (int64_t)g0 * c < n;   // a range that owns no element needs no buffers
+  if (owns && (!indexes || !out)) return ICM_ERR_ARG;
+  if (owns) lanes_decode_run(D, g0, g1, elem0, indexes, n, T, out);
+  return D.status_of(g0, g1) ? ICM_ERR_ARG : ICM_OK;
 }
 
 int icm_rans_lanes_decoder_finish(void* handle) {
   if (!handle) return -1;
-  LaneDecoder& D = *static_cast<LaneDecoder*>(handle);
-  for (int g = 0; g < D.G; ++g) {
-    if (D.cur[g] != D.body[g].words) D.status |= ICM_LANES_ST_CURSOR;
-    for (int l = 0; l < kLanes; ++l)
-      if (D.x[(size_t)g * kLanes + l] != kL) D.status |= ICM_LANES_ST_STATE;
-  }
-  return D.status;
+  return icm_rans_lanes_decoder_finish_waves(handle, 0, static_cast<LaneDecoder*>(handle)->G, 1);
 }
+
+int icm_rans_lanes_decoder_finish_waves(void* handle, int g0, int g1, int end) {
+  if (!handle) return -1;
+  LaneDecoder& D = *static_cast<LaneDecoder*>(handle);
+  if (g0 < 0 || g0 > g1 || g1 > D.G) return -1;
+  for (int g = g0; end && g < g1; ++g) {
+    if (D.cur[g] != D.body[g].words) D.status[g] |= ICM_LANES_ST_CURSOR;
+    for (int l = 0; l < kLanes; ++l)
+      if (D.x[(size_t)g * kLanes + l] != kL) D.status[g] |= ICM_LANES_ST_STATE;
+  }
+  return D.status_of(g0, g1);
+}
+
+int icm_rans_lanes_decoder_waves(void* handle) { return handle ? static_cast<LaneDecoder*>(handle)->G : -1; }
 
 void icm_rans_lanes_decoder_destroy(void* handle) { delete static_cast<LaneDecoder*>(handle); }
 

@@ -10,6 +10,11 @@
 // consecutive words in ascending lane order = a 64-bit ballot and a popcount of the lower lanes (v_mbcnt), no LDS.
 // The word cursor is wave-uniform and lives in a scalar register between steps.
 //
+// Ranges.  Bodies share nothing, so the decoder's two kernels take a range of waves [g0, g1): the grid holds those waves
+// alone (g = g0 + the wave's place in the grid, a scalar), the caller's indexes / out begin at element elem0 <= g0 c of
+// the run, and state, cursor and status of every other wave are neither read nor written.  The whole-run entries are
+// the range (0, G) from element 0.  A region decode of the residual layer is the user (icm_amd/residual.py).
+//
 // Bounds.  Every loop is counted by the run length and G (steps), by the constant 3 (escape phases) or by
 // ceil(log2(cdf_stride)) (table search); nothing in a stream can lengthen one.  Every word read is checked against
 // the body's word count first and sets ICM_LANES_ST_OVERRUN instead of reading; every CDF index is checked against
@@ -196,14 +201,18 @@ template <bool CENTRE>
 __global__ __launch_bounds__(kBlock) void lanes_dec_run_kernel(const uint8_t* __restrict__ string, WaveCtl* __restrict__ ctl,
                                                                uint32_t* __restrict__ states,
                                                                const int32_t* __restrict__ indexes, long long n,
-                                                               long long c, Tab T, int32_t* __restrict__ out, int G) {
-  const int g = __builtin_amdgcn_readfirstlane((int)(blockIdx.x * (blockDim.x / kLanes) + threadIdx.x / kLanes));
-  if (g >= G) return;
+                                                               long long c, Tab T, int32_t* __restrict__ out, int g0,
+                                                               int g1, long long elem0) {
+  // the grid holds the waves g0 .. g1 - 1 alone; g0 is a kernel argument, so g stays a scalar
+  const int g = g0 + __builtin_amdgcn_readfirstlane((int)(blockIdx.x * (blockDim.x / kLanes) + threadIdx.x / kLanes));
+  if (g >= g1) return;
   const int lane = lane_id();
   const long long e0 = (long long)g * c;
   const long long e1 = min(n, e0 + c);
   if (e1 <= e0) return;
   const int steps = (int)((e1 - e0 + kLanes - 1) / kLanes);
+  indexes -= elem0;   // the caller's buffers begin at element elem0 <= g0 c <= e0: element e lies at [e] again
+  out -= elem0;
   const uint16_t* __restrict__ words = reinterpret_cast<const uint16_t*>(string + ctl[g].off);
   const uint32_t nwords = __builtin_amdgcn_readfirstlane(ctl[g].nwords);
   uint32_t cur = __builtin_amdgcn_readfirstlane(ctl[g].cursor);
@@ -279,14 +288,17 @@ __global__ __launch_bounds__(kBlock) void lanes_dec_run_kernel(const uint8_t* __
   }
 }
 
+// the status word of the waves g0 .. g1 - 1; end: with the checks of a body that has decoded its last run
 __global__ void lanes_dec_finish_kernel(const WaveCtl* __restrict__ ctl, const uint32_t* __restrict__ states,
-                                        uint32_t* __restrict__ status, int G) {
-  const int g = blockIdx.x * blockDim.x + threadIdx.x;
-  if (g >= G) return;
+                                        uint32_t* __restrict__ status, int g0, int g1, int end) {
+  const int g = g0 + blockIdx.x * blockDim.x + threadIdx.x;
+  if (g >= g1) return;
   uint32_t st = ctl[g].status;
-  if (ctl[g].cursor != ctl[g].nwords) st |= ICM_LANES_ST_CURSOR;
-  for (int l = 0; l < kLanes; ++l)
-    if (states[g * kLanes + l] != kL) st |= ICM_LANES_ST_STATE;
+  if (end) {
+    if (ctl[g].cursor != ctl[g].nwords) st |= ICM_LANES_ST_CURSOR;
+    for (int l = 0; l < kLanes; ++l)
+      if (states[g * kLanes + l] != kL) st |= ICM_LANES_ST_STATE;
+  }
   status[g] = st;
 }
 
@@ -431,33 +443,55 @@ void* icm_rans_lanes_decoder_gpu_create(const uint8_t* stream_bytes, int64_t nby
 int icm_rans_lanes_decoder_gpu_decode_run(void* decoder, const int32_t* indexes, int64_t n, const int32_t* cdfs,
                                           int cdf_stride, const int32_t* cdf_sizes, const int32_t* offsets, int ncdf,
                                           int32_t* out, void* stream) {
+  if (!decoder) return ICM_ERR_ARG;
+  return icm_rans_lanes_decoder_gpu_decode_run_waves(decoder, 0, static_cast<GpuDecoder*>(decoder)->G, 0, indexes, n,
+                                                     cdfs, cdf_stride, cdf_sizes, offsets, ncdf, out, stream);
+}
+
+int icm_rans_lanes_decoder_gpu_waves(void* decoder) { return decoder ? static_cast<GpuDecoder*>(decoder)->G : -1; }
+
+int icm_rans_lanes_decoder_gpu_decode_run_waves(void* decoder, int g0, int g1, int64_t elem0, const int32_t* indexes,
+                                                int64_t n, const int32_t* cdfs, int cdf_stride,
+                                                const int32_t* cdf_sizes, const int32_t* offsets, int ncdf,
+                                                int32_t* out, void* stream) {
   Tab T;
-  if (!decoder || n < 0 || (n > 0 && (!indexes || !out)) || !make_tab(cdfs, cdf_stride, cdf_sizes, offsets, ncdf, T))
-    return ICM_ERR_ARG;
+  if (!decoder || n < 0 || !make_tab(cdfs, cdf_stride, cdf_sizes, offsets, ncdf, T)) return ICM_ERR_ARG;
   GpuDecoder& D = *static_cast<GpuDecoder*>(decoder);
-  if (n == 0) return ICM_OK;
+  const int64_t c = chunk(n, D.G);
+  if (g0 < 0 || g0 > g1 || g1 > D.G || elem0 < 0 || elem0 > (int64_t)g0 * c) return ICM_ERR_ARG;
+  const bool owns = g0 < g1 && (int64_t)g0 * c < n;   // a range that owns no element needs no buffers
+  if (owns && (!indexes || !out)) return ICM_ERR_ARG;
+  if (!owns) return ICM_OK;
   const int wpb = waves_per_block();
-  const int blocks = (D.G + wpb - 1) / wpb;
+  const int blocks = (g1 - g0 + wpb - 1) / wpb;   // the range's waves alone
   WaveCtl* ctl = reinterpret_cast<WaveCtl*>(D.dev + D.o_ctl);
   uint32_t* states = reinterpret_cast<uint32_t*>(D.dev + D.o_states);
   // the kernel addresses the string from the allocation's base: WaveCtl.off includes o_string
   hipLaunchKernelGGL(g_search_centre ? lanes_dec_run_kernel<true> : lanes_dec_run_kernel<false>, dim3(blocks),
-                     dim3(wpb * kLanes), 0, ST, D.dev, ctl, states, indexes, (long long)n, (long long)chunk(n, D.G), T,
-                     out, D.G);
+                     dim3(wpb * kLanes), 0, ST, D.dev, ctl, states, indexes, (long long)n, (long long)c, T, out, g0, g1,
+                     (long long)elem0);
   ICM_CHECK_LAUNCH();
   return ICM_OK;
 }
 
 int icm_rans_lanes_decoder_gpu_finish(void* decoder, void* stream) {
   if (!decoder) return -1;
+  return icm_rans_lanes_decoder_gpu_finish_waves(decoder, 0, static_cast<GpuDecoder*>(decoder)->G, 1, stream);
+}
+
+int icm_rans_lanes_decoder_gpu_finish_waves(void* decoder, int g0, int g1, int end, void* stream) {
+  if (!decoder) return -1;
   GpuDecoder& D = *static_cast<GpuDecoder*>(decoder);
+  if (g0 < 0 || g0 > g1 || g1 > D.G) return -1;
+  if (g0 == g1) return 0;
+  const int ng = g1 - g0;
   uint32_t* status = reinterpret_cast<uint32_t*>(D.dev + D.o_status);
-  hipLaunchKernelGGL(lanes_dec_finish_kernel, dim3((D.G + kBlock - 1) / kBlock), dim3(kBlock), 0, ST,
+  hipLaunchKernelGGL(lanes_dec_finish_kernel, dim3((ng + kBlock - 1) / kBlock), dim3(kBlock), 0, ST,
                      reinterpret_cast<const WaveCtl*>(D.dev + D.o_ctl),
-                     reinterpret_cast<const uint32_t*>(D.dev + D.o_states), status, D.G);
+                     reinterpret_cast<const uint32_t*>(D.dev + D.o_states), status, g0, g1, end ? 1 : 0);
   if (hipGetLastError() != hipSuccess) return -1;
-  std::vector<uint32_t> h((size_t)D.G);
-  if (hipMemcpyAsync(h.data(), status, 4 * (size_t)D.G, hipMemcpyDeviceToHost, ST) != hipSuccess) return -1;
+  std::vector<uint32_t> h((size_t)ng);
+  if (hipMemcpyAsync(h.data(), status + g0, 4 * (size_t)ng, hipMemcpyDeviceToHost, ST) != hipSuccess) return -1;
   if (hipStreamSynchronize(ST) != hipSuccess) return -1;
   int st = 0;
   for (uint32_t v : h) st |= (int)v;

@@ -14,6 +14,12 @@
 // residual_apply_map_kernel, where a run of four window pixels may straddle a cell boundary of the image.  A map byte
 // above 32 counts as 32 in both, so that the reciprocal below always divides.
 //
+// Bands.  The decoder's two operations also take buffers that hold a band of every plane instead of the planes: the
+// elements [e_lo, e_hi) of the row-major plane, plane c at c (e_hi - e_lo), which is what a region decode has of the
+// symbols (icm_residual_indexes_band / icm_residual_apply_band / icm_residual_apply_map_band).  A band starts and ends
+// anywhere in a row.  The kernels and element bodies are the same: Band{stride, lo, hi} says where element e of a
+// plane lies, and the whole planes are the band [0, H W).
+//
 // Integer work only, byte-bound: 6 bytes in and 24 out per pixel for the first, 12 out for the second, 15 in and 3 out
 // for the third.  A thread owns four adjacent pixels of one row: 12 interleaved bytes = three dword accesses where the
 // run lies inside its row and its first byte is dword-aligned, and four int32 per plane = one 16-byte access where its
@@ -158,27 +164,49 @@ __global__ __launch_bounds__(BLOCK) void residual_code_map_kernel(const uint8_t*
   }, gw, cy, cx, threadIdx.x & 63, symbols, indexes, classes);
 }
 
-// a thread owns four adjacent samples of one row (they share a cell) in the three planes
-__global__ __launch_bounds__(BLOCK) void residual_indexes_kernel(const int32_t* __restrict__ classes, int H, int W,
-                                                                  int gw, int32_t* __restrict__ indexes,
-                                                                  int runs_per_row, long long total_runs) {
+// where the elements of a plane lie in a symbols / indexes buffer: element e of plane c, lo <= e < hi, at
+// c stride + e - lo.  The whole planes: {H W, 0, H W}.
+struct Band {
+  long long stride, lo, hi;
+};
+
+// a thread owns four adjacent samples of one row (they share a cell) in the three planes; the rows are those of the
+// band, y_first onwards, and the samples of its first and last row that lie outside it are not stored
+__global__ __launch_bounds__(BLOCK) void residual_indexes_kernel(const int32_t* __restrict__ classes, int W, int gw,
+                                                                  Band band, int y_first,
+                                                                  int32_t* __restrict__ indexes, int runs_per_row,
+                                                                  long long total_runs) {
   const long long g = (long long)blockIdx.x * BLOCK + threadIdx.x;
   if (g >= total_runs) return;
-  const int y = (int)(g / runs_per_row);
-  const int x0 = ((int)(g - (long long)y * runs_per_row)) * RUN;
-  const int n = min(W - x0, RUN);
+  const int yr = (int)(g / runs_per_row);
+  const int y = y_first + yr;
+  const int x0 = ((int)(g - (long long)yr * runs_per_row)) * RUN;
+  const long long e0 = (long long)y * W + x0;
+  const int j0 = (int)min(max(band.lo - e0, 0ll), (long long)RUN);             // the run's samples inside the band:
+  const int n = (int)max(min(min((long long)(W - x0), band.hi - e0), (long long)RUN), 0ll);   // j0 <= j < n
+  if (j0 >= n) return;
   const int cls = classes[(size_t)(y / CELL) * gw + x0 / CELL];
   const int k[RUN] = {cls, cls, cls, cls};
-  const size_t plane = (size_t)H * W, e0 = (size_t)y * W + x0;
 #pragma unroll
-  for (int c = 0; c < 3; ++c) store_run(indexes + c * plane + e0, n == RUN, n, k);
+  for (int c = 0; c < 3; ++c) {
+    // where the run's first sample would lie: in front of the band, even of the buffer, if j0 > 0 -- an address only,
+    // the stores below touch o[j0 .. n - 1] alone, all inside the band
+    int32_t* o = indexes + c * band.stride + (e0 - band.lo);
+    if (j0 == 0) {
+      store_run(o, n == RUN, n, k);
+    } else {
+#pragma unroll
+      for (int j = 0; j < RUN; ++j)
+        if (j >= j0 && j < n) o[j] = cls;
+    }
+  }
 }
 
 // a thread owns four adjacent pixels of one row of the window; s[j] is the step 2 D + 1 of pixel j's cell.  |q| >= 256
 // saturates whatever s is, so q is clamped to +-256 first and the product stays small: the result is that of the exact
 // integers for every int32 q
-__device__ __forceinline__ void apply_run(const uint8_t* __restrict__ xhat, const int32_t* __restrict__ symbols, int H,
-                                          int W, int y0, int x0, int w, int y, int x, const int (&s)[RUN],
+__device__ __forceinline__ void apply_run(const uint8_t* __restrict__ xhat, const int32_t* __restrict__ symbols,
+                                          Band band, int W, int y0, int x0, int w, int y, int x, const int (&s)[RUN],
                                           uint8_t* __restrict__ out) {
   const int n = min(w - x, RUN);
   const bool full = n == RUN;
@@ -186,11 +214,11 @@ __device__ __forceinline__ void apply_run(const uint8_t* __restrict__ xhat, cons
   uint32_t e[3];
   load_run(xhat + o, full, n, e);
 
-  const size_t plane = (size_t)H * W, e0 = (size_t)(y0 + y) * W + x0 + x;
+  const long long e0 = (long long)(y0 + y) * W + x0 + x - band.lo;   // the window lies inside the band
   uint32_t r[3] = {0u, 0u, 0u};
 #pragma unroll
   for (int c = 0; c < 3; ++c) {
-    const int32_t* sp = symbols + c * plane + e0;
+    const int32_t* sp = symbols + c * band.stride + e0;
     int q[RUN];
     if (full && aligned_to(sp, 16)) {
       const i32x4 t = *reinterpret_cast<const i32x4*>(sp);
@@ -220,8 +248,8 @@ __device__ __forceinline__ void apply_run(const uint8_t* __restrict__ xhat, cons
 }
 
 __global__ __launch_bounds__(BLOCK) void residual_apply_kernel(const uint8_t* __restrict__ xhat,
-                                                                const int32_t* __restrict__ symbols, int H, int W,
-                                                                int y0, int x0, int h, int w, int s,
+                                                                const int32_t* __restrict__ symbols, Band band,
+                                                                int W, int y0, int x0, int h, int w, int s,
                                                                 uint8_t* __restrict__ out, int runs_per_row,
                                                                 long long total_runs) {
   const long long g = (long long)blockIdx.x * BLOCK + threadIdx.x;
@@ -229,7 +257,7 @@ __global__ __launch_bounds__(BLOCK) void residual_apply_kernel(const uint8_t* __
   const int y = (int)(g / runs_per_row);
   const int x = ((int)(g - (long long)y * runs_per_row)) * RUN;
   const int sj[RUN] = {s, s, s, s};
-  apply_run(xhat, symbols, H, W, y0, x0, w, y, x, sj, out);
+  apply_run(xhat, symbols, band, W, y0, x0, w, y, x, sj, out);
 }
 
 // The cell of a pixel is that of its image position (y0 + y, x0 + x + j).  The run's pixels inside the window span at
@@ -237,8 +265,8 @@ __global__ __launch_bounds__(BLOCK) void residual_apply_kernel(const uint8_t* __
 // only where it is another cell, and every pixel takes the one of its own column.  Both lie inside the map: the window
 // lies inside the image.
 __global__ __launch_bounds__(BLOCK) void residual_apply_map_kernel(const uint8_t* __restrict__ xhat,
-                                                                    const int32_t* __restrict__ symbols, int H, int W,
-                                                                    int y0, int x0, int h, int w,
+                                                                    const int32_t* __restrict__ symbols, Band band,
+                                                                    int W, int y0, int x0, int h, int w,
                                                                     const uint8_t* __restrict__ dmap, int gw,
                                                                     uint8_t* __restrict__ out, int runs_per_row,
                                                                     long long total_runs) {
@@ -254,10 +282,19 @@ __global__ __launch_bounds__(BLOCK) void residual_apply_map_kernel(const uint8_t
   int sj[RUN];
 #pragma unroll
   for (int j = 0; j < RUN; ++j) sj[j] = (px + j) / CELL == c0 ? s0 : s1;   // pixels past the window are not stored
-  apply_run(xhat, symbols, H, W, y0, x0, w, y, x, sj, out);
+  apply_run(xhat, symbols, band, W, y0, x0, w, y, x, sj, out);
 }
 
 bool side_ok(int v) { return v >= 1 && v <= MAX_SIDE; }
+
+// a band of the planes of an H x W image that is not empty
+bool band_ok(int H, int W, int64_t e_lo, int64_t e_hi) { return e_lo >= 0 && e_lo < e_hi && e_hi <= (int64_t)H * W; }
+
+// the window inside the image, and every one of its samples inside the band
+bool window_ok(int H, int W, int y0, int x0, int h, int w, int64_t e_lo, int64_t e_hi) {
+  if (y0 < 0 || x0 < 0 || (long long)y0 + h > H || (long long)x0 + w > W) return false;
+  return (int64_t)y0 * W + x0 >= e_lo && (int64_t)(y0 + h - 1) * W + x0 + w <= e_hi;
+}
 
 }  // namespace
 
@@ -290,37 +327,57 @@ int icm_residual_code_map(const uint8_t* x, const uint8_t* xhat, int H, int W, c
 }
 
 int icm_residual_indexes(const int32_t* classes, int H, int W, int32_t* indexes, void* stream) {
-  if (!classes || !indexes || !side_ok(H) || !side_ok(W)) return ICM_ERR_ARG;
+  if (!side_ok(H) || !side_ok(W)) return ICM_ERR_ARG;
+  return icm_residual_indexes_band(classes, H, W, 0, (int64_t)H * W, indexes, stream);
+}
+
+int icm_residual_indexes_band(const int32_t* classes, int H, int W, int64_t e_lo, int64_t e_hi, int32_t* indexes,
+                              void* stream) {
+  if (!classes || !indexes || !side_ok(H) || !side_ok(W) || !band_ok(H, W, e_lo, e_hi)) return ICM_ERR_ARG;
   const int rpr = (W + RUN - 1) / RUN;
-  const long long total = (long long)H * rpr;                     // <= 32768 * 8192
+  const int y_first = (int)(e_lo / W), y_last = (int)((e_hi - 1) / W);
+  const long long total = (long long)(y_last - y_first + 1) * rpr;   // <= 32768 * 8192
   hipLaunchKernelGGL(residual_indexes_kernel, dim3((unsigned)((total + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, ST, classes,
-                     H, W, (W + CELL - 1) / CELL, indexes, rpr, total);
+                     W, (W + CELL - 1) / CELL, Band{e_hi - e_lo, e_lo, e_hi}, y_first, indexes, rpr, total);
   ICM_CHECK_LAUNCH();
   return ICM_OK;
 }
 
 int icm_residual_apply(const uint8_t* xhat, const int32_t* symbols, int H, int W, int y0, int x0, int h, int w, int D,
                        uint8_t* out, void* stream) {
+  if (!side_ok(H) || !side_ok(W)) return ICM_ERR_ARG;
+  return icm_residual_apply_band(xhat, symbols, H, W, 0, (int64_t)H * W, y0, x0, h, w, D, out, stream);
+}
+
+int icm_residual_apply_band(const uint8_t* xhat, const int32_t* symbols, int H, int W, int64_t e_lo, int64_t e_hi,
+                            int y0, int x0, int h, int w, int D, uint8_t* out, void* stream) {
   if (!xhat || !symbols || !out) return ICM_ERR_ARG;
   if (!side_ok(H) || !side_ok(W) || !side_ok(h) || !side_ok(w) || D < 0 || D > MAX_D) return ICM_ERR_ARG;
-  if (y0 < 0 || x0 < 0 || (long long)y0 + h > H || (long long)x0 + w > W) return ICM_ERR_ARG;
+  if (!band_ok(H, W, e_lo, e_hi) || !window_ok(H, W, y0, x0, h, w, e_lo, e_hi)) return ICM_ERR_ARG;
   const int rpr = (w + RUN - 1) / RUN;
   const long long total = (long long)h * rpr;
   hipLaunchKernelGGL(residual_apply_kernel, dim3((unsigned)((total + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, ST, xhat,
-                     symbols, H, W, y0, x0, h, w, 2 * D + 1, out, rpr, total);
+                     symbols, Band{e_hi - e_lo, e_lo, e_hi}, W, y0, x0, h, w, 2 * D + 1, out, rpr, total);
   ICM_CHECK_LAUNCH();
   return ICM_OK;
 }
 
 int icm_residual_apply_map(const uint8_t* xhat, const int32_t* symbols, int H, int W, int y0, int x0, int h, int w,
                            const uint8_t* dmap, uint8_t* out, void* stream) {
+  if (!side_ok(H) || !side_ok(W)) return ICM_ERR_ARG;
+  return icm_residual_apply_map_band(xhat, symbols, H, W, 0, (int64_t)H * W, y0, x0, h, w, dmap, out, stream);
+}
+
+int icm_residual_apply_map_band(const uint8_t* xhat, const int32_t* symbols, int H, int W, int64_t e_lo, int64_t e_hi,
+                                int y0, int x0, int h, int w, const uint8_t* dmap, uint8_t* out, void* stream) {
   if (!xhat || !symbols || !dmap || !out) return ICM_ERR_ARG;
   if (!side_ok(H) || !side_ok(W) || !side_ok(h) || !side_ok(w)) return ICM_ERR_ARG;
-  if (y0 < 0 || x0 < 0 || (long long)y0 + h > H || (long long)x0 + w > W) return ICM_ERR_ARG;
+  if (!band_ok(H, W, e_lo, e_hi) || !window_ok(H, W, y0, x0, h, w, e_lo, e_hi)) return ICM_ERR_ARG;
   const int rpr = (w + RUN - 1) / RUN;
   const long long total = (long long)h * rpr;
   hipLaunchKernelGGL(residual_apply_map_kernel, dim3((unsigned)((total + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, ST, xhat,
-                     symbols, H, W, y0, x0, h, w, dmap, (W + CELL - 1) / CELL, out, rpr, total);
+                     symbols, Band{e_hi - e_lo, e_lo, e_hi}, W, y0, x0, h, w, dmap, (W + CELL - 1) / CELL, out, rpr,
+                     total);
   ICM_CHECK_LAUNCH();
   return ICM_OK;
 }

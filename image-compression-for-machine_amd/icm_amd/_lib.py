@@ -85,6 +85,9 @@ SYMBOLS = [
     "icm_rans_lanes_decoder_decode_run", "icm_rans_lanes_decoder_finish", "icm_rans_lanes_decoder_destroy",
     "icm_rans_lanes_encode_gpu_workspace", "icm_rans_lanes_encode_gpu", "icm_rans_lanes_decoder_gpu_create",
     "icm_rans_lanes_decoder_gpu_decode_run", "icm_rans_lanes_decoder_gpu_finish", "icm_rans_lanes_decoder_gpu_destroy",
+    "icm_rans_lanes_decoder_waves", "icm_rans_lanes_decoder_decode_run_waves", "icm_rans_lanes_decoder_finish_waves",
+    "icm_rans_lanes_decoder_gpu_waves", "icm_rans_lanes_decoder_gpu_decode_run_waves",
+    "icm_rans_lanes_decoder_gpu_finish_waves",
     "icm_debug_lanes_search",
     "icm_eb_table_bounds", "icm_eb_pmf_table", "icm_gc_table_centers", "icm_gc_pmf_table", "icm_gc_build_indexes",
     "icm_quantize", "icm_dequantize", "icm_clamp", "icm_pad2d",
@@ -98,6 +101,7 @@ SYMBOLS = [
     "icm_image_batch_u8_to_f32", "icm_image_tile_blend", "icm_image_cell_stats",
     "icm_residual_code", "icm_residual_indexes", "icm_residual_apply",
     "icm_residual_code_map", "icm_residual_apply_map",
+    "icm_residual_indexes_band", "icm_residual_apply_band", "icm_residual_apply_map_band",
 ]
 REDUCE_WS_FLOATS = 8192   # ICM_REDUCE_WS_FLOATS
 
@@ -232,6 +236,13 @@ def lib():
         L.icm_rans_lanes_decoder_gpu_finish.argtypes = [vp, vp]
         L.icm_rans_lanes_decoder_gpu_destroy.argtypes = [vp]
         L.icm_rans_lanes_decoder_gpu_destroy.restype = None
+        L.icm_rans_lanes_decoder_waves.argtypes = [vp]
+        L.icm_rans_lanes_decoder_decode_run_waves.argtypes = [vp, i32, i32, i64, i32p, i64, i32p, i32, i32p, i32p, i32,
+                                                             i32p]
+        L.icm_rans_lanes_decoder_finish_waves.argtypes = [vp, i32, i32, i32]
+        L.icm_rans_lanes_decoder_gpu_waves.argtypes = [vp]
+        L.icm_rans_lanes_decoder_gpu_decode_run_waves.argtypes = [vp, i32, i32, i64, vp, i64, vp, i32, vp, vp, i32, vp, vp]
+        L.icm_rans_lanes_decoder_gpu_finish_waves.argtypes = [vp, i32, i32, i32, vp]
         L.icm_debug_lanes_search.argtypes = [i32]
         L.icm_debug_lanes_search.restype = None
         L.icm_eb_table_bounds.argtypes = [vp, i32, vp, vp, vp]
@@ -263,6 +274,9 @@ def lib():
         L.icm_residual_apply.argtypes = [vp, vp, i32, i32, i32, i32, i32, i32, i32, vp, vp]
         L.icm_residual_code_map.argtypes = [vp, vp, i32, i32, vp, vp, vp, vp, vp]
         L.icm_residual_apply_map.argtypes = [vp, vp, i32, i32, i32, i32, i32, i32, vp, vp, vp]
+        L.icm_residual_indexes_band.argtypes = [vp, i32, i32, i64, i64, vp, vp]
+        L.icm_residual_apply_band.argtypes = [vp, vp, i32, i32, i64, i64, i32, i32, i32, i32, i32, vp, vp]
+        L.icm_residual_apply_map_band.argtypes = [vp, vp, i32, i32, i64, i64, i32, i32, i32, i32, vp, vp, vp]
         L.icm_zigzag_order.argtypes = [i32, i32, i32, vp, i32]
         L.icm_zigzag_splits.argtypes = [vp, i64, vp, i32, i32, i32, i32, i32, i32, i32, vp]
         L.icm_zigzag_reverse.argtypes = [vp, vp, i64, i32, i32, i32, i32, i32, i32, i32, vp]

@@ -183,6 +183,22 @@ def lanes_waves(run_lengths, symbols_per_wave: int = SYMBOLS_PER_WAVE) -> int:
     return g
 
 
+def lanes_chunk(n: int, G: int) -> int:
+    """c of a run of ``n`` elements in a stream of ``G`` waves: wave g owns the elements [g c, min(n, (g + 1) c)) -- the
+    per-wave share rounded up to whole steps of 64 lanes (``chunk`` of csrc/rans_lanes_common.h)"""
+    return (-(-int(n) // int(G)) + 63) // 64 * 64
+
+
+def _wave_range(G: int, g0: int, g1: int, elem0: int, n: int, have: int) -> None:
+    """the checks of a ranged call that the C entry makes, plus the one it cannot: the buffers' length"""
+    if not (0 <= g0 <= g1 <= G and 0 <= elem0 <= g0 * lanes_chunk(n, G)):
+        raise ValueError(f"lane stream: waves [{g0}, {g1}) from element {elem0} are not a range of a run of {n} in "
+                         f"{G} waves")
+    need = max(0, min(n, g1 * lanes_chunk(n, G)) - elem0) if g1 > g0 else 0
+    if have < need:
+        raise ValueError(f"lane stream: waves [{g0}, {g1}) from element {elem0} need {need} indexes, got {have}")
+
+
 def lanes_encode(symbols, indexes, run_lengths, t: _Tables, symbols_per_wave: int = SYMBOLS_PER_WAVE) -> bytes:
     """host encoder: the runs back to back in ``symbols`` / ``indexes`` -> one lane stream"""
     sym, idx = _arr(symbols), _arr(indexes)
@@ -211,6 +227,7 @@ class _LanesHandle:
         if not self._h:
             raise ValueError("lane stream decode: not a lane stream (magic, version, G or a length table that "
                              "disagrees with the string's length)")
+        self.G = getattr(L.lib(), self._waves)(self._h)      # the stream's wave bodies
 
     def close(self):
         if self._h:
@@ -225,8 +242,14 @@ class _LanesHandle:
 
 
 class LanesDecoder(_LanesHandle):
-    """host decoder of one lane stream: ``decode_run`` per run in stream order, then ``finish``"""
+    """host decoder of one lane stream: ``decode_run`` per run in stream order, then ``finish``.
+
+    The waves of a stream share nothing, so a range of them can be decoded alone: ``decode_run_waves(g0, g1, elem0,
+    ...)`` has the waves g0 <= g < g1 decode their elements of the run, and ``finish_waves(g0, g1, end)`` answers for
+    those waves only and leaves the decoder open (``close`` it).  The caller's contract: a wave is given the runs of
+    the stream in their order, none skipped; different waves may stand at different runs.  ``G``: the stream's waves."""
     _create, _destroy = "icm_rans_lanes_decoder_create", "icm_rans_lanes_decoder_destroy"
+    _waves = "icm_rans_lanes_decoder_waves"
 
     def decode_run(self, indexes, t: _Tables) -> np.ndarray:
         idx = _arr(indexes)
@@ -237,10 +260,28 @@ class LanesDecoder(_LanesHandle):
             _lanes_status(L.lib().icm_rans_lanes_decoder_finish(self._h) or -1)
         return out
 
+    def decode_run_waves(self, g0: int, g1: int, elem0: int, indexes, n: int, t: _Tables) -> np.ndarray:
+        """the waves [g0, g1) decode their elements of a run of ``n`` (the whole run's length).  ``indexes`` holds the
+        run's elements from ``elem0`` (at most g0 c, ``lanes_chunk``) up to at least the last one of wave g1 - 1; the
+        result has its shape, element e at e - elem0, and only the elements of those waves are written"""
+        idx = _arr(indexes)
+        _wave_range(self.G, g0, g1, elem0, n, int(idx.size))
+        out = np.zeros(idx.size, dtype=np.int32)
+        rc = L.lib().icm_rans_lanes_decoder_decode_run_waves(self._h, g0, g1, elem0, idx.ctypes.data_as(_i32p), int(n),
+                                                             *t.args(), out.ctypes.data_as(_i32p))
+        if rc:
+            _lanes_status(L.lib().icm_rans_lanes_decoder_finish_waves(self._h, g0, g1, 0) or -1)
+        return out
+
     def finish(self) -> None:
         st = L.lib().icm_rans_lanes_decoder_finish(self._h)
         self.close()
         _lanes_status(st)
+
+    def finish_waves(self, g0: int, g1: int, end: bool = True) -> None:
+        """ValueError unless the waves [g0, g1) decoded cleanly; ``end``: and have reached the end of their bodies
+        (for waves that have decoded their last run).  The decoder stays open."""
+        _lanes_status(L.lib().icm_rans_lanes_decoder_finish_waves(self._h, g0, g1, 1 if end else 0))
 
 
 def lanes_decode(stream: bytes, indexes, run_lengths, t: _Tables) -> np.ndarray:
@@ -299,9 +340,12 @@ def lanes_encode_gpu(symbols, indexes, run_lengths, cdf, sizes, offsets,
 
 class LanesDecoderGpu(_LanesHandle):
     """device decoder of one lane stream.  ``decode_run`` is one launch on the current stream and returns a device
-    tensor; nothing is known to be valid until ``finish`` has looked at the status words."""
+    tensor; nothing is known to be valid until ``finish`` has looked at the status words.  ``decode_run_waves`` /
+    ``finish_waves`` / ``G``: the ranged forms, as on ``LanesDecoder`` and bit for bit its results; a ranged launch
+    holds the range's waves alone."""
 
     _create, _destroy = "icm_rans_lanes_decoder_gpu_create", "icm_rans_lanes_decoder_gpu_destroy"
+    _waves = "icm_rans_lanes_decoder_gpu_waves"
 
     def __init__(self, stream: bytes):
         super().__init__(stream, L.stream())
@@ -317,10 +361,29 @@ class LanesDecoderGpu(_LanesHandle):
                                                               L.stream()), "lanes decode_run")
         return out
 
+    def decode_run_waves(self, g0: int, g1: int, elem0: int, indexes, n: int, cdf, sizes, offsets, out=None):
+        """as ``LanesDecoder.decode_run_waves`` on flat device tensors; ``out`` (same length as ``indexes``) is written
+        only where those waves own elements -- a fresh one is zero elsewhere"""
+        import torch
+        if not (indexes.is_cuda and indexes.dtype == torch.int32 and indexes.is_contiguous()):
+            raise ValueError("lane stream: indexes must be a contiguous int32 device tensor")
+        _wave_range(self.G, g0, g1, elem0, n, int(indexes.numel()))
+        if out is None:
+            out = torch.zeros(indexes.shape, dtype=torch.int32, device=indexes.device)
+        elif not (out.is_cuda and out.dtype == torch.int32 and out.is_contiguous() and out.numel() == indexes.numel()):
+            raise ValueError("lane stream: out must be a contiguous int32 device tensor as long as indexes")
+        L.check(L.lib().icm_rans_lanes_decoder_gpu_decode_run_waves(self._h, g0, g1, elem0, indexes.data_ptr(), int(n),
+                                                                    *_dev_tables(cdf, sizes, offsets), out.data_ptr(),
+                                                                    L.stream()), "lanes decode_run_waves")
+        return out
+
     def finish(self) -> None:
         st = L.lib().icm_rans_lanes_decoder_gpu_finish(self._h, L.stream())
         self.close()
         _lanes_status(st)
+
+    def finish_waves(self, g0: int, g1: int, end: bool = True) -> None:
+        _lanes_status(L.lib().icm_rans_lanes_decoder_gpu_finish_waves(self._h, g0, g1, 1 if end else 0, L.stream()))
 
 
 # ------------------------------------------------------------------------------------------- one coder behind both
@@ -328,7 +391,8 @@ class HostCoder:
     """the reference's scalar stream, coded on the host from ``em._tables()`` (``em``: the EntropyModel whose tables
     apply).  ``encode``: flat int32 symbols and indexes cross to the host once each; the runs are concatenated.
     ``decoder(string, em)``: ``decode_run(indexes, out=None)`` -> int32 symbols shaped like ``indexes`` on its device (a
-    copy down and one up per call), ``finish()`` (the scalar stream has no end mark to check) and ``close()``."""
+    copy down and one up per call), ``finish()`` (the scalar stream has no end mark to check) and ``close()``.
+    ``waves`` is None: the scalar stream is one chain and has no ranged forms."""
     name = "host"
 
     def encode(self, symbols, indexes, run_lengths, em) -> bytes:
@@ -343,13 +407,15 @@ class HostCoder:
         def decode_run(indexes, out=None):
             sym = torch.from_numpy(dec.decode_stream_np(_arr(indexes.detach().cpu().numpy()), t).reshape(indexes.shape))
             return sym.to(indexes.device) if out is None else out.copy_(sym)
-        return SimpleNamespace(decode_run=decode_run, finish=lambda: None, close=dec._close)
+        return SimpleNamespace(decode_run=decode_run, finish=lambda: None, close=dec._close, waves=None)
 
 
 class LanesCoder(HostCoder):
     """lane streams, coded by the kernels from ``em._device_tables()`` where the symbols lie: the same surface; host
     indexes are brought to the device, ``decode_run`` is one launch without a wait and answers on the device, and
-    nothing is known to be valid until ``finish`` has read the status words."""
+    nothing is known to be valid until ``finish`` has read the status words.  Its decoder also has ``waves`` (G of the
+    string), ``decode_run_waves(g0, g1, elem0, indexes, n, out=None)`` and ``finish_waves(g0, g1, end=True)``, the
+    ranged forms of ``LanesDecoderGpu``; after ``finish_waves`` the decoder is still to be closed."""
     name = "lanes"
 
     def __init__(self, symbols_per_wave):
@@ -364,7 +430,9 @@ class LanesCoder(HostCoder):
         import torch
         dec, t = LanesDecoderGpu(string), em._device_tables()
         return SimpleNamespace(finish=dec.finish, close=dec.close, decode_run=lambda indexes, out=None: dec.decode_run(
-            indexes.to(t[0].device, torch.int32).contiguous(), *t, out=out))
+            indexes.to(t[0].device, torch.int32).contiguous(), *t, out=out), waves=dec.G, finish_waves=dec.finish_waves,
+            decode_run_waves=lambda g0, g1, elem0, indexes, n, out=None: dec.decode_run_waves(
+                g0, g1, elem0, indexes.to(t[0].device, torch.int32).contiguous(), n, *t, out=out))
 
 
 def coder_for(coder, symbols_per_wave=None):

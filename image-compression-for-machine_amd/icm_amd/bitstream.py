@@ -99,7 +99,11 @@ the decoder's reconstruction of the base, which bound the error of every sample 
 begins with neither inner magic and -- given the reader's own table CRC -- a file written with other tables, so that a
 reader built with other tables stops instead of decoding garbage.  ``unpack`` and ``unpack_tiled`` are unchanged and
 refuse the magic, as a reader from before this container does (exit code 4 of the CLI).  The residual string is one
-string of four runs under the layer's tables: the class map, then the R, G and B planes.
+string of four runs under the layer's tables: the class map, then the R, G and B planes.  Coded as a lane stream it can
+be decoded in part without any change to these bytes: its G wave bodies share nothing, and body g holds the elements
+[g c, min(n, (g + 1) c)) of every run of n (c: the lane stream's share per wave, below), so the rows of a window are a
+range of bodies, the same for the three planes, and their cells' classes another range of the class run
+(``icm_amd.residual.region_plan``; a decoder hands a body its runs in order, none skipped).
 
 An error-bounded image whose bound varies over the picture is a fourth container with its own magic: the bound is one
 byte per 16 x 16-pixel cell of the residual layer's grid (``error_grid``: anchored at pixel (0, 0) of the whole image,

@@ -57,8 +57,10 @@ The base is coded as without the flag (every flag above applies to it; a byte bu
 the encoder then decodes it on the device, as the decoder will, and codes the quantised differences as a second layer
 (``icm_amd.residual``, csrc/residual.hip: a uniform quantiser of step 2 D + 1, one context class per 16 x 16-pixel cell,
 static two-sided geometric tables, the coder ``--coder`` names), both wrapped in an ``ICMR`` container
-(``icm_amd.bitstream``).  ``decode`` needs no flag; with ``--region`` it decodes the base's region only but the residual
-string whole -- decoding only the window's part of the lane bodies is not built.  Files written without the flag are
+(``icm_amd.bitstream``).  ``decode`` needs no flag; with ``--region`` it decodes the base's region, and of a residual
+string coded with ``--coder lanes`` only the wave bodies that hold the window's rows and their cells' classes (the report's
+"residual_waves": [decoded, G]) -- whole waves, so rows and not columns are saved; a host-coded residual string is one
+chain and decodes whole.  Files written without the flag are
 byte for byte what they were.  Parity unpinned: no counterpart in the reference.
 
 ``--error-roi Y0,X0,H,W:D'`` (repeatable, with ``--max-error``) gives the bound the form every other knob has: the
@@ -643,10 +645,14 @@ def decode_image(model, data: bytes, reference=None, region=None) -> Tuple[torch
     index the stream was coded with (0: none), or the list per tile should they differ; None for a stream (in the
     list: a tile) coded with a quality map, which "qmap" then holds: the int8 map, or of a tiled stream the list per
     tile with None for the tiles of a scalar step.  Streams without a map have no "qmap".
-    An ICMR stream: the base is decoded as above (with ``region``, only that region), the residual string is decoded
-    whole -- also with ``region``: decoding only the window's part of the lane bodies is not built -- and applied to
-    the window; a region decode is bit for bit the crop of the full decode.  ``info`` is the base's with "bytes" and
-    "bpp" of the whole file, and "max_error", "base_bytes" and "residual_bytes"; with ``reference`` also
+    An ICMR stream: the base is decoded as above (with ``region``, only that region); of a residual string coded with
+    the lanes coder only the wave bodies that hold the window's rows, and those that hold their cells' classes, are
+    decoded (``residual.region_plan``), into a band of the planes instead of the planes; the residual is applied to
+    the window, and a region decode is bit for bit the crop of the full decode.  A window costs whole waves: every row
+    of the waves that hold its rows, at full width (rows, not columns).  A host-coded residual string is one chain and
+    is decoded whole.  ``info`` is the base's with "bytes" and "bpp" of the whole file, and "max_error", "base_bytes",
+    "residual_bytes" and "residual_waves": [the distinct waves of the residual string that decoded anything, its G],
+    [G, G] without a region, None for a host-coded string; with ``reference`` also
     "max_abs_error", the largest absolute difference of a sample to the reference's, and "sse" / "psnr" of the final
     image.
     An ICME stream, an ICMR stream with a bound per 16 x 16-pixel cell, decodes the same way, each sample under its own
@@ -664,10 +670,11 @@ def decode_image(model, data: bytes, reference=None, region=None) -> Tuple[torch
         H, W, D = head["height"], head["width"], head["max_error"]
         if (info["height"], info["width"]) != (H, W):
             raise ValueError(f"codec: the ICMR stream holds a {H}x{W} image, its base a {info['height']}x{info['width']}")
-        sym = R.decode_residual(string, H, W, coder_for(head["coder"]), device)
-        out = R.residual_apply(out, sym, (ry, rx, rh, rw), D if dmap is None else dmap)
+        res = R.decode_residual(string, H, W, coder_for(head["coder"]), device, window=(ry, rx, rh, rw))
+        out = R.residual_apply(out, res.symbols, (ry, rx, rh, rw), D if dmap is None else dmap, band=res.band,
+                               size=(H, W))
         info.update(bytes=len(data), bpp=8.0 * len(data) / (H * W), max_error=D, base_bytes=len(base),
-                    residual_bytes=len(string))
+                    residual_bytes=len(string), residual_waves=None if res.waves is None else list(res.waves))
         if dmap is not None:
             info.update(max_error_range=[int(dmap.min()), int(dmap.max())], max_error_map=dmap)
         if reference is not None:

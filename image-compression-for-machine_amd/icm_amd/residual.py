@@ -34,11 +34,19 @@ or a host map, which is checked here and then uploaded (``icm_residual_code_map`
 decode is within D[cy, cx] of the original in every sample of the cell, bit-exact where the byte is 0.
 
 String -- one string of four runs: the class map (gh gw symbols, all with index 19), then the R, G and B planes (H W
-symbols each, the index of a sample being the class of its cell)."""
+symbols each, the index of a sample being the class of its cell).
+
+Region decode -- a lane stream is G independent wave bodies, and wave g owns the elements [g c, min(n, (g + 1) c)) of
+every run of n (c = ``ans.lanes_chunk(n, G)``).  The rows of a window are therefore a contiguous range of waves, the
+same for the three planes, and the classes those waves need are a (small) range of waves of the class run:
+``region_plan`` works both out, and ``decode_residual(..., window=...)`` decodes those waves alone into a band
+[3, e_hi - e_lo] of the planes (``ResidualBand``), which ``residual_indexes`` and ``residual_apply`` take through their
+``band`` argument.  What a window costs is whole waves: every row of the waves that hold its rows, at full width (rows,
+not columns).  A host-coded string is one chain and is decoded whole."""
 from __future__ import annotations
 
 import zlib
-from typing import Tuple
+from typing import NamedTuple, Optional, Tuple
 
 import numpy as np
 import torch
@@ -179,31 +187,64 @@ def residual_code(x: torch.Tensor, xhat: torch.Tensor, d):
     return sym, idx, cls
 
 
-def residual_indexes(classes: torch.Tensor, H: int, W: int) -> torch.Tensor:
-    """device int32 classes [gh, gw] (as decoded) -> int32 [3, H, W], every sample's class (``icm_residual_indexes``)"""
+def _check_band(band, H: int, W: int) -> Tuple[int, int]:
+    e_lo, e_hi = int(band[0]), int(band[1])
+    if not 0 <= e_lo < e_hi <= H * W:
+        raise ValueError(f"residual: [{e_lo}, {e_hi}) is not a band of the {H}x{W} planes")
+    return e_lo, e_hi
+
+
+def residual_indexes(classes: torch.Tensor, H: int, W: int, band=None) -> torch.Tensor:
+    """device int32 classes [gh, gw] (as decoded) -> int32 [3, H, W], every sample's class (``icm_residual_indexes``).
+    ``band`` = (e_lo, e_hi): only the elements e_lo <= e < e_hi of every row-major plane, int32 [3, e_hi - e_lo]
+    (``icm_residual_indexes_band``); the band may start and end inside a row"""
     if classes.dtype != torch.int32 or classes.numel() != grid(H, W)[0] * grid(H, W)[1] or not classes.is_cuda:
         raise ValueError(f"residual: classes must be {grid(H, W)} device int32, got {classes.dtype} {tuple(classes.shape)}")
     classes = classes.contiguous()
+    if band is not None:
+        e_lo, e_hi = _check_band(band, H, W)
+        idx = torch.empty((3, e_hi - e_lo), dtype=torch.int32, device=classes.device)
+        check(L.lib().icm_residual_indexes_band(classes.data_ptr(), H, W, e_lo, e_hi, idx.data_ptr(), L.stream()),
+              "residual_indexes_band")
+        return idx
     idx = torch.empty((3, H, W), dtype=torch.int32, device=classes.device)
     check(L.lib().icm_residual_indexes(classes.data_ptr(), H, W, idx.data_ptr(), L.stream()), "residual_indexes")
     return idx
 
 
-def residual_apply(xhat: torch.Tensor, symbols: torch.Tensor, window, d) -> torch.Tensor:
+def residual_apply(xhat: torch.Tensor, symbols: torch.Tensor, window, d, band=None, size=None) -> torch.Tensor:
     """device 8-bit [h, w, 3] reconstruction of the window (y0, x0, h, w) and the image's symbols int32 [3, H, W] -> the
     window with the residual applied, 8-bit [h, w, 3].  ``d``: the bound, an int (``icm_residual_apply``) or the host
     map of the whole image's cells (``icm_residual_apply_map``): a window pixel takes the bound of the cell of its image
-    position"""
+    position.  With ``band`` = (e_lo, e_hi) and ``size`` = (H, W), ``symbols`` is int32 [3, e_hi - e_lo], that band of
+    the planes (``icm_residual_apply_band`` / ``icm_residual_apply_map_band``); the window must lie inside it"""
     xhat = _u8(xhat, "the reconstruction")
     y0, x0, h, w = window
-    if symbols.dtype != torch.int32 or symbols.dim() != 3 or symbols.size(0) != 3 or tuple(xhat.shape[:2]) != (h, w):
+    if band is not None:
+        H, W = size
+        e_lo, e_hi = _check_band(band, H, W)
+        fits = symbols.dim() == 2 and symbols.size(1) == e_hi - e_lo
+        if fits and not (0 <= y0 and 0 <= x0 and 1 <= h and 1 <= w and y0 + h <= H and x0 + w <= W and
+                         y0 * W + x0 >= e_lo and (y0 + h - 1) * W + x0 + w <= e_hi):
+            raise ValueError(f"residual: window {window} does not lie inside the band [{e_lo}, {e_hi}) of the {H}x{W} "
+                             f"planes")
+    else:
+        fits = symbols.dim() == 3
+    if symbols.dtype != torch.int32 or not fits or symbols.size(0) != 3 or tuple(xhat.shape[:2]) != (h, w):
         raise ValueError(f"residual: symbols {symbols.dtype} {tuple(symbols.shape)} / window {window} / reconstruction "
                          f"{tuple(xhat.shape)} do not fit")
     symbols = symbols.contiguous()
     out = torch.empty_like(xhat)
-    H, W = symbols.size(1), symbols.size(2)
-    if _is_map(d):
-        dmap = torch.from_numpy(check_error_map(d, H, W, "residual: ")).to(xhat.device)
+    if band is None:
+        H, W = symbols.size(1), symbols.size(2)
+    dmap = torch.from_numpy(check_error_map(d, H, W, "residual: ")).to(xhat.device) if _is_map(d) else None
+    if band is not None and dmap is not None:
+        check(L.lib().icm_residual_apply_map_band(xhat.data_ptr(), symbols.data_ptr(), H, W, e_lo, e_hi, y0, x0, h, w,
+                                                  dmap.data_ptr(), out.data_ptr(), L.stream()), "residual_apply_map_band")
+    elif band is not None:
+        check(L.lib().icm_residual_apply_band(xhat.data_ptr(), symbols.data_ptr(), H, W, e_lo, e_hi, y0, x0, h, w, d,
+                                              out.data_ptr(), L.stream()), "residual_apply_band")
+    elif dmap is not None:
         check(L.lib().icm_residual_apply_map(xhat.data_ptr(), symbols.data_ptr(), H, W, y0, x0, h, w, dmap.data_ptr(),
                                              out.data_ptr(), L.stream()), "residual_apply_map")
     else:
@@ -224,19 +265,83 @@ def encode_residual(x: torch.Tensor, xhat: torch.Tensor, d, coder) -> Tuple[byte
     return string, (int(lo), int(hi))
 
 
-def decode_residual(string: bytes, H: int, W: int, coder, device) -> torch.Tensor:
+class RegionPlan(NamedTuple):
+    """what a window of an H x W image needs of a residual string of G waves (``region_plan``)"""
+    plane_waves: Tuple[int, int]     # [pa, pb): the waves of runs 1 .. 3 that hold the window's rows
+    band: Tuple[int, int]            # [e_lo, e_hi) = [pa c, min(H W, pb c)): the plane elements those waves own
+    cell_rows: Tuple[int, int]       # [cr0, cr1): the rows of cells the band touches
+    class_waves: Tuple[int, int]     # [ka, kb): the waves of run 0 that hold the classes of those rows of cells
+
+
+def region_plan(H: int, W: int, G: int, window) -> RegionPlan:
+    """the waves of a residual string of ``G`` waves that the window (y0, x0, h, w) of an H x W image needs; pure
+    host arithmetic.  The window's rows y0 .. y0 + h - 1, at full width, are the plane elements [y0 W, (y0 + h) W), which
+    lie in the waves [pa, pb).  A wave decodes its whole chunk, so it needs the class of every pixel of the band
+    [pa c, min(H W, pb c)), not only of the window's rows: the band's first and last row give the rows of cells, whose
+    classes are the elements [cr0 gw, cr1 gw) of run 0 and lie in its waves [ka, kb)."""
+    y0, x0, h, w = (int(v) for v in window)
+    if not (H >= 1 and W >= 1 and G >= 1 and 0 <= y0 and 0 <= x0 and h >= 1 and w >= 1 and y0 + h <= H and x0 + w <= W):
+        raise ValueError(f"residual: window {(y0, x0, h, w)} is not inside the {H}x{W} image (G = {G})")
+    from .ans import lanes_chunk
+    n = H * W
+    c = lanes_chunk(n, G)
+    pa, pb = (y0 * W) // c, ((y0 + h) * W - 1) // c + 1
+    e_lo, e_hi = pa * c, min(n, pb * c)
+    gh, gw = grid(H, W)
+    cr0, cr1 = (e_lo // W) // CELL, ((e_hi - 1) // W) // CELL + 1
+    kc = lanes_chunk(gh * gw, G)
+    ka, kb = (cr0 * gw) // kc, (cr1 * gw - 1) // kc + 1
+    return RegionPlan((pa, pb), (e_lo, e_hi), (cr0, cr1), (ka, kb))
+
+
+class ResidualBand(NamedTuple):
+    """the symbols a window needs: ``symbols`` int32 [3, e_hi - e_lo] on the device, the elements ``band`` =
+    (e_lo, e_hi) of every plane; ``waves`` = (distinct waves that decoded anything, G of the string), None for a
+    host-coded string"""
+    symbols: torch.Tensor
+    band: Tuple[int, int]
+    waves: Optional[Tuple[int, int]]
+
+
+def decode_residual(string: bytes, H: int, W: int, coder, device, window=None):
     """inverse of ``encode_residual``: the symbols, int32 [3, H, W] on ``device``.  With the lanes coder the class run
     is decoded, expanded to indexes on the device and the planes decoded without anything coming back to the host
-    before ``finish()``.  ValueError for a string that is not one of this layer's."""
+    before ``finish()``.  ValueError for a string that is not one of this layer's.
+
+    ``window`` = (y0, x0, h, w): a ``ResidualBand`` instead, with at least the symbols of that window.  With the lanes
+    coder only the waves of ``region_plan`` are decoded: run 0 by the class waves and the plane waves (a wave is given
+    its runs in order, so the plane waves take their part of run 0 too, often an empty one) into the full class
+    buffer, the band's indexes are expanded, runs 1 .. 3 are decoded by the plane waves into the band, and then the
+    plane waves are held to the end checks and the class-only waves, which stop after run 0, to their status alone.
+    With the host coder, whose stream is one chain, or when the window's waves own the whole planes, the string is
+    decoded whole and the band is [0, H W)."""
     gh, gw = grid(H, W)
+    n, cells = H * W, gh * gw
     dec = coder.decoder(string, tables())
     try:
-        cls = dec.decode_run(torch.full((gh * gw,), NCLASSES, dtype=torch.int32, device=device))
-        idx = residual_indexes(cls.reshape(gh, gw), H, W)
-        sym = torch.empty((3, H, W), dtype=torch.int32, device=device)
+        G = dec.waves
+        plan = region_plan(H, W, G, window) if window is not None and G is not None else None
+        if plan is None or plan.band == (0, n):
+            cls = dec.decode_run(torch.full((cells,), NCLASSES, dtype=torch.int32, device=device))
+            idx = residual_indexes(cls.reshape(gh, gw), H, W)
+            sym = torch.empty((3, H, W), dtype=torch.int32, device=device)
+            for c in range(3):
+                dec.decode_run(idx[c], out=sym[c])
+            dec.finish()
+            return sym if window is None else ResidualBand(sym.reshape(3, n), (0, n), None if G is None else (G, G))
+        (pa, pb), (e_lo, e_hi), _, (ka, kb) = plan
+        only = [(a, b) for a, b in ((ka, min(kb, pa)), (max(ka, pb), kb)) if a < b]     # class waves outside [pa, pb)
+        cls = torch.zeros((cells,), dtype=torch.int32, device=device)      # cells no wave decodes are never looked at
+        idx0 = torch.full((cells,), NCLASSES, dtype=torch.int32, device=device)
+        for a, b in only + [(pa, pb)]:
+            dec.decode_run_waves(a, b, 0, idx0, cells, out=cls)
+        idx = residual_indexes(cls.reshape(gh, gw), H, W, band=(e_lo, e_hi))
+        sym = torch.empty((3, e_hi - e_lo), dtype=torch.int32, device=device)
         for c in range(3):
-            dec.decode_run(idx[c], out=sym[c])
-        dec.finish()
+            dec.decode_run_waves(pa, pb, e_lo, idx[c], n, out=sym[c])
+        dec.finish_waves(pa, pb, True)
+        for a, b in only:
+            dec.finish_waves(a, b, False)
+        return ResidualBand(sym, (e_lo, e_hi), (pb - pa + sum(b - a for a, b in only), G))
     finally:
         dec.close()
-    return sym

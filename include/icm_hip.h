@@ -347,6 +347,26 @@ int icm_rans_lanes_decoder_decode_run(void* decoder, const int32_t* indexes, int
                                       int32_t* out);
 int icm_rans_lanes_decoder_finish(void* decoder);
 void icm_rans_lanes_decoder_destroy(void* decoder);
+/* A range of waves (the bodies of a stream share nothing, so any of them can be decoded alone).
+ * waves: G of the decoder's stream, -1 for NULL.
+ * decode_run_waves: waves g0 <= g < g1 decode their elements of a run of length n -- n is the whole run's length, which
+ *   fixes c = 64 ceil(ceil(n / G) / 64); wave g owns the elements [g c, min(n, (g + 1) c)).  Element e reads
+ *   indexes[e - elem0] and writes out[e - elem0], so the two buffers hold the elements [elem0, min(n, g1 c)) and need
+ *   not start at the run's first; a range that owns no element of the run (g0 = g1, or g0 c >= n) needs none and does
+ *   nothing.  Requires 0 <= g0 <= g1 <= G and 0 <= elem0 <= g0 c, otherwise ICM_ERR_ARG before anything is done;
+ *   ICM_ERR_ARG also once a status bit of one of these waves is set.  State, cursor and status of every other wave are
+ *   untouched.  decode_run is decode_run_waves(0, G, 0).
+ * finish_waves: the ICM_LANES_ST_* bits of the waves g0 <= g < g1 only; end = 1 adds the end checks (cursor at the
+ *   body's last word, every lane at 2^16), end = 0 is for waves that stop before their last run.  -1 for NULL or a bad
+ *   range.  It leaves the decoder as it is, usable and still to be destroyed.  finish is finish_waves(0, G, 1).
+ * The caller's contract: a wave is given the runs of the stream in their order, none skipped -- a wave that is to
+ * decode its part of run r must have decoded its parts of the runs 0 .. r - 1 (parts that own no element included: they
+ * are no work).  Different waves may stand at different runs. */
+int icm_rans_lanes_decoder_waves(void* decoder);
+int icm_rans_lanes_decoder_decode_run_waves(void* decoder, int g0, int g1, int64_t elem0, const int32_t* indexes,
+                                            int64_t n, const int32_t* cdfs, int cdf_stride, const int32_t* cdf_sizes,
+                                            const int32_t* offsets, int ncdf, int32_t* out);
+int icm_rans_lanes_decoder_finish_waves(void* decoder, int g0, int g1, int end);
 
 /* Device side.  symbols / indexes / tables / ws are DEVICE memory, run_lengths is host memory.
  * encode: ws = icm_rans_lanes_encode_gpu_workspace(...) bytes, 16-byte aligned.  worst_case = 0 gives every wave one
@@ -370,6 +390,16 @@ int icm_rans_lanes_decoder_gpu_decode_run(void* decoder, const int32_t* indexes,
                                           int32_t* out, void* stream);
 int icm_rans_lanes_decoder_gpu_finish(void* decoder, void* stream);
 void icm_rans_lanes_decoder_gpu_destroy(void* decoder);
+/* The ranged forms of the host decoder above, same arguments, contract and symbols bit for bit; indexes / out are
+ * device memory that holds the elements [elem0, min(n, g1 c)).  decode_run_waves launches g1 - g0 waves (none for a
+ * range that owns nothing) and, like decode_run, does not wait: the status is finish_waves' to report, which copies
+ * back the status words of the range alone and waits on `stream`. */
+int icm_rans_lanes_decoder_gpu_waves(void* decoder);
+int icm_rans_lanes_decoder_gpu_decode_run_waves(void* decoder, int g0, int g1, int64_t elem0, const int32_t* indexes,
+                                                int64_t n, const int32_t* cdfs, int cdf_stride,
+                                                const int32_t* cdf_sizes, const int32_t* offsets, int ncdf,
+                                                int32_t* out, void* stream);
+int icm_rans_lanes_decoder_gpu_finish_waves(void* decoder, int g0, int g1, int end, void* stream);
 /* CDF search of the decode kernel: 1 probes outward from the table's centre bin, 0 = plain binary search; the
  * default is the form DESIGN.md 5 measured faster */
 void icm_debug_lanes_search(int centre);
@@ -690,6 +720,22 @@ int icm_residual_code_map(const uint8_t* x, const uint8_t* xhat, int H, int W, c
                           int32_t* indexes, int32_t* classes, void* stream);
 int icm_residual_apply_map(const uint8_t* xhat, const int32_t* symbols, int H, int W, int y0, int x0, int h, int w,
                            const uint8_t* dmap, uint8_t* out, void* stream);
+/* The decoder's operations on a band of the planes, what a region decode has of the symbols: indexes / symbols =
+ * [3, e_hi - e_lo] int32, plane c's elements e_lo <= e < e_hi of the row-major [H, W] plane at c (e_hi - e_lo) + e -
+ * e_lo.  A band starts and ends anywhere in a row (it is a range of a lane stream's waves, not of rows).
+ * residual_indexes_band: writes every element of the band, from the whole image's classes [gh, gw] (only the cell rows
+ *   the band touches are read).
+ * residual_apply_band / residual_apply_map_band: as residual_apply / residual_apply_map; every sample of the window
+ *   must lie inside the band.
+ * The same kernels and element bodies: the entries above are the band [0, H W) and keep their results bit for bit.
+ * Launch, alignment and ICM_ERR_ARG as above; also ICM_ERR_ARG unless 0 <= e_lo < e_hi <= H W and, for the two apply
+ * entries, y0 W + x0 >= e_lo and (y0 + h - 1) W + x0 + w <= e_hi. */
+int icm_residual_indexes_band(const int32_t* classes, int H, int W, int64_t e_lo, int64_t e_hi, int32_t* indexes,
+                              void* stream);
+int icm_residual_apply_band(const uint8_t* xhat, const int32_t* symbols, int H, int W, int64_t e_lo, int64_t e_hi,
+                            int y0, int x0, int h, int w, int D, uint8_t* out, void* stream);
+int icm_residual_apply_map_band(const uint8_t* xhat, const int32_t* symbols, int H, int W, int64_t e_lo, int64_t e_hi,
+                                int y0, int x0, int h, int w, const uint8_t* dmap, uint8_t* out, void* stream);
 
 /* ---- device-resident training data (icm_amd/datasets.py DeviceImageCache; stands in for the reference's per-step
  * CenterCrop / RandomCrop(pad_if_needed) + ToTensor + collate on the host, train.py:393-425).  A training batch cut out

@@ -20,8 +20,15 @@ The model is a randomly initialised ``cnn`` (seeded): its base reconstruction is
 dominates the file and the sizes say nothing about a trained codec.  The bound is what is verified, not the rate.  Prints
 one JSON line per part.
 
+    region   (--region, alone) decode_image with ``region`` = the central --region-size window against the whole decode,
+             on a 2048x3072 untiled and a 3008x4032 tiled file of ``--max-error`` / ``--coder``, alternating, medians of
+             --rounds wall times; the residual string alone (``residual.decode_residual`` with and without the window);
+             the residual waves decoded of G; and the peak device memory of the region decode, and of the residual
+             string's decode alone, above what was allocated before it (the allocator's peak: the decoder's own upload
+             of the string, one copy of ``residual_bytes``, is not in it).  Runs unchanged on a checkout from before the ranged decode, where the window changes nothing.
+
     python tools/bench_codec_residual.py [--iters 100] [--rounds 3] [--kernel-only] [--coder {host,lanes}] [--max-error D]
-                                          [--error-roi Y0,X0,H,W:D' ...]
+                                          [--error-roi Y0,X0,H,W:D' ...] [--region [--region-size 512]]
 
 --kernel-only runs the kernel part alone (the run to put under rocprofv3 --kernel-trace --stats).
 """
@@ -164,6 +171,61 @@ def codec_part(args, torch, np, codec, rois=None):
               flush=True)
 
 
+def region_part(args, torch, np, codec, R):
+    import inspect
+    from bench_codec_tiles import OVERLAP, TILE
+    from icm_amd import bitstream as B
+    from icm_amd.ans import coder_for
+    from icm_amd.zoo import models
+    torch.manual_seed(0)
+    model = models["cnn"]().to("cuda:0").eval()
+    model.update(force=True)
+    ranged = "window" in inspect.signature(R.decode_residual).parameters
+    n = args.region_size
+    for name, (h, w), kw in (("untiled", (H, W), {}), ("tiled", (3008, 4032), {"tile": TILE, "overlap": OVERLAP})):
+        a = synthetic(np, h, w, 1)
+        region = ((h - n) // 2, (w - n) // 2, n, n)
+        data = codec.encode_image(model, a, coder=args.coder, max_error=args.max_error, **kw)
+        string = B.unpack_residual(data, R.tables().crc)[2]
+        full, finfo = codec.decode_image(model, data)                       # warm both shapes up
+        crop, rinfo = codec.decode_image(model, data, region=region)
+        assert torch.equal(crop, full[region[0]:region[0] + n, region[1]:region[1] + n])
+        del full, crop
+
+        def residual(window):
+            kwargs = {"window": window} if ranged and window is not None else {}
+            return R.decode_residual(string, h, w, coder_for(args.coder), "cuda:0", **kwargs)
+        t = {k: [] for k in ("whole", "region", "residual_whole", "residual_region")}
+        for _ in range(args.rounds):                                        # alternating: drift hits all alike
+            t["whole"].append(wall(lambda: codec.decode_image(model, data), torch)[0])
+            t["region"].append(wall(lambda: codec.decode_image(model, data, region=region), torch)[0])
+            t["residual_whole"].append(wall(lambda: residual(None), torch)[0])
+            t["residual_region"].append(wall(lambda: residual(region), torch)[0])
+        def peak_of(fn):
+            torch.cuda.synchronize()
+            torch.cuda.empty_cache()
+            before = torch.cuda.memory_allocated()
+            torch.cuda.reset_peak_memory_stats()
+            fn()
+            torch.cuda.synchronize()
+            return int(torch.cuda.max_memory_allocated() - before)
+        peak = peak_of(lambda: codec.decode_image(model, data, region=region))
+        peak_res = {"residual_region_peak_device_bytes": peak_of(lambda: residual(region)),
+                    "residual_whole_peak_device_bytes": peak_of(lambda: residual(None))}
+        waves = rinfo.get("residual_waves")
+        res = {"metric": "codec_residual_region", "input": name, "coder": args.coder, "height": h, "width": w,
+               "max_error": args.max_error, "region": list(region), "ranged_decode": ranged, "rounds": args.rounds,
+               "residual_bytes": len(string), "residual_waves": waves, "tiles_decoded": rinfo.get("tiles_decoded"),
+               "region_peak_device_bytes": peak, **peak_res}
+        for k, v in t.items():
+            res[f"{k}_decode_s"] = round(statistics.median(v), 4)
+            res[f"{k}_decode_s_all"] = [round(x, 4) for x in v]
+        if waves:
+            res["residual_region_us_per_wave"] = round(1e6 * statistics.median(t["residual_region"]) / waves[0], 1)
+            res["residual_whole_us_per_wave"] = round(1e6 * statistics.median(t["residual_whole"]) / waves[1], 1)
+        print(json.dumps(res), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--iters", type=int, default=100)
@@ -174,6 +236,9 @@ def main():
     ap.add_argument("--error-roi", action="append", default=None, metavar="Y0,X0,H,W:D",
                     help="rectangle with its own absolute bound, repeatable: also time the map kernels and encode the "
                          "mapped file")
+    ap.add_argument("--region", action="store_true",
+                    help="the region part alone: a central window of an untiled and a tiled file against the whole decode")
+    ap.add_argument("--region-size", type=int, default=512, metavar="N", help="side of the window of --region")
     args = ap.parse_args()
     import numpy as np
     import torch
@@ -182,6 +247,8 @@ def main():
     from icm_amd import _lib as L
     from icm_amd import codec
     from icm_amd import residual as R
+    if args.region:
+        return region_part(args, torch, np, codec, R)
     rois = dmap = None
     if args.error_roi:
         rois = [codec._roi(t) for t in args.error_roi]
